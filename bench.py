@@ -12,13 +12,20 @@ Workloads (BASELINE.json `configs`):
               of the projection keys, gather of per-model state, broadcast of the label image + background pose + control record.
               STRONG scaling: value = scene frames/s.  (N = 1: every model on rank 0 through the same three phases.)
   --config 4  the per-GPU share of configs[4]: 1280x960 stream, NUM_GSURFELS = 32M.
-A "step" = one processFrame over one frame whose rgb / depth (/ mask) already sit in HBM.  The timed region is `--steps` steps,
-repeated as a whole until it has lasted at least `--min-seconds` (a 6 ms region says little); `steps` in the JSON line is the
-number of steps actually timed.  N > 1 (weak scaling): every rank owns one surfel model (the reference's per-model independence,
-SURVEY.md 8e) and tracks / fuses it against the frame rank 0 broadcasts over RCCL each step; value = model-frames of all ranks
-/ max-over-ranks time.
+A "step" = one processFrame over one frame whose rgb / depth (/ mask) already sit in HBM.  The timed region is `--steps` steps after
+`--warmup` untimed ones; `--min-seconds S` repeats it as a whole until it has lasted at least S seconds (default: no repetition);
+`steps` in the JSON line is the number of steps actually timed and `ms_per_step` the time of one.  N > 1 (weak scaling): every rank
+owns one surfel model (the reference's per-model independence) and tracks / fuses it against the frame rank 0
+broadcasts over RCCL each step; value = model-frames of all ranks / max-over-ranks time.
 
-The JSON line also carries
+A plain run sets up, warms up, times the steps, writes `--dump-outputs DIR` if asked (below) and prints the result line; only the
+distinct frames the warm-up and the timed steps visit are ray-cast and kept in HBM.  `--dump-outputs DIR`: what the last timed step left
+for a caller, as .npy files in DIR (float32 / float64, <= 64 MB in all): every model's pose and surfel count, every model's surfel map
+(Model::downloadMap rows in a canonical order -- the device appends surfels in no fixed order -- and, beyond the byte budget, a fixed
+seeded sample of them) and, where masks are used, the label image of the last frame.
+
+With `--full` the JSON line also carries the side measurements below (each can still be switched off with its --no-* option), and at
+N > 1 the model-sharded scene is timed beside the weak-scaling line:
   roofline       -- the dominant kernel (the ICP Gauss-Newton iteration): algorithmic bytes per launch / average launch duration
                     measured here with HIP events on the library's stream, against the 8 TB/s HBM peak; `traffic` = HBM bytes
                     per launch from the newest committed PMC profile (profiles/r*_pmc.json) when it was taken on this kernel;
@@ -79,29 +86,84 @@ def _render(args):
     return _stream(cfg).frame(k)
 
 
-def gen_frames(cfg, n, workers=0, cache=None):
+MAX_GEN_WORKERS = 16     # ray-casting processes at most: more only compete for the cores the run is given
+
+
+def _usable_cpus():
+    try:
+        return len(os.sched_getaffinity(0))
+    except AttributeError:
+        return os.cpu_count() or 1
+
+
+def gen_frames(cfg, n, workers=0, cache=None, later=False):
     """n frames of the synthetic stream, ray-cast in parallel on the host cores (must run before CUDA is initialised: fork).
     workers = 1: no fork at all (under rocprofv3 --pmc the tool has initialised HSA before Python starts; forked workers hang at exit).
     cache: directory the rendered frames are kept in / taken from (profiler passes over the full 600-frame stream re-use the frames of the
-    timing run instead of ray-casting them again without fork)."""
+    timing run instead of ray-casting them again without fork).
+    later: return (stream, result) at once, result() waiting for the frames -- the forked workers ray-cast while this process goes on
+    (imports torch, initialises the device)."""
     st = _stream(cfg)
     tag = None
     if cache:
         tag = os.path.join(cache, f"frames_{cfg['W']}x{cfg['H']}_o{cfg['n_objects']}{'_s3' if cfg.get('s3') else ''}_n{n}")
         if os.path.exists(tag + "_rgb.npy"):
             rgb, depth, mask = (np.load(tag + s + ".npy", mmap_mode="r") for s in ("_rgb", "_depth", "_mask"))
-            return st, [(np.ascontiguousarray(rgb[k]), np.ascontiguousarray(depth[k]), np.ascontiguousarray(mask[k])) for k in range(n)]
-    workers = workers or max(1, min(48, (os.cpu_count() or 1) - 2, n))
+            frames = [(np.ascontiguousarray(rgb[k]), np.ascontiguousarray(depth[k]), np.ascontiguousarray(mask[k])) for k in range(n)]
+            return st, ((lambda: frames) if later else frames)
+    workers = workers or max(1, min(MAX_GEN_WORKERS, _usable_cpus() - 2, n))
+    pool = job = None
     if workers > 1:
-        with mp.get_context("fork").Pool(workers) as pool:
-            frames = pool.map(_render, [(cfg, k) for k in range(n)], chunksize=max(1, n // (4 * workers)))
-    else:
-        frames = [st.frame(k) for k in range(n)]
-    if tag:
-        os.makedirs(cache, exist_ok=True)
-        for s, j in (("_rgb", 0), ("_depth", 1), ("_mask", 2)):
-            np.save(tag + s + ".npy", np.stack([f[j] for f in frames]))
-    return st, frames
+        pool = mp.get_context("fork").Pool(workers)
+        job = pool.map_async(_render, [(cfg, k) for k in range(n)], chunksize=max(1, n // (4 * workers)))
+
+    done = []
+
+    def result():
+        if done:
+            return done[0]
+        if job is not None:
+            try:
+                frames = job.get()
+            finally:
+                pool.terminate()
+                pool.join()
+        else:
+            frames = [st.frame(k) for k in range(n)]
+        if tag:
+            os.makedirs(cache, exist_ok=True)
+            for s, j in (("_rgb", 0), ("_depth", 1), ("_mask", 2)):
+                np.save(tag + s + ".npy", np.stack([f[j] for f in frames]))
+        done.append(frames)
+        return frames
+    return st, (result if later else result())
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs: all files together
+
+
+def dump_outputs(mf, out_dir, multi, seed=0):
+    """--dump-outputs: what the last step left for a caller of processFrame.  poses.npy (models x 4 x 4, float64), surfel_counts.npy,
+    surfels_model<i>.npy (Model::downloadMap: rows of 12 float32 sorted lexicographically -- the device appends new surfels in no fixed
+    order -- and, when all maps together exceed the byte budget, the same seeded sample of each sorted map's rows), segmentation.npy (the
+    label image of the last frame, float32; multi-model configurations only)."""
+    os.makedirs(out_dir, exist_ok=True)
+    models = mf.getModels()
+    out = {"poses": np.stack([m.getPose() for m in models]).astype(np.float64),
+           "surfel_counts": np.array([m.lastCount() for m in models], np.float64)}
+    if multi:
+        out["segmentation"] = mf.downloadSegmentation().astype(np.float32)
+    budget_rows = (DUMP_BYTES - sum(a.nbytes for a in out.values()) - 1024 * (len(out) + len(models))) // 48
+    total = int(out["surfel_counts"].sum())
+    for i, m in enumerate(models):
+        surf = m.downloadMap()
+        surf = surf[np.lexsort(surf.T[::-1])]
+        if total > budget_rows:
+            keep = np.random.default_rng(seed + i).choice(len(surf), int(len(surf) * budget_rows / total), replace=False)
+            surf = surf[np.sort(keep)]
+        out[f"surfels_model{i}"] = np.ascontiguousarray(surf, np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def pingpong(n_frames, steps):
@@ -340,7 +402,7 @@ def single_context_scene(args, cfg, local_rank, st, frames, steps, min_seconds):
             "note": "one context holding every model on rank 0's GPU, mf_process_frame with host pointers (the boundary the sharded form uses)"}
 
 
-def run_sharded(args, cfg, rank, local_rank, world, st, frames):
+def run_sharded(args, cfg, rank, local_rank, world, st, frames, min_seconds):
     """--config 3: the model-sharded scene as the bench's own line."""
     import torch
     import torch.distributed as dist
@@ -349,7 +411,7 @@ def run_sharded(args, cfg, rank, local_rank, world, st, frames):
         torch.cuda.set_device(local_rank)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     seen = ranks_seen(world, local_rank)
-    out = sharded_scene(args, cfg, rank, local_rank, world, st, frames, args.steps, args.min_seconds)
+    out = sharded_scene(args, cfg, rank, local_rank, world, st, frames, args.steps, min_seconds)
     if rank == 0:
         out["ranks_seen"] = seen
         print(json.dumps(out))
@@ -661,12 +723,12 @@ def small_variant(cfg_key, local_rank, frames, n_timed, warm):
             "models": len(counts), "surfels": sum(counts)}
 
 
-def run_config4(args, local_rank, frames, room_job):
+def run_config4(args, local_rank, frames, room_job, min_seconds):
     """--config 4 as the bench's own line"""
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (there is no CPU path)")
-    res = config4_scene(local_rank, frames, room_job, seconds=args.min_seconds, frames_per_rep=max(10, min(args.steps, 60)), tracked=not args.static_objects,
+    res = config4_scene(local_rank, frames, room_job, seconds=min_seconds, frames_per_rep=max(10, min(args.steps, 60)), tracked=not args.static_objects,
                         params=[tuple((kv.partition("=")[0], float(kv.partition("=")[2]))) for kv in args.param])
     out = {"metric": f"frames/sec (1280x960 RGB-D, background + {res['models'] - 1} object models, 32M / 4M surfel budgets filled >= 80 %, ICP + surfel fusion)",
            "value": res["value"], "unit": "frames/s", "n_gpus": 1, "steps": res["steps"], "steps_requested": args.steps, "warmup": 4,
@@ -690,7 +752,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=60)
     ap.add_argument("--frames", type=int, default=0, help="distinct synthetic frames kept in HBM (0: the config's default; ping-ponged)")
     ap.add_argument("--config", default="1", choices=tuple(CONFIGS), help="workload (1 = the metric's)")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="the timed region is repeated until it has lasted this long")
+    ap.add_argument("--min-seconds", type=float, default=None, help="the timed region is repeated until it has lasted this long (default: timed "
+                    "once, exactly --steps steps; --config 4: 2 s of its repetitions)")
     ap.add_argument("--max-reps", type=int, default=100000, help="runaway guard on the repetitions of the timed region")
     ap.add_argument("--icp-weight", type=float, default=100.0, help="icpWeight (>= 100: geometric term only, the metric's setting; "
                     "the reference GUI default is 20: photometric term on, two launches per Gauss-Newton iteration)")
@@ -710,40 +773,54 @@ def main():
     ap.add_argument("--no-variants", action="store_true", help="skip the side measurements of config 1: reference defaults (icpWeight 20 + SO(3)) and the dense configs[4] scenario")
     ap.add_argument("--force-sharded-scene", action="store_true", help="run that part at N = 1 as well (rehearsal of the N > 1 code path on one GPU)")
     ap.add_argument("--no-sharded-scene", action="store_true", help="N > 1: skip the model-sharded 8-object scene that is timed beside the weak-scaling line")
+    ap.add_argument("--full", action="store_true", help="also the side measurements: roofline, host_input, cpu_baseline, the variants of config 1 "
+                    "and, at N > 1, the model-sharded scene (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (poses, surfel counts, surfel maps, "
+                    "label image) as .npy files into DIR")
     args = ap.parse_args()
+    # the timed region once, exactly --steps steps, unless --min-seconds asks for repetitions; the side measurements keep their own windows
+    side_seconds = 2.0 if args.min_seconds is None else args.min_seconds
+    timed_min_seconds = args.min_seconds or 0.0
+    if args.dump_outputs and args.config in ("3", "4"):
+        raise SystemExit("--dump-outputs: configs 1, 2s and 4n")
     cfg = CONFIGS[args.config]
     W, H, F = cfg["W"], cfg["H"], cfg["f"]
     CX, CY = W / 2.0, H / 2.0
     multi = cfg["n_objects"] > 0
     n_frames = args.frames or cfg["frames"]
+    # ping-ponged: warm-up + one timed region visit the first warmup + steps frames of the stream; repetitions and side measurements go on
+    n_render = n_frames if (args.full or timed_min_seconds > 0.0 or args.config in ("3", "4")) else max(1, min(n_frames, args.warmup + args.steps))
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # the stream is ray-cast before CUDA exists in this process (the generator forks); only rank 0 owns frames
-    st, frames = gen_frames(cfg, n_frames, args.gen_workers, args.frame_cache or None) if rank == 0 else (None, None)
-    # N > 1 on the metric's config: the north star's multi-GPU scene (configs[3], 8 objects sharded by model) is timed in the same run,
-    # beside the weak-scaling line whose per-N values the driver compares
-    with_scene = (world > 1 or args.force_sharded_scene) and args.config == "1" and not args.no_sharded_scene
+    st, frames_job = gen_frames(cfg, n_render, args.gen_workers, args.frame_cache or None, later=True) if rank == 0 else (None, lambda: None)
+    # N > 1 on the metric's config (--full): the north star's multi-GPU scene (configs[3], 8 objects sharded by model) is timed in the same
+    # run, beside the weak-scaling line whose per-N values the driver compares
+    with_scene = ((world > 1 and args.full) or args.force_sharded_scene) and args.config == "1" and not args.no_sharded_scene
     st3, frames3 = gen_frames(CONFIGS["3"], CONFIGS["3"]["frames"], args.gen_workers) if (with_scene and rank == 0) else (None, None)
     # the dense configs[4] scenario rides along as a variant of the default line (and is --config 4's own line): its frames are ray-cast and
     # its background map generated (a forked child) before CUDA exists in this process
-    with_c4 = rank == 0 and world == 1 and ((args.config == "1" and not args.no_variants and args.icp_weight >= 100.0 and not args.so3) or args.config == "4")
+    with_c4 = rank == 0 and world == 1 and ((args.config == "1" and args.full and not args.no_variants and args.icp_weight >= 100.0 and not args.so3)
+                                            or args.config == "4")
     frames4 = room_job = frames2s = frames4n = None
+    if with_scene or with_c4:
+        frames_job()         # the other streams are ray-cast after this one (their workers would compete for the same cores)
     if with_c4:
         room_job = RoomMapJob(4, fork=args.gen_workers != 1)
-        frames4 = frames if args.config == "4" else gen_frames(CONFIGS["4"], C4_LEAD_IN + 12, args.gen_workers, args.frame_cache or None)[1]
+        frames4 = frames_job() if args.config == "4" else gen_frames(CONFIGS["4"], C4_LEAD_IN + 12, args.gen_workers, args.frame_cache or None)[1]
         if args.config == "1":   # the two small variants of the default line
             frames2s = gen_frames(CONFIGS["2s"], 60, args.gen_workers, args.frame_cache or None)[1]
             frames4n = gen_frames(CONFIGS["4n"], 40, args.gen_workers, args.frame_cache or None)[1]
     if args.config == "4":
         if world > 1:
             raise SystemExit("--config 4 is a one-GPU scenario (configs[4]'s per-GPU share); run it with --gpus 1")
-        return run_config4(args, local_rank, frames4, room_job)
+        return run_config4(args, local_rank, frames4, room_job, side_seconds)
     if args.config == "3":
         if args.steps == 600:
             args.steps = 120
-        return run_sharded(args, cfg, rank, local_rank, world, st, frames)
+        return run_sharded(args, cfg, rank, local_rank, world, st, frames_job(), timed_min_seconds)
 
     import torch
     dist = None
@@ -756,6 +833,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (there is no CPU path); cpu_baseline is only a side measurement")
     dev = torch.device("cuda", local_rank)
+    torch.zeros(1, device=dev)     # the device is initialised while the forked workers still ray-cast
+    frames = frames_job()
 
     from maskfusion_amd import MaskFusion
     d_rgb = d_depth = d_mask = None
@@ -831,9 +910,11 @@ def main():
         dt = mfd.max_over_ranks(time.perf_counter() - t0, dev)
         total_steps += args.steps
         total_dt += dt
-        if total_dt >= args.min_seconds or reps >= args.max_reps:   # (max_reps: a runaway guard only -- 100 000 by default)
+        if total_dt >= timed_min_seconds or reps >= args.max_reps:   # (max_reps: a runaway guard only -- 100 000 by default)
             break
     fps = world * total_steps / total_dt
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(mf, args.dump_outputs, multi)
 
     n_models = len(mf.getModels())
     count = sum(m.lastCount() for m in mf.getModels())
@@ -846,7 +927,7 @@ def main():
 
     roofline = roofline_frame = None
     P = W * H
-    if rank == 0 and not args.no_roofline and args.icp_weight >= 100.0:
+    if rank == 0 and args.full and not args.no_roofline and args.icp_weight >= 100.0:
         # instrumented pass over the same stream: per-stage HIP events on the library's own stream
         mf.enableTimings(True)
         acc = {}
@@ -903,7 +984,7 @@ def main():
                           "note": "(741 P per tracked model + 192 N) bytes per frame, SURVEY.md 8d; N = live surfels of all models"}
 
     host_input = None
-    if rank == 0 and world == 1 and not args.no_host_input:
+    if rank == 0 and world == 1 and args.full and not args.no_host_input:
         # the reference's own boundary: FrameData in host memory (MaskFusion.cpp:212-216 uploads it every frame)
         n = args.host_input_frames
         ks = [order[(cursor[0] + i) % len(order)] for i in range(n)]
@@ -933,11 +1014,11 @@ def main():
                               "(rounds 1-3: one hipStreamSynchronize per frame)"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not multi:   # rank 0 at N = 1 only (the other ranks would sit in a collective)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not multi:   # rank 0 at N = 1 only (the other ranks would sit in a collective)
         cpu = cpu_baseline(cfg, frames)
 
     variants = None
-    if rank == 0 and world == 1 and args.config == "1" and not args.no_variants and args.icp_weight >= 100.0 and not args.so3:
+    if rank == 0 and world == 1 and args.config == "1" and args.full and not args.no_variants and args.icp_weight >= 100.0 and not args.so3:
         try:
             variants = {"reference_default": reference_default_variant(cfg, local_rank, d_rgb, d_depth, order)}
         except Exception as e:   # a side measurement: never the reason the bench line is missing
@@ -970,10 +1051,10 @@ def main():
     scene = None
     if with_scene:
         mf.close()   # the weak-scaling contexts are done: the scene gets the GPUs to itself
-        scene = sharded_scene(args, CONFIGS["3"], rank, local_rank, world, st3, frames3, steps=120, min_seconds=min(args.min_seconds, 2.0))
+        scene = sharded_scene(args, CONFIGS["3"], rank, local_rank, world, st3, frames3, steps=120, min_seconds=min(side_seconds, 2.0))
         if rank == 0:
             try:
-                ref = single_context_scene(args, CONFIGS["3"], local_rank, st3, frames3, steps=60, min_seconds=min(args.min_seconds, 1.0))
+                ref = single_context_scene(args, CONFIGS["3"], local_rank, st3, frames3, steps=60, min_seconds=min(side_seconds, 1.0))
             except Exception as e:   # the reference figure must not cost the other ranks (waiting at the barrier below) their run
                 ref = {"value": float("nan"), "error": repr(e)}
             scene = {"frames_per_s": scene["value"], "ms_per_frame": scene["ms_per_step"], "n_gpus": world, "scaling": "strong",
@@ -991,7 +1072,7 @@ def main():
             "value": fps, "unit": "frames/s", "n_gpus": world, "steps": total_steps, "steps_requested": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * total_dt / total_steps, "timed_seconds": total_dt, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": cfg["workload"] + variant, "frames_in_hbm": n_frames, "models": n_models, "surfels": count,
+            "config": {"workload": cfg["workload"] + variant, "frames_in_hbm": len(frames) if frames is not None else n_frames, "models": n_models, "surfels": count,
                        "pose_drift_vs_gt_m": drift, "parallelism": f"context-per-gpu x{world}",
                        **({"params": extra_params} if extra_params else {})},
             "roofline": roofline, "roofline_frame": roofline_frame, "host_input": host_input, "cpu_baseline": cpu, "variants": variants,
