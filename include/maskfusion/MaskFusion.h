@@ -338,6 +338,25 @@ public:
     void savePly() { check(mf_save_ply(ctx_, exportDir_.c_str())); }          // MaskFusion.h:282
     void exportPoses() { check(mf_export_poses(ctx_, exportDir_.c_str())); }  // MaskFusion.h:284
 
+    // Headless rendering of the maps (no upstream twin: what Model::renderPointCloud draws for MainController::drawScene, mf_render_view in
+    // maskfusion_amd.h).  Non-virtual and inline: a program that never renders needs no render symbol of the library.
+    mf_render_view_t defaultRenderView(int width, int height, bool icl = false) {
+        mf_render_view_t v;
+        check(mf_default_render_view(ctx_, width, height, icl ? 1 : 0, &v));
+        return v;
+    }
+    // rgba: H*W*4 bytes; depth / model (optional): camera z (0: nothing drawn) / model list index (-1: none) per pixel; palette: RGB triples
+    // for colour type 4 (empty: the library's palette)
+    void renderView(const mf_render_view_t& view, std::vector<uint8_t>& rgba, std::vector<float>* depth = nullptr, std::vector<int32_t>* model = nullptr,
+                    const std::vector<float>& palette = std::vector<float>()) {
+        const size_t n = (size_t)(view.width > 0 ? view.width : 0) * (size_t)(view.height > 0 ? view.height : 0);
+        rgba.resize(n * 4);
+        if (depth) depth->resize(n);
+        if (model) model->resize(n);
+        check(mf_render_view(ctx_, &view, palette.empty() ? nullptr : palette.data(), (int32_t)(palette.size() / 3), rgba.data(),
+                             depth ? depth->data() : nullptr, model ? model->data() : nullptr));
+    }
+
     ModelPointer getBackgroundModel() { return models_.front(); }  // MaskFusion.h:88
     ModelList& getModels() { return models_; }                     // MaskFusion.h:90
     Matrix4f getCurrPose() { return getBackgroundModel()->getPose(); }  // MaskFusion.h:218

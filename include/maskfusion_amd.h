@@ -157,6 +157,41 @@ int mf_download_segmentation(mf_ctx* ctx, uint8_t* out);
 int mf_export_segmentation_png(mf_ctx* ctx, const char* path);
 /* The cv::imwrite(<name>.png, CV_8UC1) of that branch on its own: H*W bytes -> 8-bit greyscale PNG.  HOST pointer, no GPU involved. */
 int mf_write_png_gray8(const char* path, const uint8_t* img, int32_t width, int32_t height);
+/* Headless rendering of the surfel maps (Model::renderPointCloud as MainController::drawScene calls it, Core/Model/Model.cpp:287-346,
+ * GUI/MainController.cpp:609-720): every drawn surfel is the disc of radius nr.w around its position, in the plane normal to nr.xyz, seen
+ * from a virtual pinhole camera; a pixel is covered where the ray through its centre meets the disc, the smaller camera z wins (ties: the
+ * surfel drawn first -- the background, then the objects in list order, buffer order within a model).  Vertex test: confidence above the
+ * model's threshold, or draw_unstable.  Colour types (MainController.h:38): 1 normals, 2 colour, 3 times (also unstable surfels unless the
+ * type is 1 or 2), 4 labels (palette[classID mod n] x max(|n.(1,1,1)|, 0.8); the background in grey), anything else grey; draw_window
+ * darkens surfels not seen within timeDelta by 0.25; channels are round(clamp(c, 0, 1) 255).  draw_points: a confident surfel covers the
+ * pixel its centre projects into (types 1, 2, else grey).  DESIGN.md "Rendering" has the whole restatement and the deviations.
+ * The render reads the models and changes nothing (no compaction, run table, bounding box, timing slot or visibility cache). */
+typedef struct mf_render_view_t {
+    int32_t width, height;                      /* 1 .. 4096 each */
+    float fx, fy, cx, cy;
+    float near_z, far_z;                        /* fragments outside [near_z, far_z] of camera z are dropped; 0 < near_z < far_z */
+    float pose16[16];                           /* camera -> world, column-major (mf_get_pose's layout); camera x right, y down, z forward */
+    int32_t background_color_type, object_color_type;
+    int32_t draw_unstable, draw_points, draw_window, draw_background, draw_objects;
+    uint8_t clear_rgba[4];                      /* pixels no surfel covers (the GUI clears to white) */
+    uint64_t model_mask;                        /* 0: every model draw_background / draw_objects allow; else bit i = model list index i (< 64) */
+    int32_t reserved[8];                        /* zero */
+} mf_render_view_t;
+/* The GUI's follow-pose view (MainController.cpp:610-640, GUI.h:73,198-211): the current camera pose moved 0.2 m back along its optical
+ * axis, fx = fy = 420, the principal point at the image centre, near 0.1, far 1000, colour types 2, the background and the objects drawn,
+ * cleared to white.  icl != 0 rolls the view by 180 degrees about its axis (upstream's up vector for ICL-NUIM). */
+int mf_default_render_view(mf_ctx* ctx, int32_t width, int32_t height, int32_t icl, mf_render_view_t* out);
+/* The library's own label palette: n = min(capacity, 64) RGB triples in [0, 1] -> out (out may be NULL to query *n = 64). */
+int mf_default_palette(float* out_rgb, int32_t capacity, int32_t* n);
+/* Renders `view` into out_rgba (H*W*4 bytes, row-major; HOST pointer), optionally the camera z of every pixel (0 where nothing is drawn) and
+ * the model list index that drew it (-1: none).  palette: n_palette RGB triples for colour type 4 (class ids index it modulo n_palette;
+ * palette NULL with n_palette 0: the library's palette).  MF_EINVAL (mf_last_error says why) for a bad size, a null output, a model mask
+ * naming a model that does not exist, an empty palette with type 4.  Synchronous. */
+int mf_render_view(mf_ctx* ctx, const mf_render_view_t* view, const float* palette, int32_t n_palette, uint8_t* out_rgba,
+                   float* out_depth, int32_t* out_model);
+/* The same with DEVICE outputs, enqueued on mf_get_stream(ctx) without waiting. */
+int mf_render_view_dev(mf_ctx* ctx, const mf_render_view_t* view, const float* palette, int32_t n_palette, uint8_t* d_out_rgba,
+                       float* d_out_depth, int32_t* d_out_model);
 /* whether the last tracking step used the fill-in maps (MaskFusion::requiresFillIn, MaskFusion.cpp:630-648) */
 int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import numpy as np
 
-from .lib import load, MFError, Config, ModelInfo, MF_N_TIMINGS, TIMING_LABELS, MF_N_PASSES, PASS_LABELS
+from .lib import load, MFError, Config, ModelInfo, RenderView, MF_N_TIMINGS, TIMING_LABELS, MF_N_PASSES, PASS_LABELS
 
 
 class Model:
@@ -354,6 +354,59 @@ class MaskFusion:
         return int(self._L.mf_get_input_stream(self._h) or 0)
 
     # -- differential-test taps ----------------------------------------------------------------------
+    # -- headless rendering (Model::renderPointCloud as MainController::drawScene draws the models; include/maskfusion_amd.h) ----------
+    def defaultRenderView(self, width: int = 1280, height: int = 980, icl: bool = False) -> RenderView:
+        """The GUI's follow-pose view: the current camera 0.2 m back along its axis, fx = fy = 420, centred principal point, near 0.1, far 1000"""
+        v = RenderView()
+        self._chk(self._L.mf_default_render_view(self._h, int(width), int(height), int(bool(icl)), C.byref(v)))
+        return v
+
+    @staticmethod
+    def defaultPalette() -> np.ndarray:
+        """the library's own label palette, (n, 3) float32 RGB in [0, 1] (class ids index it modulo n)"""
+        L, n = load(), C.c_int32(0)
+        if L.mf_default_palette(None, 0, C.byref(n)) != 0:
+            raise MFError("mf_default_palette failed")
+        out = np.zeros((n.value, 3), np.float32)
+        if L.mf_default_palette(out.ctypes.data, n.value, C.byref(n)) != 0:
+            raise MFError("mf_default_palette failed")
+        return out
+
+    def renderView(self, view: RenderView | None = None, palette=None, depth: bool = False, models: bool = False):
+        """Renders the maps from `view` (default: defaultRenderView()).  Returns the (H, W, 4) uint8 image, plus the (H, W) float32 camera z
+        (0: nothing drawn) with depth=True and the (H, W) int32 model list index (-1: none) with models=True, in that order.
+        palette: (n, 3) RGB for colour type 4 (None: the library's palette)."""
+        if view is None:
+            view = self.defaultRenderView()
+        H, W = int(view.height), int(view.width)
+        rgba = np.zeros((max(H, 1), max(W, 1), 4), np.uint8)
+        dep = np.zeros((max(H, 1), max(W, 1)), np.float32) if depth else None
+        mod = np.zeros((max(H, 1), max(W, 1)), np.int32) if models else None
+        if palette is None:
+            pal_ptr, n_pal = None, 0
+        else:
+            pal = np.ascontiguousarray(np.asarray(palette, np.float32).reshape(-1, 3))
+            n_pal = len(pal)
+            if n_pal == 0:
+                pal = np.zeros((1, 3), np.float32)   # an empty palette: a valid pointer with n = 0 (the library refuses it for colour type 4)
+            pal_ptr = pal.ctypes.data
+        self._chk(self._L.mf_render_view(self._h, C.byref(view), pal_ptr, n_pal, rgba.ctypes.data,
+                                         dep.ctypes.data if dep is not None else None, mod.ctypes.data if mod is not None else None))
+        out = [rgba]
+        if depth:
+            out.append(dep)
+        if models:
+            out.append(mod)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def renderViewDevice(self, view: RenderView, d_rgba: int, d_depth: int = 0, d_model: int = 0, palette=None):
+        """mf_render_view_dev: device outputs (raw pointers), enqueued on stream() without waiting"""
+        pal_ptr, n_pal, keep = None, 0, None
+        if palette is not None:
+            keep = np.ascontiguousarray(np.asarray(palette, np.float32).reshape(-1, 3))
+            pal_ptr, n_pal = keep.ctypes.data, len(keep)
+        self._chk(self._L.mf_render_view_dev(self._h, C.byref(view), pal_ptr, n_pal, d_rgba, d_depth or None, d_model or None))
+
     def debugRead(self, what: str, model: int = 0, count: int | None = None) -> np.ndarray:
         """count: number of records for the variable-length taps (cand_op, cand_rec, clean_flags, clean_newconf)"""
         W, H = self.width, self.height

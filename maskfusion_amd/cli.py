@@ -3,8 +3,11 @@
     python -m maskfusion_amd.cli -l log.klg -run -q -ep -em -exportdir out/
     python -m maskfusion_amd.cli -dir seq/ -maskdir seq/masks/ -tum3 -run -q -ep
 
-Flags keep their upstream names and meaning; GUI-only flags (-sc, -ev, -el, -en, -es, -run, -q ...) are accepted and ignored
-(this driver always runs to the end of the log and quits).  Parameter defaults are the ones the GUI pushes into the core
+Flags keep their upstream names and meaning; GUI-only flags (-sc, -run, -q ...) are accepted and ignored (this driver always runs to
+the end of the log and quits).  -el / -en / -ev write what the GUI's export branch saves after every frame (MainController.cpp:468-481), rendered
+headless (MaskFusion.renderView) from the GUI's follow-pose view at 1280 x 980 -- the GUI window without its panel: Labels<tick>.png (the
+background in colour, the objects in label colours, the library's palette), Normals<tick>.png (both in normals) and Viewport<tick>.png (both in
+colour, the GUI defaults), <tick> being the frame just processed (upstream's getTick() - 1); -icl rolls that view by 180 degrees.  Parameter defaults are the ones the GUI pushes into the core
 every frame (GUI/Tools/GUI.h:188-196,342-347,367-374; MainController.cpp:215-228,528-571): depth cutoff 4 m, ICP
 weight 20, outlier coefficient 0.1, confidence 10 / 0.01, spawn offset 22, open loop, trackAllModels OFF, MfSegmentation
 threshold 0.3 / weights 150, 2.8 / morphology 0x1, 0x2, new-model size 0.015 .. 0.4.  The frame queue (-frameQ, default 30) is
@@ -118,6 +121,24 @@ def open_reader(flags, st):
     raise SystemExit("no input: use -l <file.klg> or -dir <directory>")
 
 
+RENDER_W, RENDER_H = 1280, 980      # GUI/Tools/GUI.h:73: the window is 1280 + panel wide, 980 high; the panel is not part of the render
+_RENDER_EXPORTS = (("-el", "Labels", 2, 4), ("-en", "Normals", 1, 1), ("-ev", "Viewport", 2, 2))   # flag, file name, background / object type
+
+
+def export_renders(mf, flags, export_dir):
+    """the -el / -en / -ev branch of the GUI's frame loop (MainController.cpp:468-481) after the frame just processed"""
+    wanted = [e for e in _RENDER_EXPORTS if e[0] in flags]
+    if not wanted:
+        return
+    from PIL import Image
+    tick = mf.getTick() - 1
+    for _, name, bg, obj in wanted:
+        v = mf.defaultRenderView(RENDER_W, RENDER_H, icl="-icl" in flags)
+        v.background_color_type, v.object_color_type = bg, obj
+        rgba = mf.renderView(v)
+        Image.fromarray(np.ascontiguousarray(rgba[:, :, :3]), "RGB").save(os.path.join(export_dir, f"{name}{tick}.png"))
+
+
 def main(argv=None):
     flags = parse(sys.argv[1:] if argv is None else argv)
     st = settings(flags)
@@ -153,6 +174,7 @@ def main(argv=None):
         mf.processFrame(frame.rgb, frame.depth, mask=frame.mask, timestamp=int(frame.timestamp), classIDs=tuple(frame.classIDs))
         if st["exportSegmentation"] and st["multi"] and tick > 1:   # MaskFusion.cpp:299-303
             mf.exportSegmentation(os.path.join(export_dir, f"Segmentation{tick}.png"))
+        export_renders(mf, flags, export_dir)
         n += 1
     dt = time.time() - t0
     models = mf.getModels()

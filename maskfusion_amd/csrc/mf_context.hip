@@ -10,6 +10,8 @@
 
 #include <float.h>
 #include <math.h>
+#include <algorithm>
+#include <cmath>
 #include <stdio.h>
 #include <string.h>
 #include <memory>
@@ -133,6 +135,9 @@ struct LabelsScratch {
 };
 
 }  // namespace
+
+struct RenderScratch;                          // mf_render.inl: the headless render's scratch, allocated on its first call
+static void render_free(RenderScratch* r);
 
 struct mf_ctx {
     mf_config cfg;
@@ -291,6 +296,7 @@ struct mf_ctx {
     float last_ms[MF_N_TIMINGS] = {};
     std::vector<void*> allocs;
     std::vector<void*> host_allocs;
+    RenderScratch* render = nullptr;
 };
 
 #define MF_HIP(ctx, call)                                                                         \
@@ -627,6 +633,7 @@ extern "C" void mf_destroy(mf_ctx* c) {
     if (!c) return;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->models.clear();
+    if (c->render) render_free(c->render);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->d_splat_prof) (void)hipFree(c->d_splat_prof);
     for (void* p : c->host_allocs) (void)hipHostFree(p);
@@ -1227,3 +1234,4 @@ extern "C" int mf_debug_read_model(mf_ctx* c, int32_t model, const char* what, v
 }
 
 #include "mf_ktest.inl"      // kernel-level entry points of the parity tests
+#include "mf_render.inl"     // headless rendering of the maps

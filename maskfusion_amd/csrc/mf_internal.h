@@ -408,6 +408,32 @@ void launch_static_pose(PoseDev* obj, const PoseDev* bg, PoseDev* host_mirror, h
 void launch_override_pose(PoseDev* pose, const float* in_pose16_colmajor, int mode, PoseDev* host_mirror, hipStream_t s);
 void launch_model_state(const PoseDev* pose, const FrameDev* frame, float* out16, hipStream_t s);
 
+// ---------------- headless rendering (mf_render.hip) ----------------
+constexpr int kMaxRenderModels = 256;
+struct RenderModel {                  // one drawn model, in draw order (device array; M is filled by the render's first launch)
+    Surfels s; const FrameDev* frame; const PoseDev* pose;
+    unsigned base;                    // draw index of slot 0: {depth, base + slot} is the z-test key
+    int max_runs;                     // entries of the render's cull grid for this model (runs of its table, or chunks of kRun slots)
+    float thr; int class_id, color_type, index, is_background;
+    float M[12];                      // model -> view, row-major 3 x 4
+};
+struct RenderView { float Vi[12]; };  // world -> view, row-major 3 x 4
+struct RenderArgs {
+    RenderModel* models; int n_models;
+    int W, H; Intr k; float near_z, far_z;
+    int drawUnstable, drawPoints, drawWindow, timeDelta;
+    const FrameDev* tick_frame;       // the background's frame state: `time` of the shaders
+    const float* palette; int n_palette;
+    uchar4 clear;
+    int* work; int* work_count;       // the runs k_render_cull listed: model << 24 | run; their number (zero on entry)
+    int tilesX, tilesY, tile_cap;
+    int* tile_count;                  // [tiles], zero on entry
+    uint2* entries;                   // [tiles][tile_cap] {draw index, tile-local box}
+    int* overflow;                    // set when a tile's list ran over its slice (pinned host memory)
+    uchar4* out_rgba; float* out_depth; int* out_model;
+};
+void launch_render(RenderArgs a, const RenderView& v, const PoseDev* bg_pose, int max_runs, hipStream_t s);
+
 // end-of-frame bookkeeping: tick++, cover -> useFillIn decision for the next frame
 // ... and the pose-log entry of this frame (MaskFusion.cpp:580-596) when log != nullptr
 void launch_pose_log(const PoseDev* pose, const PoseDev* bg_pose /*nullptr: the background itself*/, float* slot, hipStream_t s);

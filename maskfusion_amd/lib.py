@@ -4,6 +4,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmaskfusion_amd.so")
 
@@ -39,6 +41,22 @@ class Config(C.Structure):
                 ("num_osurfels", C.c_int32), ("enable_multiple_models", C.c_int32), ("model_spawn_offset", C.c_int32),
                 ("track_all_models", C.c_int32), ("max_models", C.c_int32), ("rgb_only", C.c_int32),
                 ("pose_log_capacity", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class RenderView(C.Structure):
+    """mf_render_view_t (include/maskfusion_amd.h)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("near_z", C.c_float), ("far_z", C.c_float), ("pose16", C.c_float * 16), ("background_color_type", C.c_int32),
+                ("object_color_type", C.c_int32), ("draw_unstable", C.c_int32), ("draw_points", C.c_int32), ("draw_window", C.c_int32),
+                ("draw_background", C.c_int32), ("draw_objects", C.c_int32), ("clear_rgba", C.c_uint8 * 4), ("model_mask", C.c_uint64),
+                ("reserved", C.c_int32 * 8)]
+
+    def pose(self):
+        """camera -> world as a 4 x 4 float64 array"""
+        return np.array(self.pose16, np.float64).reshape(4, 4).T
+
+    def set_pose(self, T):
+        self.pose16[:] = [float(x) for x in np.asarray(T, np.float64).T.reshape(16)]
 
 
 # every symbol declared in include/maskfusion_amd.h (tests/test_abi.py checks the header against this table)
@@ -138,6 +156,10 @@ SYMBOLS = {
     "mf_k_model_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_int32, C.c_void_p]),
     "mf_k_gn_solve": (C.c_int, [C.c_void_p] * 10 + [C.c_void_p]),
+    "mf_default_render_view": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "mf_default_palette": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "mf_render_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mf_render_view_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_k_icp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                 C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
                                 C.c_int32, C.c_void_p, C.c_void_p]),
