@@ -192,6 +192,25 @@ int mf_render_view(mf_ctx* ctx, const mf_render_view_t* view, const float* palet
 /* The same with DEVICE outputs, enqueued on mf_get_stream(ctx) without waiting. */
 int mf_render_view_dev(mf_ctx* ctx, const mf_render_view_t* view, const float* palette, int32_t n_palette, uint8_t* d_out_rgba,
                        float* d_out_depth, int32_t* d_out_model);
+/* Run evaluation: fixed-radius nearest neighbour from every query point to a target cloud, on the GPU (kernels: mf_eval.hip; DESIGN.md
+ * "Cloud evaluation").  For query i, the target j with the smallest fp32 d2 = dx*dx + dy*dy + dz*dz (d = query - target, evaluated in that
+ * order without contraction) among the finite targets with d2 <= fl(radius * radius); ties go to the smallest j.  d_dist[i] = sqrtf(d2),
+ * d_idx[i] = j; +inf and -1 when no target is in range or the query is not finite.  The result is bit-identical to an fp32 brute force and
+ * the same for every call.  Targets are read as x, y, z at d_target + j * target_stride floats (3: xyz, 4: float4, 12: mf_download_map's
+ * records), queries likewise; query_to_target16 (HOST, column-major 4 x 4, or NULL) maps each query first: x' = ((T00 x + T01 y) + T02 z)
+ * + T03 in fp32.  MF_EINVAL for a radius <= 0 or not finite, a stride < 3, more than 2^30 targets or queries, a null pointer, a workspace smaller
+ * than mf_cloud_nn_workspace says or not 16-byte aligned, a transform that is not finite, and a finite coordinate (target, or query after
+ * the transform) with |x / radius| >= 2^30.  Enqueued on `stream`, which the call synchronises before it returns (to report the last case). */
+int mf_cloud_nn_workspace(int64_t n_target, uint64_t* bytes);   /* device workspace bytes mf_cloud_nn_dev needs for n_target targets */
+int mf_cloud_nn_dev(const float* d_target, int32_t target_stride, int64_t n_target, const float* d_query, int32_t query_stride, int64_t n_query,
+                    const float* query_to_target16, float radius, float* d_dist, int32_t* d_idx, void* d_workspace, uint64_t workspace_bytes,
+                    void* stream);
+/* The same against the live map of `model`, read where it lies: its surfels with confidence > conf_threshold are the targets (the model's own
+ * threshold selects what mf_save_ply writes), and d_idx indexes the array mf_download_map returns for the model.  query_to_model16 (HOST or
+ * NULL) maps the queries into the model's frame.  Runs on mf_get_stream(ctx) with a workspace the context owns and grows on demand; writes
+ * no model state (frames processed afterwards are bit-identical to frames processed without the call).  Synchronous. */
+int mf_model_cloud_nn_dev(mf_ctx* ctx, int32_t model, float conf_threshold, const float* d_query, int32_t query_stride, int64_t n_query,
+                          const float* query_to_model16, float radius, float* d_dist, int32_t* d_idx);
 /* whether the last tracking step used the fill-in maps (MaskFusion::requiresFillIn, MaskFusion.cpp:630-648) */
 int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
 

@@ -407,6 +407,36 @@ class MaskFusion:
             pal_ptr, n_pal = keep.ctypes.data, len(keep)
         self._chk(self._L.mf_render_view_dev(self._h, C.byref(view), pal_ptr, n_pal, d_rgba, d_depth or None, d_model or None))
 
+    # -- run evaluation (include/maskfusion_amd.h: mf_model_cloud_nn_dev) ------------------------------------------------------------
+    def modelCloudNN(self, model: int, points, radius: float, transform=None, confThreshold=None):
+        """Nearest surfel of `model` within `radius` of every point, read from the live map without downloading it.  points: (n, 3 or more)
+        float32, a numpy array or a torch tensor on the library's device; transform: 4 x 4 mapping the points into the model's frame;
+        confThreshold: the surfels taken (confidence > it; None: the model's own threshold, what savePly writes).  Returns (dist, idx) of the
+        kind it was given: dist float32 (+inf: none), idx int32 indexing Model.downloadMap() (-1: none)."""
+        import torch
+        from .lib import torch_device
+        as_numpy = not isinstance(points, torch.Tensor)
+        q = torch.as_tensor(np.ascontiguousarray(points, np.float32)) if as_numpy else points
+        if q.dtype != torch.float32 or q.dim() != 2 or q.shape[1] < 3:
+            raise MFError("modelCloudNN: points must be (n, >= 3) float32")
+        q = q.to(torch_device()).contiguous()
+        n = int(q.shape[0])
+        dist = torch.empty(max(n, 1), dtype=torch.float32, device=q.device)
+        idx = torch.empty(max(n, 1), dtype=torch.int32, device=q.device)
+        thr = Model(self, model).getConfidenceThreshold() if confThreshold is None else float(confThreshold)
+        T = None if transform is None else np.ascontiguousarray(np.asarray(transform, np.float32).T.reshape(16))
+        if q.device.type == "cuda":
+            # the call runs on the context's own (non-blocking) stream: torch's pending work on the queries, and on the memory the caching
+            # allocator handed out for dist / idx, must be done first.  The call waits for its stream before returning, so the outputs are
+            # complete for any stream afterwards.
+            torch.cuda.current_stream(q.device).synchronize()
+        self._chk(self._L.mf_model_cloud_nn_dev(self._h, int(model), thr, q.data_ptr() if n else None, int(q.shape[1]), n,
+                                                T.ctypes.data if T is not None else None, float(radius), dist.data_ptr(), idx.data_ptr()))
+        dist, idx = dist[:n], idx[:n]
+        if as_numpy:
+            return dist.cpu().numpy(), idx.cpu().numpy()
+        return dist, idx
+
     def debugRead(self, what: str, model: int = 0, count: int | None = None) -> np.ndarray:
         """count: number of records for the variable-length taps (cand_op, cand_rec, clean_flags, clean_newconf)"""
         W, H = self.width, self.height

@@ -138,6 +138,8 @@ struct LabelsScratch {
 
 struct RenderScratch;                          // mf_render.inl: the headless render's scratch, allocated on its first call
 static void render_free(RenderScratch* r);
+struct EvalScratch;                            // mf_eval.inl: the model nearest-neighbour query's scratch, allocated on its first call
+static void eval_free(EvalScratch* e);
 
 struct mf_ctx {
     mf_config cfg;
@@ -297,6 +299,7 @@ struct mf_ctx {
     std::vector<void*> allocs;
     std::vector<void*> host_allocs;
     RenderScratch* render = nullptr;
+    EvalScratch* eval = nullptr;
 };
 
 #define MF_HIP(ctx, call)                                                                         \
@@ -634,6 +637,7 @@ extern "C" void mf_destroy(mf_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->models.clear();
     if (c->render) render_free(c->render);
+    if (c->eval) eval_free(c->eval);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->d_splat_prof) (void)hipFree(c->d_splat_prof);
     for (void* p : c->host_allocs) (void)hipHostFree(p);
@@ -1235,3 +1239,4 @@ extern "C" int mf_debug_read_model(mf_ctx* c, int32_t model, const char* what, v
 
 #include "mf_ktest.inl"      // kernel-level entry points of the parity tests
 #include "mf_render.inl"     // headless rendering of the maps
+#include "mf_eval.inl"       // nearest-neighbour queries against a live map

@@ -434,6 +434,17 @@ struct RenderArgs {
 };
 void launch_render(RenderArgs a, const RenderView& v, const PoseDev* bg_pose, int max_runs, hipStream_t s);
 
+// ---------------- run evaluation: fixed-radius nearest neighbour (mf_eval.hip) ----------------
+uint64_t nn_workspace_bytes(int64_t n_target);
+// the whole of mf_cloud_nn_dev (include/maskfusion_amd.h): grid build + query on stream s, then a synchronisation of s; *why: the reason of an error
+int nn_run(const float* d_target, int target_stride, int64_t n_target, const float* d_query, int query_stride, int64_t n_query,
+           const float* T16 /*host, column-major, or null*/, float radius, float* d_dist, int32_t* d_idx, void* d_ws, uint64_t ws_bytes, hipStream_t s,
+           const char** why);
+// a model's live surfels in download order: offs[r] = surfels before run r, *total = all of them (launch_nn_live), then their positions -> out[n]
+// (NaN for confidence <= thr; launch_nn_gather).  offs: run_table_runs() + 1 ints
+void launch_nn_live(Surfels s, const FrameDev* frame, int* offs, int* total, hipStream_t st);
+void launch_nn_gather(Surfels s, const FrameDev* frame, const int* offs, float thr, float4* out, int n, int max_runs, hipStream_t st);
+
 // end-of-frame bookkeeping: tick++, cover -> useFillIn decision for the next frame
 // ... and the pose-log entry of this frame (MaskFusion.cpp:580-596) when log != nullptr
 void launch_pose_log(const PoseDev* pose, const PoseDev* bg_pose /*nullptr: the background itself*/, float* slot, hipStream_t s);

@@ -160,12 +160,24 @@ SYMBOLS = {
     "mf_default_palette": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "mf_render_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_render_view_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mf_cloud_nn_workspace": (C.c_int, [C.c_int64, C.POINTER(C.c_uint64)]),
+    "mf_cloud_nn_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mf_model_cloud_nn_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_float,
+                                        C.c_void_p, C.c_void_p]),
     "mf_k_icp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                 C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
                                 C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
+
+
+def torch_device() -> str:
+    """Where the loaded library's device memory lives, as a torch device type: "cuda" for the HIP build; "cpu" for a build of the same
+    C ABI whose kernels execute on the host (the test suite's), where device pointers are host pointers."""
+    L = load()
+    return "cuda" if os.path.abspath(getattr(L, "_name", LIB_PATH)) == os.path.abspath(LIB_PATH) else "cpu"
 
 
 def load():

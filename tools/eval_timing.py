@@ -1,0 +1,121 @@
+"""Times the run evaluation's nearest-neighbour kernels (mf_cloud_nn_dev, mf_model_cloud_nn_dev; maskfusion_amd/csrc/mf_eval.hip) at configs[4]
+size: a dense room map of 26.9 M points (synth.dense_room_map, the background of stress.make_context's scenario) as the targets, 5 M queries
+sampled from it and jittered by N(0, 5 mm) per axis, radius 5 cm.
+
+  grid build   mf_cloud_nn_dev with no queries (count, scan, scatter)
+  query        the same call with the queries, minus the build
+  live model   mf_model_cloud_nn_dev against the same map uploaded into a stress.make_context context (gather + build + query)
+
+Device times are medians of 10 calls after 2 warm-up calls, between HIP events on the call's stream.  One CPU line for contrast:
+scipy.spatial.cKDTree with 16 workers on the same clouds (tree build + query), if scipy is present.
+
+    python tools/eval_timing.py [--targets 26.9e6] [--queries 5e6] [--radius 0.05] [--no-cpu]
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _median_ms(fn, stream, reps=10, warm=2):
+    import torch
+    for _ in range(warm):
+        fn()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        fn()
+        b.record(stream)
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return float(np.median(out)), float(min(out)), float(max(out))
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--targets", type=float, default=26.9e6)
+    ap.add_argument("--queries", type=float, default=5e6)
+    ap.add_argument("--radius", type=float, default=0.05)
+    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-live", action="store_true")
+    a = ap.parse_args(argv)
+    import torch
+    from maskfusion_amd import stress, synth
+    from maskfusion_amd.lib import load
+    L = load()
+    t0 = time.perf_counter()
+    st = stress.stream()
+    room = synth.dense_room_map(st.scene, int(a.targets), last_time=1.0, furniture_above=st.masked_objects)
+    rng = np.random.default_rng(0)
+    nq = int(a.queries)
+    xyz = np.ascontiguousarray(room[:, :3])
+    q = (xyz[rng.integers(0, len(xyz), nq)] + rng.normal(scale=0.005, size=(nq, 3))).astype(np.float32)
+    print(f"clouds: {len(xyz)} targets, {nq} queries, radius {a.radius} m (generated in {time.perf_counter() - t0:.1f} s)")
+    dt, dq = torch.from_numpy(xyz).cuda(), torch.from_numpy(q).cuda()
+    need = C.c_uint64(0)
+    assert L.mf_cloud_nn_workspace(len(xyz), C.byref(need)) == 0
+    ws = torch.empty(int(need.value), dtype=torch.uint8, device="cuda")
+    dist = torch.empty(nq, dtype=torch.float32, device="cuda")
+    idx = torch.empty(nq, dtype=torch.int32, device="cuda")
+    s = torch.cuda.current_stream()
+
+    def call(n_query):
+        rc = L.mf_cloud_nn_dev(dt.data_ptr(), 3, len(xyz), dq.data_ptr(), 3, n_query, None, a.radius, dist.data_ptr(), idx.data_ptr(),
+                               ws.data_ptr(), int(need.value), s.cuda_stream)
+        assert rc == 0, rc
+    build = _median_ms(lambda: call(0), s)
+    full = _median_ms(lambda: call(nq), s)
+    hits = (idx >= 0).float().mean().item()
+    N, B = len(xyz), 64
+    while B < 2 * N:
+        B <<= 1
+    # algorithmic bytes: build = targets read twice (count, scatter) + rank written / read + records written + bucket array memset, counted,
+    # scanned (read twice, written once); query = queries read + outputs written + the grid's start pairs (the bucket scans hit cached lines)
+    b_build = N * 12 * 2 + N * 4 * 2 + N * 16 + (B + 1) * 4 * 4
+    print(f"workspace: {need.value / 2**20:.0f} MiB ({B} buckets)")
+    print(f"grid build : median {build[0]:.2f} ms (min {build[1]:.2f}, max {build[2]:.2f}); algorithmic bytes {b_build / 1e9:.2f} GB "
+          f"-> {b_build / build[0] / 1e6:.0f} GB/s")
+    qm = full[0] - build[0]
+    print(f"query      : median {qm:.2f} ms (build + query {full[0]:.2f} ms, min {full[1]:.2f}, max {full[2]:.2f}); "
+          f"{nq / qm / 1e3:.0f} M queries/s; hits {hits:.4f}")
+    print(f"build + query on {N / 1e6:.1f} M targets x {nq / 1e6:.1f} M queries: {full[0]:.2f} ms (target < 1000 ms)")
+    if not a.no_live:
+        mf = stress.make_context()
+        rgb, depth, mask = st.frame(0)
+        mf.processFrame(rgb, depth, mask=mask, timestamp=0)
+        mf.getBackgroundModel().uploadMap(room)
+        mf.sync()
+        live = _median_ms(lambda: mf.modelCloudNN(0, dq, a.radius), s)
+        d2, i2 = mf.modelCloudNN(0, dq, a.radius)
+        same = bool(torch.equal(d2, dist)) and bool(torch.equal(i2, idx))
+        print(f"live model : median {live[0]:.2f} ms (min {live[1]:.2f}, max {live[2]:.2f}) for {mf.getBackgroundModel().lastCount()} surfels "
+              f"(gather + build + query + host waits); same result as the plain call: {same}")
+        mf.close()
+    if not a.no_cpu:
+        try:
+            from scipy.spatial import cKDTree
+        except ImportError:
+            print("cpu        : scipy not present, skipped")
+            return 0
+        t0 = time.perf_counter()
+        tree = cKDTree(xyz)
+        t1 = time.perf_counter()
+        kd, _ = tree.query(q, k=1, distance_upper_bound=a.radius, workers=16)
+        t2 = time.perf_counter()
+        gd = dist.cpu().numpy()
+        both = np.isfinite(kd) & np.isfinite(gd)
+        print(f"cpu        : scipy.spatial.cKDTree (16 workers, CPU): build {1e3 * (t1 - t0):.0f} ms + query {1e3 * (t2 - t1):.0f} ms = "
+              f"{1e3 * (t2 - t0):.0f} ms; max |d_gpu - d_cpu| over common hits {np.abs(gd[both] - kd[both]).max():.2e} m")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
