@@ -240,7 +240,7 @@ int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
  * sparse buffer is compacted every n frames whatever the host's bounds say -- a test switch; by default only when the slots behind the last run or
  * the table entries could run out, before a download, before a model returns to the small-map forms); read-only: "densifyCount" (compactions so
  * far), "cleanRuns" / "visibleRuns" / "backgroundRuns" (runs the last in-place clean visited / on the last visibility list / of the
- * background's table),
+ * background's table), "unstampedRuns" (live runs of that table that hold a surfel with lastTime <= 0: the in-place clean visits them every frame),
  * "literalFusionWeight" (1: Model::computeFusionWeight's log map takes cos(theta) from the float trace of a float matrix as the reference's
  * text does -- its rotation term is then quantised in steps of ~4.9e-4 rad; 0: the same formula evaluated accurately in double.  See
  * DESIGN.md, finding F5; default 1 since round 3), "frameToFrameRGB" (0; MaskFusion::setFrameToFrameRGB, "-ftf": the photometric term tracks

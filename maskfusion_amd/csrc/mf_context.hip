@@ -1081,8 +1081,12 @@ extern "C" int mf_set_param(mf_ctx* c, const char* key, double value) {
     if (!strcmp(key, "fusedRgbPyramid")) { c->fused_rgb_pyramid = value != 0; return MF_OK; }
     if (!strcmp(key, "inPlaceElements")) { c->in_place_elements = (int)value; return MF_OK; }
     if (!strcmp(key, "rebuildRunTable")) {   // tooling: the background's run table from scratch (what an upload / Model::initialise does)
-        launch_run_table(c->models[0]->surf[c->models[0]->cur], c->models[0]->d_frame, c->stream);
-        c->vis_tag.model = nullptr;
+        // fixed runs over slots [0, count) describe a DENSE buffer only: a sparse one is compacted first, and the host's bounds start afresh
+        ModelState& bg = *c->models[0];
+        require_dense(c, bg);
+        MF_HIP(c, hipStreamSynchronize(c->stream));   // (the exact count: the pinned mirror as of the last clean pass / the compaction)
+        launch_run_table(bg.surf[bg.cur], bg.d_frame, c->stream);
+        fresh_table(c, bg, (long)*bg.h_count);
         return check_launch(c);
     }
     if (!strcmp(key, "cleanLiteralWindow")) { c->clean_literal = value != 0; return MF_OK; }   // 0: the exact-arithmetic 4 x 4 window
@@ -1115,6 +1119,19 @@ extern "C" int mf_get_param(mf_ctx* c, const char* key, double* value) {
     if (!strcmp(key, "splatTileEntries")) { *value = c->tile_entries_cap; return MF_OK; }
     if (!strcmp(key, "cullRuns")) { *value = c->cull_runs ? 1 : 0; return MF_OK; }
     if (!strcmp(key, "densifyCount")) { *value = (float)c->densify_count; return MF_OK; }
+    if (!strcmp(key, "unstampedRuns")) {   // test tap: live runs of the background's table that carry "holds a time stamp <= 0" (k_cull_clean lists them)
+        MF_HIP(c, hipStreamSynchronize(c->stream));
+        ModelState& bg = *c->models[0];
+        FrameDev f; MF_HIP(c, hipMemcpy(&f, bg.d_frame, sizeof(FrameDev), hipMemcpyDeviceToHost));
+        const size_t cap_runs = run_table_runs((long)bg.cap, (long)c->P);
+        const size_t runs = bg.table_valid ? std::min((size_t)std::max(f.runs, 0), cap_runs) : 0;
+        std::vector<int4> box(kBoxStride * runs);
+        if (runs) MF_HIP(c, hipMemcpy(box.data(), bg.surf[bg.cur].box, box.size() * sizeof(int4), hipMemcpyDeviceToHost));
+        int v = 0;
+        for (size_t r = 0; r < runs; ++r) v += (box[kBoxStride * r + 2].x > 0 && box[kBoxStride * r + 2].z != 0) ? 1 : 0;
+        *value = v;
+        return MF_OK;
+    }
     if (!strcmp(key, "visibleRuns") || !strcmp(key, "backgroundRuns") || !strcmp(key, "cleanRuns")) {   // test taps: size of the last visibility list / of the
         MF_HIP(c, hipStreamSynchronize(c->stream));                                                      // background's run table / of the last clean list
         int v = 0;

@@ -272,10 +272,10 @@ static void require_dense(mf_ctx* c, ModelState& m) { if (m.sparse) densify(c, m
 static int prepare_in_place(mf_ctx* c, ModelState& m, bool& ok) {
     const long cm = cand_max(c), nr = new_runs_max(c), table = (long)run_table_runs((long)m.cap, (long)c->P);
     ok = true;
-    if (c->densify_every > 0 && m.sparse && (c->frame_no % c->densify_every) == 0) densify(c, m);   // ("densifyEvery": tests)
+    const bool every = c->densify_every > 0 && m.sparse && (c->frame_no % c->densify_every) == 0;   // ("densifyEvery": tests)
     // The host's own bounds grow by a frame's worth of CANDIDATES per pass, the buffer by the few that survive.  The device leaves where the buffer
     // really ended behind every pass in pinned memory (append_mirror): bounds from the newest pass that has run are P / 4 per pass still in flight.
-    long pub = m.phys_ub, rub = m.runs_ub;
+    long pub = every ? -1 : m.phys_ub, rub = every ? -1 : m.runs_ub;
     if (pub >= 0) {
         const unsigned long long v = *(volatile unsigned long long*)m.h_append;
         const unsigned mask = (1u << kAppendSeqBits) - 1u, seq = (unsigned)(v >> (kAppendRunBits + kAppendPhysBits)) & mask;
@@ -285,8 +285,11 @@ static int prepare_in_place(mf_ctx* c, ModelState& m, bool& ok) {
             rub = std::min(rub, (long)((v >> kAppendPhysBits) & ((1ull << kAppendRunBits) - 1ull)) + (long)behind * nr);
         }
     }
-    PassTimer timer(c, (m.sparse || !m.table_valid) ? MF_PASS_COMPACTION : -1);
-    if (pub < 0 || pub + cm > (long)m.cap || rub + nr > table) {
+    const bool out_of_room = pub < 0 || pub + cm > (long)m.cap || rub + nr > table;
+    // "compaction" = launch_densify and / or a fresh run table: timed only in a frame that launches one of them (it reads 0 otherwise)
+    PassTimer timer(c, ((out_of_room && m.sparse) || !m.table_valid) ? MF_PASS_COMPACTION : -1);
+    if (every) densify(c, m);
+    if (out_of_room) {
         require_dense(c, m);
         MF_HIP(c, hipStreamSynchronize(c->stream));
         const long n = (long)*m.h_count;
@@ -826,6 +829,10 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
     float* depthF_prev = c->d_depthF[(k + 2) % 3];
     ModelState& bg = *c->models[0];
     bool bg_fused = false;
+    // "passTimings" reports the passes of THIS frame: one that does not run in it (a compaction, bgAppend in the two-launch form, the batched object
+    // passes) reads 0, not the duration of its last run
+    if (c->pass_timings_on)
+        for (int q = 0; q < MF_N_PASSES; ++q) { c->pass_recorded[q] = false; c->pass_ms[q] = 0.f; }
     c->mm_marked = false;
     ObjStreamWindow obj_window(c);   // (joins on every way out of this function)
 

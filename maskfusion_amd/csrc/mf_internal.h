@@ -101,7 +101,7 @@ struct Surfels {               // SoA of float4, 48 B per surfel in three coales
     // Run table: the buffer as consecutive RUNS of at most kRun slots (after Model::initialise / an uploaded map / a compaction: slots
     // [r kRun, (r + 1) kRun); behind them the runs Model::clean appended, one frame's new surfels after the other), kBoxStride int4 per run:
     //   {enc(min x), enc(min y), enc(min z), enc(newest lastTime)}, {enc(max x), enc(max y), enc(max z), first slot of the run},
-    //   {live surfels of the run (they are its FIRST slots, in order), enc(lowest confidence), 0, 0}
+    //   {live surfels of the run (they are its FIRST slots, in order), enc(lowest confidence), 1 if a surfel of the run carries lastTime <= 0, 0}
     // (enc: order-preserving float -> int, mf_device.h box_enc).
     // Surfels are stored in creation order, i.e. in spatially coherent runs; a full map is mostly out of view (the 26.5 M-surfel map of
     // configs[4]: 86 %), and the projection passes (index map x 2, prediction, GlobalProjection) only visit the runs whose box meets the viewing

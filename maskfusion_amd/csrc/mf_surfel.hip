@@ -239,10 +239,13 @@ void launch_index_scatter(Surfels src, const FrameDev* frame, const PoseDev* pos
 // ------------------------------------------------------------------------------------------------
 // run table (Surfels::box) from scratch, and the visibility test over it
 // ------------------------------------------------------------------------------------------------
-// what a run's table entry says about its surfels, per thread: box of the positions, newest lastTime, lowest confidence (order-preserving ints)
+// what a run's table entry says about its surfels, per thread: box of the positions, newest lastTime, lowest confidence (order-preserving ints),
+// and whether one of them carries a time stamp <= 0 (`unstamped`: the age rule of Model::clean treats those apart, k_cull_clean rule (b))
 struct RunAcc {
-    int lo[3], hi[3], tmax, cmin;
-    __device__ __forceinline__ void reset() { lo[0] = lo[1] = lo[2] = kBoxEmptyMin; hi[0] = hi[1] = hi[2] = kBoxEmptyMax; tmax = kBoxEmptyMax; cmin = kBoxEmptyMin; }
+    int lo[3], hi[3], tmax, cmin, unstamped;
+    __device__ __forceinline__ void reset() {
+        lo[0] = lo[1] = lo[2] = kBoxEmptyMin; hi[0] = hi[1] = hi[2] = kBoxEmptyMax; tmax = kBoxEmptyMax; cmin = kBoxEmptyMin; unstamped = 0;
+    }
     __device__ __forceinline__ void add(float4 pc, float lastTime) {
         if (pc.x == pc.x && pc.y == pc.y && pc.z == pc.z) {   // (a NaN position is never in view)
             const int ex = box_enc(pc.x), ey = box_enc(pc.y), ez = box_enc(pc.z);
@@ -252,23 +255,26 @@ struct RunAcc {
         // (a NaN time stamp passes every "seen within timeDelta" test of the passes -- !(time - NaN > delta) -- : such a surfel counts as seen now)
         tmax = max(tmax, lastTime == lastTime ? box_enc(lastTime) : 0x7F800000);
         if (pc.w == pc.w) cmin = min(cmin, box_enc(pc.w));   // (a NaN confidence is below no threshold: the age rule of clean never drops it)
+        if (lastTime <= 0.f) unstamped = 1;                  // (false for a NaN stamp: it passes every age test, see above)
     }
 };
-// block reduction of one run's entry: per-thread (already reduced over the thread's own surfels) -> s_red[wavefront][8]
-__device__ __forceinline__ void run_box_reduce(const RunAcc& t, int (*s_red)[8]) {
+// block reduction of one run's entry: per-thread (already reduced over the thread's own surfels) -> s_red[wavefront][kRunRed]
+constexpr int kRunRed = 9;
+__device__ __forceinline__ void run_box_reduce(const RunAcc& t, int (*s_red)[kRunRed]) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int lo[3], hi[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) { lo[q] = wave_min_i(t.lo[q]); hi[q] = wave_max_i(t.hi[q]); }
     const int tmax = wave_max_i(t.tmax), cmin = wave_min_i(t.cmin);
+    const int unstamped = __ballot(t.unstamped != 0) != 0ull ? 1 : 0;
     if (lane == 0) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) { s_red[wave][q] = lo[q]; s_red[wave][4 + q] = hi[q]; }
-        s_red[wave][3] = tmax; s_red[wave][7] = cmin;
+        s_red[wave][3] = tmax; s_red[wave][7] = cmin; s_red[wave][8] = unstamped;
     }
 }
 // one thread: the four wavefronts' partial results -> the table entry of run r (start slot, live surfels)
-__device__ __forceinline__ void run_box_store(int4* __restrict__ box, int r, int start, int len, const int (*s_red)[8]) {
+__device__ __forceinline__ void run_box_store(int4* __restrict__ box, int r, int start, int len, const int (*s_red)[kRunRed]) {
     int4 a, b;
     a.x = min(min(s_red[0][0], s_red[1][0]), min(s_red[2][0], s_red[3][0]));
     a.y = min(min(s_red[0][1], s_red[1][1]), min(s_red[2][1], s_red[3][1]));
@@ -279,13 +285,14 @@ __device__ __forceinline__ void run_box_store(int4* __restrict__ box, int r, int
     b.z = max(max(s_red[0][6], s_red[1][6]), max(s_red[2][6], s_red[3][6]));
     b.w = start;
     const int cmin = min(min(s_red[0][7], s_red[1][7]), min(s_red[2][7], s_red[3][7]));
-    box[kBoxStride * r] = a; box[kBoxStride * r + 1] = b; box[kBoxStride * r + 2] = make_int4(len, cmin, 0, 0);
+    const int unstamped = s_red[0][8] | s_red[1][8] | s_red[2][8] | s_red[3][8];
+    box[kBoxStride * r] = a; box[kBoxStride * r + 1] = b; box[kBoxStride * r + 2] = make_int4(len, cmin, unstamped, 0);
 }
 
 // A DENSE buffer (slots [0, count)) gets its table: fixed runs of kRun slots.  refresh != 0: the buffer HAS a table (frame->runs > 0) and only the
 // entries' contents are recomputed from the surfels (after an in-place update outside a frame: merged surfels moved, their time stamps changed).
 __global__ __launch_bounds__(256) void k_run_table(Surfels s, FrameDev* __restrict__ frame, int refresh) {
-    __shared__ int s_red[4][8];
+    __shared__ int s_red[4][kRunRed];
     const int n = frame->count;
     const int runs = refresh ? frame->runs : (n + kRun - 1) / kRun;
     for (int r = blockIdx.x; r < runs; r += gridDim.x) {
@@ -1046,11 +1053,13 @@ __device__ __forceinline__ void clean_small_compact_body(const CleanArgs& a) {
                     int v[8] = {acc.lo[0], acc.lo[1], acc.lo[2], acc.tmax, acc.hi[0], acc.hi[1], acc.hi[2], acc.cmin};
 #pragma unroll
                     for (int q = 0; q < 8; ++q) v[q] = (q < 3 || q == 7) ? wave_min_i(v[q]) : wave_max_i(v[q]);
+                    const bool unstamped = __ballot(acc.unstamped != 0) != 0ull;
                     if (lane == 0) {
                         int* e = reinterpret_cast<int*>(&a.dst.box[kBoxStride * (r0 + j0 + g)]);
                         atomicMin(&e[0], v[0]); atomicMin(&e[1], v[1]); atomicMin(&e[2], v[2]); atomicMax(&e[3], v[3]);
                         atomicMax(&e[4], v[4]); atomicMax(&e[5], v[5]); atomicMax(&e[6], v[6]);
                         atomicAdd(&e[8], __popcll(mm)); atomicMin(&e[9], v[7]);
+                        if (unstamped) atomicMax(&e[10], 1);   // (a frame's new surfels are stamped with its tick: tick <= 0 only)
                     }
                 }
             }
@@ -1105,7 +1114,8 @@ __global__ __launch_bounds__(256) void k_clean_small_compact(const CleanArgs a) 
 // rounds 1-5 here (round 5: one launch with a decoupled look-back, 3.6 GB moved in 1.28 ms on the 26.9 M-surfel map of configs[4], >= 78 % of it
 // copies of surfels no test of copy_unstable.vert:53-157 can touch).  What the pass can do to a surfel of the buffer:
 //   (a) drop it by the window rules (:77-106)          -- only a surfel inside the image, in front of the camera, seen within timeDelta;
-//   (b) drop it by the age rule (:118-125)             -- only an UNSTABLE surfel (confidence below the threshold) last seen within timeDelta;
+//   (b) drop it by the age rule (:118-125)             -- only an UNSTABLE surfel (confidence below the threshold) last seen within timeDelta, or
+//       a surfel whose time stamp is <= 0 (-1: dropped whatever its confidence; unstable ones: the rescue of old surfels asks for a stamp > 0);
 //   (c) lower its confidence, mask disagreement (:139-156) -- a surfel whose texel (clamped to the image border when it projects outside) carries a
 //       foreign mask value and a filtered depth within 5 cm of its own.
 // The buffer is kept as RUNS (Surfels::box): k_cull_clean lists the runs in which (a), (b) or (c) can apply at all -- from the run's box, its newest
@@ -1134,6 +1144,9 @@ __global__ __launch_bounds__(256) void k_cull_clean(Surfels s, const FrameDev* _
         if (c.x > 0) {
             const bool recent = !(time - box_dec(a.w) > (float)timeDelta);
             if (c.y != kBoxEmptyMin && box_dec(c.y) < confThreshold && recent) visit = true;              // (b)
+            // (b) without an age limit: a stamp of -1 drops a surfel at any confidence, an unstable surfel stamped <= 0 is never rescued by
+            // `lastTime > 0 && age > timeDelta` (copy_unstable.vert:134-136), and a stamp of -2 is replaced by the tick (:131)
+            else if (c.z != 0) visit = true;
             else if (a.x <= b.x && a.y <= b.y && a.z <= b.z) {     // (a run of NaN positions only: every comparison of (a) and (c) fails)
                 float zlo, zhi;
                 int outside = 0;
@@ -1177,7 +1190,7 @@ void launch_cull_clean(Surfels s, const FrameDev* frame, const PoseDev* pose, in
 // particular order, expensive -- in view -- and cheap ones mixed).
 __device__ __forceinline__ void clean_runs_body(const CleanArgs& a) {
     __shared__ int s_cnt[2][4];
-    __shared__ int s_red[4][8];
+    __shared__ int s_red[4][kRunRed];
     __shared__ int s_bb[6];
     static_assert(kRun == 512, "two slots per thread");
     // Model::lastBoundingBox of an OBJECT model: see clean_small_compact_body (here: the box of the buffer's own survivors; the append pass adds
@@ -1212,8 +1225,10 @@ __device__ __forceinline__ void clean_runs_body(const CleanArgs& a) {
         const bool keep1 = live1 && clean_test(a, pc1, make_float4(0.f, 0.f, tm1.x, tm1.y), make_float4(0, 0, 0, 0), time, Ri, ti, nc1, dk, &a.src.nr[start + off1]);
         RunAcc acc;
         acc.reset();
-        if (keep0) acc.add(make_float4(pc0.x, pc0.y, pc0.z, nc0), tm0.y);
-        if (keep1) acc.add(make_float4(pc1.x, pc1.y, pc1.z, nc1), tm1.y);
+        // copy_unstable.vert:131: a surfel stamped -2 ("seen in this frame") leaves the pass stamped with the tick -- only an uploaded map holds one
+        const bool st0 = keep0 && tm0.y == -2.f, st1 = keep1 && tm1.y == -2.f;
+        if (keep0) acc.add(make_float4(pc0.x, pc0.y, pc0.z, nc0), st0 ? time : tm0.y);
+        if (keep1) acc.add(make_float4(pc1.x, pc1.y, pc1.z, nc1), st1 ? time : tm1.y);
         const unsigned long long m0 = __ballot(keep0), m1 = __ballot(keep1);
         if (lane == 0) { s_cnt[0][wave] = __popcll(m0); s_cnt[1][wave] = __popcll(m1); }
         int o0 = lane_rank(m0), o1 = lane_rank(m1);
@@ -1232,13 +1247,23 @@ __device__ __forceinline__ void clean_runs_body(const CleanArgs& a) {
             if (mv1) { c41 = a.src.ct[start + off1]; n41 = a.src.nr[start + off1]; }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every record that moves is in registers before any slot of the run is rewritten
             __syncthreads();
+            if (st0) c40.w = time;
+            if (st1) c41.w = time;
             if (mv0) { a.src.pc[start + o0] = make_float4(pc0.x, pc0.y, pc0.z, nc0); a.src.ct[start + o0] = c40; a.src.nr[start + o0] = n40; }
-            else if (conf0) reinterpret_cast<float*>(&a.src.pc[start + off0])[3] = nc0;
+            else {
+                if (conf0) reinterpret_cast<float*>(&a.src.pc[start + off0])[3] = nc0;
+                if (st0) reinterpret_cast<float*>(&a.src.ct[start + off0])[3] = time;
+            }
             if (mv1) { a.src.pc[start + o1] = make_float4(pc1.x, pc1.y, pc1.z, nc1); a.src.ct[start + o1] = c41; a.src.nr[start + o1] = n41; }
-            else if (conf1) reinterpret_cast<float*>(&a.src.pc[start + off1])[3] = nc1;
-        } else {     // nobody moves: only a decayed confidence is written
+            else {
+                if (conf1) reinterpret_cast<float*>(&a.src.pc[start + off1])[3] = nc1;
+                if (st1) reinterpret_cast<float*>(&a.src.ct[start + off1])[3] = time;
+            }
+        } else {     // nobody moves: only a decayed confidence (and a -2 stamp's replacement) is written
             if (conf0) reinterpret_cast<float*>(&a.src.pc[start + off0])[3] = nc0;
             if (conf1) reinterpret_cast<float*>(&a.src.pc[start + off1])[3] = nc1;
+            if (st0) reinterpret_cast<float*>(&a.src.ct[start + off0])[3] = time;
+            if (st1) reinterpret_cast<float*>(&a.src.ct[start + off1])[3] = time;
         }
         if (threadIdx.x == 0) {
             run_box_store(a.src.box, r, start, kept, s_red);

@@ -46,3 +46,13 @@ def test_in_place_clean_rules_on_the_cpu_executed_kernels():
     r, tail = _emu_gpu_tests(["test_gpu_switches.py::test_in_place_clean_first_surfel_rule", "test_gpu_switches.py::test_run_culling_changes_nothing"])
     assert r.returncode == 0, tail
     assert "2 passed" in r.stdout, tail
+
+
+def test_minefield_run_culling_on_the_cpu_executed_kernels():
+    """The conservativeness of the run culling on a crafted map (tests/test_gpu_run_culling.py at 200 x 152): the premises, every class of mines
+    against the shader text, and the culled frame-level path against the oracle -- the assertions of the -m gpu tests, on the CPU-executed kernels."""
+    r, tail = _emu_gpu_tests(["test_gpu_run_culling.py::test_premises_box_and_culling[200x152]",
+                              "test_gpu_run_culling.py::test_culled_clean_does_what_the_shader_text_says[200x152]",
+                              "test_gpu_run_culling.py::test_culled_frame_level_path_against_oracle[200x152]"])
+    assert r.returncode == 0, tail
+    assert "3 passed" in r.stdout and "premise (ii)" in r.stdout, tail

@@ -419,6 +419,9 @@ def test_run_culling_changes_nothing(hip):
             bg = mf.getBackgroundModel()
             out.append(dict(pose=mf.getCurrPose(), count=bg.lastCount(), pv=bg.debugRead("pred_vertex"), pi=bg.debugRead("pred_image")))
         vis, runs, cleaned = mf.getParam("visibleRuns"), mf.getParam("backgroundRuns"), mf.getParam("cleanRuns")   # (before the download: it compacts the buffer)
+        # a map that grew from frames carries no time stamp <= 0 (ticks start at 1): the table's "unstamped" bit, which makes the in-place clean visit
+        # a run whatever its age (tests/test_gpu_run_culling.py), lists nothing here
+        assert mf.getParam("unstampedRuns") == 0
         cloud = mf.getBackgroundModel().downloadMap()
         mf.close()
         return out, cloud, vis, runs, cleaned
