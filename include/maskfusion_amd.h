@@ -211,6 +211,25 @@ int mf_cloud_nn_dev(const float* d_target, int32_t target_stride, int64_t n_targ
  * no model state (frames processed afterwards are bit-identical to frames processed without the call).  Synchronous. */
 int mf_model_cloud_nn_dev(mf_ctx* ctx, int32_t model, float conf_threshold, const float* d_query, int32_t query_stride, int64_t n_query,
                           const float* query_to_model16, float radius, float* d_dist, int32_t* d_idx);
+/* Rigid registration of a query cloud onto a target cloud, one Gauss-Newton step at a time (kernels: mf_eval.hip; DESIGN.md "Cloud
+ * registration"; the loop around it: maskfusion_amd.eval.register).  mf_cloud_icp_build_dev builds mf_cloud_nn_dev's grid for `radius` once, into a
+ * workspace of mf_cloud_icp_workspace(n_target, n_query) bytes (16-byte aligned) that the steps then read; it keeps every target's position and,
+ * with normal_offset >= 3 (floats from the start of the target's record, normal_offset + 3 <= target_stride), its normal, which is used as given
+ * and expected to have unit length.  normal_offset < 0: no normals, the steps are point-to-point.  A target whose position or normal is not finite
+ * is skipped.  mf_cloud_icp_step_dev maps every query by query_to_target16 and pairs it with a target exactly as mf_cloud_nn_dev does (the same
+ * fp32 transform, distance, radius test and tie rule: the pairs are those of mf_cloud_nn_dev on the same inputs), then sums, in fp64 from the
+ * fp32 x', the target p and the normal n:  point-to-plane  r = n . (x' - p),  J = [n, x' x n];  point-to-point the three rows of [I, -[x']x]
+ * with r = x' - p.  d_out29 (DEVICE, 29 doubles) = for i = 0..5: (J^T J)[i][i..5], (J^T r)[i]; then sum r^2; then the number of pairs -- the
+ * layout of mf_k_gn_solve's sys29.  The update x = (t, w) solves J^T J x = -J^T r and composes as T <- [exp(w) | t] T.  The sums use no
+ * floating-point atomics and do not depend on the order of execution: the same inputs give the same 29 doubles bit for bit.  The step writes
+ * only the workspace and d_out29.  MF_EINVAL as for mf_cloud_nn_dev, and for a normal_offset of 0..2 or beyond the stride, a workspace no build
+ * has filled or one smaller than mf_cloud_icp_workspace says for n_query.  Both calls are enqueued on `stream` and synchronise it before they return.
+ * (Against a live model: mf_download_map first; its records carry the normal at offset 8.) */
+int mf_cloud_icp_workspace(int64_t n_target, int64_t n_query, uint64_t* bytes);
+int mf_cloud_icp_build_dev(const float* d_target, int32_t target_stride, int32_t normal_offset, int64_t n_target, float radius,
+                           void* d_workspace, uint64_t workspace_bytes, void* stream);
+int mf_cloud_icp_step_dev(void* d_workspace, uint64_t workspace_bytes, const float* d_query, int32_t query_stride, int64_t n_query,
+                          const float* query_to_target16, double* d_out29, void* stream);
 /* whether the last tracking step used the fill-in maps (MaskFusion::requiresFillIn, MaskFusion.cpp:630-648) */
 int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
 

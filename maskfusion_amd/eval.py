@@ -2,9 +2,13 @@
 
 Reads what a run writes -- poses-<id>.txt (mf_export_poses; TUM `ts tx ty tz qx qy qz qw`, also a TUM groundtruth.txt) and cloud-<id>.ply
 (mf_save_ply; binary little endian, or ASCII PLY with x / y / z) -- from this library or from the reference.  The cloud distances run on the
-GPU through mf_cloud_nn_dev (kernels: csrc/mf_eval.hip); everything else is numpy.
+GPU through mf_cloud_nn_dev (kernels: csrc/mf_eval.hip); everything else is numpy.  register() refines the rigid alignment of two clouds
+before they are scored: point-to-plane (or point-to-point) Gauss-Newton steps on the GPU (mf_cloud_icp_build_dev / mf_cloud_icp_step_dev), the
+6 x 6 solve and the pose update in fp64 here.
 
     python -m maskfusion_amd.eval --est DIR [--ref DIR] [--gt FILE] [--radius R] [--tau a,b,c] [--pair est_id:ref_id ...]
+                                  [--register [--register-radius R0,R1,...] [--register-iterations N] [--point-to-point]]
+                                  [--ref-cloud FILE [--init FILE]]
 
 prints one JSON object per model on stdout (INTEGRATION.md "Evaluating a run").
 """
@@ -176,9 +180,10 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply(path: str) -> np.ndarray:
+def read_ply(path: str, normals: bool = False):
     """The vertex positions of a PLY file, (n, 3) float32: binary little endian (mf_save_ply's and the reference's layout) or ASCII.
-    The vertex element must come first; other elements after it are ignored."""
+    The vertex element must come first; other elements after it are ignored.  normals=True: (positions, normals) with the file's
+    nx / ny / nz as (n, 3) float32 (mf_save_ply writes them), or None in their place when the file has none."""
     with open(path, "rb") as f:
         raw = f.read()
     end = raw.find(b"end_header")
@@ -205,15 +210,22 @@ def read_ply(path: str) -> np.ndarray:
     names = [p[0] for p in props]
     if not all(k in names for k in ("x", "y", "z")) or any(t is None for _, t in props):
         raise ValueError(f"{path}: vertices need x, y, z and no list properties")
+    has_n = all(k in names for k in ("nx", "ny", "nz"))
     if fmt == "binary_little_endian":
         dt = np.dtype([(nm, "<" + t) for nm, t in props])
         v = np.frombuffer(raw, dt, count=n, offset=body_at)
-        return np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float32)
+        xyz = np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float32)
+        if not normals:
+            return xyz
+        return xyz, (np.stack([v["nx"], v["ny"], v["nz"]], 1).astype(np.float32) if has_n else None)
     if fmt == "ascii":
         lines = raw[body_at:].decode("ascii").split("\n")
         rows = [l.split() for l in lines if l.strip()][:n]
         a = np.array(rows, np.float64).reshape(n, len(props))
-        return a[:, [names.index("x"), names.index("y"), names.index("z")]].astype(np.float32)
+        xyz = a[:, [names.index("x"), names.index("y"), names.index("z")]].astype(np.float32)
+        if not normals:
+            return xyz
+        return xyz, (a[:, [names.index("nx"), names.index("ny"), names.index("nz")]].astype(np.float32) if has_n else None)
     raise ValueError(f"{path}: format {fmt} is not supported")
 
 
@@ -268,8 +280,19 @@ def cloud_stats(dist, radius: float, taus) -> dict:
     return out
 
 
-def compare_clouds(est, ref, radius: float = 0.05, taus=(0.01, 0.02, 0.05)) -> dict:
-    """accuracy = est -> ref distances, completeness = ref -> est, and F-score(tau) = 2 P R / (P + R) with P, R their fractions <= tau"""
+def transform_f32(T, pts) -> np.ndarray:
+    """mf_cloud_nn_dev's query transform, on the host and with the same bits: x' = ((T00 x + T01 y) + T02 z) + T03 in fp32"""
+    T = np.asarray(T, np.float32)
+    p = np.asarray(pts, np.float32)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([T[r, 0] * x + T[r, 1] * y + T[r, 2] * z + T[r, 3] for r in range(3)], 1)
+
+
+def compare_clouds(est, ref, radius: float = 0.05, taus=(0.01, 0.02, 0.05), T=None) -> dict:
+    """accuracy = est -> ref distances, completeness = ref -> est, and F-score(tau) = 2 P R / (P + R) with P, R their fractions <= tau.
+    T (4 x 4, est -> ref; e.g. register()'s): est is moved by it first (transform_f32), for both directions."""
+    if T is not None:
+        est = transform_f32(T, est.cpu().numpy() if hasattr(est, "cpu") else est)
     acc = cloud_stats(nearest(ref, est, radius)[0], radius, taus)
     comp = cloud_stats(nearest(est, ref, radius)[0], radius, taus)
     f = {}
@@ -278,6 +301,202 @@ def compare_clouds(est, ref, radius: float = 0.05, taus=(0.01, 0.02, 0.05)) -> d
         p, r = acc["fraction"][k], comp["fraction"][k]
         f[k] = 2 * p * r / (p + r) if p + r > 0 else 0.0
     return {"radius": radius, "accuracy": acc, "completeness": comp, "fscore": f}
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# registration
+# ------------------------------------------------------------------------------------------------------------------------------------
+class Registration:
+    """The device side of register(): the reference cloud's grid for one radius (mf_cloud_icp_build_dev) and the Gauss-Newton system of a
+    query cloud under a transform (mf_cloud_icp_step_dev).  ref: (n, >= 3) float32 array or device tensor, x, y, z first; normals: None
+    (point-to-point), an (n, 3) array, or the column of ref where nx, ny, nz start (8 for mf_download_map's records)."""
+
+    def __init__(self, ref, radius: float, normals=None, n_query: int = 0):
+        import torch
+        from .lib import load, MFError
+        self._L = load()
+        t = _device_points(ref)
+        if normals is None:
+            off = -1
+        elif isinstance(normals, (int, np.integer)):
+            off = int(normals)
+        else:
+            nr = _device_points(normals)
+            if nr.shape[0] != t.shape[0]:
+                raise ValueError("normals must have one row per reference point")
+            t, off = torch.cat([t[:, :3], nr[:, :3]], 1).contiguous(), 3
+        self.target, self.plane, self.radius = t, off >= 0, float(radius)
+        self.n_query = int(n_query)
+        need = C.c_uint64(0)
+        if self._L.mf_cloud_icp_workspace(int(t.shape[0]), self.n_query, C.byref(need)) != 0:
+            raise MFError("mf_cloud_icp_workspace failed")
+        self._need = int(need.value)
+        self._ws = torch.empty(self._need, dtype=torch.uint8, device=t.device)
+        self._out = torch.zeros(29, dtype=torch.float64, device=t.device)
+        self._stream = (lambda: torch.cuda.current_stream().cuda_stream) if t.device.type == "cuda" else (lambda: None)
+        nt = int(t.shape[0])
+        rc = self._L.mf_cloud_icp_build_dev(t.data_ptr() if nt else None, int(t.shape[1]), off, nt, self.radius, self._ws.data_ptr(), self._need,
+                                            self._stream())
+        if rc != 0:
+            raise MFError(f"mf_cloud_icp_build_dev failed with code {rc} (radius must be finite and > 0, coordinates |x / radius| < 2^30, "
+                          "normals inside the record)")
+
+    def step(self, query, T=None) -> np.ndarray:
+        """sys29 (float64 [29], see unpack_sys29) of `query` (device tensor or array, at most n_query points) mapped by T (4 x 4 or None)"""
+        from .lib import MFError
+        q = _device_points(query)
+        nq = int(q.shape[0])
+        if nq > self.n_query:
+            raise MFError(f"{nq} queries, but the workspace was sized for {self.n_query}")
+        T16 = None if T is None else np.ascontiguousarray(np.asarray(T, np.float32).T.reshape(16))
+        rc = self._L.mf_cloud_icp_step_dev(self._ws.data_ptr(), self._need, q.data_ptr() if nq else None, int(q.shape[1]), nq,
+                                           T16.ctypes.data if T16 is not None else None, self._out.data_ptr(), self._stream())
+        if rc != 0:
+            raise MFError(f"mf_cloud_icp_step_dev failed with code {rc} (finite transform, at most {self.n_query} queries, "
+                          "coordinates |x / radius| < 2^30)")
+        return self._out.cpu().numpy().copy()
+
+
+def unpack_sys29(sys29):
+    """(A = J^T J 6 x 6, b = J^T r, sum r^2, correspondences) from the packed upper triangle (mf_k_gn_solve's layout)"""
+    s = np.asarray(sys29, np.float64)
+    A, b, k = np.zeros((6, 6)), np.zeros(6), 0
+    for i in range(6):
+        for j in range(i, 7):
+            if j == 6:
+                b[i] = s[k]
+            else:
+                A[i, j] = A[j, i] = s[k]
+            k += 1
+    return A, b, float(s[27]), int(s[28])
+
+
+def solve_step(sys29):
+    """The Gauss-Newton step x = (t, w) with J^T J x = -J^T r by an unpivoted LDL^T in fp64, or (None, reason) outside the solver's stated
+    domain (DESIGN.md finding F4): fewer than 6 correspondences, or a smallest pivot below 1e-8 of the largest diagonal entry."""
+    A, b, _, n = unpack_sys29(sys29)
+    if n < 6:
+        return None, f"fewer than 6 correspondences ({n})"
+    maxdiag = float(np.abs(np.diag(A)).max())
+    Lm, D = np.eye(6), np.zeros(6)
+    for j in range(6):
+        D[j] = A[j, j] - float((Lm[j, :j] ** 2) @ D[:j])
+        if not (D[j] >= 1e-8 * maxdiag and D[j] > 0.0):
+            return None, (f"the system is rank deficient: pivot {j} is {D[j]:.3g}, below 1e-8 of the largest diagonal entry {maxdiag:.3g} "
+                          "(the surface does not constrain all six degrees of freedom)")
+        for i in range(j + 1, 6):
+            Lm[i, j] = (A[i, j] - float((Lm[i, :j] * Lm[j, :j]) @ D[:j])) / D[j]
+    y = np.zeros(6)
+    for i in range(6):
+        y[i] = -b[i] - float(Lm[i, :i] @ y[:i])
+    y /= D
+    x = np.zeros(6)
+    for i in range(5, -1, -1):
+        x[i] = y[i] - float(Lm[i + 1:, i] @ x[i + 1:])
+    return x, None
+
+
+def rodrigues(w) -> np.ndarray:
+    """exp of the rotation vector w, 3 x 3"""
+    w = np.asarray(w, np.float64)
+    th = float(np.linalg.norm(w))
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-8:
+        return np.eye(3) + K + 0.5 * (K @ K)
+    return np.eye(3) + (math.sin(th) / th) * K + ((1.0 - math.cos(th)) / (th * th)) * (K @ K)
+
+
+def update_se3(T, x) -> np.ndarray:
+    """T <- [exp(w) | t] T with x = (t, w): the tracker's twist convention (computeUpdateSE3)"""
+    U = np.eye(4)
+    U[:3, :3] = rodrigues(x[3:])
+    U[:3, 3] = x[:3]
+    return U @ np.asarray(T, np.float64)
+
+
+def rotation_angle(R) -> float:
+    """angle of a 3 x 3 rotation in radians (atan2 of the antisymmetric part and the trace: accurate near 0)"""
+    R = np.asarray(R, np.float64)
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    return float(math.atan2(0.5 * np.linalg.norm(v), 0.5 * (np.trace(R) - 1.0)))
+
+
+def register(est, ref, radius: float, T0=None, ref_normals=None, max_iterations: int = 50, schedule=None, method: str = "plane",
+             tol_translation: float = 1e-6, tol_rotation: float = 1e-6, trace: bool = False) -> dict:
+    """Rigid registration of `est` onto `ref` from the start T0 (4 x 4, est -> ref; identity when None): no scale, no global search.
+    method "plane": point-to-plane, needs ref_normals ((n, 3) array, or the column of ref where the normals start); "point":
+    point-to-point, normals are not used.  Every iteration pairs each est point with its nearest ref point within the radius
+    (exactly nearest(ref, est, radius, T)), sums the Gauss-Newton system on the GPU, solves it here (solve_step) and applies
+    T <- [exp(w) | t] T (update_se3).  schedule: the radii to run in turn, coarse to fine (default: [radius]); each runs until its step is
+    below tol_translation (m) and tol_rotation (rad) -- 1e-6: ten times the fp32 resolution of the transform the device applies, below
+    which steps are rounding -- or for max_iterations.  A system outside solve_step's domain ends the loop.
+    Returns {"T", "iterations", "inliers", "inlier_share", "rmse", "converged", "reason", "radius", "method", "trace"}: inliers / rmse are
+    those of the returned T at the last radius (rmse = sqrt(sum r^2 / inliers): point-to-plane distances for "plane"); converged is True
+    only when the last radius met the stop rule; trace (trace=True) lists per iteration {"radius", "T" (before the step), "sys29", "x",
+    "inliers", "rmse"}."""
+    if method not in ("plane", "point"):
+        raise ValueError('method must be "plane" or "point"')
+    if method == "plane" and ref_normals is None:
+        raise ValueError("point-to-plane registration needs the reference's normals (ref_normals; a PLY without nx / ny / nz has none): "
+                         'give them, or use method="point"')
+    radii = [float(r) for r in (schedule if schedule is not None else [radius])]
+    if not radii:
+        raise ValueError("the radius schedule is empty")
+    q = _device_points(est)
+    nq = int(q.shape[0])
+    T = np.eye(4) if T0 is None else np.array(T0, np.float64).reshape(4, 4)
+    normals = ref_normals if method == "plane" else None
+    tr, iters, converged, reason = [], 0, False, None
+    reg = None
+    for stage, r in enumerate(radii):
+        reg = Registration(ref, r, normals, nq)
+        converged = False
+        for _ in range(int(max_iterations)):
+            s = reg.step(q, T)
+            x, why = solve_step(s)
+            if trace:
+                tr.append({"radius": r, "T": T.copy(), "sys29": s, "x": None if x is None else x.copy(), "inliers": int(s[28]),
+                           "rmse": math.sqrt(s[27] / s[28]) if s[28] > 0 else None})
+            if x is None:
+                reason = why
+                break
+            T = update_se3(T, x)
+            iters += 1
+            if float(np.linalg.norm(x[:3])) < tol_translation and float(np.linalg.norm(x[3:])) < tol_rotation:
+                converged = True
+                break
+        if reason is not None:
+            break
+        if not converged and stage == len(radii) - 1:
+            reason = f"no step below the tolerances within {int(max_iterations)} iterations at radius {r:g}"
+    s = reg.step(q, T)
+    n = int(s[28])
+    return {"T": T, "iterations": iters, "inliers": n, "inlier_share": (n / nq if nq else 0.0), "rmse": math.sqrt(s[27] / n) if n else None,
+            "converged": bool(converged and reason is None), "reason": reason, "radius": radii[-1], "method": method, "trace": tr}
+
+
+def registration_summary(res: dict) -> dict:
+    """what the command prints of a register() result"""
+    T = res["T"]
+    return {"T": [[float(v) for v in row] for row in T], "rotation_rad": rotation_angle(T[:3, :3]), "translation_m": float(np.linalg.norm(T[:3, 3])),
+            "iterations": res["iterations"], "inliers": res["inliers"], "inlier_share": res["inlier_share"], "rmse": res["rmse"],
+            "converged": res["converged"], "reason": res["reason"], "radius": res["radius"], "method": res["method"]}
+
+
+def read_transform(path: str) -> np.ndarray:
+    """a 4 x 4 rigid transform from a text file: 16 numbers (four rows of four; commas and `#` comments allowed), last row 0 0 0 1"""
+    v = []
+    with open(path) as f:
+        for line in f:
+            v += [float(x) for x in line.split("#", 1)[0].replace(",", " ").split()]
+    if len(v) != 16:
+        raise ValueError(f"{path}: expected 16 numbers (a 4 x 4 matrix), got {len(v)}")
+    T = np.array(v, np.float64).reshape(4, 4)
+    if not np.isfinite(T).all() or np.abs(T[3] - [0, 0, 0, 1]).max() > 1e-9:
+        raise ValueError(f"{path}: not a finite matrix with the last row 0 0 0 1")
+    if np.abs(T[:3, :3] @ T[:3, :3].T - np.eye(3)).max() > 1e-4 or np.linalg.det(T[:3, :3]) < 0:
+        raise ValueError(f"{path}: the upper 3 x 3 is not a rotation (registration is rigid, without scale)")
+    return T
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -327,8 +546,43 @@ def main(argv=None) -> int:
     ap.add_argument("--max-dt", type=float, default=0.02, help="timestamp association window in seconds (default 0.02)")
     ap.add_argument("--rpe-delta", type=float, default=1.0, help="RPE delta (default 1.0)")
     ap.add_argument("--rpe-unit", choices=("s", "f"), default="s", help="RPE delta in seconds or frames (default s)")
+    ap.add_argument("--register", action="store_true", help="refine the rigid alignment of every compared cloud pair on the GPU before scoring "
+                    "(adds cloud_registered and registration; cloud stays as without the flag)")
+    ap.add_argument("--register-radius", metavar="R0,R1,...", help="the registration's radii, coarse to fine (default 4, 2 and 1 times --radius)")
+    ap.add_argument("--register-iterations", type=int, default=50, help="iteration cap per radius (default 50)")
+    ap.add_argument("--point-to-point", action="store_true", help="register point-to-point (for a reference cloud without normals)")
+    ap.add_argument("--ref-cloud", metavar="FILE", help="a single reference PLY (a ground-truth model) for the background cloud of --est")
+    ap.add_argument("--init", metavar="FILE", help="with --ref-cloud: text file with the 4 x 4 est -> ref start")
     a = ap.parse_args(argv)
+    if a.init and not a.ref_cloud:
+        ap.error("--init needs --ref-cloud")
+    if a.ref_cloud and a.ref:
+        ap.error("give --ref or --ref-cloud, not both")
+    if not a.register and (a.register_radius or a.point_to_point):
+        ap.error("--register-radius and --point-to-point need --register")
+    if a.register and not (a.ref or a.ref_cloud):
+        ap.error("--register needs --ref or --ref-cloud")
     taus = tuple(float(x) for x in a.tau.split(",") if x.strip())
+    if a.register:
+        try:
+            radii = [float(x) for x in a.register_radius.split(",") if x.strip()] if a.register_radius else [4 * a.radius, 2 * a.radius, a.radius]
+        except ValueError:
+            ap.error("--register-radius takes comma-separated numbers")
+        if not radii or not all(math.isfinite(r) and r > 0 for r in radii) or a.register_iterations < 1:
+            ap.error("--register-radius needs positive radii, --register-iterations at least 1")
+
+    def registered(o, ce, cr, nr, T0):
+        """adds registration and cloud_registered to o; False (after a message) when the reference has no normals and point-to-plane is asked"""
+        if nr is None and not a.point_to_point:
+            sys.stderr.write(f"eval: the reference cloud of model {o['model']} has no normals (nx ny nz): point-to-plane registration needs "
+                             "them; give --point-to-point to register without\n")
+            return False
+        res = register(ce, cr, radii[-1], T0=T0, ref_normals=None if a.point_to_point else nr, max_iterations=a.register_iterations,
+                       schedule=radii, method="point" if a.point_to_point else "plane")
+        o["cloud_registered"] = compare_clouds(ce, cr, a.radius, taus, T=res["T"])
+        o["registration"] = registration_summary(res)
+        return True
+
     est = _run_files(a.est)
     results = []
     if a.gt:
@@ -356,23 +610,43 @@ def main(argv=None) -> int:
             if el is not None and rl is not None:
                 o["trajectory_vs_ref"] = {"ate": ate(el, rl, a.max_dt), "rpe": rpe(el, rl, a.rpe_delta, a.rpe_unit)}
             if "cloud" in E and "cloud" in R:
-                ce, cr = read_ply(E["cloud"]), read_ply(R["cloud"])
+                ce, (cr, nr) = read_ply(E["cloud"]), read_ply(R["cloud"], normals=True)
                 if ei != 0 or ri != 0:   # object models: model frame -> world with each run's own obj -> world pose
                     w = _object_to_world(el, rl, a.max_dt) if el is not None and rl is not None else None
                     if w is None:
                         o["cloud_error"] = "no common timestamp in the two pose logs: the object clouds cannot be placed in the world"
                     else:
                         ce, cr = _apply(w[0], ce), _apply(w[1], cr)
+                        if nr is not None:
+                            nr = (nr.astype(np.float64) @ w[1][:3, :3].T).astype(np.float32)
                         o["cloud_pose_time"] = w[2]
                 if "cloud_error" not in o:
                     o["cloud"] = compare_clouds(ce, cr, a.radius, taus)
+                    if a.register and not registered(o, ce, cr, nr, None):
+                        return 2
             if ei == 0 and a.gt:
                 o["trajectory_vs_gt"] = gt_res
             results.append(o)
+    elif a.ref_cloud:
+        if 0 not in est or "cloud" not in est[0]:
+            sys.stderr.write(f"eval: {a.est} holds no cloud-0.ply (background map)\n")
+            return 2
+        try:
+            T0 = read_transform(a.init) if a.init else None
+        except (OSError, ValueError) as e:
+            sys.stderr.write(f"eval: --init: {e}\n")
+            return 2
+        ce, (cr, nr) = read_ply(est[0]["cloud"]), read_ply(a.ref_cloud, normals=True)
+        o = {"model": 0, "ref_cloud": a.ref_cloud, "cloud": compare_clouds(ce, cr, a.radius, taus, T=T0)}
+        if a.register and not registered(o, ce, cr, nr, T0):
+            return 2
+        if a.gt:
+            o["trajectory_vs_gt"] = gt_res
+        results.append(o)
     elif a.gt:
         results.append({"model": 0, "trajectory_vs_gt": gt_res})
     else:
-        ap.error("give --ref, --gt or both")
+        ap.error("give --ref, --ref-cloud, --gt or a combination")
     for o in results:
         print(json.dumps(_clean(o)))
     return 0

@@ -165,6 +165,9 @@ SYMBOLS = {
                                   C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "mf_model_cloud_nn_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_float,
                                         C.c_void_p, C.c_void_p]),
+    "mf_cloud_icp_workspace": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_uint64)]),
+    "mf_cloud_icp_build_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mf_cloud_icp_step_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_k_icp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                 C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
                                 C.c_int32, C.c_void_p, C.c_void_p]),

@@ -5,6 +5,9 @@ sampled from it and jittered by N(0, 5 mm) per axis, radius 5 cm.
   grid build   mf_cloud_nn_dev with no queries (count, scan, scatter)
   query        the same call with the queries, minus the build
   live model   mf_model_cloud_nn_dev against the same map uploaded into a stress.make_context context (gather + build + query)
+  icp step     mf_cloud_icp_step_dev (point-to-plane, the map's own normals) on the same clouds next to the mf_cloud_nn_dev query, both as
+               medians of 20 calls after 5 warm-ups, and their ratio; then the wall time of a whole eval.register() from a start 1 degree
+               and 1 cm off
 
 Device times are medians of 10 calls after 2 warm-up calls, between HIP events on the call's stream.  One CPU line for contrast:
 scipy.spatial.cKDTree with 16 workers on the same clouds (tree build + query), if scipy is present.
@@ -46,6 +49,7 @@ def main(argv=None) -> int:
     ap.add_argument("--radius", type=float, default=0.05)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-live", action="store_true")
+    ap.add_argument("--no-icp", action="store_true")
     a = ap.parse_args(argv)
     import torch
     from maskfusion_amd import stress, synth
@@ -87,6 +91,35 @@ def main(argv=None) -> int:
     print(f"query      : median {qm:.2f} ms (build + query {full[0]:.2f} ms, min {full[1]:.2f}, max {full[2]:.2f}); "
           f"{nq / qm / 1e3:.0f} M queries/s; hits {hits:.4f}")
     print(f"build + query on {N / 1e6:.1f} M targets x {nq / 1e6:.1f} M queries: {full[0]:.2f} ms (target < 1000 ms)")
+    if not a.no_icp:
+        from maskfusion_amd import eval as ev
+        drec = torch.from_numpy(room).cuda()                # 12-float records: the normal at offset 8
+        t0 = time.perf_counter()
+        reg = ev.Registration(drec, a.radius, 8, nq)
+        torch.cuda.synchronize()
+        t_build = time.perf_counter() - t0
+        out29 = torch.zeros(29, dtype=torch.float64, device="cuda")
+
+        def step():
+            rc = L.mf_cloud_icp_step_dev(reg._ws.data_ptr(), reg._need, dq.data_ptr(), 3, nq, None, out29.data_ptr(), s.cuda_stream)
+            assert rc == 0, rc
+        full20 = _median_ms(lambda: call(nq), s, reps=20, warm=5)
+        build20 = _median_ms(lambda: call(0), s, reps=20, warm=5)
+        step20 = _median_ms(step, s, reps=20, warm=5)
+        q20 = full20[0] - build20[0]
+        pairs = int(out29[28].item())
+        print(f"icp step   : median {step20[0]:.2f} ms (min {step20[1]:.2f}, max {step20[2]:.2f}) against the nn query's {q20:.2f} ms "
+              f"(build + query {full20[0]:.2f} - build {build20[0]:.2f}; 20 calls after 5 warm-ups): ratio {step20[0] / q20:.3f}; "
+              f"{pairs} pairs (nn hits {int((idx >= 0).sum().item())}); workspace {reg._need / 2**20:.0f} MiB, its build {1e3 * t_build:.0f} ms wall")
+        T0 = synth.make_pose(synth.rot_xyz(*np.deg2rad([1.0, -1.0, 1.0])), [0.01, -0.01, 0.01])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = ev.register(dq, drec, a.radius, T0=T0, ref_normals=8, schedule=[2 * a.radius, a.radius])
+        t_reg = time.perf_counter() - t0
+        print(f"register   : {t_reg:.2f} s wall for {res['iterations']} iterations at radii {2 * a.radius:g}, {a.radius:g} (converged {res['converged']}, "
+              f"inlier share {res['inlier_share']:.4f}, rmse {res['rmse']:.3g} m, |t| {np.linalg.norm(res['T'][:3, 3]):.2e} m, "
+              f"angle {ev.rotation_angle(res['T'][:3, :3]):.2e} rad from the identity)")
+        del drec, reg
     if not a.no_live:
         mf = stress.make_context()
         rgb, depth, mask = st.frame(0)
