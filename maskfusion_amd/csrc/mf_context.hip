@@ -23,23 +23,45 @@ using namespace mf;
 
 namespace {
 
+// Host bookkeeping of one model's surfel buffer.  The buffer is in one of three shapes: dense without a run table | dense with a fresh table |
+// sparse with a table that the device maintains.  The member functions are the only writers of these fields.  Two rules hold across all of them:
+//   - every mirror (append_mirror) older than a buffer replacement is void: a transition that replaces the buffer moves mirror_from past clean_seq;
+//   - gen changes whenever a cached visibility list could be stale: the buffer, its table, the pose or the tick may have changed.
+struct SurfelBufferState {
+    int cur = 0;                           // which of the model's two buffers is live
+    bool table_valid = false;              // the live buffer has a run table (Surfels::box; device: frame->runs > 0)
+    bool sparse = false;                   // ... and the buffer may have unused slots inside its runs: only the run-aware passes can read it (densify() first)
+    long phys_ub = -1, runs_ub = -1;       // upper bounds of frame->phys / frame->runs (the device appends up to P / 4 surfels in up to P / (4 kRun) + 1 runs per
+                                           // frame): the host compacts the buffer before the slots behind the last run or the table could run out; -1: unknown
+    unsigned clean_seq = 0, mirror_from = 1;  // in-place clean passes enqueued so far on this model / the first one whose mirror describes the present buffer
+    unsigned gen = 0;                      // what visibility lists are cached against
+
+    // an empty model (pooled re-use, retirement): dense, no table, nothing known
+    void reset_empty() { became_dense(0); }
+    // `live` now holds a dense buffer without a table (a compaction, the two-launch clean)
+    void became_dense(int live) { cur = live; sparse = false; table_valid = false; phys_ub = runs_ub = -1; mirror_from = clean_seq + 1; gen++; }
+    // `live` now holds a dense buffer of at most n surfels with a fresh table (initialise, an uploaded map, a table rebuilt from scratch)
+    void fresh_table(int live, long n) { became_dense(live); table_valid = true; exact_count(n); }
+    // the host has read the exact count of the (dense) buffer
+    void exact_count(long n) { phys_ub = n; runs_ub = (n + kRun - 1) / kRun; }
+    // a table was built on the dense buffer
+    void table_built() { table_valid = true; gen++; }
+    // an in-place clean pass was enqueued: the device maintains the table from here on and may append a frame's candidates
+    void cleaned_in_place(long cand_max, long new_runs_max) { sparse = true; table_valid = true; phys_ub += cand_max; runs_ub += new_runs_max; clean_seq++; gen++; }
+    // the pose or the tick changed
+    void touched() { gen++; }
+};
+
 // One surfel model (Core/Model/Model.h): persistent per-model device state.  Everything else (maps, index map, candidate
 // buffers, z-buffer keys) is scratch shared by all models: the reference's per-model passes never overlap in time.
-struct ModelState {
+struct ModelState : SurfelBufferState {
     int id = 0, classID = -1;
     bool isStatic = true, allowFillIn = false;
     unsigned age = 0;
     float confThr = 0.f, maxDepth = FLT_MAX;
     Surfels surf[2];
-    int cur = 0, cap = 0;
-    bool table_valid = false;              // the live buffer has a run table (Surfels::box; device: frame->runs > 0): written by initialise / upload / launch_run_table,
-                                           // maintained by the in-place clean; the two-launch clean leaves a dense buffer without one
-    bool sparse = false;                   // ... and the buffer may have unused slots inside its runs: only the run-aware passes can read it (densify() first)
-    long phys_ub = -1, runs_ub = -1;       // upper bounds of frame->phys / frame->runs (the device appends up to P / 4 surfels in up to P / (4 kRun) + 1 runs per
-                                           // frame): the host compacts the buffer before the slots behind the last run or the table could run out; -1: unknown
+    int cap = 0;
     unsigned long long* h_append = nullptr;   // pinned: append_mirror() of the last in-place clean pass that has RUN (mf_internal.h)
-    unsigned clean_seq = 0, mirror_from = 1;  // in-place clean passes enqueued so far on this model / the first one whose mirror describes the present buffer
-    unsigned gen = 0;                      // bumped whenever the buffer, its table, the pose or the tick may have changed (visibility lists are cached against it)
     PoseDev* d_pose = nullptr; FrameDev* d_frame = nullptr;
     float4* d_predV = nullptr; float4* d_predN = nullptr; uchar4* d_predImage = nullptr; uint16_t* d_predTime = nullptr;
     uint8_t* d_predGray = nullptr; uint8_t* d_fillGray = nullptr;  // intensity of the RGB projection / of the fill-in image
@@ -177,10 +199,9 @@ struct mf_ctx {
     // share read-only inputs (frame, label image, poses).  Fork: behind the label stage (the host has waited for it); join: the end of the frame.
     // obj_s: where the batched object passes are enqueued right now (the main stream outside that window); obj_dep_main: main-stream work the object
     // chain depends on has been enqueued since the fork (a spawn, a compaction) -- the object stream waits for it first.
-    // "fusedPreprocessLaunch": a single tracked background's model-side pyramid is built in the depth filter's launch (k_bilateral_model_pyramid);
-    // pyr_done: the model whose pyramid of THIS frame that launch has built (enqueue_track then skips its own launch)
+    // "fusedPreprocessLaunch": the model-side pyramids of the frame's tracking plan are built in the depth filter's launch (k_bilateral_model_pyramid):
+    // the background's, or every tracked model's of a batched plan (mf_frame.inl: process_frame_impl hands the fact to the tracking loop)
     bool fused_preprocess = true;
-    ModelState* pyr_done = nullptr; bool pyr_batch_done = false;   // (... or the batched tracker's pyramids of this frame)
     bool object_stream = true;
     hipStream_t stream_obj = nullptr, obj_s = nullptr;
     hipEvent_t ev_obj_dep = nullptr, ev_obj_done = nullptr;
@@ -1086,7 +1107,8 @@ extern "C" int mf_set_param(mf_ctx* c, const char* key, double value) {
         require_dense(c, bg);
         MF_HIP(c, hipStreamSynchronize(c->stream));   // (the exact count: the pinned mirror as of the last clean pass / the compaction)
         launch_run_table(bg.surf[bg.cur], bg.d_frame, c->stream);
-        fresh_table(c, bg, (long)*bg.h_count);
+        bg.fresh_table(bg.cur, (long)*bg.h_count);
+        c->vis_tag.model = nullptr;
         return check_launch(c);
     }
     if (!strcmp(key, "cleanLiteralWindow")) { c->clean_literal = value != 0; return MF_OK; }   // 0: the exact-arithmetic 4 x 4 window

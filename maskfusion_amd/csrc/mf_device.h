@@ -52,6 +52,17 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// inclusive scan over the 64 lanes of a wavefront: lane l (the caller's threadIdx.x & 63) gets the sum of lanes 0 .. l
+// (a template: the shuffle is looked up where a kernel instantiates it -- host compilations of this header for its scalar math never do)
+template <typename T>
+__device__ __forceinline__ T wave_scan(T v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T y = __shfl_up(v, d, 64);
+        if (lane >= d) v += y;
+    }
+    return v;
+}
 
 __device__ __forceinline__ int wave_min_i(int v) {
 #pragma unroll

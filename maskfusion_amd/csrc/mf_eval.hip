@@ -26,6 +26,7 @@
 #include "../../include/maskfusion_amd.h"
 #include "mf_internal.h"
 #include "mf_device.h"
+#include "mf_walk.h"
 
 namespace mf {
 
@@ -119,12 +120,7 @@ __global__ __launch_bounds__(kNnThreads) void k_nn_scan_apply(NnGrid g, unsigned
     for (unsigned i0 = beg; i0 < end; i0 += kNnThreads) {
         const unsigned i = i0 + threadIdx.x;
         const unsigned c = i < end ? g.start[i] : 0u;
-        unsigned x = c;   // inclusive scan of the wavefront
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned y = (unsigned)__shfl_up((int)x, d, 64);
-            if (lane >= d) x += y;
-        }
+        const unsigned x = wave_scan(c, lane);
         if (lane == 63) s_w[wave] = x;
         __syncthreads();
         unsigned off = base;
@@ -312,54 +308,14 @@ __global__ __launch_bounds__(64) void k_icp_sum(const double* __restrict__ parti
 }
 
 // ---------------- live surfels of a model -> float4 points (mf_eval.inl) ----------------
-// offs[r] = live surfels before run r (a dense buffer without a table: one run [0, count)); offs[kNnLiveTotal slot] = all of them.  One workgroup.
-__global__ __launch_bounds__(1024) void k_nn_live_offsets(Surfels s, const FrameDev* __restrict__ frame, int* __restrict__ offs, int* __restrict__ total) {
-    __shared__ int s_w[16];
-    const int runs = frame->runs;
-    if (runs == 0) {
-        if (threadIdx.x == 0) { offs[0] = 0; *total = frame->count; }
-        return;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < runs; base += 1024) {
-        const int r = base + (int)threadIdx.x;
-        const int v = r < runs ? run_len(s.box, r) : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) s_w[wave] = x;
-        __syncthreads();
-        int before = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) { if (w < wave) before += s_w[w]; tot += s_w[w]; }
-        if (r < runs) offs[r] = carry + before + x - v;
-        carry += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
 // the live surfels in download order (mf_download_map: the runs in order, each run's first len slots) -> out, position + index; a surfel at or
 // below the confidence threshold becomes a NaN point, which the grid does not hold
 __global__ __launch_bounds__(kNnThreads) void k_nn_live_gather(Surfels s, const FrameDev* __restrict__ frame, const int* __restrict__ offs, float thr,
                                                                float4* __restrict__ out, int n) {
-    const int runs = frame->runs;
-    const int nr = runs > 0 ? runs : (frame->count + kRun - 1) / kRun;
-    for (int r = blockIdx.x; r < nr; r += gridDim.x) {
-        int start, len, o;
-        if (runs > 0) { start = run_start(s.box, r); len = run_len(s.box, r); o = offs[r]; }
-        else { start = o = r * kRun; len = min(kRun, frame->count - start); }
-        for (int q = threadIdx.x; q < len; q += kNnThreads) {
-            if (o + q >= n) break;
-            const float4 p = s.pc[start + q];
-            out[o + q] = p.w > thr ? make_float4(p.x, p.y, p.z, 0.f) : make_float4(NAN, NAN, NAN, 0.f);
-        }
-    }
-}
-void launch_nn_live(Surfels s, const FrameDev* frame, int* offs, int* total, hipStream_t st) {
-    hipLaunchKernelGGL(k_nn_live_offsets, dim3(1), dim3(1024), 0, st, s, frame, offs, total);
+    for_each_live_ordered(s, frame, offs, n, [&](int from, int to) {
+        const float4 p = s.pc[from];
+        out[to] = p.w > thr ? make_float4(p.x, p.y, p.z, 0.f) : make_float4(NAN, NAN, NAN, 0.f);
+    });
 }
 void launch_nn_gather(Surfels s, const FrameDev* frame, const int* offs, float thr, float4* out, int n, int max_runs, hipStream_t st) {
     const int blocks = std::max(1, std::min(max_runs, 2048));

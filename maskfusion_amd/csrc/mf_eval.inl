@@ -35,7 +35,7 @@ extern "C" int mf_model_cloud_nn_dev(mf_ctx* c, int32_t model, float conf_thresh
         e.offs_cap = runs;
     }
     const Surfels& sf = m->surf[m->cur];
-    launch_nn_live(sf, m->d_frame, e.d_offs, e.d_offs + (runs - 1), s);
+    launch_run_offsets(sf, m->d_frame, e.d_offs, e.d_offs + (runs - 1), s);
     MF_HIP(c, hipMemcpyAsync(e.h_total, e.d_offs + (runs - 1), sizeof(int), hipMemcpyDeviceToHost, s));
     MF_HIP(c, hipStreamSynchronize(s));
     const int n = std::max(0, std::min(*e.h_total, m->cap));

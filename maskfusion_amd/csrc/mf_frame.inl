@@ -67,17 +67,17 @@ static bool photometric_on(const mf_ctx* c) { return c->cfg.rgb_only != 0 || c->
 
 // Model::performTracking (Core/Model/Model.cpp:427-447): initICP (model pyramid + fill-in, RGB pyramids), the optional
 // SO(3) pre-alignment, then the Gauss-Newton loop (ICP only: one launch per iteration; with the photometric term: two).
-static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, float jump_limit, long frame_k) {
+// pyr_built: the model-side pyramid of this step was built beside the frame's depth filter (enqueue_preprocess, "fusedPreprocessLaunch")
+static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, float jump_limit, long frame_k, bool pyr_built) {
     const mf_config& g = c->cfg;
-    m.gen++;   // the pose changes: cached visibility lists are stale
+    m.touched();   // the pose changes
     const int set = (int)(frame_k & 1);
     float* const* cur_vmap = c->d_vmap[set];
     float* const* cur_nmap = c->d_nmap[set];
     const int W = c->W, H = c->H;
     hipStream_t s = c->stream;
-    if (c->pyr_done == &m) c->pyr_done = nullptr;   // built beside the frame's depth filter (enqueue_preprocess, "fusedPreprocessLaunch")
-    else launch_model_pyramid(m.d_predV, m.d_predN, m.allowFillIn ? fillDepth : nullptr, m.d_frame, m.d_pose, nullptr, m.d_vmap_g,
-                              m.d_nmap_g, W, H, c->K, s);
+    if (!pyr_built)
+        launch_model_pyramid(m.d_predV, m.d_predN, m.allowFillIn ? fillDepth : nullptr, m.d_frame, m.d_pose, nullptr, m.d_vmap_g, m.d_nmap_g, W, H, c->K, s);
     const bool rgb = photometric_on(c);
     const bool icp = !g.rgb_only && g.icp_weight > 0.f;
     // the previous frame's intensity pyramid is RGBDOdometry::lastNextImage (identical for every tracked model)
@@ -166,17 +166,20 @@ static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, floa
 // The same for several models at once (geometric term only; MaskFusion.cpp:247-276 tracks the models one after the other, their
 // steps are independent): the model pyramid, every Gauss-Newton iteration and the final pose update of ALL of them are one
 // launch each, so that a frame with M tracked models costs ~40 launches instead of M x 21 latency-bound ones.
-static void enqueue_track_batch(mf_ctx* c, const std::vector<ModelState*>& ms, const float* fillDepth, long frame_k) {
-    const mf_config& g = c->cfg;
-    const int set = (int)(frame_k & 1);
-    const int W = c->W, H = c->H;
-    hipStream_t s = c->stream;
+static TrackBatch track_batch_of(const std::vector<ModelState*>& ms) {
     TrackBatch b;
     memset(&b, 0, sizeof(b));
     b.n = (int)ms.size();
     for (int i = 0; i < b.n; ++i) b.m[i] = ms[i]->d_track;
-    if (c->pyr_batch_done) c->pyr_batch_done = false;   // built beside the frame's depth filter (enqueue_preprocess, "fusedPreprocessLaunch")
-    else launch_model_pyramid_batch(b, fillDepth, W, H, c->K, s);
+    return b;
+}
+static void enqueue_track_batch(mf_ctx* c, const std::vector<ModelState*>& ms, const float* fillDepth, long frame_k, bool pyr_built) {
+    const mf_config& g = c->cfg;
+    const int set = (int)(frame_k & 1);
+    const int W = c->W, H = c->H;
+    hipStream_t s = c->stream;
+    const TrackBatch b = track_batch_of(ms);
+    if (!pyr_built) launch_model_pyramid_batch(b, fillDepth, W, H, c->K, s);
     const bool so3 = g.so3 != 0 && c->gray_frame[set ^ 1] == frame_k - 1 && c->gray_frame[set] == frame_k;
     if (so3)   // one pre-alignment serves every model: it only looks at the two frames (RGBDOdometry.cpp:264-324)
         (void)launch_so3_prealign(c->d_gray[set ^ 1][2], c->d_gray[set][2], W >> 2, H >> 2, Intr{g.fx / 4, g.fy / 4, g.cx / 4, g.cy / 4},
@@ -256,9 +259,7 @@ static bool append_mirror_fits(const mf_ctx* c, const ModelState& m) {
 static void densify(mf_ctx* c, ModelState& m) {
     launch_densify(m.surf[m.cur], m.surf[1 - m.cur], m.d_frame, c->d_run_offs, m.h_count, c->stream);
     c->obj_dep_main = true;
-    m.cur = 1 - m.cur;
-    m.sparse = false; m.table_valid = false; m.phys_ub = m.runs_ub = -1; m.gen++;
-    m.mirror_from = m.clean_seq + 1;      // (mirrors of earlier passes describe the buffer that was)
+    m.became_dense(1 - m.cur);
     c->densify_count++;
 }
 // the passes that read a buffer slot by slot (copy-update, two-launch clean, download) need a dense one
@@ -293,21 +294,37 @@ static int prepare_in_place(mf_ctx* c, ModelState& m, bool& ok) {
         require_dense(c, m);
         MF_HIP(c, hipStreamSynchronize(c->stream));
         const long n = (long)*m.h_count;
-        m.phys_ub = n; m.runs_ub = (n + kRun - 1) / kRun;
+        m.exact_count(n);
         if (n + cm > (long)m.cap) { ok = false; return MF_OK; }
     }
     if (!m.table_valid) {
         launch_run_table(m.surf[m.cur], m.d_frame, c->stream);
         c->obj_dep_main = true;
-        m.table_valid = true; m.gen++;
+        m.table_built();
     }
     return MF_OK;
 }
-// bookkeeping behind a model's clean pass
-static void after_clean(mf_ctx* c, ModelState& m, bool in_place) {
-    if (in_place) { m.sparse = true; m.table_valid = true; m.phys_ub += cand_max(c); m.runs_ub += new_runs_max(c); m.clean_seq++; }
-    else { m.sparse = false; m.table_valid = false; m.phys_ub = m.runs_ub = -1; m.mirror_from = m.clean_seq + 1; }
-    m.gen++;
+// Which forms the passes of the models ms[0 .. n) take this frame, with their buffers made ready for them.  One launch has one form, so the models
+// share it.  want_in_place: a model is big enough for the in-place clean (clean_small says no); it is taken when every model has room for a
+// frame's candidates (prepare_in_place), else all of them get the two-launch clean on dense buffers.  Every model is prepared before any of
+// them is compacted for the fallback.  The copying update pairs with the two-launch clean of small maps only.
+struct CleanForm { bool in_place, update_copy; };
+static int prepare_clean(mf_ctx* c, ModelState* const* ms, size_t n, bool want_in_place, CleanForm& form) {
+    form.in_place = want_in_place; form.update_copy = !want_in_place;
+    for (size_t i = 0; i < n; ++i) form.update_copy = form.update_copy && update_copy(c, *ms[i]);
+    for (size_t i = 0; i < n && want_in_place; ++i) {
+        bool ok = true;
+        int rc = prepare_in_place(c, *ms[i], ok);
+        if (rc != MF_OK) return rc;
+        form.in_place = form.in_place && ok;
+    }
+    if (!form.in_place) for (size_t i = 0; i < n; ++i) require_dense(c, *ms[i]);
+    return MF_OK;
+}
+// bookkeeping behind a model's clean pass; live: the buffer the two-launch form wrote
+static void after_clean(mf_ctx* c, ModelState& m, bool in_place, int live) {
+    if (in_place) m.cleaned_in_place(cand_max(c), new_runs_max(c));
+    else m.became_dense(live);
 }
 // the arguments every clean form of model m shares (shared scratch of the single-model path)
 static CleanIn clean_in(mf_ctx* c, ModelState& m, int time_delta, bool packed, const float* depthF, const uint8_t* mask) {
@@ -344,16 +361,10 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
     const int W = c->W, H = c->H;
     hipStream_t s = c->stream;
     // Which forms a model's passes take is a matter of its size alone (mf_context.hip: in_place_elements / big_map_elements); the results are the same.
-    bool small = clean_small(c, m);
-    const bool copy = update_copy(c, m);
-    if (!small) {
-        bool ok = true;
-        int rc = prepare_in_place(c, m, ok);
-        if (rc != MF_OK) return rc;
-        small = !ok;
-    } else {
-        require_dense(c, m);
-    }
+    ModelState* const one = &m;
+    CleanForm form;
+    int rc = prepare_clean(c, &one, 1, !clean_small(c, m), form);
+    if (rc != MF_OK) return rc;
     const int src = m.cur, dst = 1 - m.cur;
     const int blocks = surfel_blocks(c, m);
     const bool timed = m.id == 0;       // "passTimings": the background's passes one by one
@@ -377,9 +388,9 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
     if (marks) mark(c, 5);
     // the in-place clean of the background visits only the runs its rules can touch (k_cull_clean); the resolve pass that feeds clean gathers
     // the frame's statistics for that test
-    const bool in_place = !small, cull_clean = in_place && c->cull_runs && secondIndexPass && m.id == 0;
+    const bool in_place = form.in_place, cull_clean = in_place && c->cull_runs && secondIndexPass && m.id == 0;
     int live = src;      // the buffer that holds the updated surfels
-    if (copy && small) {
+    if (form.update_copy) {
         // small map (rounds 1-4's pass): update.vert as a copy src -> dst with the second index scatter (:556) riding on it; clean goes
         // dst -> src: two swaps leave the live buffer where it was
         {
@@ -415,9 +426,8 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
     } else {
         PassTimer t(c, timed ? MF_PASS_BG_CLEAN : -1);
         launch_clean_small(in, m.surf[live], m.surf[1 - live], s, compact_blocks_for((long)*m.h_count + cand_max(c)));
-        m.cur = 1 - live;
     }
-    after_clean(c, m, in_place);
+    after_clean(c, m, in_place, 1 - live);
     return MF_OK;
 }
 
@@ -512,14 +522,33 @@ static int take_next_model_id(mf_ctx* c) {
     return next;
 }
 
+// which models the tracking loop over models[first..] tracks and which follow the background (MaskFusion.cpp:261-274); batch: the tracked ones go
+// through the batched loop.  A frame computes its plan once: the preprocessing and the tracking loop must see the same one.
+struct TrackingPlan { std::vector<ModelState*> tracked, follow; bool batch = false; };
+static void tracking_plan(mf_ctx* c, size_t first, bool track_all, TrackingPlan& p) {
+    ModelState& bg = *c->models[0];
+    p.tracked.clear(); p.follow.clear();
+    if (first == 0) p.tracked.push_back(&bg);
+    for (size_t i = 1; i < c->models.size(); ++i) {
+        ModelState& m = *c->models[i];
+        // trackable = trackableClassIds.empty() || trackableClassIds.count(classID), :261
+        bool trackable = c->trackable.empty();
+        for (int id : c->trackable) trackable |= (id == m.classID);
+        if ((!m.isStatic || track_all) && trackable) p.tracked.push_back(&m);   // jump rule of :268-272 in the finalize step
+        else p.follow.push_back(&m);
+    }
+    p.batch = !photometric_on(c) && p.tracked.size() >= 2 && (int)p.tracked.size() <= kMaxTrackBatch && c->batch_tracking;
+}
+
 // filterDepth (Core/MaskFusion.cpp:217) + Model::generateCUDATextures (Model.cpp:350-389) + the frame's intensity pyramid and
 // derivative images, for frame index k (buffer set k & 1, filtered-depth ring slot k % 3).
 // (It runs at the head of the frame's chain on the context's stream.  Running it one frame ahead on a stream of its own, beside the previous
 // frame's fusion kernels, lost in rounds 2 and 5 -- also with that stream masked to 16 / 32 / 64 compute units: DESIGN.md, "Measured and rejected".)
-// pyr_model: the model whose tracking step follows on this stream with nothing in between that its model-side pyramid depends on -- the pyramid
-// (launch_model_pyramid's arguments, as enqueue_track passes them) is then built in the filter's launch
-static int enqueue_preprocess(mf_ctx* c, const uint8_t* d_rgb, const float* d_depth, long k, bool with_maps, ModelState* pyr_model = nullptr,
-                              const float* pyr_fill_depth = nullptr, const std::vector<ModelState*>* pyr_batch = nullptr) {
+// pyr_plan: the tracking plan whose steps follow on this stream with nothing in between that their model-side pyramids depend on -- the pyramids
+// (launch_model_pyramid[_batch]'s arguments, as enqueue_track[_batch] pass them) are then built in the filter's launch: every tracked model's of
+// a batched plan, else the first one's (the background's; the others build theirs behind its step).  The caller tells the tracking loop so.
+static int enqueue_preprocess(mf_ctx* c, const uint8_t* d_rgb, const float* d_depth, long k, bool with_maps, const TrackingPlan* pyr_plan = nullptr,
+                              const float* pyr_fill_depth = nullptr) {
     const int W = c->W, H = c->H, P = c->P;
     hipStream_t s = c->stream;
     const mf_config& g = c->cfg;
@@ -527,18 +556,12 @@ static int enqueue_preprocess(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
     float* depthF = c->d_depthF[k % 3];
     hipStream_t sp = s;
     mark(c, 0, sp);
-    if (pyr_model) {
-        ModelState& m = *pyr_model;
+    if (pyr_plan && pyr_plan->batch) {   // the batched tracker's pyramids (enqueue_track_batch's first launch) beside the filter
+        launch_bilateral_model_pyramid_batch(d_depth, depthF, track_batch_of(pyr_plan->tracked), pyr_fill_depth, W, H, c->K, sp);
+    } else if (pyr_plan) {
+        ModelState& m = *pyr_plan->tracked.front();
         launch_bilateral_model_pyramid(d_depth, depthF, m.d_predV, m.d_predN, m.allowFillIn ? pyr_fill_depth : nullptr, m.d_frame, m.d_pose, m.d_vmap_g,
                                        m.d_nmap_g, W, H, c->K, sp);
-        c->pyr_done = pyr_model;
-    } else if (pyr_batch) {   // the batched tracker's pyramids (enqueue_track_batch's first launch) beside the filter
-        TrackBatch b;
-        memset(&b, 0, sizeof(b));
-        b.n = (int)pyr_batch->size();
-        for (int i = 0; i < b.n; ++i) b.m[i] = (*pyr_batch)[i]->d_track;
-        launch_bilateral_model_pyramid_batch(d_depth, depthF, b, pyr_fill_depth, W, H, c->K, sp);
-        c->pyr_batch_done = true;
     } else {
         launch_bilateral(d_depth, depthF, W, H, sp);
     }
@@ -603,7 +626,8 @@ static int spawn_object(mf_ctx* c, int id, int classID) {
         c->pool.erase(c->pool.begin());
         nm->id = id;
         nm->confThr = g.conf_object;
-        nm->age = 0; nm->isStatic = true; nm->log_ts.clear(); nm->cur = 0; nm->table_valid = false; nm->sparse = false; nm->phys_ub = nm->runs_ub = -1; nm->gen++; nm->mirror_from = nm->clean_seq + 1;
+        nm->age = 0; nm->isStatic = true; nm->log_ts.clear();
+        nm->reset_empty();
         hipLaunchKernelGGL(k_pose_identity, dim3(1), dim3(64), 0, s, nm->d_pose, c->weight_literal ? 1 : 0);
         hipLaunchKernelGGL(k_frame_init, dim3(1), dim3(64), 0, s, nm->d_frame, c->host_tick);
         nm->h_frame->tick = c->host_tick;
@@ -622,34 +646,20 @@ static int spawn_object(mf_ctx* c, int id, int classID) {
     return MF_OK;
 }
 
-// The tracking loop of processFrame (Core/MaskFusion.cpp:247-276) over models[first..]: every model that is tracked this frame goes
-// into one batch (geometric term) or is tracked on its own (photometric term: its scratch images are shared); static objects then follow
-// the background's NEW pose (models[0]'s pose: on a context that holds only objects the caller has overridden it with the owner's).
-// which models the tracking loop tracks and which follow the background (MaskFusion.cpp:261-274); true: the tracked ones go through the batched loop
-static bool tracking_plan(mf_ctx* c, size_t first, bool track_all, std::vector<ModelState*>& tracked, std::vector<ModelState*>& follow) {
+// The tracking loop of processFrame (Core/MaskFusion.cpp:247-276) over a plan: every model that is tracked this frame goes into one batch
+// (geometric term) or is tracked on its own (photometric term: its scratch images are shared); static objects then follow the background's NEW
+// pose (models[0]'s pose: on a context that holds only objects the caller has overridden it with the owner's).
+// pyr_built: enqueue_preprocess has built the plan's model-side pyramids beside this frame's depth filter (see there for which)
+static void enqueue_tracking_loop(mf_ctx* c, const TrackingPlan& plan, const float* depthF_prev, long k, bool pyr_built) {
     ModelState& bg = *c->models[0];
-    tracked.clear(); follow.clear();
-    if (first == 0) tracked.push_back(&bg);
-    for (size_t i = 1; i < c->models.size(); ++i) {
-        ModelState& m = *c->models[i];
-        // trackable = trackableClassIds.empty() || trackableClassIds.count(classID), :261
-        bool trackable = c->trackable.empty();
-        for (int id : c->trackable) trackable |= (id == m.classID);
-        if ((!m.isStatic || track_all) && trackable) tracked.push_back(&m);   // jump rule of :268-272 in the finalize step
-        else follow.push_back(&m);
-    }
-    return !photometric_on(c) && tracked.size() >= 2 && (int)tracked.size() <= kMaxTrackBatch && c->batch_tracking;
-}
-static void enqueue_tracking_loop(mf_ctx* c, size_t first, bool track_all, const float* depthF_prev, long k) {
-    ModelState& bg = *c->models[0];
-    std::vector<ModelState*> tracked, follow;
-    if (tracking_plan(c, first, track_all, tracked, follow)) {
-        enqueue_track_batch(c, tracked, depthF_prev, k);
+    if (plan.batch) {
+        enqueue_track_batch(c, plan.tracked, depthF_prev, k, pyr_built);
     } else {
-        for (ModelState* m : tracked) enqueue_track(c, *m, m == &bg ? depthF_prev : nullptr, m == &bg ? 0.f : 0.2f, k);
+        for (ModelState* m : plan.tracked)
+            enqueue_track(c, *m, m == &bg ? depthF_prev : nullptr, m == &bg ? 0.f : 0.2f, k, pyr_built && m == plan.tracked.front());
     }
-    for (ModelState* m : follow) launch_static_pose(m->d_pose, bg.d_pose, m->h_pose, c->stream);   // updateStaticPose, :274
-    for (auto& m : c->models) m->gen++;   // the poses changed: cached visibility lists are stale
+    for (ModelState* m : plan.follow) launch_static_pose(m->d_pose, bg.d_pose, m->h_pose, c->stream);   // updateStaticPose, :274
+    for (auto& m : c->models) m->touched();   // the poses changed
 }
 
 // The fusion loop of processFrame (Core/MaskFusion.cpp:539-565) over models[first..]: predictIndices -> fuse -> predictIndices -> clean;
@@ -667,35 +677,27 @@ static int enqueue_fusion_loop(mf_ctx* c, size_t first, bool multi, const uint8_
         object_models(c, objs, orders);
         // one form per launch: the batch takes the form of its largest model.  In place (every model keeps a run table) when a model is big and
         // none of them is within a frame's candidates of its capacity; else the two-launch clean on dense buffers
-        bool any_big = false, in_place = true;
+        bool any_big = false;
         for (ModelState* m : objs) any_big |= !clean_small(c, *m);
-        if (any_big) {
-            for (ModelState* m : objs) {
-                bool ok = true;
-                int rc = prepare_in_place(c, *m, ok);
-                if (rc != MF_OK) return rc;
-                in_place &= ok;
-            }
-        } else in_place = false;
-        if (!in_place) for (ModelState* m : objs) require_dense(c, *m);
+        CleanForm form;
+        int rc = prepare_clean(c, objs.data(), objs.size(), any_big, form);
+        if (rc != MF_OK) return rc;
+        const bool in_place = form.in_place;
         ObjBatch ob; int blocks = 0;
         obj_stream_catch_up(c);
-        int rc = make_obj_batch(c, objs, orders, d_rgb, d_depth, depthF, mask, weight_multiplier, nullptr, ob, blocks, c->obj_s);   // (after the compactions: they change the live buffer)
+        rc = make_obj_batch(c, objs, orders, d_rgb, d_depth, depthF, mask, weight_multiplier, nullptr, ob, blocks, c->obj_s);   // (after the compactions: they change the live buffer)
         if (rc != MF_OK) return rc;
         int cblocks = 64;
         for (ModelState* m : objs) cblocks = std::max(cblocks, clean_runs_grid((long)*m->h_count + kRun));
-        ob.cleanSmall = in_place ? 0 : 1; ob.updateCopy = in_place ? 0 : 1;
-        if (!in_place) for (ModelState* m : objs) if (!update_copy(c, *m)) ob.updateCopy = 0;
+        ob.cleanSmall = in_place ? 0 : 1; ob.updateCopy = form.update_copy ? 1 : 0;
         {
             PassTimer timer(c, MF_PASS_OBJ_FUSE_CLEAN, c->obj_s);
             long most = 0;
             for (ModelState* m : objs) most = std::max(most, (long)*m->h_count);
             launch_obj_fuse_clean(ob, blocks, cblocks, c->obj_s, in_place ? kCompactBlocks : compact_blocks_for(most + cand_max(c)));
         }
-        for (ModelState* m : objs) {   // copy-update: a -> b -> a; in-place update + two-launch clean: a -> b -- b is the live buffer now; in place: a
-            if (!in_place && !ob.updateCopy) m->cur = 1 - m->cur;
-            after_clean(c, *m, in_place);
-        }
+        // copy-update: a -> b -> a; in-place update + two-launch clean: a -> b -- b is the live buffer now; in place: a
+        for (ModelState* m : objs) after_clean(c, *m, in_place, form.update_copy ? m->cur : 1 - m->cur);
     }
     return MF_OK;
 }
@@ -775,9 +777,9 @@ static int retire_model(mf_ctx* c, size_t i) {
         if (c->d_retired && c->retired_used + n <= c->retired_cap) {
             // chronological order: entries n_all - n .. n_all - 1 of a ring of `cap` slots -> at most two contiguous pieces
             const size_t first = (n_all - n) % cap, run1 = (first + n <= cap) ? n : cap - first;
-            MF_HIP(c, hipMemcpyAsync(c->d_retired + c->retired_used * 8, m->d_poselog + first * 8, run1 * 8 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            if (run1 < n)
-                MF_HIP(c, hipMemcpyAsync(c->d_retired + (c->retired_used + run1) * 8, m->d_poselog, (n - run1) * 8 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            float* const to = c->d_retired + c->retired_used * 8;
+            MF_HIP(c, hipMemcpyAsync(to, m->d_poselog + first * 8, run1 * 8 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            if (run1 < n) MF_HIP(c, hipMemcpyAsync(to + run1 * 8, m->d_poselog, (n - run1) * 8 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
             r.arena_off = c->retired_used; r.in_arena = true;
             c->retired_used += n;
         } else {
@@ -789,8 +791,10 @@ static int retire_model(mf_ctx* c, size_t i) {
     }
     std::unique_ptr<ModelState> owned = std::move(c->models[i]);
     c->models.erase(c->models.begin() + (long)i);
-    owned->id = -1; owned->classID = -1; owned->age = 0; owned->isStatic = true; owned->log_ts.clear(); owned->cur = 0; owned->table_valid = false; owned->sparse = false; owned->phys_ub = owned->runs_ub = -1; owned->gen++; owned->mirror_from = owned->clean_seq + 1; owned->pred_gray_valid = false;
+    owned->id = -1; owned->classID = -1; owned->age = 0; owned->isStatic = true; owned->log_ts.clear();   // the identity of no model
+    owned->pred_gray_valid = false;
     owned->maxDepth = FLT_MAX;
+    owned->reset_empty();
     *owned->h_count = 0;
     if (c->vis_tag.model == owned.get()) c->vis_tag.model = nullptr;
     c->pool.push_back(std::move(owned));
@@ -836,17 +840,12 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
     c->mm_marked = false;
     ObjStreamWindow obj_window(c);   // (joins on every way out of this function)
 
-    // the background's tracking step follows the preprocessing directly (model by model: the batched loop builds every model's pyramid in its own
-    // launch): its model-side pyramid rides in the depth filter's launch
-    ModelState* pyr_model = nullptr;
-    std::vector<ModelState*> pyr_tracked, pyr_follow;
-    bool pyr_batch = false;
-    c->pyr_done = nullptr; c->pyr_batch_done = false;
-    if (c->fused_preprocess && c->map_ready && !(in_pose16 && !bootstrap)) {
-        if (tracking_plan(c, 0, g.track_all_models != 0, pyr_tracked, pyr_follow)) pyr_batch = true;   // ... or every tracked model's, batched
-        else pyr_model = &bg;
-    }
-    int prc = enqueue_preprocess(c, d_rgb, d_depth, k, c->map_ready, pyr_model, depthF_prev, pyr_batch ? &pyr_tracked : nullptr);
+    // the frame's tracking plan, computed once.  In a frame that tracks, the tracking loop follows the preprocessing directly: the plan's model-side
+    // pyramids ride in the depth filter's launch ("fusedPreprocessLaunch"), and the loop is told so
+    TrackingPlan plan;
+    tracking_plan(c, 0, g.track_all_models != 0, plan);
+    const bool pyr_built = c->fused_preprocess && c->map_ready && !(in_pose16 && !bootstrap);
+    int prc = enqueue_preprocess(c, d_rgb, d_depth, k, c->map_ready, pyr_built ? &plan : nullptr, depthF_prev);
     if (prc != MF_OK) return prc;
 
     if (!c->map_ready) {
@@ -854,17 +853,16 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
         mark(c, 2); mark(c, 3); mark(c, 4); mark(c, 5); mark(c, 6);
         // :235-238
         launch_init_surfels(d_rgb, d_depth, depthF, W, H, c->K, g.max_depth_processed, bg.d_frame, c->d_cand_rec, c->d_flags, s);
-        bg.cur = 0;
         launch_compact_records(c->d_cand_rec, c->d_flags, P, bg.surf[0], bg.d_frame, c->d_block_counts, bg.h_count, s);
         launch_run_table(bg.surf[0], bg.d_frame, s);
-        bg.table_valid = true; bg.sparse = false; bg.phys_ub = P; bg.runs_ub = ((long)P + kRun - 1) / kRun; bg.gen++; bg.mirror_from = bg.clean_seq + 1;
+        bg.fresh_table(0, (long)P);
         mark(c, 7);
     } else if (in_pose16 && !bootstrap) {
         // the caller supplies the camera pose: no tracking, no segmentation, object poses untouched
         // (MaskFusion.cpp:243,413-415 -- the whole "regular" block is skipped)
         mark(c, 2);
         launch_override_pose(bg.d_pose, in_pose16, 0, bg.h_pose, s);
-        bg.gen++;
+        bg.touched();
         mark(c, 3); mark(c, 4);
         if (!g.rgb_only)   // :539
           for (size_t i = 0; i < c->models.size(); ++i) {
@@ -876,8 +874,8 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
         mark(c, 2);
         // tracking, :247-276.  Every model that is tracked this frame goes into one batch (geometric term) or is tracked on its
         // own (photometric term: its scratch images are shared); static objects then follow the background's NEW pose
-        enqueue_tracking_loop(c, 0, g.track_all_models != 0, depthF_prev, k);
-        if (bootstrap && in_pose16) { launch_override_pose(bg.d_pose, in_pose16, 1, bg.h_pose, s); bg.gen++; }   // :280-283 (after the object loop)
+        enqueue_tracking_loop(c, plan, depthF_prev, k, pyr_built);
+        if (bootstrap && in_pose16) { launch_override_pose(bg.d_pose, in_pose16, 1, bg.h_pose, s); bg.touched(); }   // :280-283 (after the object loop)
         mark(c, 3);
 
         if (multi) {

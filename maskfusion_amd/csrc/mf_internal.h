@@ -332,6 +332,9 @@ void launch_cull_clean(Surfels s, const FrameDev* frame, const PoseDev* pose, in
                        int* list, int* count, int* ctl, int max_runs, hipStream_t st);
 // compaction of a sparse buffer: the surfels of src's runs -> dst, dense (no table); offs: scratch of run_table_runs() + 1 ints
 void launch_densify(Surfels src, Surfels dst, FrameDev* frame, int* offs, int* host_count, hipStream_t st);
+// its first step on its own (k_run_offsets): offs[r] = live surfels before run r, offs[runs] = all of them; *total (optional) = the live surfels of the
+// buffer, with or without a table
+void launch_run_offsets(Surfels s, const FrameDev* frame, int* offs, int* total, hipStream_t st);
 // generic ordered compaction of [n_dev] records (3 x float4 each, record-major) -> surfels, sets frame->count
 void launch_compact_records(const float4* rec, const uint8_t* flags, int n, Surfels dst, FrameDev* frame,
                             int* block_counts, int* host_count_mirror, hipStream_t s);
@@ -440,9 +443,7 @@ uint64_t nn_workspace_bytes(int64_t n_target);
 int nn_run(const float* d_target, int target_stride, int64_t n_target, const float* d_query, int query_stride, int64_t n_query,
            const float* T16 /*host, column-major, or null*/, float radius, float* d_dist, int32_t* d_idx, void* d_ws, uint64_t ws_bytes, hipStream_t s,
            const char** why);
-// a model's live surfels in download order: offs[r] = surfels before run r, *total = all of them (launch_nn_live), then their positions -> out[n]
-// (NaN for confidence <= thr; launch_nn_gather).  offs: run_table_runs() + 1 ints
-void launch_nn_live(Surfels s, const FrameDev* frame, int* offs, int* total, hipStream_t st);
+// a model's live surfels in download order (offs: launch_run_offsets): their positions -> out[n], NaN for confidence <= thr
 void launch_nn_gather(Surfels s, const FrameDev* frame, const int* offs, float thr, float4* out, int n, int max_runs, hipStream_t st);
 
 // end-of-frame bookkeeping: tick++, cover -> useFillIn decision for the next frame

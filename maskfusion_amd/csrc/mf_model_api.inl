@@ -18,12 +18,7 @@ static __global__ void k_set_count(FrameDev* f, int count, int* host_count) {
 }
 static void set_model_tick(mf_ctx* c, ModelState& m, int tick) {
     hipLaunchKernelGGL(k_set_tick, dim3(1), dim3(64), 0, c->stream, m.d_frame, tick, m.h_frame);
-    m.gen++;   // (what is "seen within timeDelta" changes with the tick: cached visibility lists are stale)
-}
-// bookkeeping behind a call that replaced m's buffer by a dense one of (at most) n surfels and built its run table
-static void fresh_table(mf_ctx* c, ModelState& m, long n) {
-    m.table_valid = true; m.sparse = false; m.phys_ub = n; m.runs_ub = (n + kRun - 1) / kRun; m.gen++; m.mirror_from = m.clean_seq + 1;
-    c->vis_tag.model = nullptr;
+    m.touched();   // (what is "seen within timeDelta" changes with the tick)
 }
 static long staged_frame(const mf_ctx* c) { return c->frame_no - 1; }   // index of the frame staged / processed last
 static const uint8_t* current_mask(const mf_ctx* c) { return c->cfg.enable_multiple_models ? c->d_mask_tex : c->d_zero_mask; }
@@ -68,7 +63,8 @@ extern "C" int mf_model_initialise(mf_ctx* c, int32_t model) {
                         c->d_flags, c->stream);
     launch_compact_records(c->d_cand_rec, c->d_flags, c->P, m->surf[m->cur], m->d_frame, c->d_block_counts, m->h_count, c->stream);
     launch_run_table(m->surf[m->cur], m->d_frame, c->stream);
-    fresh_table(c, *m, (long)c->P);
+    m->fresh_table(m->cur, (long)c->P);
+    c->vis_tag.model = nullptr;
     if (model == 0) c->map_ready = true;
     return check_launch(c);
 }
@@ -92,7 +88,8 @@ extern "C" int mf_model_upload_map(mf_ctx* c, int32_t model, const float* surfel
     }
     hipLaunchKernelGGL(k_set_count, dim3(1), dim3(64), 0, c->stream, m->d_frame, (int)count, m->h_count);
     launch_run_table(m->surf[m->cur], m->d_frame, c->stream);
-    fresh_table(c, *m, (long)count);
+    m->fresh_table(m->cur, (long)count);
+    c->vis_tag.model = nullptr;
     if (model == 0) c->map_ready = true;   // the map exists: the next mf_process_frame tracks instead of initialising
     return check_launch(c);
 }
@@ -102,7 +99,7 @@ extern "C" int mf_model_override_pose(mf_ctx* c, int32_t model, const float* pos
     ModelState* m = model_at(c, model);
     if (!m || !pose16) return MF_EINVAL;
     launch_override_pose(m->d_pose, pose16, 0, m->h_pose, c->stream);
-    m->gen++;
+    m->touched();
     c->vis_tag.model = nullptr;   // a visibility list belongs to ONE pose
     return check_launch(c);
 }
@@ -148,7 +145,7 @@ extern "C" int mf_model_perform_tracking(mf_ctx* c, int32_t model, int32_t frame
     // tryFillIn = MaskFusion::requiresFillIn(model) (:630-648): the decision itself is taken on the device from the coverage of the
     // last prediction; here it only gates whether the fill-in source (the previous frame's filtered depth) is offered at all
     // object models carry the 0.2 m jump rule of the caller (MaskFusion.cpp:268-272): pose->alive = 0 marks "remove this model"
-    enqueue_track(c, *m, (try_fill_in && m->allowFillIn) ? c->d_depthF[(k + 2) % 3] : nullptr, model == 0 ? 0.f : 0.2f, k);
+    enqueue_track(c, *m, (try_fill_in && m->allowFillIn) ? c->d_depthF[(k + 2) % 3] : nullptr, model == 0 ? 0.f : 0.2f, k, false);
     c->cfg = keep;
     c->ftf_rgb = keep_ftf;
     return check_launch(c);
@@ -186,7 +183,7 @@ extern "C" int mf_model_fuse(mf_ctx* c, int32_t model, int32_t time, float depth
     // merged surfels moved and were seen now: the boxes and time stamps of their runs are refreshed (inside mf_process_frame the clean pass that
     // follows rewrites the entries of every run it visits -- and it visits every run a merge can have touched)
     if (m->table_valid) launch_run_table(m->surf[m->cur], m->d_frame, s, true);
-    m->gen++;
+    m->touched();
     return check_launch(c);
 }
 
@@ -199,23 +196,13 @@ extern "C" int mf_model_clean(mf_ctx* c, int32_t model, int32_t time, int32_t ti
     const long k = staged_frame(c);
     set_model_tick(c, *m, time);
     const bool packed = c->model_api_packed != 0;
-    bool small = clean_small(c, *m);
-    if (!small) {
-        bool ok = true;
-        int rc = prepare_in_place(c, *m, ok);
-        if (rc != MF_OK) return rc;
-        small = !ok;
-    } else {
-        require_dense(c, *m);
-    }
+    CleanForm form;
+    int rc = prepare_clean(c, &m, 1, !clean_small(c, *m), form);
+    if (rc != MF_OK) return rc;
     CleanIn in = clean_in(c, *m, time_delta, packed, c->d_depthF[k % 3], current_mask(c));
-    if (small) {
-        launch_clean_small(in, m->surf[m->cur], m->surf[1 - m->cur], c->stream);
-        m->cur = 1 - m->cur;
-    } else {
-        enqueue_clean_in_place(c, *m, in, false);   // (no decay statistics outside a frame: every run is visited)
-    }
-    after_clean(c, *m, !small);
+    if (form.in_place) enqueue_clean_in_place(c, *m, in, false);   // (no decay statistics outside a frame: every run is visited)
+    else launch_clean_small(in, m->surf[m->cur], m->surf[1 - m->cur], c->stream);
+    after_clean(c, *m, form.in_place, 1 - m->cur);
     return check_launch(c);
 }
 
@@ -270,7 +257,9 @@ extern "C" int mf_track_models(mf_ctx* c, int32_t first_model, int32_t track_all
         for (size_t i = (size_t)first_model; i < c->models.size(); ++i) ok = ok && c->models[i]->pred_gray_valid;
         if (!ok) { c->err = "mf_track_models: photometric term configured, but the staged frame / a prediction carries no intensity images"; return MF_ESTATE; }
     }
-    enqueue_tracking_loop(c, (size_t)first_model, track_all_models != 0, c->d_depthF[(k + 2) % 3], k);
+    TrackingPlan plan;
+    tracking_plan(c, (size_t)first_model, track_all_models != 0, plan);
+    enqueue_tracking_loop(c, plan, c->d_depthF[(k + 2) % 3], k, false);   // (a staged frame's preprocessing builds no model-side pyramid)
     return check_launch(c);
 }
 // the fusion loop, Core/MaskFusion.cpp:539-565, preceded -- when spawned_model >= 1 -- by the spawn-frame pass of that model

@@ -1331,8 +1331,9 @@ int clean_runs_grid(long elements) {
 // compaction of a sparse buffer: src's runs -> dst, dense (slots [0, count), no table).  Host-driven (mf_frame.inl: densify), when the slots
 // behind the last run or the table entries run out, before a download, before a model's passes return to the small-map forms.
 // ------------------------------------------------------------------------------------------------
-// offs[r] = live surfels of the runs before run r (offs[runs] = all of them): one workgroup
-__global__ __launch_bounds__(1024) void k_run_offsets(Surfels s, const FrameDev* __restrict__ frame, int* __restrict__ offs) {
+// offs[r] = live surfels of the runs before run r, offs[runs] = all of them; *total (optional) = the buffer's live surfels, also of a dense buffer
+// without a table (runs == 0: offs[0] = 0, *total = count).  One workgroup.
+__global__ __launch_bounds__(1024) void k_run_offsets(Surfels s, const FrameDev* __restrict__ frame, int* __restrict__ offs, int* __restrict__ total) {
     __shared__ int s_w[16];
     const int runs = frame->runs;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1340,31 +1341,27 @@ __global__ __launch_bounds__(1024) void k_run_offsets(Surfels s, const FrameDev*
     for (int base = 0; base < runs; base += 1024) {
         const int r = base + (int)threadIdx.x;
         const int v = r < runs ? run_len(s.box, r) : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
+        const int x = wave_scan(v, lane);
         if (lane == 63) s_w[wave] = x;
         __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < 16; ++w) { if (w < wave) before += s_w[w]; total += s_w[w]; }
+        int before = 0, sum = 0;
+        for (int w = 0; w < 16; ++w) { if (w < wave) before += s_w[w]; sum += s_w[w]; }
         if (r < runs) offs[r] = carry + before + x - v;
-        carry += total;
+        carry += sum;
         __syncthreads();
     }
-    if (threadIdx.x == 0) offs[runs] = carry;
+    if (threadIdx.x == 0) {
+        offs[runs] = carry;
+        if (total) *total = runs > 0 ? carry : frame->count;
+    }
+}
+void launch_run_offsets(Surfels s, const FrameDev* frame, int* offs, int* total, hipStream_t st) {
+    hipLaunchKernelGGL(k_run_offsets, dim3(1), dim3(1024), 0, st, s, frame, offs, total);
 }
 __global__ __launch_bounds__(256) void k_densify(Surfels src, Surfels dst, const FrameDev* __restrict__ frame, const int* __restrict__ offs) {
-    const int runs = frame->runs;
-    for (int r = blockIdx.x; r < runs; r += gridDim.x) {
-        const int start = run_start(src.box, r), len = run_len(src.box, r), o = offs[r];
-        for (int q = threadIdx.x; q < len; q += 256) {
-            if (o + q >= dst.cap) break;
-            dst.pc[o + q] = src.pc[start + q]; dst.ct[o + q] = src.ct[start + q]; dst.nr[o + q] = src.nr[start + q];
-        }
-    }
+    for_each_live_ordered(src, frame, offs, dst.cap, [&](int from, int to) {
+        dst.pc[to] = src.pc[from]; dst.ct[to] = src.ct[from]; dst.nr[to] = src.nr[from];
+    });
 }
 __global__ void k_densify_finish(FrameDev* __restrict__ frame, const int* __restrict__ offs, int cap, int* __restrict__ host_count) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -1374,7 +1371,7 @@ __global__ void k_densify_finish(FrameDev* __restrict__ frame, const int* __rest
     if (host_count) *host_count = n;
 }
 void launch_densify(Surfels src, Surfels dst, FrameDev* frame, int* offs, int* host_count, hipStream_t st) {
-    hipLaunchKernelGGL(k_run_offsets, dim3(1), dim3(1024), 0, st, src, frame, offs);
+    launch_run_offsets(src, frame, offs, nullptr, st);
     hipLaunchKernelGGL(k_densify, dim3(2048), dim3(256), 0, st, src, dst, frame, offs);
     hipLaunchKernelGGL(k_densify_finish, dim3(1), dim3(64), 0, st, frame, offs, dst.cap, host_count);
 }

@@ -29,5 +29,19 @@ __device__ __forceinline__ void for_each_surfel_slice(const Surfels& src, const 
     for (int i0 = blockIdx.x * kPer; i0 < n; i0 += gridDim.x * kPer) f(i0 + sub, i0 + sub < n);
 }
 
+// The live surfels of a buffer in download order (mf_download_map: the runs in order, each run's first len slots; a dense buffer without a table:
+// slots [0, count) in chunks of kRun): f(source slot, ordinal) for every one whose ordinal is below `limit`.  offs[r] = live surfels before run r
+// (k_run_offsets; not read for a dense buffer).  Workgroups of 256 threads, any grid.
+template <class F>
+__device__ __forceinline__ void for_each_live_ordered(const Surfels& s, const FrameDev* __restrict__ frame, const int* __restrict__ offs, int limit, F&& f) {
+    const int runs = frame->runs;
+    const int nr = runs > 0 ? runs : (frame->count + kRun - 1) / kRun;
+    for (int r = blockIdx.x; r < nr; r += gridDim.x) {
+        int start, len, o;
+        if (runs > 0) { start = run_start(s.box, r); len = run_len(s.box, r); o = offs[r]; }
+        else { start = o = r * kRun; len = min(kRun, frame->count - start); }
+        for (int q = threadIdx.x; q < len && o + q < limit; q += 256) f(start + q, o + q);
+    }
+}
 
 }  // namespace mf

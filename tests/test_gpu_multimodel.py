@@ -256,39 +256,44 @@ def test_tiled_global_projection_equals_scatter_form(hip):
     assert len(runs[0][-1][2]) >= 2 and nonzero > 500, "objects must spawn and project"
 
 
+def _small_scene_run(track_all=False, n_frames=11, preallocate=0, **params):
+    """a 320 x 240 scene of three standing boxes through mf_process_frame: the final models' ids, poses, counts, clouds and predictions, every label image"""
+    from maskfusion_amd import MaskFusion, synth
+    W, H, f = 320, 240, 264.0
+    st = synth.Stream(W=W, H=H, fx=f, fy=f, cx=W / 2.0, cy=H / 2.0, n_objects=3, noise=True, object_motion=0.0)
+    mf = MaskFusion(W, H, f, f, W / 2.0, H / 2.0, icpThresh=100.0, so3=False, numGSurfels=1 << 18, numOSurfels=1 << 16, enableMultipleModels=True,
+                    modelSpawnOffset=2, trackAllModels=track_all)
+    if preallocate:
+        mf.preallocateModels(preallocate)
+    for k, v in dict(mfThreshold=SEG["threshold"], mfWeightDistance=SEG["weightDistance"], mfWeightConvexity=SEG["weightConvexity"],
+                     mfMorphEdgeIterations=0, mfMorphMaskIterations=0, newModelMinRelativeSize=SEG["minRelSizeNew"], **params).items():
+        mf.setParam(k, v)
+    segs = []
+    for k in range(n_frames):
+        rgb, d, mask = st.frame(k)
+        mf.processFrame(rgb, d, mask=mask, classIDs=[0, 41, 42, 43], timestamp=k)
+        segs.append(mf.downloadSegmentation())
+    ms = mf.getModels()
+    out = dict(ids=[m.getID() for m in ms], poses=[m.getPose() for m in ms], counts=[m.lastCount() for m in ms], clouds=[m.downloadMap() for m in ms],
+               segs=segs, preds=[m.debugRead("pred_vertex") for m in ms])
+    mf.close()
+    return out
+
+
+def _same(a, b):
+    if isinstance(a, dict):
+        return all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, list):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
+
+
 def test_object_model_launch_switches_change_nothing(hip):
     """"objectSmallGrids" (the grid-stride surfel kernels of an object model on a grid sized from its last known count),
     "objectScatterSplat" (object models predicted with the scatter form instead of tile lists) and "batchObjectPasses" (one launch per
     surfel pass for ALL object models, grid.z = model) only re-arrange launches of the launch-bound multi-model frames: label images,
     poses, clouds and predictions must stay bit-identical"""
-    from maskfusion_amd import MaskFusion, synth
-
-    def run(track_all=False, **params):
-        W, H, f = 320, 240, 264.0
-        st = synth.Stream(W=W, H=H, fx=f, fy=f, cx=W / 2.0, cy=H / 2.0, n_objects=3, noise=True, object_motion=0.0)
-        mf = MaskFusion(W, H, f, f, W / 2.0, H / 2.0, icpThresh=100.0, so3=False, numGSurfels=1 << 18, numOSurfels=1 << 16, enableMultipleModels=True,
-                        modelSpawnOffset=2, trackAllModels=track_all)
-        for k, v in dict(mfThreshold=SEG["threshold"], mfWeightDistance=SEG["weightDistance"], mfWeightConvexity=SEG["weightConvexity"],
-                         mfMorphEdgeIterations=0, mfMorphMaskIterations=0, newModelMinRelativeSize=SEG["minRelSizeNew"], **params).items():
-            mf.setParam(k, v)
-        segs = []
-        for k in range(11):
-            rgb, d, mask = st.frame(k)
-            mf.processFrame(rgb, d, mask=mask, classIDs=[0, 41, 42, 43], timestamp=k)
-            segs.append(mf.downloadSegmentation())
-        ms = mf.getModels()
-        out = dict(ids=[m.getID() for m in ms], poses=[m.getPose() for m in ms], clouds=[m.downloadMap() for m in ms], segs=segs,
-                   preds=[m.debugRead("pred_vertex") for m in ms])
-        mf.close()
-        return out
-
-    def same(a, b):
-        if isinstance(a, dict):
-            return all(same(a[k], b[k]) for k in a)
-        if isinstance(a, list):
-            return len(a) == len(b) and all(same(x, y) for x, y in zip(a, b))
-        return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
-
+    run, same = _small_scene_run, _same
     off = dict(objectSmallGrids=0, objectScatterSplat=0, batchObjectPasses=0)
     base = run(**off)
     assert len(base["ids"]) >= 3, "the scenario must hold two object models (the batched passes need two)"
@@ -313,3 +318,19 @@ def test_object_model_launch_switches_change_nothing(hip):
     assert same(tracked_one, run(track_all=True, objectStream=0, fusedPreprocessLaunch=0))
     assert same(tracked_one, run(track_all=True, objectStream=0, batchSolveInPixelPass=0))
     assert same(tracked_one, run(track_all=True, objectStream=0, fusedPreprocessLaunch=0, batchSolveInPixelPass=0))
+
+
+def test_pooled_model_reused_after_an_in_place_life(hip):
+    """A model that goes back to the pool and out again starts from an empty buffer whatever shape its last life left: with `bigMapElements` =
+    `inPlaceElements` = 0 every model's clean is in place from its first one (a sparse buffer with a device-maintained run table, bounds and
+    mirrors on the host), with the defaults these maps stay dense.  At 320 x 240 a tracked 0.3 m box falls to the 0.2 m jump rule at once and is
+    re-spawned every other frame (test_gpu_switches.py: test_trackable_class_ids_vs_oracle), so with two preallocated models every spawn after
+    the first two takes a retired one.  The forms compute the same bits: ids, poses, counts, clouds, predictions and label images agree."""
+    in_place = _small_scene_run(track_all=True, n_frames=8, preallocate=2, bigMapElements=0, inPlaceElements=0)
+    defaults = _small_scene_run(track_all=True, n_frames=8, preallocate=2)
+    for r in (in_place, defaults):
+        print("final ids", r["ids"], "counts", r["counts"])
+        assert len(r["ids"]) >= 2 and r["ids"][0] == 0
+        assert all(i > 1 for i in r["ids"][1:]), "no retirement and re-spawn: the first id handed out (1) is still in the list"
+    assert in_place["ids"] == defaults["ids"] and in_place["counts"] == defaults["counts"]
+    assert _same(in_place, defaults)

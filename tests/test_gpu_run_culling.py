@@ -725,7 +725,7 @@ def test_entry_points_on_a_sparse_buffer(field152, call, tmp_path):
 
 
 def test_model_cloud_nn_on_a_sparse_map_of_more_than_1024_runs(hip):
-    """k_nn_live_offsets scans the run table in chunks of 1024 runs with a carry: a sparse map of > 1024 runs (>= 600 k live surfels) with EMPTIED runs among
+    """k_run_offsets scans the run table in chunks of 1024 runs with a carry: a sparse map of > 1024 runs (>= 600 k live surfels) with EMPTIED runs among
     them (every 9th run of the uploaded map dies in the first frame), against ev.nearest on the download with the same NaN filter, bit for bit."""
     from maskfusion_amd import eval as ev, synth
     sc = _scenario(200, 152)
