@@ -230,6 +230,29 @@ int mf_cloud_icp_build_dev(const float* d_target, int32_t target_stride, int32_t
                            void* d_workspace, uint64_t workspace_bytes, void* stream);
 int mf_cloud_icp_step_dev(void* d_workspace, uint64_t workspace_bytes, const float* d_query, int32_t query_stride, int64_t n_query,
                           const float* query_to_target16, double* d_out29, void* stream);
+/* Segmentation scores on the GPU (kernels: mf_eval.hip; DESIGN.md "Segmentation evaluation"; the metrics built on them:
+ * maskfusion_amd.eval.seg_metrics).  Both calls compare two label streams d_est, d_gt (DEVICE, uint8 [n_frames][height][width], any byte
+ * alignment).  lut_est and lut_gt (HOST, 256 entries each) map a raw label value to a compact class index < n_est (< n_gt), or to 255: void.
+ * n_est and n_gt are 1..64; by the callers' convention class 0 is the background.  The tables are copied into the launch's argument block when
+ * the call is made: the call adds no copy to the stream and the host arrays may be reused at once.  Both calls zero their output on `stream`,
+ * enqueue one kernel on it and return without waiting; they need no context.  All counters are integers: the result is exact and the same
+ * for every call.  MF_EINVAL, with nothing enqueued, for a null pointer, width, height or n_frames < 1 (or width * height > 2^30), n_est or
+ * n_gt outside 1..64, a table entry that is neither below its n nor 255, a pair entry that is neither < n_est nor 255, a radius outside 0..16.
+ *
+ * mf_label_confusion_dev: d_counts (DEVICE, uint32 [n_frames][n_gt][n_est]): [f][g][e] = the pixels of frame f whose ground truth maps to g
+ * and whose estimate maps to e.  A pixel that is void on either side is counted nowhere.
+ *
+ * mf_label_boundary_dev: pair (HOST, n_gt entries): the estimate class matched to ground-truth class g, or 255 for none (two g may name
+ * the same class).  A pixel is a boundary pixel of class k in a label image when its label maps to k and at least one of its 4-neighbours
+ * inside the image maps to something else, void included; the image border by itself makes no boundary and a void pixel is a boundary
+ * pixel of nothing.  d_out (DEVICE, uint32 [n_frames][n_gt][4]) = {n_est_boundary, est_hit, n_gt_boundary, gt_hit}: for g with pair[g] = e,
+ * n_est_boundary counts the boundary pixels of e in the estimate and est_hit those of them that have a boundary pixel of g in the ground
+ * truth at dx^2 + dy^2 <= radius^2 (integers; radius 0: the same pixel); n_gt_boundary and gt_hit are the mirror image.  For g with
+ * pair[g] = 255 the row is {0, 0, n_gt_boundary, 0}. */
+int mf_label_confusion_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_frames, int32_t height, int32_t width, const uint8_t* lut_est,
+                           int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, uint32_t* d_counts, void* stream);
+int mf_label_boundary_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_frames, int32_t height, int32_t width, const uint8_t* lut_est,
+                          int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, const uint8_t* pair, int32_t radius, uint32_t* d_out, void* stream);
 /* whether the last tracking step used the fill-in maps (MaskFusion::requiresFillIn, MaskFusion.cpp:630-648) */
 int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
 

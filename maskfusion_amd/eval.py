@@ -9,8 +9,11 @@ before they are scored: point-to-plane (or point-to-point) Gauss-Newton steps on
     python -m maskfusion_amd.eval --est DIR [--ref DIR] [--gt FILE] [--radius R] [--tau a,b,c] [--pair est_id:ref_id ...]
                                   [--register [--register-radius R0,R1,...] [--register-iterations N] [--point-to-point]]
                                   [--ref-cloud FILE [--init FILE]]
+                                  [--seg-gt DIR [--seg-gt-prefix Mask] [--seg-index-width 4] [--seg-radius R] [--seg-void V]]
 
-prints one JSON object per model on stdout (INTEGRATION.md "Evaluating a run").
+prints one JSON object per model on stdout (INTEGRATION.md "Evaluating a run"); with --seg-gt, one per ground-truth object of the
+segmentation and a summary (region similarity J and boundary accuracy F of the -es label images, counted on the GPU:
+mf_label_confusion_dev / mf_label_boundary_dev).
 """
 from __future__ import annotations
 
@@ -500,6 +503,323 @@ def read_transform(path: str) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
+# segmentation
+# ------------------------------------------------------------------------------------------------------------------------------------
+VOID = 255                # a look-up table entry: the raw value belongs to no class
+MAX_CLASSES = 64          # classes per side of the device calls (mf_label_confusion_dev)
+MAX_RADIUS = 16           # mf_label_boundary_dev
+
+
+def _device_labels(a):
+    """uint8 (n_frames, H, W) on the library's device; a single (H, W) image becomes one frame"""
+    import torch
+    from .lib import torch_device
+    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(a, np.uint8)))
+    if t.dim() == 2:
+        t = t[None]
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.numel() == 0:
+        raise ValueError("labels must be uint8 of shape (n_frames, H, W) or (H, W), not empty")
+    return t.to(torch_device()).contiguous()
+
+
+def _lut_arg(lut, n):
+    lut = np.ascontiguousarray(np.asarray(lut, np.uint8).reshape(-1))
+    if lut.size != 256:
+        raise ValueError("a look-up table has 256 entries")
+    if n is None:
+        used = lut[lut != VOID]
+        n = int(used.max()) + 1 if used.size else 1
+    return lut, int(n)
+
+
+def _label_call(est, gt, lut_est, lut_gt, n_est, n_gt):
+    import torch
+    from .lib import load
+    e, g = _device_labels(est), _device_labels(gt)
+    if e.shape != g.shape:
+        raise ValueError(f"estimate {tuple(e.shape)} and ground truth {tuple(g.shape)} differ in shape")
+    le, n_est = _lut_arg(lut_est, n_est)
+    lg, n_gt = _lut_arg(lut_gt, n_gt)
+    stream = torch.cuda.current_stream().cuda_stream if e.device.type == "cuda" else None
+    return load(), e, g, le, n_est, lg, n_gt, stream
+
+
+def label_confusion_dev(est, gt, lut_est, lut_gt, n_est=None, n_gt=None):
+    """label_confusion() with the result left on the device: an int32 tensor (n_frames, n_gt, n_est) holding the uint32 counts"""
+    import torch
+    from .lib import MFError
+    L, e, g, le, n_est, lg, n_gt, stream = _label_call(est, gt, lut_est, lut_gt, n_est, n_gt)
+    out = torch.empty((e.shape[0], n_gt, n_est), dtype=torch.int32, device=e.device)
+    rc = L.mf_label_confusion_dev(e.data_ptr(), g.data_ptr(), int(e.shape[0]), int(e.shape[1]), int(e.shape[2]), le.ctypes.data, n_est,
+                                  lg.ctypes.data, n_gt, out.data_ptr(), stream)
+    if rc != 0:
+        raise MFError(f"mf_label_confusion_dev failed with code {rc} (1..64 classes per side; table entries below the class count, or 255)")
+    return out
+
+
+def label_confusion(est, gt, lut_est, lut_gt, n_est=None, n_gt=None) -> np.ndarray:
+    """Region counts of two label streams (mf_label_confusion_dev): est, gt uint8 (n_frames, H, W) numpy arrays or device tensors; lut_est,
+    lut_gt 256 entries, raw value -> class index or 255 (void); n_est, n_gt: the class counts (default: the largest index in the table + 1).
+    Returns uint32 (n_frames, n_gt, n_est): [f, g, e] = the pixels of frame f with ground truth g and estimate e, void pixels left out."""
+    return label_confusion_dev(est, gt, lut_est, lut_gt, n_est, n_gt).cpu().numpy().view(np.uint32)
+
+
+def label_boundary(est, gt, lut_est, lut_gt, pair, radius: int, n_est=None, n_gt=None) -> np.ndarray:
+    """Boundary counts of two label streams (mf_label_boundary_dev; the definitions: include/maskfusion_amd.h).  pair: one entry per
+    ground-truth class, the estimate class matched to it or 255; its length is n_gt unless n_gt is given.  radius: 0..16 pixels.
+    Returns uint32 (n_frames, n_gt, 4) = n_est_boundary, est_hit, n_gt_boundary, gt_hit."""
+    import torch
+    from .lib import MFError
+    pr = np.ascontiguousarray(np.asarray(pair, np.uint8).reshape(-1))
+    L, e, g, le, n_est, lg, n_gt, stream = _label_call(est, gt, lut_est, lut_gt, n_est, len(pr) if n_gt is None else n_gt)
+    if len(pr) != n_gt:
+        raise ValueError(f"pair has {len(pr)} entries for {n_gt} ground-truth classes")
+    out = torch.empty((e.shape[0], n_gt, 4), dtype=torch.int32, device=e.device)
+    rc = L.mf_label_boundary_dev(e.data_ptr(), g.data_ptr(), int(e.shape[0]), int(e.shape[1]), int(e.shape[2]), le.ctypes.data, n_est,
+                                 lg.ctypes.data, n_gt, pr.ctypes.data, int(radius), out.data_ptr(), stream)
+    if rc != 0:
+        raise MFError(f"mf_label_boundary_dev failed with code {rc} (1..64 classes per side; table and pair entries below the class count, "
+                      "or 255; radius 0..16)")
+    return out.cpu().numpy().view(np.uint32)
+
+
+def build_lut(present, void=None, also_background=()):
+    """The look-up table of one side: the distinct raw values that occur (`present`: the values, or 256 flags / counts by value), in ascending
+    order, are the classes, with raw 0 -> class 0 whether it occurs or not; `void` (a raw value, or None) -> 255; the raw values in
+    also_background -> class 0.  Raw values that do not occur map to 255.  Returns (lut uint8 [256], ids): ids[k] = the raw value of class k.
+    More than 64 classes: ValueError."""
+    p = np.asarray(present)
+    flags = np.zeros(256, bool)
+    if p.shape == (256,) and p.dtype != np.uint8:
+        flags[:] = p != 0
+    else:
+        flags[p.astype(np.int64).reshape(-1)] = True
+    flags[0] = True
+    for v in ([] if void is None else [int(void)]) + [int(v) for v in also_background]:
+        if not 0 < v < 256:
+            raise ValueError(f"raw value {v}: void and background aliases are raw values 1..255")
+        flags[v] = False
+    ids = [int(v) for v in np.flatnonzero(flags)]
+    if len(ids) > MAX_CLASSES:
+        raise ValueError(f"{len(ids)} distinct label values: the segmentation scores handle at most {MAX_CLASSES} per side (background included)")
+    lut = np.full(256, VOID, np.uint8)
+    lut[ids] = np.arange(len(ids), dtype=np.uint8)
+    for v in also_background:
+        lut[int(v)] = 0
+    return lut, ids
+
+
+def default_radius(width: int, height: int) -> int:
+    """the boundary measure's pixel radius: 0.008 of the image diagonal, at least 1, at most 16 (6 at 640 x 480)"""
+    return int(min(MAX_RADIUS, max(1, round(0.008 * math.hypot(width, height)))))
+
+
+def match_objects(counts) -> np.ndarray:
+    """The pairing of seg_metrics: uint8 [n_gt], the estimate class matched to every ground-truth class or 255.  Background (class 0) pairs
+    with background; the objects (classes >= 1) are matched one to one so that the sum of their sequence IoUs -- intersections summed over
+    the frames by unions summed over the frames -- is largest; a pair without a common pixel is left unmatched."""
+    from scipy.optimize import linear_sum_assignment
+    c = np.asarray(counts).astype(np.int64).sum(0)
+    n_gt, n_est = c.shape
+    pair = np.full(n_gt, VOID, np.uint8)
+    pair[0] = 0
+    if n_gt > 1 and n_est > 1:
+        inter = c[1:, 1:]
+        union = c.sum(1)[1:, None] + c.sum(0)[None, 1:] - inter
+        iou = np.where(union > 0, inter / np.maximum(union, 1), 0.0)
+        for r, k in zip(*linear_sum_assignment(iou, maximize=True)):
+            if inter[r, k] > 0:
+                pair[r + 1] = k + 1
+    return pair
+
+
+def _ratio(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.where(b > 0, a / np.where(b > 0, b, 1.0), 0.0)
+
+
+def seg_metrics(counts, boundary_fn, gt_ids=None, est_ids=None) -> dict:
+    """From counts to scores, without a GPU.  counts: (n_frames, n_gt, n_est) region counts (label_confusion's); boundary_fn(pair) -> the
+    (n_frames, n_gt, 4) boundary counts for that pairing (label_boundary's); gt_ids / est_ids: the raw value of every class (build_lut's
+    ids; default: the class indices), used to name objects and models.  Class 0 is the background on both sides.
+
+    Returns {"pair", "objects", "summary"}.  pair: match_objects(counts).  objects: one entry per ground-truth class >= 1:
+      gt_id, model_id (None: unmatched), iou -- the sequence IoU, intersections over unions both summed over the frames --, and
+      J, P, R, F, JF -- the means, over the frames in which the object has at least one counted ground-truth pixel (`frames` of them), of
+      the frame's J = intersection / union, P = est_hit / n_est_boundary, R = gt_hit / n_gt_boundary, F = 2 P R / (P + R) and (J + F) / 2.
+      A ratio with a zero denominator is 0, F is 0 when P + R = 0, an object seen in no frame has means 0, an unmatched object scores 0.
+    summary: objects, matched, the means over the objects of iou, J, P, R, F, JF (None without objects), unmatched_models (the estimate's
+    classes >= 1 matched to nothing) and background_iou (the sequence IoU of class 0 with class 0)."""
+    c = np.asarray(counts).astype(np.int64)
+    if c.ndim != 3:
+        raise ValueError("counts must have the shape (n_frames, n_gt, n_est)")
+    n_frames, n_gt, n_est = c.shape
+    gt_ids = list(range(n_gt)) if gt_ids is None else [int(v) for v in gt_ids]
+    est_ids = list(range(n_est)) if est_ids is None else [int(v) for v in est_ids]
+    pair = match_objects(c)
+    b = np.asarray(boundary_fn(pair)).astype(np.int64)
+    if b.shape != (n_frames, n_gt, 4):
+        raise ValueError(f"boundary_fn returned the shape {b.shape}, expected {(n_frames, n_gt, 4)}")
+    gt_area, est_area = c.sum(2), c.sum(1)               # [f, g], [f, e]
+    keys = ("iou", "J", "P", "R", "F", "JF")
+    objects = []
+    for g in range(1, n_gt):
+        o = {"gt_id": gt_ids[g], "model_id": None, "frames": int(np.count_nonzero(gt_area[:, g]))}
+        o.update({k: 0.0 for k in keys})
+        e = int(pair[g])
+        if e != VOID:
+            seen = gt_area[:, g] > 0
+            inter = c[:, g, e]
+            union = gt_area[:, g] + est_area[:, e] - inter
+            J = _ratio(inter, union)
+            P, R = _ratio(b[:, g, 1], b[:, g, 0]), _ratio(b[:, g, 3], b[:, g, 2])
+            F = _ratio(2.0 * P * R, P + R)
+            o["model_id"] = est_ids[e]
+            o["iou"] = float(_ratio(inter.sum(), union.sum()))
+            if seen.any():
+                for k, v in (("J", J), ("P", P), ("R", R), ("F", F), ("JF", 0.5 * (J + F))):
+                    o[k] = float(v[seen].mean())
+        objects.append(o)
+    matched = {int(e) for e in pair[1:] if e != VOID}
+    bg_inter = c[:, 0, 0].sum()
+    summary = {"objects": len(objects), "matched": len(matched), "frames": int(n_frames)}
+    for k in keys:
+        summary[k] = float(np.mean([o[k] for o in objects])) if objects else None
+    summary["unmatched_models"] = [est_ids[e] for e in range(1, n_est) if e not in matched]
+    summary["background_iou"] = float(_ratio(bg_inter, gt_area[:, 0].sum() + est_area[:, 0].sum() - bg_inter))
+    return {"pair": pair, "objects": objects, "summary": summary}
+
+
+class SegmentationScorer:
+    """Collects the frames of a run, estimate and ground truth, on the device and scores them there.  add() takes label images from the
+    host or the device, add_from() takes the estimate from a live context's label image without a download.  Alongside the frames the
+    scorer keeps, on the device, how often every raw value occurred on either side: result() builds the look-up tables from that
+    (build_lut), counts regions (mf_label_confusion_dev), matches the objects (match_objects), counts boundaries for that pairing
+    (mf_label_boundary_dev) and returns seg_metrics' scores.
+
+    void: a raw ground-truth value that marks pixels to leave out (None: no such value).  The estimate's value 255 -- "ignored" in the
+    context's label image, written as 0 by the -es export -- counts as background."""
+
+    EST_IGNORED = 255
+
+    def __init__(self, void=None):
+        self.void = void
+        self._est, self._gt, self._hist = [], [], []
+        self.shape = None
+
+    # a 256-bin histogram of raw values from the region kernel itself: class (v >> 6, v & 63) of a stream compared with itself
+    _LO = (np.arange(256) & 63).astype(np.uint8)
+    _HI = (np.arange(256) >> 6).astype(np.uint8)
+
+    def _raw_counts(self, t):
+        return label_confusion_dev(t, t, self._LO, self._HI, 64, 4).sum(0)
+
+    @staticmethod
+    def _own(a):
+        """device labels that nobody else writes: a copy, unless moving `a` to the device already made one"""
+        t = _device_labels(a)
+        shared = a.data_ptr() == t.data_ptr() if hasattr(a, "data_ptr") else t.device.type == "cpu"
+        return t.clone() if shared else t
+
+    def _add(self, e, g):
+        if e.shape != g.shape:
+            raise ValueError(f"estimate {tuple(e.shape)} and ground truth {tuple(g.shape)} differ in shape")
+        if self.shape is None:
+            self.shape = tuple(e.shape[1:])
+        if tuple(e.shape[1:]) != self.shape:
+            raise ValueError(f"frames of {tuple(e.shape[1:])} added to a scorer of {self.shape} frames")
+        self._est.append(e)
+        self._gt.append(g)
+        self._hist.append((self._raw_counts(e), self._raw_counts(g)))
+
+    def add(self, est, gt):
+        """one frame (H, W) or a batch (n, H, W) of both sides, numpy arrays or device tensors; the scorer keeps device copies"""
+        self._add(self._own(est), self._own(gt))
+
+    def add_from(self, mf, gt):
+        """the frame `mf` (a MaskFusion context) processed last against its ground truth (H, W): the estimate is the context's label image,
+        copied device to device (mf_export_segmentation_dev)"""
+        import torch
+        from .lib import torch_device
+        e = torch.empty((1, mf.height, mf.width), dtype=torch.uint8, device=torch_device())
+        mf._chk(mf._L.mf_export_segmentation_dev(mf._h, e.data_ptr()))
+        mf.sync()               # the copy runs on the context's stream, what follows on torch's
+        self._add(e, self._own(gt))
+
+    @property
+    def frames(self) -> int:
+        return sum(int(t.shape[0]) for t in self._est)
+
+    def tables(self):
+        """((lut_est, est_ids), (lut_gt, gt_ids)) for the frames added so far"""
+        if not self._est:
+            raise ValueError("no frames were added")
+        he = sum(h[0] for h in self._hist).cpu().numpy().reshape(256)
+        hg = sum(h[1] for h in self._hist).cpu().numpy().reshape(256)
+        alias = (self.EST_IGNORED,) if he[self.EST_IGNORED] else ()
+        return build_lut(he, also_background=alias), build_lut(hg, void=self.void)
+
+    def stacked(self):
+        """(est, gt) as two device tensors (n_frames, H, W)"""
+        import torch
+        if len(self._est) > 1:
+            self._est, self._gt = [torch.cat(self._est)], [torch.cat(self._gt)]
+        return self._est[0], self._gt[0]
+
+    def result(self, radius=None) -> dict:
+        """seg_metrics of everything added, with "radius" in the summary and the region counts (n_frames, n_gt, n_est) under "counts";
+        radius None: default_radius of the frame size"""
+        (le, est_ids), (lg, gt_ids) = self.tables()
+        est, gt = self.stacked()
+        r = default_radius(self.shape[1], self.shape[0]) if radius is None else int(radius)
+        if not 0 <= r <= MAX_RADIUS:
+            raise ValueError(f"radius {r}: the boundary measure takes 0..{MAX_RADIUS} pixels")
+        counts = label_confusion(est, gt, le, lg, len(est_ids), len(gt_ids))
+        res = seg_metrics(counts, lambda pair: label_boundary(est, gt, le, lg, pair, r, len(est_ids), len(gt_ids)), gt_ids, est_ids)
+        res["summary"]["radius"] = r
+        res["counts"] = counts
+        return res
+
+
+def read_segmentation_run(est_dir: str, gt_dir: str, prefix: str = "Mask", index_width: int = 4):
+    """The label images a run wrote with -es and the ground-truth masks of its sequence: (est, gt, ticks), est and gt uint8 (n, H, W).
+    est_dir holds Segmentation<tick>.png (model id per pixel, 0: background or ignored); gt_dir holds <prefix>####.png / .pgm id images,
+    found and loaded as the image-directory reader does (io.readers.mask_files, load_mask).  The frame processed at tick t is the reader's
+    frame t - 1: mask file index t - 1 + startIndex.  ValueError naming the file for a segmentation image without its mask file or of
+    another size."""
+    from .io.readers import load_mask, mask_files
+    ticks = sorted(int(m.group(1)) for m in (re.fullmatch(r"Segmentation(\d+)\.png", fn) for fn in os.listdir(est_dir)) if m)
+    if not ticks:
+        raise ValueError(f"{est_dir} holds no Segmentation<tick>.png (the -es export)")
+    ext, start = mask_files(gt_dir, prefix, index_width)
+    est, gt = [], []
+    for t in ticks:
+        ep = os.path.join(est_dir, f"Segmentation{t}.png")
+        gp = os.path.join(gt_dir, f"{prefix}{t - 1 + start:0{index_width}d}{ext}")
+        if not os.path.exists(gp):
+            raise ValueError(f"{ep}: its mask file {gp} does not exist (tick t pairs with mask index t - 1 + {start})")
+        e, g = load_mask(ep), load_mask(gp)
+        if e.shape != g.shape:
+            raise ValueError(f"{ep} has {e.shape[1]} x {e.shape[0]} pixels, its mask file {gp} {g.shape[1]} x {g.shape[0]}")
+        if est and e.shape != est[0].shape:
+            raise ValueError(f"{ep} has {e.shape[1]} x {e.shape[0]} pixels, the images before it {est[0].shape[1]} x {est[0].shape[0]}")
+        est.append(e)
+        gt.append(g)
+    return np.stack(est), np.stack(gt), ticks
+
+
+def score_segmentation(est_dir: str, gt_dir: str, prefix: str = "Mask", index_width: int = 4, radius=None, void=None) -> list:
+    """what the command prints for --seg-gt: one dict per ground-truth object and the summary last"""
+    est, gt, ticks = read_segmentation_run(est_dir, gt_dir, prefix, index_width)
+    sc = SegmentationScorer(void=void)
+    sc.add(est, gt)
+    res = sc.result(radius)
+    out = [dict(segmentation_object=o.pop("gt_id"), **o) for o in (dict(o) for o in res["objects"])]
+    out.append({"segmentation": dict(res["summary"], first_tick=ticks[0], last_tick=ticks[-1])})
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
 # the command
 # ------------------------------------------------------------------------------------------------------------------------------------
 def _run_files(d: str):
@@ -553,7 +873,17 @@ def main(argv=None) -> int:
     ap.add_argument("--point-to-point", action="store_true", help="register point-to-point (for a reference cloud without normals)")
     ap.add_argument("--ref-cloud", metavar="FILE", help="a single reference PLY (a ground-truth model) for the background cloud of --est")
     ap.add_argument("--init", metavar="FILE", help="with --ref-cloud: text file with the 4 x 4 est -> ref start")
+    ap.add_argument("--seg-gt", metavar="DIR", help="ground-truth mask images (Mask####.png / .pgm, instance id per pixel) of the sequence: scores "
+                    "the Segmentation<tick>.png label images of --est (the -es export)")
+    ap.add_argument("--seg-gt-prefix", default="Mask", help="file name prefix of the masks (default Mask)")
+    ap.add_argument("--seg-index-width", type=int, default=4, help="digits of the masks' file index (default 4)")
+    ap.add_argument("--seg-radius", type=int, help="pixel radius of the boundary measure, 0..16 (default: 0.008 of the image diagonal)")
+    ap.add_argument("--seg-void", type=int, help="ground-truth value that marks pixels to leave out (default: none)")
     a = ap.parse_args(argv)
+    if not a.seg_gt and (a.seg_radius is not None or a.seg_void is not None):
+        ap.error("--seg-radius and --seg-void need --seg-gt")
+    if a.seg_radius is not None and not 0 <= a.seg_radius <= MAX_RADIUS:
+        ap.error(f"--seg-radius takes 0..{MAX_RADIUS}")
     if a.init and not a.ref_cloud:
         ap.error("--init needs --ref-cloud")
     if a.ref_cloud and a.ref:
@@ -645,8 +975,14 @@ def main(argv=None) -> int:
         results.append(o)
     elif a.gt:
         results.append({"model": 0, "trajectory_vs_gt": gt_res})
-    else:
-        ap.error("give --ref, --ref-cloud, --gt or a combination")
+    elif not a.seg_gt:
+        ap.error("give --ref, --ref-cloud, --gt, --seg-gt or a combination")
+    if a.seg_gt:
+        try:
+            results += score_segmentation(a.est, a.seg_gt, a.seg_gt_prefix, a.seg_index_width, a.seg_radius, a.seg_void)
+        except (OSError, ValueError) as e:
+            sys.stderr.write(f"eval: --seg-gt: {e}\n")
+            return 2
     for o in results:
         print(json.dumps(_clean(o)))
     return 0

@@ -126,6 +126,23 @@ def _count_files(path, prefix, exts):
     return n, ext
 
 
+def load_mask(path: str) -> np.ndarray:
+    """an id image (Mask####.png / .pgm, or a label image the -es export wrote) as uint8 (H, W): cv::imread(..., IMREAD_GRAYSCALE)"""
+    return np.ascontiguousarray(np.asarray(_pil().open(path).convert("L"), np.uint8))
+
+
+def mask_files(directory: str, prefix: str = "Mask", indexWidth: int = 4):
+    """(extension, start index) of the mask images of a directory, by the reader's rules: one extension among .png / .pgm, the first file
+    index 0 or 1.  ValueError when there are none."""
+    n, ext = _count_files(directory, prefix, (".png", ".pgm"))
+    if n == 0:
+        raise ValueError(f"{directory} holds no {prefix}<index>.png / .pgm mask images")
+    for idx in range(2):
+        if os.path.exists(os.path.join(directory, f"{prefix}{idx:0{indexWidth}d}{ext}")):
+            return ext, idx
+    raise ValueError(f"Error: Could not find start index ({directory}, {prefix}, {indexWidth} digits).")
+
+
 class ImageLogReader:
     rateHz = 24.0  # ImageLogReader.h:96
 
@@ -212,10 +229,10 @@ class ImageLogReader:
             if os.path.exists(mpath + ".txt"):
                 f.classIDs, f.rois = self.loadMaskIDs(mpath + ".txt")
             if index < self.maxMasks:
-                m = np.asarray(Image.open(mpath + self.mext).convert("L"), np.uint8)
+                m = load_mask(mpath + self.mext)
                 if m.shape != rgb.shape[:2]:
                     raise ValueError("Could not read mask-image file.")
-                f.mask = np.ascontiguousarray(m)
+                f.mask = m
         if self.flip:
             f.flipColors()
         return f
