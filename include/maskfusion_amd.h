@@ -230,6 +230,23 @@ int mf_cloud_icp_build_dev(const float* d_target, int32_t target_stride, int32_t
                            void* d_workspace, uint64_t workspace_bytes, void* stream);
 int mf_cloud_icp_step_dev(void* d_workspace, uint64_t workspace_bytes, const float* d_query, int32_t query_stride, int64_t n_query,
                           const float* query_to_target16, double* d_out29, void* stream);
+/* Normals of a point cloud from its own radius neighbourhoods, on the GPU (kernels: mf_eval.hip; DESIGN.md "Cloud normals"): what a cloud
+ * without nx / ny / nz needs before it can be the target of a point-to-plane registration.  Points are read as x, y, z at d_points + i * stride
+ * floats.  The neighbours of point i are the finite points j, i itself included, whose fp32 d2 = dx*dx + dy*dy + dz*dz (d = p_j - p_i, without
+ * contraction) passes d2 <= fl(radius * radius): mf_cloud_nn_dev's radius test, over mf_cloud_nn_dev's grid.  d_count[i] = k, their number
+ * (exact).  With d in fp64 and every sum in fp64: m = sum d / k, C = sum d d^T / k - m m^T; C is decomposed by cyclic Jacobi rotations in fp64
+ * (a fixed number of sweeps) into l0 <= l1 <= l2.  d_normals[i] = (the unit eigenvector of l0, the surface variation l0 / (l0 + l1 + l2)).
+ * Sign: with viewpoint3 (HOST, 3 floats: v) the normal faces it, n . (v - p_i) >= 0; with NULL, or where that product is exactly 0, the
+ * component of largest magnitude is positive (ties: the lowest axis).  No normal -- NaN in all four lanes, d_count[i] still k -- for a point
+ * that is not finite (k = 0), for k < min_neighbours, and for l1 <= 1e-12 l2: neighbours on one line or in one place (twelve digits lie
+ * between that and both the rounding of C and any sampled surface).  A bucket of the grid holds its points in the order of the build's atomics,
+ * so the fp64 sums and the normal are reproducible to rounding only (about k 2^-53 over the relative gap of the eigenvalues between two calls);
+ * d_count is the same for every call.  MF_EINVAL as for mf_cloud_nn_dev (radius, stride, more than 2^30 points, a null pointer, the workspace
+ * -- mf_cloud_normals_workspace(n) bytes, 16-byte aligned --, a finite coordinate with |x / radius| >= 2^30), and for min_neighbours < 3 or a
+ * viewpoint that is not finite.  Enqueued on `stream`, which the call synchronises before it returns. */
+int mf_cloud_normals_workspace(int64_t n, uint64_t* bytes);
+int mf_cloud_normals_dev(const float* d_points, int32_t stride, int64_t n, float radius, int32_t min_neighbours, const float* viewpoint3,
+                         float* d_normals /* [n][4] */, int32_t* d_count /* [n] */, void* d_workspace, uint64_t workspace_bytes, void* stream);
 /* Segmentation scores on the GPU (kernels: mf_eval.hip; DESIGN.md "Segmentation evaluation"; the metrics built on them:
  * maskfusion_amd.eval.seg_metrics).  Both calls compare two label streams d_est, d_gt (DEVICE, uint8 [n_frames][height][width], any byte
  * alignment).  lut_est and lut_gt (HOST, 256 entries each) map a raw label value to a compact class index < n_est (< n_gt), or to 255: void.

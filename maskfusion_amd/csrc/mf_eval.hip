@@ -308,6 +308,135 @@ __global__ __launch_bounds__(64) void k_icp_sum(const double* __restrict__ parti
     out29[threadIdx.x] = v;
 }
 
+// ---------------- normals of a cloud (mf_cloud_normals_dev; DESIGN.md "Cloud normals") ----------------
+// The cloud is target and query at once.  Two launches over the grid nn_build makes of it.
+// k_normals_walk: one lane per point i, grid-stride as k_nn_query.  The walk visits every cell nn_cell_range names and adds, for every record j
+// that passes mf_cloud_nn_dev's radius test (i itself does: d2 = 0), d = p_j - p_i in fp64 to ten accumulators -- the count, sum d and the upper
+// triangle of sum d d^T.  Two cells of the walk may share a bucket, and a sum, unlike a minimum, must not meet a record twice: a record counts
+// only in the visit of its OWN cell (nn_cell of its coordinates, the build's product).  A cell whose box lies beyond the radius is skipped
+// by nn_find's bound.  The nine sums go to a scratch record behind the grid (component-major, [9][n] doubles), the count to d_count.
+// k_normals_solve: C = sum d d^T / k - m m^T, m = sum d / k, decomposed per lane by cyclic Jacobi rotations in fp64 (not the trigonometric
+// closed form, which loses the small eigenvalue to cancellation), then the rules of the header.
+// Why two, as k_icp_find / k_icp_accum: the walk lives on occupancy.  In one kernel the rotations' nine-double V and six-double C overlap the
+// walk's registers only in part: 72 VGPRs, 7 wavefronts per SIMD.  Apart, the walk takes 64 -- the 8 wavefronts k_nn_query (46) has -- and
+// the solve 62.  The price is 72 B per point written and read once.
+// kNrmSweeps: Jacobi converges quadratically once the off-diagonal is small, and a 3 x 3 gets there in few sweeps; see DESIGN.md "Cloud
+// normals" for how the count was chosen on the test clouds.
+// A bucket's records lie in the order of the build's atomics, so the fp64 sums, and with them the normal, are reproducible to rounding
+// only: the count is exact, the normal moves by about k 2^-53 over the relative eigenvalue gap from call to call.
+constexpr int kNrmSweeps = 6;
+struct NrmArgs {
+    const float* p; int stride, n;
+    int min_k;
+    int has_view; float view[3];
+    float4* out; int* count;
+};
+// rotation in the (p, q) plane that zeroes a_pq; r is the third index: (a_rp, a_rq) and the columns p, q of V turn with it
+__device__ __forceinline__ void nrm_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double (&vp)[3], double (&vq)[3]) {
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));   // (theta^2 = inf: t = 0)
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    app -= t * apq; aqq += t * apq; apq = 0.0;
+    const double rp = arp, rq = arq;
+    arp = c * rp - s * rq; arq = s * rp + c * rq;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double a = vp[k], b = vq[k];
+        vp[k] = c * a - s * b; vq[k] = s * a + c * b;
+    }
+}
+__device__ __forceinline__ void nrm_add_bucket(const NnGrid& g, int cx, int cy, int cz, float x, float y, float z, double (&s)[9], int& k) {
+    const unsigned b = nn_hash(cx, cy, cz) & g.mask;
+    const unsigned e = g.start[b + 1];
+    for (unsigned r = g.start[b]; r < e; ++r) {
+        const float4 p = g.rec[r];
+        const float fx = p.x - x, fy = p.y - y, fz = p.z - z;
+        const float d2 = fx * fx + fy * fy + fz * fz;
+        if (!(d2 <= g.r2)) continue;
+        if (nn_cell(g, p.x) != cx || nn_cell(g, p.y) != cy || nn_cell(g, p.z) != cz) continue;   // another cell's record in a shared bucket
+        const double dx = (double)p.x - (double)x, dy = (double)p.y - (double)y, dz = (double)p.z - (double)z;
+        s[0] += dx; s[1] += dy; s[2] += dz;
+        s[3] += dx * dx; s[4] += dx * dy; s[5] += dx * dz; s[6] += dy * dy; s[7] += dy * dz; s[8] += dz * dz;
+        ++k;
+    }
+}
+// the ten sums of point (x, y, z), finite and in range: k and s = {sum d (3), the upper triangle of sum d d^T (6)}
+__device__ __forceinline__ void nrm_walk(const NnGrid& g, float x, float y, float z, double (&s)[9], int& k) {
+    int x0, x1, y0, y1, z0, z1;
+    nn_cell_range(g, x, x0, x1); nn_cell_range(g, y, y0, y1); nn_cell_range(g, z, z0, z1);
+    for (int cz = z0; cz <= z1; ++cz) {
+        const double gz = nn_box_gap(g, z, cz);
+        for (int cy = y0; cy <= y1; ++cy) {
+            const double gy = nn_box_gap(g, y, cy);
+            for (int cx = x0; cx <= x1; ++cx) {
+                const double gap = (gz + gy + nn_box_gap(g, x, cx)) * (1.0 - 3.814697265625e-06);   // (nn_find's bound)
+                if (gap > (double)g.r2) continue;
+                nrm_add_bucket(g, cx, cy, cz, x, y, z, s, k);
+            }
+        }
+    }
+}
+// sums -> (normal, surface variation), NaN where the rules give no normal
+__device__ __forceinline__ float4 nrm_solve(const NrmArgs& a, float x, float y, float z, const double (&s)[9], int k) {
+    const float4 none = make_float4(NAN, NAN, NAN, NAN);
+    if (k < a.min_k) return none;
+    const double ik = 1.0 / (double)k;
+    const double mx = s[0] * ik, my = s[1] * ik, mz = s[2] * ik;
+    double a00 = s[3] * ik - mx * mx, a01 = s[4] * ik - mx * my, a02 = s[5] * ik - mx * mz;
+    double a11 = s[6] * ik - my * my, a12 = s[7] * ik - my * mz, a22 = s[8] * ik - mz * mz;
+    double v0[3] = {1.0, 0.0, 0.0}, v1[3] = {0.0, 1.0, 0.0}, v2[3] = {0.0, 0.0, 1.0};   // the columns of V
+    for (int sweep = 0; sweep < kNrmSweeps; ++sweep) {
+        nrm_rotate(a00, a11, a01, a02, a12, v0, v1);
+        nrm_rotate(a00, a22, a02, a01, a12, v0, v2);
+        nrm_rotate(a11, a22, a12, a01, a02, v1, v2);
+    }
+    // l0 <= l1 <= l2, n = the column of l0
+    double l0 = a00, l1 = a11, l2 = a22, nx = v0[0], ny = v0[1], nz = v0[2];
+    if (l1 < l0) { const double t = l0; l0 = l1; l1 = t; nx = v1[0]; ny = v1[1]; nz = v1[2]; }
+    if (l2 < l0) { const double t = l0; l0 = l2; l2 = t; nx = v2[0]; ny = v2[1]; nz = v2[2]; }
+    if (l2 < l1) { const double t = l1; l1 = l2; l2 = t; }
+    if (l1 <= 1e-12 * l2) return none;
+    const double inv = 1.0 / sqrt((nx * nx + ny * ny) + nz * nz);
+    nx *= inv; ny *= inv; nz *= inv;
+    // the sign: the viewpoint's side when there is one and it decides; else a rule of the vector alone (the component of largest magnitude
+    // positive, ties to the lowest axis).  Nothing of the sweeps' history is left in it.
+    const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
+    bool flip = ((ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz)) < 0.0;
+    if (a.has_view) {
+        const double dot = (nx * ((double)a.view[0] - (double)x) + ny * ((double)a.view[1] - (double)y)) + nz * ((double)a.view[2] - (double)z);
+        if (dot != 0.0) flip = dot < 0.0;
+    }
+    if (flip) { nx = -nx; ny = -ny; nz = -nz; }
+    return make_float4((float)nx, (float)ny, (float)nz, (float)(l0 / ((l0 + l1) + l2)));
+}
+__global__ __launch_bounds__(kNnThreads) void k_normals_walk(NnGrid g, NrmArgs a, double* __restrict__ sums) {
+    for (int i = blockIdx.x * kNnThreads + threadIdx.x; i < a.n; i += gridDim.x * kNnThreads) {
+        const float* pp = a.p + (size_t)i * a.stride;
+        const float x = pp[0], y = pp[1], z = pp[2];
+        int k = 0;
+        double s[9];
+#pragma unroll
+        for (int m = 0; m < 9; ++m) s[m] = 0.0;
+        if (nn_finite(x, y, z)) {
+            if (!nn_in_range(g, x, y, z)) atomicOr(g.flag, 1);
+            else nrm_walk(g, x, y, z, s, k);
+        }
+#pragma unroll
+        for (int m = 0; m < 9; ++m) sums[(size_t)m * a.n + i] = s[m];
+        a.count[i] = k;
+    }
+}
+__global__ __launch_bounds__(kNnThreads) void k_normals_solve(NrmArgs a, const double* __restrict__ sums) {
+    for (int i = blockIdx.x * kNnThreads + threadIdx.x; i < a.n; i += gridDim.x * kNnThreads) {
+        const float* pp = a.p + (size_t)i * a.stride;
+        double s[9];
+#pragma unroll
+        for (int m = 0; m < 9; ++m) s[m] = sums[(size_t)m * a.n + i];
+        a.out[i] = nrm_solve(a, pp[0], pp[1], pp[2], s, a.count[i]);
+    }
+}
+
 // ---------------- live surfels of a model -> float4 points (mf_eval.inl) ----------------
 // the live surfels in download order (mf_download_map: the runs in order, each run's first len slots) -> out, position + index; a surfel at or
 // below the confidence threshold becomes a NaN point, which the grid does not hold
@@ -465,6 +594,30 @@ static int icp_step(void* d_ws, uint64_t ws_bytes, const float* d_query, int que
     if (h.plane) hipLaunchKernelGGL(k_icp_accum<true>, dim3(nb), dim3(kNnThreads), 0, s, g, a);
     else hipLaunchKernelGGL(k_icp_accum<false>, dim3(nb), dim3(kNnThreads), 0, s, g, a);
     hipLaunchKernelGGL(k_icp_sum, dim3(1), dim3(64), 0, s, (const double*)a.partial, nb, d_out29);
+    return nn_finish(g, s, &why);
+}
+
+// ---------------- normals: workspace = the grid's workspace | sums [9][n] double ----------------
+static uint64_t normals_workspace_bytes(int64_t n) { return nn_workspace_bytes(n) + nn_align((uint64_t)std::max<int64_t>(n, 0) * 72); }
+static int normals_run(const float* d_points, int stride, int64_t n, float radius, int min_neighbours, const float* viewpoint3, float4* d_normals,
+                       int32_t* d_count, void* d_ws, uint64_t ws_bytes, hipStream_t s) {
+    const char* why = nullptr;
+    if (!(std::isfinite(radius) && radius > 0.f) || stride < 3 || min_neighbours < 3) return MF_EINVAL;
+    if (n < 0 || n > (int64_t)1 << 30 || (n > 0 && (!d_points || !d_normals || !d_count))) return MF_EINVAL;
+    if (!d_ws || ((uintptr_t)d_ws & 15) != 0 || ws_bytes < normals_workspace_bytes(n)) return MF_EINVAL;
+    if (viewpoint3 && !(std::isfinite(viewpoint3[0]) && std::isfinite(viewpoint3[1]) && std::isfinite(viewpoint3[2]))) return MF_EINVAL;
+    const NnGrid g = nn_layout(d_ws, n, radius);
+    const int rc = nn_build(g, d_points, stride, -1, nullptr, n, s, &why);
+    if (rc != MF_OK) return rc;
+    if (n > 0) {
+        NrmArgs a;
+        memset(&a, 0, sizeof(a));
+        a.p = d_points; a.stride = stride; a.n = (int)n; a.min_k = min_neighbours; a.out = d_normals; a.count = d_count;
+        if (viewpoint3) { a.has_view = 1; memcpy(a.view, viewpoint3, sizeof(a.view)); }
+        double* sums = (double*)((char*)d_ws + nn_workspace_bytes(n));
+        hipLaunchKernelGGL(k_normals_walk, dim3(nn_grid_blocks(n)), dim3(kNnThreads), 0, s, g, a, sums);
+        hipLaunchKernelGGL(k_normals_solve, dim3(nn_grid_blocks(n)), dim3(kNnThreads), 0, s, a, (const double*)sums);
+    }
     return nn_finish(g, s, &why);
 }
 
@@ -783,6 +936,17 @@ extern "C" int mf_cloud_icp_build_dev(const float* d_target, int32_t target_stri
 extern "C" int mf_cloud_icp_step_dev(void* d_workspace, uint64_t workspace_bytes, const float* d_query, int32_t query_stride, int64_t n_query,
                                      const float* query_to_target16, double* d_out29, void* stream) {
     return icp_step(d_workspace, workspace_bytes, d_query, query_stride, n_query, query_to_target16, d_out29, (hipStream_t)stream);
+}
+
+extern "C" int mf_cloud_normals_workspace(int64_t n, uint64_t* bytes) {
+    if (!bytes || n < 0 || n > (int64_t)1 << 30) return MF_EINVAL;
+    *bytes = normals_workspace_bytes(n);
+    return MF_OK;
+}
+
+extern "C" int mf_cloud_normals_dev(const float* d_points, int32_t stride, int64_t n, float radius, int32_t min_neighbours, const float* viewpoint3,
+                                    float* d_normals, int32_t* d_count, void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    return normals_run(d_points, stride, n, radius, min_neighbours, viewpoint3, (float4*)d_normals, d_count, d_workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int mf_label_confusion_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_frames, int32_t height, int32_t width,

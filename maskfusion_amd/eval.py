@@ -4,11 +4,12 @@ Reads what a run writes -- poses-<id>.txt (mf_export_poses; TUM `ts tx ty tz qx 
 (mf_save_ply; binary little endian, or ASCII PLY with x / y / z) -- from this library or from the reference.  The cloud distances run on the
 GPU through mf_cloud_nn_dev (kernels: csrc/mf_eval.hip); everything else is numpy.  register() refines the rigid alignment of two clouds
 before they are scored: point-to-plane (or point-to-point) Gauss-Newton steps on the GPU (mf_cloud_icp_build_dev / mf_cloud_icp_step_dev), the
-6 x 6 solve and the pose update in fp64 here.
+6 x 6 solve and the pose update in fp64 here.  estimate_normals() gives a cloud that has no normals the ones point-to-plane needs, from its
+own radius neighbourhoods on the GPU (mf_cloud_normals_dev); normal_consistency() scores the normals of two clouds against each other.
 
     python -m maskfusion_amd.eval --est DIR [--ref DIR] [--gt FILE] [--radius R] [--tau a,b,c] [--pair est_id:ref_id ...]
                                   [--register [--register-radius R0,R1,...] [--register-iterations N] [--point-to-point]]
-                                  [--ref-cloud FILE [--init FILE]]
+                                  [--ref-cloud FILE [--init FILE]] [--estimate-normals[=R]] [--normals]
                                   [--seg-gt DIR [--seg-gt-prefix Mask] [--seg-index-width 4] [--seg-radius R] [--seg-void V]]
 
 prints one JSON object per model on stdout (INTEGRATION.md "Evaluating a run"); with --seg-gt, one per ground-truth object of the
@@ -503,6 +504,67 @@ def read_transform(path: str) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
+# normals
+# ------------------------------------------------------------------------------------------------------------------------------------
+def estimate_normals(points, radius: float, min_neighbours: int = 5, viewpoint=None):
+    """Normals of a cloud from its own radius neighbourhoods (mf_cloud_normals_dev; the definition: include/maskfusion_amd.h).  points:
+    (n, >= 3) float32 numpy array or device tensor, x, y, z first; viewpoint: three numbers the normals are turned towards, or None (the
+    component of largest magnitude is made positive).  Returns numpy (normals float32 (n, 3), variation float32 (n,), count int32 (n,)):
+    the unit eigenvector of the smallest eigenvalue of the neighbourhood's covariance, the surface variation l0 / (l0 + l1 + l2) and the
+    number of neighbours within `radius`, the point itself included.  A row is NaN (its count still true) where the point is not finite, has
+    fewer than min_neighbours (>= 3) neighbours, or its neighbours lie on a line or in one place."""
+    import torch
+    from .lib import load, MFError
+    L = load()
+    p = _device_points(points)
+    n = int(p.shape[0])
+    need = C.c_uint64(0)
+    if L.mf_cloud_normals_workspace(n, C.byref(need)) != 0:
+        raise MFError("mf_cloud_normals_workspace failed")
+    ws = torch.empty(int(need.value), dtype=torch.uint8, device=p.device)
+    out = torch.empty((max(n, 1), 4), dtype=torch.float32, device=p.device)
+    cnt = torch.empty(max(n, 1), dtype=torch.int32, device=p.device)
+    v = None if viewpoint is None else np.ascontiguousarray(np.asarray(viewpoint, np.float32).reshape(3))
+    stream = torch.cuda.current_stream().cuda_stream if p.device.type == "cuda" else None
+    rc = L.mf_cloud_normals_dev(p.data_ptr() if n else None, int(p.shape[1]), n, float(radius), int(min_neighbours),
+                                v.ctypes.data if v is not None else None, out.data_ptr(), cnt.data_ptr(), ws.data_ptr(), int(need.value), stream)
+    if rc != 0:
+        raise MFError(f"mf_cloud_normals_dev failed with code {rc} (radius must be finite and > 0, min_neighbours >= 3, a finite viewpoint, "
+                      "coordinates |x / radius| < 2^30)")
+    o = out[:n].cpu().numpy()
+    return np.ascontiguousarray(o[:, :3]), np.ascontiguousarray(o[:, 3]), cnt[:n].cpu().numpy()
+
+
+def normal_angles(est_normals, ref_normals, idx, T=None) -> np.ndarray:
+    """The numpy part of normal_consistency: for every est point i with a partner idx[i] >= 0 whose two normals are finite, the angle in
+    degrees between (the rotation of T applied to) est_normals[i] and ref_normals[idx[i]], folded to [0, 90]: acos |n_e . n_r|, taken as
+    atan2(|n_e x n_r|, |n_e . n_r|), which keeps its digits near 0.  The normals need not have unit length."""
+    ne = np.asarray(est_normals, np.float64).reshape(-1, 3)
+    nr = np.asarray(ref_normals, np.float64).reshape(-1, 3)
+    idx = np.asarray(idx, np.int64)
+    if T is not None:
+        ne = ne @ np.asarray(T, np.float64)[:3, :3].T
+    hit = np.flatnonzero(idx >= 0)
+    a, b = ne[hit], nr[idx[hit]]
+    ok = np.isfinite(a).all(1) & np.isfinite(b).all(1)
+    a, b = a[ok], b[ok]
+    return np.degrees(np.arctan2(np.linalg.norm(np.cross(a, b), axis=1), np.abs((a * b).sum(1))))
+
+
+def normal_consistency(est, est_normals, ref, ref_normals, radius: float, T=None) -> dict:
+    """How well the normals of two clouds agree where the clouds meet: every est point (moved by T, 4 x 4 est -> ref, when given) is paired
+    with its nearest ref point within `radius` -- nearest(ref, est, radius, T) -- and the pair's angle is that between their normals, folded
+    to [0, 90 degrees] so that the orientation of either does not matter.  Returns {"radius", "count" (est points), "pairs" (with a partner
+    and two finite normals), "mean_deg", "median_deg", "below": {"10", "20", "30": the share of the pairs under that many degrees}}."""
+    _, idx = nearest(ref, est, radius, T)
+    ang = normal_angles(est_normals, ref_normals, idx, T)
+    out = {"radius": radius, "count": int(len(idx)), "pairs": int(ang.size)}
+    out.update({"mean_deg": float(ang.mean()), "median_deg": float(np.median(ang))} if ang.size else {"mean_deg": None, "median_deg": None})
+    out["below"] = {str(d): (float(np.count_nonzero(ang < d)) / ang.size if ang.size else 0.0) for d in (10, 20, 30)}
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
 # segmentation
 # ------------------------------------------------------------------------------------------------------------------------------------
 VOID = 255                # a look-up table entry: the raw value belongs to no class
@@ -873,6 +935,10 @@ def main(argv=None) -> int:
     ap.add_argument("--point-to-point", action="store_true", help="register point-to-point (for a reference cloud without normals)")
     ap.add_argument("--ref-cloud", metavar="FILE", help="a single reference PLY (a ground-truth model) for the background cloud of --est")
     ap.add_argument("--init", metavar="FILE", help="with --ref-cloud: text file with the 4 x 4 est -> ref start")
+    ap.add_argument("--estimate-normals", nargs="?", const=True, type=float, metavar="R", help="estimate the normals of a reference cloud whose PLY "
+                    "has none, on the GPU from neighbourhoods of radius R (default 2 x --radius): --register then runs point-to-plane against it")
+    ap.add_argument("--normals", action="store_true", help="add normal_consistency to every cloud comparison in which both clouds have normals "
+                    "(read or estimated), under the registered transform when there is one")
     ap.add_argument("--seg-gt", metavar="DIR", help="ground-truth mask images (Mask####.png / .pgm, instance id per pixel) of the sequence: scores "
                     "the Segmentation<tick>.png label images of --est (the -es export)")
     ap.add_argument("--seg-gt-prefix", default="Mask", help="file name prefix of the masks (default Mask)")
@@ -892,6 +958,13 @@ def main(argv=None) -> int:
         ap.error("--register-radius and --point-to-point need --register")
     if a.register and not (a.ref or a.ref_cloud):
         ap.error("--register needs --ref or --ref-cloud")
+    if (a.estimate_normals is not None or a.normals) and not (a.ref or a.ref_cloud):
+        ap.error("--estimate-normals and --normals need --ref or --ref-cloud")
+    normals_radius = None
+    if a.estimate_normals is not None:
+        normals_radius = 2 * a.radius if a.estimate_normals is True else a.estimate_normals
+        if not (math.isfinite(normals_radius) and normals_radius > 0):
+            ap.error("--estimate-normals takes a positive radius")
     taus = tuple(float(x) for x in a.tau.split(",") if x.strip())
     if a.register:
         try:
@@ -901,7 +974,18 @@ def main(argv=None) -> int:
         if not radii or not all(math.isfinite(r) and r > 0 for r in radii) or a.register_iterations < 1:
             ap.error("--register-radius needs positive radii, --register-iterations at least 1")
 
-    def registered(o, ce, cr, nr, T0):
+    def ref_normals(o, cr, nr):
+        """the reference's normals: the file's, or with --estimate-normals and none in the file the estimated ones (recorded in o)"""
+        if nr is None and normals_radius is not None and (a.normals or (a.register and not a.point_to_point)):
+            nr = estimate_normals(cr, normals_radius)[0]
+            o["reference_normals"] = {"estimated": True, "radius": normals_radius, "without_normal": int(np.count_nonzero(np.isnan(nr).any(1)))}
+        return nr
+
+    def consistency(o, ce, ne, cr, nr, T):
+        if a.normals and ne is not None and nr is not None:
+            o["normal_consistency"] = normal_consistency(ce, ne, cr, nr, a.radius, T)
+
+    def registered(o, ce, ne, cr, nr, T0):
         """adds registration and cloud_registered to o; False (after a message) when the reference has no normals and point-to-plane is asked"""
         if nr is None and not a.point_to_point:
             sys.stderr.write(f"eval: the reference cloud of model {o['model']} has no normals (nx ny nz): point-to-plane registration needs "
@@ -911,6 +995,7 @@ def main(argv=None) -> int:
                        schedule=radii, method="point" if a.point_to_point else "plane")
         o["cloud_registered"] = compare_clouds(ce, cr, a.radius, taus, T=res["T"])
         o["registration"] = registration_summary(res)
+        consistency(o, ce, ne, cr, nr, res["T"])
         return True
 
     est = _run_files(a.est)
@@ -940,7 +1025,7 @@ def main(argv=None) -> int:
             if el is not None and rl is not None:
                 o["trajectory_vs_ref"] = {"ate": ate(el, rl, a.max_dt), "rpe": rpe(el, rl, a.rpe_delta, a.rpe_unit)}
             if "cloud" in E and "cloud" in R:
-                ce, (cr, nr) = read_ply(E["cloud"]), read_ply(R["cloud"], normals=True)
+                (ce, ne), (cr, nr) = read_ply(E["cloud"], normals=True), read_ply(R["cloud"], normals=True)
                 if ei != 0 or ri != 0:   # object models: model frame -> world with each run's own obj -> world pose
                     w = _object_to_world(el, rl, a.max_dt) if el is not None and rl is not None else None
                     if w is None:
@@ -949,11 +1034,17 @@ def main(argv=None) -> int:
                         ce, cr = _apply(w[0], ce), _apply(w[1], cr)
                         if nr is not None:
                             nr = (nr.astype(np.float64) @ w[1][:3, :3].T).astype(np.float32)
+                        if ne is not None:
+                            ne = (ne.astype(np.float64) @ w[0][:3, :3].T).astype(np.float32)
                         o["cloud_pose_time"] = w[2]
                 if "cloud_error" not in o:
                     o["cloud"] = compare_clouds(ce, cr, a.radius, taus)
-                    if a.register and not registered(o, ce, cr, nr, None):
-                        return 2
+                    nr = ref_normals(o, cr, nr)
+                    if a.register:
+                        if not registered(o, ce, ne, cr, nr, None):
+                            return 2
+                    else:
+                        consistency(o, ce, ne, cr, nr, None)
             if ei == 0 and a.gt:
                 o["trajectory_vs_gt"] = gt_res
             results.append(o)
@@ -966,10 +1057,14 @@ def main(argv=None) -> int:
         except (OSError, ValueError) as e:
             sys.stderr.write(f"eval: --init: {e}\n")
             return 2
-        ce, (cr, nr) = read_ply(est[0]["cloud"]), read_ply(a.ref_cloud, normals=True)
+        (ce, ne), (cr, nr) = read_ply(est[0]["cloud"], normals=True), read_ply(a.ref_cloud, normals=True)
         o = {"model": 0, "ref_cloud": a.ref_cloud, "cloud": compare_clouds(ce, cr, a.radius, taus, T=T0)}
-        if a.register and not registered(o, ce, cr, nr, T0):
-            return 2
+        nr = ref_normals(o, cr, nr)
+        if a.register:
+            if not registered(o, ce, ne, cr, nr, T0):
+                return 2
+        else:
+            consistency(o, ce, ne, cr, nr, T0)
         if a.gt:
             o["trajectory_vs_gt"] = gt_res
         results.append(o)

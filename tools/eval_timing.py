@@ -8,11 +8,13 @@ sampled from it and jittered by N(0, 5 mm) per axis, radius 5 cm.
   icp step     mf_cloud_icp_step_dev (point-to-plane, the map's own normals) on the same clouds next to the mf_cloud_nn_dev query, both as
                medians of 20 calls after 5 warm-ups, and their ratio; then the wall time of a whole eval.register() from a start 1 degree
                and 1 cm off
+  normals      mf_cloud_normals_dev on the targets (grid build + walk and moments + eigen-solve), radius 2 x --radius as the evaluation
+               command's --estimate-normals takes it, as the median of 5 calls after 1 warm-up; minus the grid build at that radius
 
 Device times are medians of 10 calls after 2 warm-up calls, between HIP events on the call's stream.  One CPU line for contrast:
 scipy.spatial.cKDTree with 16 workers on the same clouds (tree build + query), if scipy is present.
 
-    python tools/eval_timing.py [--targets 26.9e6] [--queries 5e6] [--radius 0.05] [--no-cpu]
+    python tools/eval_timing.py [--targets 26.9e6] [--queries 5e6] [--radius 0.05] [--no-cpu] [--no-live] [--no-icp] [--no-normals]
 """
 from __future__ import annotations
 
@@ -50,6 +52,7 @@ def main(argv=None) -> int:
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-live", action="store_true")
     ap.add_argument("--no-icp", action="store_true")
+    ap.add_argument("--no-normals", action="store_true")
     a = ap.parse_args(argv)
     import torch
     from maskfusion_amd import stress, synth
@@ -120,6 +123,30 @@ def main(argv=None) -> int:
               f"inlier share {res['inlier_share']:.4f}, rmse {res['rmse']:.3g} m, |t| {np.linalg.norm(res['T'][:3, 3]):.2e} m, "
               f"angle {ev.rotation_angle(res['T'][:3, :3]):.2e} rad from the identity)")
         del drec, reg
+    if not a.no_normals:
+        N, rn = len(xyz), 2 * a.radius
+        need_n = C.c_uint64(0)
+        assert L.mf_cloud_normals_workspace(N, C.byref(need_n)) == 0
+        ws_n = torch.empty(int(need_n.value), dtype=torch.uint8, device="cuda")
+        nrm4 = torch.empty((N, 4), dtype=torch.float32, device="cuda")
+        cnt = torch.empty(N, dtype=torch.int32, device="cuda")
+
+        def normals():
+            rc = L.mf_cloud_normals_dev(dt.data_ptr(), 3, N, rn, 5, None, nrm4.data_ptr(), cnt.data_ptr(), ws_n.data_ptr(), int(need_n.value),
+                                        s.cuda_stream)
+            assert rc == 0, rc
+
+        def build_n():
+            rc = L.mf_cloud_nn_dev(dt.data_ptr(), 3, N, dq.data_ptr(), 3, 0, None, rn, dist.data_ptr(), idx.data_ptr(), ws.data_ptr(),
+                                   int(need.value), s.cuda_stream)
+            assert rc == 0, rc
+        tn = _median_ms(normals, s, reps=5, warm=1)
+        tb = _median_ms(build_n, s, reps=5, warm=1)
+        k_mean = cnt.double().mean().item()
+        print(f"normals    : median {tn[0]:.2f} ms (min {tn[1]:.2f}, max {tn[2]:.2f}) for {N / 1e6:.1f} M points at radius {rn:g} m, {k_mean:.1f} "
+              f"neighbours a point; walk + solve {tn[0] - tb[0]:.2f} ms (grid build {tb[0]:.2f} ms): {N * k_mean / (tn[0] - tb[0]) / 1e6:.1f} G neighbours/s; "
+              f"{int(torch.isnan(nrm4[:, 3]).sum().item())} points without a normal; workspace {need_n.value / 2**20:.0f} MiB")
+        del ws_n, nrm4, cnt
     if not a.no_live:
         mf = stress.make_context()
         rgb, depth, mask = st.frame(0)
