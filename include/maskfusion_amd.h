@@ -247,6 +247,32 @@ int mf_cloud_icp_step_dev(void* d_workspace, uint64_t workspace_bytes, const flo
 int mf_cloud_normals_workspace(int64_t n, uint64_t* bytes);
 int mf_cloud_normals_dev(const float* d_points, int32_t stride, int64_t n, float radius, int32_t min_neighbours, const float* viewpoint3,
                          float* d_normals /* [n][4] */, int32_t* d_count /* [n] */, void* d_workspace, uint64_t workspace_bytes, void* stream);
+/* FPFH descriptors of a cloud with normals, on the GPU (kernels: mf_eval.hip; DESIGN.md "Global registration"): what a registration without a
+ * starting pose matches (maskfusion_amd.eval.register_global).  Points are read as x, y, z and, at normal_offset, nx, ny, nz at
+ * d_points + i * stride floats.  A point is ELIGIBLE when its position and its normal are finite and the normal is not zero; normals are
+ * normalised in fp64 first.  The neighbours N(i) of an eligible i are the eligible j != i whose fp32 d2 passes d2 <= fl(radius * radius):
+ * mf_cloud_nn_dev's test over mf_cloud_nn_dev's grid.  Pair features, in fp64 from the fp32 inputs: d = p_j - p_i, L = |d| (L == 0: the
+ * pair is not counted); a1 = n_i . d / L, a2 = n_j . d / L; if |a1| < |a2| then n1 = n_j, n2 = n_i, d <- -d, f3 = -a2, else n1 = n_i,
+ * n2 = n_j, f3 = a1; v = d x n1 (|v| == 0: not counted), v <- v / |v|, w = n1 x v; f2 = v . n2, f1 = atan2(w . n2, n1 . n2).  Bins, clamped
+ * to 0..10: b1 = floor(11 (f1 + pi) / (2 pi)), b2 = floor(11 (f2 + 1) / 2), b3 = floor(11 (f3 + 1) / 2).  SPFH_i = the 33 counts
+ * (b1 | 11 + b2 | 22 + b3) over N(i), k_i = the number of counted pairs: d_spfh[i] = (33 counts, k_i), exact and the same for every call;
+ * d_spfh may be NULL.  FPFH_i[b] = sum over j in N(i) with L_ij > 0 and k_j > 0 of (1 / L_ij^2) SPFH_j[b] / k_j, summed in fp64 -- the
+ * point's own SPFH is not added: PCL's FPFHEstimation --, each of the three 11-bin parts scaled to the sum 100 and stored as fp32 in
+ * d_fpfh[i].  A row is NaN, all 33 values, for a point that is not eligible or when a part sums to 0.  The sums follow the order of the
+ * build's atomics: d_fpfh is reproducible to the last fp64 bits before the fp32 store.  MF_EINVAL as for mf_cloud_normals_dev (radius,
+ * more than 2^30 points, a null pointer, the workspace -- mf_cloud_fpfh_workspace(n) bytes, 16-byte aligned --, an eligible point with
+ * |x / radius| >= 2^30), and for a normal_offset below 3 or a normal that ends beyond the stride.  Enqueued on `stream`, which the call
+ * synchronises before it returns. */
+int mf_cloud_fpfh_workspace(int64_t n, uint64_t* bytes);
+int mf_cloud_fpfh_dev(const float* d_points, int32_t stride, int32_t normal_offset, int64_t n, float radius, float* d_fpfh /* [n][33] */,
+                      int32_t* d_spfh /* [n][34] or NULL */, void* d_workspace, uint64_t workspace_bytes, void* stream);
+/* The nearest descriptor by brute force, on the GPU (kernel: mf_eval.hip).  d_target [n_target][dim], d_query [n_query][dim], DEVICE fp32,
+ * dim 1..64.  d_idx[i] = the target j with the smallest fp32 d2 = sum over the bins b = 0 .. dim - 1, in that order, of (q_b - t_b)^2,
+ * every operation rounded on its own; ties go to the smallest j; d_d2[i] = that d2.  A row with a NaN is nobody's match, and a query with a
+ * NaN (or no target) gets -1 and +inf.  The result is a function of the inputs alone.  MF_EINVAL for a dim outside 1..64, more than 2^30
+ * rows or a null pointer.  Enqueued on `stream`, which the call synchronises before it returns. */
+int mf_feature_match_dev(const float* d_target, int64_t n_target, const float* d_query, int64_t n_query, int32_t dim, int32_t* d_idx,
+                         float* d_d2, void* stream);
 /* Segmentation scores on the GPU (kernels: mf_eval.hip; DESIGN.md "Segmentation evaluation"; the metrics built on them:
  * maskfusion_amd.eval.seg_metrics).  Both calls compare two label streams d_est, d_gt (DEVICE, uint8 [n_frames][height][width], any byte
  * alignment).  lut_est and lut_gt (HOST, 256 entries each) map a raw label value to a compact class index < n_est (< n_gt), or to 255: void.

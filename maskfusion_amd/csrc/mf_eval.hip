@@ -437,6 +437,216 @@ __global__ __launch_bounds__(kNnThreads) void k_normals_solve(NrmArgs a, const d
     }
 }
 
+// ---------------- FPFH descriptors of a cloud (mf_cloud_fpfh_dev; DESIGN.md "Global registration") ----------------
+// The cloud is target and query at once, as for the normals.  Four launches and the grid build between the first two:
+// k_fpfh_prep: one lane per point: the eligible points (position and normal finite, the normal not zero) as float4 -- the others as NaN, which
+//   the grid does not hold -- and the normals normalised in fp64, [n][4] doubles.  The grid is built of that copy, so a point that is not
+//   eligible is nobody's neighbour and the grid code stays as it is.
+// k_fpfh_spfh: one lane per point i, grid-stride as k_normals_walk.  Every record j != i that passes the radius test in the visit of its own
+//   cell (nrm_add_bucket's rule) gives one pair: its three bins from fpfh_pair, in fp64.  The 33 counters of a lane live in LDS, bin-major
+//   (s_h[bin][lane]: a lane's column, no two lanes on one bank), because a histogram indexed by a computed bin cannot live in registers.
+//   Integer counts: the SPFH does not depend on the order of a bucket's records.
+// k_fpfh_sum: one wavefront per point, lane b < 33 owns bin b.  The wavefront walks the same cells in step (every lane tests the same
+//   record: the loads are broadcasts), reads row j of the counts as one 136-byte line and lane b adds (1 / L^2) / k_j * SPFH_j[b] in fp64.
+//   The three part sums are taken by 33 lane reads in bin order, the same for every lane, so a row is scaled by one value per part.
+//   The sums follow a bucket's record order: reproducible to the last fp64 bits only, like the normals' moments.
+constexpr int kFpfhBins = 11, kFpfhDim = 33, kFpfhRow = 34;   // a row of counts: 33 bins and k
+constexpr double kFpfhPi = 3.14159265358979323846;
+struct FpfhArgs {
+    const float* p; int stride, noff, n;
+    float4* pts;              // [n] the eligible points, NaN for the others
+    double* nrm;              // [n][4] unit normals
+    int* spfh;                // [n][kFpfhRow]
+    float* out;               // [n][kFpfhDim]
+};
+__global__ __launch_bounds__(kNnThreads) void k_fpfh_prep(FpfhArgs a) {
+    for (int i = blockIdx.x * kNnThreads + threadIdx.x; i < a.n; i += gridDim.x * kNnThreads) {
+        const float* p = a.p + (size_t)i * a.stride;
+        const float x = p[0], y = p[1], z = p[2], nx = p[a.noff], ny = p[a.noff + 1], nz = p[a.noff + 2];
+        double ux = 0.0, uy = 0.0, uz = 0.0;
+        bool ok = false;
+        if (nn_finite(x, y, z) && nn_finite(nx, ny, nz)) {
+            const double len = sqrt(((double)nx * (double)nx + (double)ny * (double)ny) + (double)nz * (double)nz);
+            if (len > 0.0) { ok = true; ux = (double)nx / len; uy = (double)ny / len; uz = (double)nz / len; }
+        }
+        a.pts[i] = ok ? make_float4(x, y, z, 0.f) : make_float4(NAN, NAN, NAN, 0.f);
+        double* o = a.nrm + (size_t)i * 4;
+        o[0] = ux; o[1] = uy; o[2] = uz; o[3] = 0.0;
+    }
+}
+// f(record) for every record within the radius of (x, y, z), each once: nrm_walk's cells and nrm_add_bucket's two tests
+template <class F>
+__device__ __forceinline__ void fpfh_walk(const NnGrid& g, float x, float y, float z, F&& f) {
+    int x0, x1, y0, y1, z0, z1;
+    nn_cell_range(g, x, x0, x1); nn_cell_range(g, y, y0, y1); nn_cell_range(g, z, z0, z1);
+    for (int cz = z0; cz <= z1; ++cz) {
+        const double gz = nn_box_gap(g, z, cz);
+        for (int cy = y0; cy <= y1; ++cy) {
+            const double gy = nn_box_gap(g, y, cy);
+            for (int cx = x0; cx <= x1; ++cx) {
+                const double gap = (gz + gy + nn_box_gap(g, x, cx)) * (1.0 - 3.814697265625e-06);   // (nn_find's bound)
+                if (gap > (double)g.r2) continue;
+                const unsigned b = nn_hash(cx, cy, cz) & g.mask;
+                const unsigned e = g.start[b + 1];
+                for (unsigned r = g.start[b]; r < e; ++r) {
+                    const float4 p = g.rec[r];
+                    const float fx = p.x - x, fy = p.y - y, fz = p.z - z;
+                    const float d2 = fx * fx + fy * fy + fz * fz;
+                    if (!(d2 <= g.r2)) continue;
+                    if (nn_cell(g, p.x) != cx || nn_cell(g, p.y) != cy || nn_cell(g, p.z) != cz) continue;   // another cell's record in a shared bucket
+                    f(p);
+                }
+            }
+        }
+    }
+}
+__device__ __forceinline__ int fpfh_bin(double t) { return t >= 10.0 ? 10 : (t > 0.0 ? (int)t : 0); }   // floor, clamped to 0..10
+// The bins of the pair (i, j), d = p_j - p_i, unit normals ni and nj; false: the pair is not counted (the header's steps 1 - 5)
+__device__ __forceinline__ bool fpfh_pair(double dx, double dy, double dz, double nix, double niy, double niz, double njx, double njy, double njz,
+                                          int& b1, int& b2, int& b3) {
+    const double L2 = (dx * dx + dy * dy) + dz * dz;
+    if (!(L2 > 0.0)) return false;
+    const double L = sqrt(L2);
+    const double a1 = ((nix * dx + niy * dy) + niz * dz) / L, a2 = ((njx * dx + njy * dy) + njz * dz) / L;
+    double n1x = nix, n1y = niy, n1z = niz, n2x = njx, n2y = njy, n2z = njz, f3 = a1;
+    if (fabs(a1) < fabs(a2)) {
+        n1x = njx; n1y = njy; n1z = njz; n2x = nix; n2y = niy; n2z = niz;
+        dx = -dx; dy = -dy; dz = -dz; f3 = -a2;
+    }
+    double vx = dy * n1z - dz * n1y, vy = dz * n1x - dx * n1z, vz = dx * n1y - dy * n1x;
+    const double vl2 = (vx * vx + vy * vy) + vz * vz;
+    if (!(vl2 > 0.0)) return false;
+    const double vl = sqrt(vl2);
+    vx /= vl; vy /= vl; vz /= vl;
+    const double wx = n1y * vz - n1z * vy, wy = n1z * vx - n1x * vz, wz = n1x * vy - n1y * vx;
+    const double f2 = (vx * n2x + vy * n2y) + vz * n2z;
+    const double f1 = atan2((wx * n2x + wy * n2y) + wz * n2z, (n1x * n2x + n1y * n2y) + n1z * n2z);
+    b1 = fpfh_bin(11.0 * (f1 + kFpfhPi) / (2.0 * kFpfhPi));
+    b2 = fpfh_bin(11.0 * (f2 + 1.0) / 2.0);
+    b3 = fpfh_bin(11.0 * (f3 + 1.0) / 2.0);
+    return true;
+}
+__global__ __launch_bounds__(kNnThreads) void k_fpfh_spfh(NnGrid g, FpfhArgs a) {
+    __shared__ int s_h[kFpfhDim][kNnThreads];
+    const int tid = threadIdx.x;
+    for (int i = blockIdx.x * kNnThreads + tid; i < a.n; i += gridDim.x * kNnThreads) {
+        for (int b = 0; b < kFpfhDim; ++b) s_h[b][tid] = 0;
+        int k = 0;
+        const float4 pi = a.pts[i];
+        if (nn_finite(pi.x, pi.y, pi.z)) {
+            if (!nn_in_range(g, pi.x, pi.y, pi.z)) atomicOr(g.flag, 1);
+            else {
+                const double* ni = a.nrm + (size_t)i * 4;
+                const double nix = ni[0], niy = ni[1], niz = ni[2];
+                fpfh_walk(g, pi.x, pi.y, pi.z, [&](const float4& pj) {
+                    const int j = __float_as_int(pj.w);
+                    if (j == i) return;
+                    const double* nj = a.nrm + (size_t)j * 4;
+                    int b1, b2, b3;
+                    if (!fpfh_pair((double)pj.x - (double)pi.x, (double)pj.y - (double)pi.y, (double)pj.z - (double)pi.z, nix, niy, niz, nj[0], nj[1],
+                                   nj[2], b1, b2, b3))
+                        return;
+                    ++s_h[b1][tid]; ++s_h[kFpfhBins + b2][tid]; ++s_h[2 * kFpfhBins + b3][tid];
+                    ++k;
+                });
+            }
+        }
+        int* o = a.spfh + (size_t)i * kFpfhRow;
+        for (int b = 0; b < kFpfhDim; ++b) o[b] = s_h[b][tid];
+        o[kFpfhDim] = k;
+    }
+}
+constexpr int kFpfhWaves = kNnThreads / 64;   // points per workgroup of k_fpfh_sum
+__global__ __launch_bounds__(kNnThreads) void k_fpfh_sum(NnGrid g, FpfhArgs a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bin = min(lane, kFpfhDim - 1);      // (the lanes past the last bin walk along and store nothing)
+    for (int i0 = blockIdx.x * kFpfhWaves; i0 < a.n; i0 += gridDim.x * kFpfhWaves) {
+        const int i = i0 + wave;
+        if (i >= a.n) continue;
+        double acc = 0.0;
+        const float4 pi = a.pts[i];
+        if (nn_finite(pi.x, pi.y, pi.z) && nn_in_range(g, pi.x, pi.y, pi.z)) {
+            fpfh_walk(g, pi.x, pi.y, pi.z, [&](const float4& pj) {
+                const int j = __float_as_int(pj.w);
+                if (j == i) return;
+                const int* sj = a.spfh + (size_t)j * kFpfhRow;
+                const int kj = sj[kFpfhDim];
+                if (kj <= 0) return;
+                const double dx = (double)pj.x - (double)pi.x, dy = (double)pj.y - (double)pi.y, dz = (double)pj.z - (double)pi.z;
+                const double L2 = (dx * dx + dy * dy) + dz * dz;
+                if (!(L2 > 0.0)) return;
+                acc += ((1.0 / L2) / (double)kj) * (double)sj[bin];
+            });
+        }
+        double p0 = 0.0, p1 = 0.0, p2 = 0.0;      // the parts' sums, every lane the same: bins in order
+#pragma unroll
+        for (int m = 0; m < kFpfhDim; ++m) {
+            const double v = __shfl(acc, m, 64);
+            if (m < kFpfhBins) p0 += v;
+            else if (m < 2 * kFpfhBins) p1 += v;
+            else p2 += v;
+        }
+        const bool ok = p0 > 0.0 && p1 > 0.0 && p2 > 0.0;
+        const double part = lane < kFpfhBins ? p0 : (lane < 2 * kFpfhBins ? p1 : p2);
+        if (lane < kFpfhDim) a.out[(size_t)i * kFpfhDim + lane] = ok ? (float)(100.0 * acc / part) : NAN;
+    }
+}
+
+// ---------------- nearest descriptor (mf_feature_match_dev; DESIGN.md "Global registration") ----------------
+// Brute force: one lane per query, one workgroup per kMatchThreads queries.  A lane's query row sits in LDS as float4 groups, group-major
+// (s_q[group][lane]: 16 contiguous bytes a lane, no conflicts), padded with zeros to a multiple of four bins; the targets pass through LDS in
+// tiles of kMatchTile rows, padded the same way, and every lane reads the same target group (a broadcast).  A padded bin adds (0 - 0)^2 = +0
+// to a sum that is >= +0 or NaN: the fp32 d2 is that of the dim bins in order.  Targets are scanned in index order and only a strictly
+// smaller d2 replaces the best, so ties go to the smallest index, a row with a NaN (d2 = NaN) never wins and a query with a NaN keeps -1, +inf.
+constexpr int kMatchThreads = 128, kMatchTile = 64, kMatchMaxDim = 64;
+struct MatchArgs {
+    const float* t; int nt;
+    const float* q; int nq;
+    int dim;
+    int* idx; float* d2;
+};
+__global__ __launch_bounds__(kMatchThreads) void k_feature_match(MatchArgs a) {
+    __shared__ float4 s_q[kMatchMaxDim / 4][kMatchThreads];
+    __shared__ float4 s_t[kMatchTile][kMatchMaxDim / 4];
+    const int tid = threadIdx.x;
+    const int i = blockIdx.x * kMatchThreads + tid;
+    const int d4 = (a.dim + 3) >> 2;
+    for (int c = 0; c < d4; ++c) {
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int b = 4 * c + k;
+            v[k] = (i < a.nq && b < a.dim) ? a.q[(size_t)i * a.dim + b] : 0.f;
+        }
+        s_q[c][tid] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+    float best = INFINITY;
+    int bj = -1;
+    float* st = (float*)s_t;
+    for (int t0 = 0; t0 < a.nt; t0 += kMatchTile) {
+        const int rows = min(kMatchTile, a.nt - t0);
+        __syncthreads();       // the tile before has been read
+        for (int e = tid; e < rows * d4 * 4; e += kMatchThreads) {
+            const int r = e / (d4 * 4), b = e - r * (d4 * 4);
+            st[r * kMatchMaxDim + b] = b < a.dim ? a.t[(size_t)(t0 + r) * a.dim + b] : 0.f;
+        }
+        __syncthreads();
+        for (int r = 0; r < rows; ++r) {
+            float d2 = 0.f;
+            for (int c = 0; c < d4; ++c) {
+                const float4 q = s_q[c][tid], t = s_t[r][c];
+                const float dx = q.x - t.x, dy = q.y - t.y, dz = q.z - t.z, dw = q.w - t.w;
+                d2 = d2 + dx * dx;
+                d2 = d2 + dy * dy;
+                d2 = d2 + dz * dz;
+                d2 = d2 + dw * dw;
+            }
+            if (d2 < best) { best = d2; bj = t0 + r; }
+        }
+    }
+    if (i < a.nq) { a.idx[i] = bj; a.d2[i] = best; }
+}
+
 // ---------------- live surfels of a model -> float4 points (mf_eval.inl) ----------------
 // the live surfels in download order (mf_download_map: the runs in order, each run's first len slots) -> out, position + index; a surfel at or
 // below the confidence threshold becomes a NaN point, which the grid does not hold
@@ -619,6 +829,51 @@ static int normals_run(const float* d_points, int stride, int64_t n, float radiu
         hipLaunchKernelGGL(k_normals_solve, dim3(nn_grid_blocks(n)), dim3(kNnThreads), 0, s, a, (const double*)sums);
     }
     return nn_finish(g, s, &why);
+}
+
+// ---------------- FPFH: workspace = points [n] float4 | normals [n][4] double | the grid's workspace | counts [n][34] int ----------------
+static uint64_t fpfh_grid_at(int64_t n) { const uint64_t N = (uint64_t)std::max<int64_t>(n, 0); return nn_align(N * 16) + nn_align(N * 32); }
+static uint64_t fpfh_workspace_bytes(int64_t n) {
+    return fpfh_grid_at(n) + nn_workspace_bytes(n) + nn_align((uint64_t)std::max<int64_t>(n, 0) * kFpfhRow * 4);
+}
+static int fpfh_run(const float* d_points, int stride, int normal_offset, int64_t n, float radius, float* d_fpfh, int32_t* d_spfh, void* d_ws,
+                    uint64_t ws_bytes, hipStream_t s) {
+    const char* why = nullptr;
+    if (!(std::isfinite(radius) && radius > 0.f) || stride < 6 || normal_offset < 3 || normal_offset + 3 > stride) return MF_EINVAL;
+    if (n < 0 || n > (int64_t)1 << 30 || (n > 0 && (!d_points || !d_fpfh))) return MF_EINVAL;
+    if (!d_ws || ((uintptr_t)d_ws & 15) != 0 || ws_bytes < fpfh_workspace_bytes(n)) return MF_EINVAL;
+    char* w = (char*)d_ws;
+    FpfhArgs a;
+    memset(&a, 0, sizeof(a));
+    a.p = d_points; a.stride = stride; a.noff = normal_offset; a.n = (int)n; a.out = d_fpfh;
+    a.pts = (float4*)w;
+    a.nrm = (double*)(w + nn_align((uint64_t)n * 16));
+    a.spfh = d_spfh ? d_spfh : (int*)(w + fpfh_grid_at(n) + nn_workspace_bytes(n));
+    const NnGrid g = nn_layout(w + fpfh_grid_at(n), n, radius);
+    if (n > 0) hipLaunchKernelGGL(k_fpfh_prep, dim3(nn_grid_blocks(n)), dim3(kNnThreads), 0, s, a);
+    const int rc = nn_build(g, (const float*)a.pts, 4, -1, nullptr, n, s, &why);
+    if (rc != MF_OK) return rc;
+    if (n > 0) {
+        hipLaunchKernelGGL(k_fpfh_spfh, dim3(nn_grid_blocks(n)), dim3(kNnThreads), 0, s, g, a);
+        const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((n + kFpfhWaves - 1) / kFpfhWaves, kNnMaxGrid));
+        hipLaunchKernelGGL(k_fpfh_sum, dim3(nb), dim3(kNnThreads), 0, s, g, a);
+    }
+    return nn_finish(g, s, &why);
+}
+
+static int feature_match(const float* d_target, int64_t n_target, const float* d_query, int64_t n_query, int dim, int32_t* d_idx, float* d_d2,
+                         hipStream_t s) {
+    if (dim < 1 || dim > kMatchMaxDim) return MF_EINVAL;
+    if (n_target < 0 || n_query < 0 || n_target > (int64_t)1 << 30 || n_query > (int64_t)1 << 30) return MF_EINVAL;
+    if ((n_target > 0 && !d_target) || (n_query > 0 && (!d_query || !d_idx || !d_d2))) return MF_EINVAL;
+    if (n_query > 0) {
+        MatchArgs a;
+        memset(&a, 0, sizeof(a));
+        a.t = d_target; a.nt = (int)n_target; a.q = d_query; a.nq = (int)n_query; a.dim = dim; a.idx = d_idx; a.d2 = d_d2;
+        hipLaunchKernelGGL(k_feature_match, dim3((unsigned)((n_query + kMatchThreads - 1) / kMatchThreads)), dim3(kMatchThreads), 0, s, a);
+    }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return MF_EHIP;
+    return MF_OK;
 }
 
 // ---------------- segmentation scores (mf_label_confusion_dev, mf_label_boundary_dev; DESIGN.md "Segmentation evaluation") ----------------
@@ -947,6 +1202,22 @@ extern "C" int mf_cloud_normals_workspace(int64_t n, uint64_t* bytes) {
 extern "C" int mf_cloud_normals_dev(const float* d_points, int32_t stride, int64_t n, float radius, int32_t min_neighbours, const float* viewpoint3,
                                     float* d_normals, int32_t* d_count, void* d_workspace, uint64_t workspace_bytes, void* stream) {
     return normals_run(d_points, stride, n, radius, min_neighbours, viewpoint3, (float4*)d_normals, d_count, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int mf_cloud_fpfh_workspace(int64_t n, uint64_t* bytes) {
+    if (!bytes || n < 0 || n > (int64_t)1 << 30) return MF_EINVAL;
+    *bytes = fpfh_workspace_bytes(n);
+    return MF_OK;
+}
+
+extern "C" int mf_cloud_fpfh_dev(const float* d_points, int32_t stride, int32_t normal_offset, int64_t n, float radius, float* d_fpfh, int32_t* d_spfh,
+                                 void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    return fpfh_run(d_points, stride, normal_offset, n, radius, d_fpfh, d_spfh, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int mf_feature_match_dev(const float* d_target, int64_t n_target, const float* d_query, int64_t n_query, int32_t dim, int32_t* d_idx,
+                                    float* d_d2, void* stream) {
+    return feature_match(d_target, n_target, d_query, n_query, dim, d_idx, d_d2, (hipStream_t)stream);
 }
 
 extern "C" int mf_label_confusion_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_frames, int32_t height, int32_t width,

@@ -6,10 +6,12 @@ GPU through mf_cloud_nn_dev (kernels: csrc/mf_eval.hip); everything else is nump
 before they are scored: point-to-plane (or point-to-point) Gauss-Newton steps on the GPU (mf_cloud_icp_build_dev / mf_cloud_icp_step_dev), the
 6 x 6 solve and the pose update in fp64 here.  estimate_normals() gives a cloud that has no normals the ones point-to-plane needs, from its
 own radius neighbourhoods on the GPU (mf_cloud_normals_dev); normal_consistency() scores the normals of two clouds against each other.
+register_global() needs no start: FPFH descriptors of voxel key points (mf_cloud_fpfh_dev) matched on the GPU (mf_feature_match_dev), a
+seeded RANSAC over the matches in numpy, then register().
 
     python -m maskfusion_amd.eval --est DIR [--ref DIR] [--gt FILE] [--radius R] [--tau a,b,c] [--pair est_id:ref_id ...]
                                   [--register [--register-radius R0,R1,...] [--register-iterations N] [--point-to-point]]
-                                  [--ref-cloud FILE [--init FILE]] [--estimate-normals[=R]] [--normals]
+                                  [--register-global[=VOXEL]] [--ref-cloud FILE [--init FILE]] [--estimate-normals[=R]] [--normals]
                                   [--seg-gt DIR [--seg-gt-prefix Mask] [--seg-index-width 4] [--seg-radius R] [--seg-void V]]
 
 prints one JSON object per model on stdout (INTEGRATION.md "Evaluating a run"); with --seg-gt, one per ground-truth object of the
@@ -427,7 +429,7 @@ def rotation_angle(R) -> float:
 
 def register(est, ref, radius: float, T0=None, ref_normals=None, max_iterations: int = 50, schedule=None, method: str = "plane",
              tol_translation: float = 1e-6, tol_rotation: float = 1e-6, trace: bool = False) -> dict:
-    """Rigid registration of `est` onto `ref` from the start T0 (4 x 4, est -> ref; identity when None): no scale, no global search.
+    """Rigid registration of `est` onto `ref` from the start T0 (4 x 4, est -> ref; identity when None): no scale, no global search (register_global finds a start).
     method "plane": point-to-plane, needs ref_normals ((n, 3) array, or the column of ref where the normals start); "point":
     point-to-point, normals are not used.  Every iteration pairs each est point with its nearest ref point within the radius
     (exactly nearest(ref, est, radius, T)), sums the Gauss-Newton system on the GPU, solves it here (solve_step) and applies
@@ -565,9 +567,226 @@ def normal_consistency(est, est_normals, ref, ref_normals, radius: float, T=None
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
+# global registration
+# ------------------------------------------------------------------------------------------------------------------------------------
+FPFH_DIM = 33
+MIN_MUTUAL = 30           # register_global: fewer mutual matches than this, and every est -> ref match is a correspondence
+
+
+def voxel_subsample(points, voxel: float) -> np.ndarray:
+    """The indices (int64, ascending) of the first point, lowest index, of every occupied voxel: cells are floor(x / voxel) per axis in
+    fp64.  Points that are not finite are left out.  Plain numpy."""
+    p = np.asarray(points)[:, :3].astype(np.float64)
+    if not (math.isfinite(voxel) and voxel > 0):
+        raise ValueError("voxel must be finite and > 0")
+    ok = np.flatnonzero(np.isfinite(p).all(1))
+    if ok.size == 0:
+        return np.zeros(0, np.int64)
+    cells = np.floor(p[ok] / float(voxel))
+    _, first = np.unique(cells, axis=0, return_index=True)       # return_index: the first occurrence
+    return np.sort(ok[first]).astype(np.int64)
+
+
+def fpfh(points, normals, radius: float):
+    """FPFH descriptors of a cloud with normals (mf_cloud_fpfh_dev; the definition: include/maskfusion_amd.h).  points (n, >= 3), normals
+    (n, 3): float32 numpy arrays or device tensors.  Returns numpy (fpfh float32 (n, 33), spfh int32 (n, 34): the 33 counts of the point's own
+    pair histogram and k, the number of counted pairs).  A row of fpfh is NaN where the point or its normal is not finite, the normal is
+    zero, or no neighbour within `radius` has a counted pair."""
+    import torch
+    from .lib import load, MFError
+    L = load()
+    p, nr_ = _device_points(points), _device_points(normals)
+    if nr_.shape[0] != p.shape[0]:
+        raise ValueError("normals must have one row per point")
+    rec = torch.cat([p[:, :3], nr_[:, :3]], 1).contiguous()
+    n = int(rec.shape[0])
+    need = C.c_uint64(0)
+    if L.mf_cloud_fpfh_workspace(n, C.byref(need)) != 0:
+        raise MFError("mf_cloud_fpfh_workspace failed")
+    ws = torch.empty(int(need.value), dtype=torch.uint8, device=rec.device)
+    out = torch.empty((max(n, 1), FPFH_DIM), dtype=torch.float32, device=rec.device)
+    cnt = torch.empty((max(n, 1), FPFH_DIM + 1), dtype=torch.int32, device=rec.device)
+    stream = torch.cuda.current_stream().cuda_stream if rec.device.type == "cuda" else None
+    rc = L.mf_cloud_fpfh_dev(rec.data_ptr() if n else None, 6, 3, n, float(radius), out.data_ptr(), cnt.data_ptr(), ws.data_ptr(),
+                             int(need.value), stream)
+    if rc != 0:
+        raise MFError(f"mf_cloud_fpfh_dev failed with code {rc} (radius must be finite and > 0, coordinates |x / radius| < 2^30)")
+    return out[:n].cpu().numpy(), cnt[:n].cpu().numpy()
+
+
+def match_features(target, query):
+    """For every query descriptor the nearest target descriptor by brute force (mf_feature_match_dev): (n, dim <= 64) float32 numpy arrays
+    or device tensors.  Returns numpy (idx int32, -1: none; d2 float32, the squared distance, +inf: none).  Ties go to the smallest index;
+    a row with a NaN matches nothing and is nobody's match."""
+    import torch
+    from .lib import load, MFError, torch_device
+    L = load()
+
+    def dev(a):
+        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(a, np.float32)))
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError("descriptors must be (n, dim) float32")
+        return t.to(torch_device()).contiguous()
+    t, q = dev(target), dev(query)
+    if t.shape[1] != q.shape[1]:
+        raise ValueError(f"target descriptors have {t.shape[1]} values, query descriptors {q.shape[1]}")
+    nt, nq = int(t.shape[0]), int(q.shape[0])
+    idx = torch.empty(max(nq, 1), dtype=torch.int32, device=q.device)
+    d2 = torch.empty(max(nq, 1), dtype=torch.float32, device=q.device)
+    stream = torch.cuda.current_stream().cuda_stream if q.device.type == "cuda" else None
+    rc = L.mf_feature_match_dev(t.data_ptr() if nt else None, nt, q.data_ptr() if nq else None, nq, int(q.shape[1]), idx.data_ptr(),
+                                d2.data_ptr(), stream)
+    if rc != 0:
+        raise MFError(f"mf_feature_match_dev failed with code {rc} (1 to 64 values per descriptor)")
+    return idx[:nq].cpu().numpy(), d2[:nq].cpu().numpy()
+
+
+def _horn_batch(src, dst):
+    """align_horn's rule on a batch: src, dst (K, m, 3) fp64 -> R (K, 3, 3), t (K, 3)"""
+    ms, md = src.mean(1), dst.mean(1)
+    H = np.einsum("kia,kib->kab", src - ms[:, None], dst - md[:, None])
+    U, _, Vt = np.linalg.svd(H)
+    V = np.swapaxes(Vt, 1, 2)
+    Ut = np.swapaxes(U, 1, 2)
+    D = np.ones((len(H), 3))
+    D[:, 2] = np.where(np.linalg.det(V @ Ut) < 0, -1.0, 1.0)
+    R = (V * D[:, None, :]) @ Ut
+    return R, md - np.einsum("kab,kb->ka", R, ms)
+
+
+def ransac_correspondences(src, dst, inlier_distance: float, hypotheses: int = 20000, seed: int = 0, edge_tolerance: float = 0.1,
+                           chunk: int = 512) -> dict:
+    """The hypothesis search of register_global over correspondences src[k] <-> dst[k] ((m, 3) each; the T sought maps src onto dst).
+    `hypotheses` triples of three different correspondences are drawn at once from numpy.random.default_rng(seed); a triple is dropped
+    when one of its three edges has lengths in src and dst that disagree by more than edge_tolerance (the shorter below 1 - edge_tolerance
+    of the longer) -- a rigid motion keeps lengths.  Every other triple is solved by align_horn's rule, in batches, and scored by the
+    number of correspondences with |T src - dst| <= inlier_distance, in fp64.  The largest count wins, ties go to the hypothesis drawn
+    earlier; T is then fitted again to the winner's inliers (align_horn).  Returns {"T" 4 x 4, "inliers": the winner's count, "inlier_mask"
+    bool (m,): under the winning triple's pose, "hypotheses": drawn, "tested": solved and scored}; without a testable triple T is None and
+    inliers 0.  The same input and seed give the same result."""
+    src, dst = np.asarray(src, np.float64).reshape(-1, 3), np.asarray(dst, np.float64).reshape(-1, 3)
+    m = len(src)
+    out = {"T": None, "inliers": 0, "inlier_mask": np.zeros(m, bool), "hypotheses": int(hypotheses), "tested": 0}
+    if m < 3 or len(dst) != m or hypotheses < 1:
+        return out
+    rng = np.random.default_rng(seed)
+    tri = rng.integers(0, m, (int(hypotheses), 3))
+    keep = (tri[:, 0] != tri[:, 1]) & (tri[:, 0] != tri[:, 2]) & (tri[:, 1] != tri[:, 2])
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        ls = np.linalg.norm(src[tri[:, a]] - src[tri[:, b]], axis=1)
+        ld = np.linalg.norm(dst[tri[:, a]] - dst[tri[:, b]], axis=1)
+        with np.errstate(invalid="ignore"):
+            keep &= np.minimum(ls, ld) >= (1.0 - edge_tolerance) * np.maximum(ls, ld)
+            keep &= np.minimum(ls, ld) > 0
+    tri = tri[keep]
+    out["tested"] = int(len(tri))
+    best, best_R, best_t = 0, None, None
+    for a in range(0, len(tri), chunk):
+        t3 = tri[a:a + chunk]
+        R, t = _horn_batch(src[t3], dst[t3])
+        moved = np.einsum("kab,mb->kma", R, src) + t[:, None, :]
+        cnt = (np.linalg.norm(moved - dst[None], axis=2) <= inlier_distance).sum(1)
+        k = int(np.argmax(cnt))                 # the first of equal counts
+        if cnt[k] > best:
+            best, best_R, best_t = int(cnt[k]), R[k], t[k]
+    if best_R is None:
+        return out
+    mask = np.linalg.norm(src @ best_R.T + best_t - dst, axis=1) <= inlier_distance
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = best_R, best_t
+    if mask.sum() >= 3:
+        T = align_horn(src[mask], dst[mask])
+    out.update({"T": T, "inliers": best, "inlier_mask": mask})
+    return out
+
+
+def _towards_centroid(points, normals):
+    """the normals turned to face the centroid of the finite points: a rule that moves with the cloud, which the descriptors need"""
+    p, n = np.asarray(points, np.float64), np.asarray(normals, np.float64)
+    c = p[np.isfinite(p).all(1)].mean(0) if np.isfinite(p).all(1).any() else np.zeros(3)
+    with np.errstate(invalid="ignore"):
+        flip = ((c - p) * n).sum(1) < 0
+    return np.where(flip[:, None], -n, n).astype(np.float32)
+
+
+def register_global(est, ref, voxel: float, est_normals=None, ref_normals=None, seed: int = 0, hypotheses: int = 20000,
+                    inlier_distance=None, refine: bool = True, min_mutual: int = MIN_MUTUAL, max_iterations: int = 50, method: str = "plane",
+                    schedule=None) -> dict:
+    """Rigid registration of `est` onto `ref` (numpy (n, 3) float32) WITHOUT a start: a coarse pose from matched FPFH descriptors, then
+    register().
+      1. both clouds are subsampled to one point per voxel (voxel_subsample);
+      2. a cloud without normals gets them from estimate_normals on the whole cloud at radius 2 voxel; for the descriptors the key points'
+         normals, given or estimated, are turned to face their cloud's centroid -- an orientation rule that moves with the cloud, which a
+         rule of the coordinate axes does not;
+      3. FPFH of the key points at radius 5 voxel (fpfh);
+      4. descriptors are matched both ways (match_features); the mutual matches are the correspondences, or, with fewer than min_mutual
+         of them, every est -> ref match;
+      5. ransac_correspondences(seed, hypotheses, inlier_distance -- default 1.5 voxel);
+      6. refine: register() on the FULL clouds from that pose, radii halving from inlier_distance down to voxel / 2, or `schedule`
+         (point-to-plane on ref_normals, given or estimated; method "point": point-to-point).
+    Returns register()'s dictionary -- with refine=False: T = the coarse pose, iterations 0, converged False, reason "not refined" --
+    plus "coarse": {"T", "correspondences", "mutual", "inliers", "hypotheses", "tested", "key_points": [est, ref]}.  Without a coarse pose
+    (fewer than three correspondences, no triple passes the edge test) T is the identity, converged False and reason says so.  With the same
+    seed the coarse stage is deterministic up to FPFH's last bits (mf_cloud_fpfh_dev sums in the order of its grid's atomics): a
+    descriptor distance that ties to fp32 rounding could change a match between two calls."""
+    if not (math.isfinite(voxel) and voxel > 0):
+        raise ValueError("voxel must be finite and > 0")
+    inlier_distance = 1.5 * voxel if inlier_distance is None else float(inlier_distance)
+    if not (math.isfinite(inlier_distance) and inlier_distance > 0):
+        raise ValueError("inlier_distance must be finite and > 0")
+    clouds = []
+    for pts, nrm in ((est, est_normals), (ref, ref_normals)):
+        pts = np.ascontiguousarray(np.asarray(pts, np.float32)[:, :3])
+        if nrm is None:
+            nrm = estimate_normals(pts, 2.0 * voxel)[0]
+        nrm = np.ascontiguousarray(np.asarray(nrm, np.float32)[:, :3])
+        if len(nrm) != len(pts):
+            raise ValueError("normals must have one row per point")
+        key = voxel_subsample(pts, voxel)
+        kp = pts[key]
+        desc = fpfh(kp, _towards_centroid(kp, nrm[key]), 5.0 * voxel)[0]
+        clouds.append((pts, nrm, kp, desc))
+    (pe, ne, ke, de), (pr, nr_, kr, dr) = clouds
+    e2r = match_features(dr, de)[0]
+    r2e = match_features(de, dr)[0]
+    hit = np.flatnonzero(e2r >= 0)
+    mutual = hit[r2e[e2r[hit]] == hit]
+    use = mutual if len(mutual) >= min_mutual else hit
+    rs = ransac_correspondences(ke[use], kr[e2r[use]], inlier_distance, hypotheses, seed)
+    coarse = {"T": rs["T"], "correspondences": int(len(use)), "mutual": int(len(mutual)), "inliers": rs["inliers"], "hypotheses": rs["hypotheses"],
+              "tested": rs["tested"], "key_points": [int(len(ke)), int(len(kr))]}
+    if rs["T"] is None:
+        res = {"T": np.eye(4), "iterations": 0, "inliers": 0, "inlier_share": 0.0, "rmse": None, "converged": False,
+               "reason": f"no coarse pose: {len(use)} correspondences, {rs['tested']} of {rs['hypotheses']} triples passed the edge test",
+               "radius": inlier_distance, "method": method, "trace": []}
+    elif refine:
+        radii = [inlier_distance]
+        while radii[-1] / 2.0 > voxel / 2.0:
+            radii.append(radii[-1] / 2.0)
+        radii.append(voxel / 2.0)
+        if schedule is not None:
+            radii = [float(r) for r in schedule]
+        res = register(pe, pr, radii[-1], T0=rs["T"], ref_normals=nr_ if method == "plane" else None, max_iterations=max_iterations,
+                       schedule=radii, method=method)
+    else:
+        res = {"T": rs["T"], "iterations": 0, "inliers": rs["inliers"], "inlier_share": rs["inliers"] / max(len(use), 1), "rmse": None,
+               "converged": False, "reason": "not refined", "radius": inlier_distance, "method": method, "trace": []}
+    res["coarse"] = coarse
+    return res
+
+
+def coarse_summary(coarse: dict) -> dict:
+    """what the command prints of register_global's coarse block"""
+    T = coarse["T"]
+    return {"T": None if T is None else [[float(v) for v in row] for row in T], "correspondences": coarse["correspondences"],
+            "mutual": coarse["mutual"], "inliers": coarse["inliers"], "hypotheses": coarse["hypotheses"], "tested": coarse["tested"],
+            "key_points": coarse["key_points"]}
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
 # segmentation
 # ------------------------------------------------------------------------------------------------------------------------------------
-VOID = 255                # a look-up table entry: the raw value belongs to no class
+VOID = 255               # a look-up table entry: the raw value belongs to no class
 MAX_CLASSES = 64          # classes per side of the device calls (mf_label_confusion_dev)
 MAX_RADIUS = 16           # mf_label_boundary_dev
 
@@ -933,6 +1152,10 @@ def main(argv=None) -> int:
     ap.add_argument("--register-radius", metavar="R0,R1,...", help="the registration's radii, coarse to fine (default 4, 2 and 1 times --radius)")
     ap.add_argument("--register-iterations", type=int, default=50, help="iteration cap per radius (default 50)")
     ap.add_argument("--point-to-point", action="store_true", help="register point-to-point (for a reference cloud without normals)")
+    ap.add_argument("--register-global", nargs="?", const=True, type=float, metavar="VOXEL", help="register without a start: a coarse pose from FPFH "
+                    "descriptors of one key point per VOXEL (default --radius) matched on the GPU and a seeded RANSAC, then --register from it "
+                    "(implies --register; adds registration.coarse; radii from 1.5 VOXEL down to VOXEL / 2 unless --register-radius is given)")
+    ap.add_argument("--register-seed", type=int, default=0, help="seed of --register-global's RANSAC (default 0)")
     ap.add_argument("--ref-cloud", metavar="FILE", help="a single reference PLY (a ground-truth model) for the background cloud of --est")
     ap.add_argument("--init", metavar="FILE", help="with --ref-cloud: text file with the 4 x 4 est -> ref start")
     ap.add_argument("--estimate-normals", nargs="?", const=True, type=float, metavar="R", help="estimate the normals of a reference cloud whose PLY "
@@ -946,6 +1169,8 @@ def main(argv=None) -> int:
     ap.add_argument("--seg-radius", type=int, help="pixel radius of the boundary measure, 0..16 (default: 0.008 of the image diagonal)")
     ap.add_argument("--seg-void", type=int, help="ground-truth value that marks pixels to leave out (default: none)")
     a = ap.parse_args(argv)
+    if a.register_seed != 0 and a.register_global is None:
+        ap.error("--register-seed needs --register-global")
     if not a.seg_gt and (a.seg_radius is not None or a.seg_void is not None):
         ap.error("--seg-radius and --seg-void need --seg-gt")
     if a.seg_radius is not None and not 0 <= a.seg_radius <= MAX_RADIUS:
@@ -954,10 +1179,18 @@ def main(argv=None) -> int:
         ap.error("--init needs --ref-cloud")
     if a.ref_cloud and a.ref:
         ap.error("give --ref or --ref-cloud, not both")
+    global_voxel = None
+    if a.register_global is not None:
+        global_voxel = a.radius if a.register_global is True else a.register_global
+        if not (math.isfinite(global_voxel) and global_voxel > 0):
+            ap.error("--register-global takes a positive voxel size")
+        if a.init:
+            ap.error("--register-global finds the start itself: give it or --init, not both")
+        a.register = True
     if not a.register and (a.register_radius or a.point_to_point):
         ap.error("--register-radius and --point-to-point need --register")
     if a.register and not (a.ref or a.ref_cloud):
-        ap.error("--register needs --ref or --ref-cloud")
+        ap.error("--register and --register-global need --ref or --ref-cloud")
     if (a.estimate_normals is not None or a.normals) and not (a.ref or a.ref_cloud):
         ap.error("--estimate-normals and --normals need --ref or --ref-cloud")
     normals_radius = None
@@ -991,10 +1224,16 @@ def main(argv=None) -> int:
             sys.stderr.write(f"eval: the reference cloud of model {o['model']} has no normals (nx ny nz): point-to-plane registration needs "
                              "them; give --point-to-point to register without\n")
             return False
-        res = register(ce, cr, radii[-1], T0=T0, ref_normals=None if a.point_to_point else nr, max_iterations=a.register_iterations,
-                       schedule=radii, method="point" if a.point_to_point else "plane")
+        if global_voxel is not None:
+            res = register_global(ce, cr, global_voxel, est_normals=ne, ref_normals=nr, seed=a.register_seed, max_iterations=a.register_iterations,
+                                  method="point" if a.point_to_point else "plane", schedule=radii if a.register_radius else None)
+        else:
+            res = register(ce, cr, radii[-1], T0=T0, ref_normals=None if a.point_to_point else nr, max_iterations=a.register_iterations,
+                           schedule=radii, method="point" if a.point_to_point else "plane")
         o["cloud_registered"] = compare_clouds(ce, cr, a.radius, taus, T=res["T"])
         o["registration"] = registration_summary(res)
+        if global_voxel is not None:
+            o["registration"]["coarse"] = coarse_summary(res["coarse"])
         consistency(o, ce, ne, cr, nr, res["T"])
         return True
 

@@ -171,6 +171,10 @@ SYMBOLS = {
     "mf_cloud_normals_workspace": (C.c_int, [C.c_int64, C.POINTER(C.c_uint64)]),
     "mf_cloud_normals_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_uint64, C.c_void_p]),
+    "mf_cloud_fpfh_workspace": (C.c_int, [C.c_int64, C.POINTER(C.c_uint64)]),
+    "mf_cloud_fpfh_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                    C.c_void_p]),
+    "mf_feature_match_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_label_confusion_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_void_p]),
     "mf_label_boundary_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,

@@ -10,11 +10,15 @@ sampled from it and jittered by N(0, 5 mm) per axis, radius 5 cm.
                and 1 cm off
   normals      mf_cloud_normals_dev on the targets (grid build + walk and moments + eigen-solve), radius 2 x --radius as the evaluation
                command's --estimate-normals takes it, as the median of 5 calls after 1 warm-up; minus the grid build at that radius
+  global       mf_cloud_fpfh_dev on --keys points of the map with the map's normals at --fpfh-radius, and mf_feature_match_dev of those
+               descriptors against the descriptors of as many other points of the map (33 values each): the two device calls of
+               eval.register_global at 50 k x 50 k key points, each as the median of 5 calls after 1 warm-up
 
 Device times are medians of 10 calls after 2 warm-up calls, between HIP events on the call's stream.  One CPU line for contrast:
 scipy.spatial.cKDTree with 16 workers on the same clouds (tree build + query), if scipy is present.
 
     python tools/eval_timing.py [--targets 26.9e6] [--queries 5e6] [--radius 0.05] [--no-cpu] [--no-live] [--no-icp] [--no-normals]
+                                [--no-global] [--keys 50000] [--fpfh-radius 0.25]
 """
 from __future__ import annotations
 
@@ -53,6 +57,9 @@ def main(argv=None) -> int:
     ap.add_argument("--no-live", action="store_true")
     ap.add_argument("--no-icp", action="store_true")
     ap.add_argument("--no-normals", action="store_true")
+    ap.add_argument("--no-global", action="store_true")
+    ap.add_argument("--keys", type=float, default=50e3)
+    ap.add_argument("--fpfh-radius", type=float, default=0.25)
     a = ap.parse_args(argv)
     import torch
     from maskfusion_amd import stress, synth
@@ -147,6 +154,37 @@ def main(argv=None) -> int:
               f"neighbours a point; walk + solve {tn[0] - tb[0]:.2f} ms (grid build {tb[0]:.2f} ms): {N * k_mean / (tn[0] - tb[0]) / 1e6:.1f} G neighbours/s; "
               f"{int(torch.isnan(nrm4[:, 3]).sum().item())} points without a normal; workspace {need_n.value / 2**20:.0f} MiB")
         del ws_n, nrm4, cnt
+    if not a.no_global:
+        nk = int(min(a.keys, len(room) // 2))
+        pick = rng.choice(len(room), 2 * nk, replace=False)
+        need_f = C.c_uint64(0)
+        assert L.mf_cloud_fpfh_workspace(nk, C.byref(need_f)) == 0
+        ws_f = torch.empty(int(need_f.value), dtype=torch.uint8, device="cuda")
+        desc, cnts = [], None
+        for half in (pick[:nk], pick[nk:]):
+            rec = torch.from_numpy(np.ascontiguousarray(room[half][:, [0, 1, 2, 8, 9, 10]])).cuda()
+            out = torch.empty((nk, 33), dtype=torch.float32, device="cuda")
+            cnts = torch.empty((nk, 34), dtype=torch.int32, device="cuda")
+
+            def fpfh_call():
+                rc = L.mf_cloud_fpfh_dev(rec.data_ptr(), 6, 3, nk, a.fpfh_radius, out.data_ptr(), cnts.data_ptr(), ws_f.data_ptr(), int(need_f.value),
+                                         s.cuda_stream)
+                assert rc == 0, rc
+            tf = _median_ms(fpfh_call, s, reps=5, warm=1)
+            desc.append(out)
+        midx = torch.empty(nk, dtype=torch.int32, device="cuda")
+        md2 = torch.empty(nk, dtype=torch.float32, device="cuda")
+
+        def match_call():
+            rc = L.mf_feature_match_dev(desc[0].data_ptr(), nk, desc[1].data_ptr(), nk, 33, midx.data_ptr(), md2.data_ptr(), s.cuda_stream)
+            assert rc == 0, rc
+        tm = _median_ms(match_call, s, reps=5, warm=1)
+        print(f"fpfh       : median {tf[0]:.2f} ms (min {tf[1]:.2f}, max {tf[2]:.2f}) for {nk} points at radius {a.fpfh_radius:g} m, "
+              f"{cnts[:, 33].double().mean().item():.1f} counted pairs a point; {int(torch.isnan(desc[1][:, 0]).sum().item())} rows without a descriptor; "
+              f"workspace {need_f.value / 2**20:.1f} MiB")
+        print(f"match      : median {tm[0]:.2f} ms (min {tm[1]:.2f}, max {tm[2]:.2f}) for {nk} x {nk} descriptors of 33 values: "
+              f"{nk * nk * 33 / tm[0] / 1e6:.1f} G terms/s; {int((midx >= 0).sum().item())} queries matched")
+        del ws_f, desc, cnts
     if not a.no_live:
         mf = stress.make_context()
         rgb, depth, mask = st.frame(0)
