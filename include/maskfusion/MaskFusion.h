@@ -345,6 +345,12 @@ public:
         check(mf_default_render_view(ctx_, width, height, icl ? 1 : 0, &v));
         return v;
     }
+    // the view of the frame just processed: the image size, intrinsics and current pose of the camera itself (mf_sensor_render_view)
+    mf_render_view_t sensorRenderView() {
+        mf_render_view_t v;
+        check(mf_sensor_render_view(ctx_, &v));
+        return v;
+    }
     // rgba: H*W*4 bytes; depth / model (optional): camera z (0: nothing drawn) / model list index (-1: none) per pixel; palette: RGB triples
     // for colour type 4 (empty: the library's palette)
     void renderView(const mf_render_view_t& view, std::vector<uint8_t>& rgba, std::vector<float>* depth = nullptr, std::vector<int32_t>* model = nullptr,

@@ -181,6 +181,10 @@ typedef struct mf_render_view_t {
  * axis, fx = fy = 420, the principal point at the image centre, near 0.1, far 1000, colour types 2, the background and the objects drawn,
  * cleared to white.  icl != 0 rolls the view by 180 degrees about its axis (upstream's up vector for ICL-NUIM). */
 int mf_default_render_view(mf_ctx* ctx, int32_t width, int32_t height, int32_t icl, mf_render_view_t* out);
+/* The view of the frame just processed, for comparing a render with that frame (mf_view_score_dev): the context's image size and
+ * intrinsics, the current camera pose itself (the one mf_default_render_view starts from, not moved back), near 0.01, far 1000, colour
+ * types 2, the background and the objects drawn, draw_unstable 0, cleared to opaque black. */
+int mf_sensor_render_view(mf_ctx* ctx, mf_render_view_t* out);
 /* The library's own label palette: n = min(capacity, 64) RGB triples in [0, 1] -> out (out may be NULL to query *n = 64). */
 int mf_default_palette(float* out_rgb, int32_t capacity, int32_t* n);
 /* Renders `view` into out_rgba (H*W*4 bytes, row-major; HOST pointer), optionally the camera z of every pixel (0 where nothing is drawn) and
@@ -296,6 +300,35 @@ int mf_label_confusion_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_
                            int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, uint32_t* d_counts, void* stream);
 int mf_label_boundary_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_frames, int32_t height, int32_t width, const uint8_t* lut_est,
                           int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, const uint8_t* pair, int32_t radius, uint32_t* d_out, void* stream);
+/* View scores on the GPU (kernel: mf_eval.hip; DESIGN.md "View evaluation"; the metrics built on them: maskfusion_amd.eval.view_metrics):
+ * a render of the map from the camera that saw a frame -- mf_render_view_dev's colour and camera z from mf_sensor_render_view -- compared
+ * with that frame.  d_render_rgba (DEVICE, uint8 [n_frames][height][width][4]; channel 3 is not read) and d_render_depth (DEVICE, float, same
+ * frames) are the render, d_rgb (DEVICE, uint8 [n_frames][height][width][3]) and d_depth (DEVICE, float, metres) the input; the uint8 inputs
+ * may have any byte alignment.  d_group (DEVICE, uint8 per pixel, or NULL: every pixel in group 0) names the group a pixel is counted in;
+ * a pixel whose group is >= n_groups (1..64) is void: counted nowhere, but still read by its neighbours' windows.  The call follows the
+ * label calls: it needs no context, zeroes d_counts on `stream`, enqueues one kernel and returns without waiting.  Every counter is an
+ * integer: the result is exact and the same for every call.
+ * A pixel is COVERED when its render depth is finite and > 0, DEPTH-VALID when its input depth is finite, > 0 and <= max_depth.
+ * d_counts (DEVICE, uint64 [n_frames][n_groups][10]), per frame and group:
+ *   0 pixels;  1 covered pixels;  2 depth-valid pixels;  3 pixels both covered and depth-valid ("pairs");
+ *   4 pairs with |dz| <= tau, dz = render - input being one fp32 subtraction;
+ *   5 the sum over the pairs of llrint((double)|dz| * 2^24) (|dz| below 2^38 m);
+ *   6 the sum over the pixels of the squared byte differences of R, G and B (render channels 0..2 against input channels 0..2);
+ *   7 the same sum over the covered pixels;
+ *   8 SSIM pixels: those whose 11 x 11 window lies wholly inside the image;
+ *   9 the sum over the SSIM pixels of llrint(s * 2^24) as a two's-complement int64, s = (s_R + s_G + s_B) / 3.0 being the mean of the
+ *     three channels' SSIM values.
+ * The uncovered pixels of the render take part in 6 and 9 with whatever the render holds there (its clear colour): a hole is an error.
+ * SSIM of one channel at one pixel, in fp64 with every operation rounded on its own: the weights are g[k] = exp(-(k - 5)^2 / 4.5),
+ * w[k] = g[k] / (g[0] + ... + g[10]), summed left to right (computed by the host, passed by value).  With x the render byte and y the input byte as
+ * doubles, each of x, y, x x, x y, y y is filtered along the row (acc = 0; for k = 0..10: acc = acc + w[k] * q[col - 5 + k]) and the row results the
+ * same way along the column, giving mx, my, Exx, Exy, Eyy.  vx = Exx - mx mx, vy = Eyy - my my, cxy = Exy - mx my and
+ * s = ((2 mx my + C1) (2 cxy + C2)) / ((mx mx + my my + C1) (vx + vy + C2)) with C1 = 6.5025, C2 = 58.5225 ((0.01 255)^2, (0.03 255)^2).
+ * Nothing is clamped.  MF_EINVAL, with nothing enqueued, for a null pointer other than d_group, width, height or n_frames < 1, width * height
+ * > 2^24, n_groups outside 1..64, a max_depth that is not positive (FLT_MAX, "no limit", is accepted), a tau that is negative or not finite. */
+int mf_view_score_dev(const uint8_t* d_render_rgba, const float* d_render_depth, const uint8_t* d_rgb, const float* d_depth,
+                      const uint8_t* d_group, int32_t n_frames, int32_t height, int32_t width, int32_t n_groups, float max_depth, float tau,
+                      uint64_t* d_counts, void* stream);
 /* whether the last tracking step used the fill-in maps (MaskFusion::requiresFillIn, MaskFusion.cpp:630-648) */
 int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
 

@@ -361,6 +361,13 @@ class MaskFusion:
         self._chk(self._L.mf_default_render_view(self._h, int(width), int(height), int(bool(icl)), C.byref(v)))
         return v
 
+    def sensorRenderView(self) -> RenderView:
+        """The view of the frame just processed (mf_sensor_render_view): the context's image size and intrinsics, the current camera pose,
+        near 0.01, far 1000, both colour types 2, cleared to opaque black -- what maskfusion_amd.eval.ViewScorer compares with the frame"""
+        v = RenderView()
+        self._chk(self._L.mf_sensor_render_view(self._h, C.byref(v)))
+        return v
+
     @staticmethod
     def defaultPalette() -> np.ndarray:
         """the library's own label palette, (n, 3) float32 RGB in [0, 1] (class ids index it modulo n)"""

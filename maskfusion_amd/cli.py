@@ -14,6 +14,10 @@ threshold 0.3 / weights 150, 2.8 / morphology 0x1, 0x2, new-model size 0.015 .. 
 forced to 0 exactly as upstream does with precomputed masks (MaskFusion.cpp:37): masks here always come from -maskdir / the log.
 Trackable classes come from config.toml ([MaskRCNN] class_names / trackable_classes, MainController.cpp:273-287) when it exists
 in the working directory (upstream refuses to start without it; here: every class is trackable then).
+
+An addition to the reference's flags: -evalviews scores the maps against the input after every processed frame -- the render from the
+sensor's own view (MaskFusion.sensorRenderView) compared with the frame on the GPU (maskfusion_amd.eval.ViewScorer: coverage, depth L1,
+PSNR, SSIM, per model and for the whole image) -- and writes the result to <exportdir>views.json at the end.
 """
 from __future__ import annotations
 
@@ -28,7 +32,7 @@ _VALUE_FLAGS = {"-l", "-dir", "-depthdir", "-maskdir", "-colorprefix", "-depthpr
                 "-ic", "-a", "-frameQ", "-method", "-p", "-segMinNew", "-segMaxNew", "-thNew", "-gpu", "-name", "-k", "-crfRGB", "-crfDepth",
                 "-crfPos", "-crfAppearance", "-crfSmooth"}
 _BOOL_FLAGS = {"-static", "-run", "-q", "-ep", "-em", "-es", "-ev", "-el", "-en", "-fo", "-nso", "-f", "-tum3", "-v2", "-icl", "-rl",
-               "-fs", "-r", "-ftf", "-sc", "-keep", "-o", "-v1", "-rgbonly"}
+               "-fs", "-r", "-ftf", "-sc", "-keep", "-o", "-v1", "-rgbonly", "-evalviews"}
 
 
 def parse(argv):
@@ -144,6 +148,10 @@ def main(argv=None):
     st = settings(flags)
     reader = open_reader(flags, st)
     from .api import MaskFusion
+    views = None
+    if "-evalviews" in flags:
+        from .eval import ViewScorer
+        views = ViewScorer()            # before the context: the scorer opens torch's side of the GPU, which has to come first
     mf = MaskFusion(st["W"], st["H"], st["fx"], st["fy"], st["cx"], st["cy"], timeDelta=st["timeDelta"],
                     initConfidenceGlobal=st["confGlobal"], initConfidenceObject=st["confObject"], depthCut=st["depthCutoff"],
                     icpThresh=st["icpWeight"], fastOdom=st["fastOdom"], so3=st["so3"], device=st["device"],
@@ -175,6 +183,8 @@ def main(argv=None):
         if st["exportSegmentation"] and st["multi"] and tick > 1:   # MaskFusion.cpp:299-303
             mf.exportSegmentation(os.path.join(export_dir, f"Segmentation{tick}.png"))
         export_renders(mf, flags, export_dir)
+        if views is not None:
+            views.add_from(mf, frame.rgb, frame.depth)
         n += 1
     dt = time.time() - t0
     models = mf.getModels()
@@ -184,6 +194,13 @@ def main(argv=None):
         mf.exportPoses(export_dir)
     if "-em" in flags:
         mf.savePly(export_dir)
+    if views is not None and views.frames:
+        import json
+        from .eval import _clean
+        res = views.result()
+        del res["counts"]
+        with open(export_dir + "views.json", "w") as f:
+            json.dump(_clean(res), f, indent=1)
     pose = mf.getCurrPose()
     print("final camera pose:\n" + np.array2string(pose, precision=5, suppress_small=True))
     mf.close()

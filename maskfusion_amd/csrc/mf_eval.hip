@@ -1159,6 +1159,190 @@ static int label_boundary(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_f
     return hipGetLastError() == hipSuccess ? MF_OK : MF_EHIP;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// view scores: the map's render against the input frame (mf_view_score_dev; DESIGN.md "View evaluation")
+// ------------------------------------------------------------------------------------------------------------------------------------
+// One workgroup per tile of kViewTW x kViewTH pixels of one frame; thread (tx, ty0) owns the tile's pixels (tx, ty0) and (tx, ty0 + 8).
+//   1. the R, G, B bytes of both images over the tile and a halo of 5 -> LDS, one plane per channel and image (0 beyond the image: such a
+//      position only enters windows that do not lie wholly inside the image, and those are not counted);
+//   2. the counters that need no window (0..8) of the thread's pixels into registers: depths and group from global memory, bytes from LDS;
+//   3. per channel: the row pass -- the five quantities x, y, xx, xy, yy filtered along the row for every row of the tile and its halo --
+//      into LDS as fp64, then the column pass of the thread's pixels from it; the channel's SSIM value is added to the pixel's sum;
+//   4. the pixel's counters -> the group's ten 64-bit counters in LDS (a thread whose two pixels share a group adds them once), and one
+//      global 64-bit atomic per non-zero counter.
+// Everything that is summed is an integer, so the result does not depend on the order of execution; the fp64 arithmetic is rounded
+// operation by operation (no contraction in this file) in the order the header gives.
+constexpr int kViewTW = 32, kViewTH = 16, kViewHalo = 5, kViewTaps = 2 * kViewHalo + 1;
+constexpr int kViewThreads = 256;
+constexpr int kViewPW = kViewTW + 2 * kViewHalo, kViewPH = kViewTH + 2 * kViewHalo;     // the staged planes: 42 x 26
+constexpr int kViewMaxGroups = 64, kViewCounters = 10;
+constexpr double kViewFix = 16777216.0;      // 2^24: the fixed point of counters 5 and 9
+static_assert(kViewTW * kViewTH == 2 * kViewThreads && kViewThreads / kViewTW * 2 == kViewTH, "a thread owns two pixels, 8 rows apart");
+struct ViewArgs {
+    const uint8_t* render; const float* render_depth;     // [n_frames][H][W][4], [n_frames][H][W]
+    const uint8_t* rgb; const float* depth;               // [n_frames][H][W][3], [n_frames][H][W]
+    const uint8_t* group;                                 // [n_frames][H][W] or null
+    unsigned long long* counts;                           // [n_frames][n_groups][10]
+    int W, H, tiles_x, tiles_y, n_groups;
+    float max_depth, tau;
+    double w[kViewTaps];
+};
+__device__ __forceinline__ bool view_depth_ok(float z) { return z - z == 0.f && z > 0.f; }   // finite and positive
+__global__ __launch_bounds__(kViewThreads) void k_view_score(ViewArgs a) {
+    __shared__ uint8_t s_x[3][kViewPW * kViewPH], s_y[3][kViewPW * kViewPH];      // render, input
+    __shared__ double s_row[5][kViewPH * kViewTW];
+    __shared__ unsigned long long s_cnt[kViewMaxGroups * kViewCounters];
+    const int tid = threadIdx.x;
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int frame = blockIdx.x / tiles, tile = blockIdx.x - frame * tiles;
+    const int x0 = (tile % a.tiles_x) * kViewTW, y0 = (tile / a.tiles_x) * kViewTH;
+    const size_t P = (size_t)a.W * a.H, fbase = (size_t)frame * P;
+    for (int k = tid; k < a.n_groups * kViewCounters; k += kViewThreads) s_cnt[k] = 0ull;
+    // 1.
+    for (int k = tid; k < kViewPW * kViewPH; k += kViewThreads) {
+        const int ly = k / kViewPW, lx = k - ly * kViewPW;
+        const int x = x0 - kViewHalo + lx, y = y0 - kViewHalo + ly;
+        unsigned r[3] = {0u, 0u, 0u}, i[3] = {0u, 0u, 0u};
+        if (x >= 0 && x < a.W && y >= 0 && y < a.H) {
+            const size_t at = fbase + (size_t)y * a.W + x;
+            const uint8_t* pr = a.render + at * 4;
+            const uint8_t* pi = a.rgb + at * 3;
+            r[0] = pr[0]; r[1] = pr[1]; r[2] = pr[2];
+            i[0] = pi[0]; i[1] = pi[1]; i[2] = pi[2];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { s_x[c][k] = (uint8_t)r[c]; s_y[c][k] = (uint8_t)i[c]; }
+    }
+    __syncthreads();
+    // 2.
+    const int tx = tid & (kViewTW - 1), ty0 = tid / kViewTW;
+    const int x = x0 + tx;
+    int grp[2];                                   // -1: outside the image, or void
+    bool window[2];                               // the 11 x 11 window lies inside the image
+    unsigned long long cnt[2][kViewCounters - 1]; // counters 0..8 of the two pixels
+    double ssum[2] = {0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int y = y0 + ty0 + j * (kViewTH / 2);
+        grp[j] = -1; window[j] = false;
+#pragma unroll
+        for (int q = 0; q < kViewCounters - 1; ++q) cnt[j][q] = 0ull;
+        if (x >= a.W || y >= a.H) continue;
+        const size_t at = fbase + (size_t)y * a.W + x;
+        const int g = a.group ? (int)a.group[at] : 0;
+        if (g >= a.n_groups) continue;
+        grp[j] = g;
+        const float zr = a.render_depth[at], zi = a.depth[at];
+        const bool covered = view_depth_ok(zr), valid = view_depth_ok(zi) && zi <= a.max_depth;
+        cnt[j][0] = 1ull; cnt[j][1] = covered ? 1ull : 0ull; cnt[j][2] = valid ? 1ull : 0ull;
+        if (covered && valid) {
+            const float dz = fabsf(zr - zi);
+            cnt[j][3] = 1ull;
+            cnt[j][4] = dz <= a.tau ? 1ull : 0ull;
+            cnt[j][5] = (unsigned long long)llrint((double)dz * kViewFix);
+        }
+        const int lk = (ty0 + j * (kViewTH / 2) + kViewHalo) * kViewPW + tx + kViewHalo;
+        unsigned sq = 0u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { const int d = (int)s_x[c][lk] - (int)s_y[c][lk]; sq += (unsigned)(d * d); }
+        cnt[j][6] = sq; cnt[j][7] = covered ? sq : 0u;
+        window[j] = x >= kViewHalo && x < a.W - kViewHalo && y >= kViewHalo && y < a.H - kViewHalo;
+        cnt[j][8] = window[j] ? 1ull : 0ull;
+    }
+    // 3.
+    for (int c = 0; c < 3; ++c) {
+        for (int k = tid; k < kViewPH * kViewTW; k += kViewThreads) {
+            const int row = k / kViewTW, col = k - row * kViewTW;
+            const uint8_t* px = &s_x[c][row * kViewPW + col];
+            const uint8_t* py = &s_y[c][row * kViewPW + col];
+            double ax = 0.0, ay = 0.0, axx = 0.0, axy = 0.0, ayy = 0.0;
+#pragma unroll
+            for (int t = 0; t < kViewTaps; ++t) {
+                const double xv = (double)px[t], yv = (double)py[t], wt = a.w[t];
+                ax = ax + wt * xv;
+                ay = ay + wt * yv;
+                axx = axx + wt * (xv * xv);
+                axy = axy + wt * (xv * yv);
+                ayy = ayy + wt * (yv * yv);
+            }
+            s_row[0][k] = ax; s_row[1][k] = ay; s_row[2][k] = axx; s_row[3][k] = axy; s_row[4][k] = ayy;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (!window[j]) continue;
+            const int k0 = (ty0 + j * (kViewTH / 2)) * kViewTW + tx;      // the window's first row of the row pass
+            double mx = 0.0, my = 0.0, exx = 0.0, exy = 0.0, eyy = 0.0;
+#pragma unroll
+            for (int t = 0; t < kViewTaps; ++t) {
+                const double wt = a.w[t];
+                mx = mx + wt * s_row[0][k0 + t * kViewTW];
+                my = my + wt * s_row[1][k0 + t * kViewTW];
+                exx = exx + wt * s_row[2][k0 + t * kViewTW];
+                exy = exy + wt * s_row[3][k0 + t * kViewTW];
+                eyy = eyy + wt * s_row[4][k0 + t * kViewTW];
+            }
+            const double vx = exx - mx * mx, vy = eyy - my * my, cxy = exy - mx * my;
+            const double num = (2.0 * mx * my + 6.5025) * (2.0 * cxy + 58.5225);
+            const double den = (mx * mx + my * my + 6.5025) * (vx + vy + 58.5225);
+            ssum[j] = ssum[j] + num / den;
+        }
+        __syncthreads();
+    }
+    // 4.
+    long long fix[2] = {0ll, 0ll};
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+        if (window[j]) fix[j] = llrint(ssum[j] / 3.0 * kViewFix);
+    if (grp[0] >= 0 && grp[0] == grp[1]) {
+#pragma unroll
+        for (int q = 0; q < kViewCounters - 1; ++q) cnt[0][q] += cnt[1][q];
+        fix[0] += fix[1];
+        grp[1] = -1;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (grp[j] < 0) continue;
+        unsigned long long* to = s_cnt + grp[j] * kViewCounters;
+#pragma unroll
+        for (int q = 0; q < kViewCounters - 1; ++q)
+            if (cnt[j][q]) atomicAdd(&to[q], cnt[j][q]);
+        if (fix[j]) atomicAdd(&to[9], (unsigned long long)fix[j]);
+    }
+    __syncthreads();
+    unsigned long long* out = a.counts + (size_t)frame * a.n_groups * kViewCounters;
+    for (int k = tid; k < a.n_groups * kViewCounters; k += kViewThreads) {
+        const unsigned long long v = s_cnt[k];
+        if (v) atomicAdd(&out[k], v);
+    }
+}
+
+static int view_score(const uint8_t* d_render_rgba, const float* d_render_depth, const uint8_t* d_rgb, const float* d_depth, const uint8_t* d_group,
+                      int32_t n_frames, int32_t height, int32_t width, int32_t n_groups, float max_depth, float tau, uint64_t* d_counts, hipStream_t s) {
+    if (!d_render_rgba || !d_render_depth || !d_rgb || !d_depth || !d_counts) return MF_EINVAL;
+    if (width < 1 || height < 1 || n_frames < 1 || (int64_t)width * height > (int64_t)1 << 24) return MF_EINVAL;
+    if (n_groups < 1 || n_groups > kViewMaxGroups) return MF_EINVAL;
+    if (!(max_depth > 0.f) || !(tau >= 0.f) || !std::isfinite(tau)) return MF_EINVAL;
+    ViewArgs a;
+    memset(&a, 0, sizeof(a));
+    a.render = d_render_rgba; a.render_depth = d_render_depth; a.rgb = d_rgb; a.depth = d_depth; a.group = d_group;
+    a.counts = reinterpret_cast<unsigned long long*>(d_counts);
+    a.W = width; a.H = height; a.n_groups = n_groups; a.max_depth = max_depth; a.tau = tau;
+    a.tiles_x = (width + kViewTW - 1) / kViewTW;
+    a.tiles_y = (height + kViewTH - 1) / kViewTH;
+    double g[kViewTaps], sum = 0.0;
+    for (int k = 0; k < kViewTaps; ++k) {
+        g[k] = std::exp(-(double)((k - kViewHalo) * (k - kViewHalo)) / 4.5);
+        sum = sum + g[k];
+    }
+    for (int k = 0; k < kViewTaps; ++k) a.w[k] = g[k] / sum;
+    const int64_t blocks = (int64_t)n_frames * a.tiles_x * a.tiles_y;
+    if (blocks > 0x7FFFFFFF) return MF_EINVAL;
+    if (hipMemsetAsync(d_counts, 0, (size_t)n_frames * n_groups * kViewCounters * sizeof(uint64_t), s) != hipSuccess) return MF_EHIP;
+    hipLaunchKernelGGL(k_view_score, dim3((unsigned)blocks), dim3(kViewThreads), 0, s, a);
+    return hipGetLastError() == hipSuccess ? MF_OK : MF_EHIP;
+}
+
 }  // namespace mf
 
 using namespace mf;
@@ -1229,4 +1413,11 @@ extern "C" int mf_label_boundary_dev(const uint8_t* d_est, const uint8_t* d_gt, 
                                      const uint8_t* lut_est, int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, const uint8_t* pair, int32_t radius,
                                      uint32_t* d_out, void* stream) {
     return label_boundary(d_est, d_gt, n_frames, height, width, lut_est, n_est, lut_gt, n_gt, pair, radius, d_out, (hipStream_t)stream);
+}
+
+extern "C" int mf_view_score_dev(const uint8_t* d_render_rgba, const float* d_render_depth, const uint8_t* d_rgb, const float* d_depth,
+                                 const uint8_t* d_group, int32_t n_frames, int32_t height, int32_t width, int32_t n_groups, float max_depth, float tau,
+                                 uint64_t* d_counts, void* stream) {
+    return view_score(d_render_rgba, d_render_depth, d_rgb, d_depth, d_group, n_frames, height, width, n_groups, max_depth, tau, d_counts,
+                      (hipStream_t)stream);
 }

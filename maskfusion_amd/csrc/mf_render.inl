@@ -1,4 +1,4 @@
-// mf_render.inl -- headless rendering of the surfel maps: mf_render_view[_dev], mf_default_render_view, mf_default_palette (kernels: mf_render.hip).
+// mf_render.inl -- headless rendering of the surfel maps: mf_render_view[_dev], mf_default_render_view, mf_sensor_render_view, mf_default_palette (kernels: mf_render.hip).
 // (part of mf_context.hip, included after the model list helpers)
 
 // Scratch of the render, allocated on the first call and freed by mf_destroy: nothing of it is shared with the frame path (the visibility list of
@@ -78,6 +78,22 @@ extern "C" int mf_default_render_view(mf_ctx* c, int32_t width, int32_t height, 
     out->background_color_type = out->object_color_type = 2;
     out->draw_background = out->draw_objects = 1;
     out->clear_rgba[0] = out->clear_rgba[1] = out->clear_rgba[2] = out->clear_rgba[3] = 255;
+    return MF_OK;
+}
+
+extern "C" int mf_sensor_render_view(mf_ctx* c, mf_render_view_t* out) {
+    if (!c || !out) return MF_EINVAL;
+    float pose[16];
+    int rc = mf_get_pose(c, 0, pose);
+    if (rc != MF_OK) return rc;
+    memset(out, 0, sizeof(*out));
+    out->width = c->W; out->height = c->H;
+    out->fx = c->K.fx; out->fy = c->K.fy; out->cx = c->K.cx; out->cy = c->K.cy;
+    out->near_z = 0.01f; out->far_z = 1000.f;
+    memcpy(out->pose16, pose, sizeof(pose));
+    out->background_color_type = out->object_color_type = 2;
+    out->draw_background = out->draw_objects = 1;
+    out->clear_rgba[3] = 255;
     return MF_OK;
 }
 

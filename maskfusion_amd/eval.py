@@ -16,7 +16,8 @@ seeded RANSAC over the matches in numpy, then register().
 
 prints one JSON object per model on stdout (INTEGRATION.md "Evaluating a run"); with --seg-gt, one per ground-truth object of the
 segmentation and a summary (region similarity J and boundary accuracy F of the -es label images, counted on the GPU:
-mf_label_confusion_dev / mf_label_boundary_dev).
+mf_label_confusion_dev / mf_label_boundary_dev).  ViewScorer scores what needs nothing from outside the run: the map's render from the
+sensor's own view against the frame it just saw (mf_view_score_dev; the driver's -evalviews flag writes its result as views.json).
 """
 from __future__ import annotations
 
@@ -1098,6 +1099,210 @@ def score_segmentation(est_dir: str, gt_dir: str, prefix: str = "Mask", index_wi
     out = [dict(segmentation_object=o.pop("gt_id"), **o) for o in (dict(o) for o in res["objects"])]
     out.append({"segmentation": dict(res["summary"], first_tick=ticks[0], last_tick=ticks[-1])})
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# views: the map's render against the input frame
+# ------------------------------------------------------------------------------------------------------------------------------------
+VIEW_GROUPS = 64          # groups per call of mf_view_score_dev
+VIEW_COUNTERS = 10
+VIEW_FIX = float(1 << 24)   # the fixed point of counters 5 and 9
+VIEW_KEYS = ("coverage", "depth_coverage", "depth_l1", "depth_within_tau", "psnr", "psnr_covered", "ssim")
+_FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def _device_frames(a, dtype, channels, what):
+    """(n_frames, H, W[, channels]) of `dtype` on the library's device; a single image becomes one frame"""
+    import torch
+    from .lib import torch_device
+    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype)))
+    want = 3 + (channels > 0)
+    if t.dim() == want - 1:
+        t = t[None]
+    if t.dtype != torch.as_tensor(np.zeros(0, dtype)).dtype or t.dim() != want or t.numel() == 0 or (channels and t.shape[-1] != channels):
+        raise ValueError(f"{what} must be {np.dtype(dtype).name} of shape (n_frames, H, W{', %d' % channels if channels else ''}), not empty")
+    return t.to(torch_device()).contiguous()
+
+
+def _view_call(r, rd, c, d, g, n_groups, max_depth, tau, stream):
+    """mf_view_score_dev on device tensors that are already in shape -> the counters as an int64 tensor (n_frames, n_groups, 10)"""
+    import torch
+    from .lib import MFError, load
+    shape = tuple(rd.shape)
+    if tuple(r.shape) != shape + (4,) or tuple(c.shape) != shape + (3,) or tuple(d.shape) != shape or (g is not None and tuple(g.shape) != shape):
+        raise ValueError(f"render {tuple(r.shape)} / {tuple(rd.shape)}, frame {tuple(c.shape)} / {tuple(d.shape)}"
+                         + (f", groups {tuple(g.shape)}" if g is not None else "") + ": the shapes do not belong together")
+    out = torch.empty((shape[0], int(n_groups), VIEW_COUNTERS), dtype=torch.int64, device=rd.device)
+    md = min(float(max_depth), _FLT_MAX)          # "no limit" is FLT_MAX
+    rc = load().mf_view_score_dev(r.data_ptr(), rd.data_ptr(), c.data_ptr(), d.data_ptr(), g.data_ptr() if g is not None else None, shape[0], shape[1],
+                                  shape[2], int(n_groups), md, float(tau), out.data_ptr(), stream)
+    if rc != 0:
+        raise MFError(f"mf_view_score_dev failed with code {rc} (1..64 groups, at most 2^24 pixels per frame, max_depth > 0, tau >= 0 and finite)")
+    return out
+
+
+def view_counts(render_rgba, render_depth, rgb, depth, group=None, n_groups=1, max_depth=math.inf, tau=0.01) -> np.ndarray:
+    """The counters behind the view scores (mf_view_score_dev; the definitions: include/maskfusion_amd.h): a render of the map -- render_rgba
+    uint8 (n_frames, H, W, 4), render_depth float32 (n_frames, H, W), 0 where nothing was drawn -- against the frames the camera saw -- rgb
+    uint8 (n_frames, H, W, 3), depth float32 in metres.  group: uint8 per pixel, the group the pixel is counted in (None: all in group 0;
+    a value >= n_groups: nowhere).  Inputs are numpy arrays or device tensors; a single image is one frame.
+    Returns uint64 (n_frames, n_groups, 10); counter 9 is a two's-complement int64."""
+    import torch
+    r, rd = _device_frames(render_rgba, np.uint8, 4, "render_rgba"), _device_frames(render_depth, np.float32, 0, "render_depth")
+    c, d = _device_frames(rgb, np.uint8, 3, "rgb"), _device_frames(depth, np.float32, 0, "depth")
+    g = None if group is None else _device_frames(group, np.uint8, 0, "group")
+    stream = torch.cuda.current_stream().cuda_stream if rd.device.type == "cuda" else None
+    return _view_call(r, rd, c, d, g, n_groups, max_depth, tau, stream).cpu().numpy().view(np.uint64)
+
+
+def _view_scores(c) -> dict:
+    """the seven scores of one row of ten counters (Python ints); None for a zero denominator or a zero error sum"""
+    c = [int(v) for v in c]
+    div = lambda a, b: a / b if b else None
+    psnr = lambda err, n: 10.0 * math.log10(255.0 * 255.0 * (3 * n) / err) if n and err else None
+    return {"coverage": div(c[1], c[0]), "depth_coverage": div(c[3], c[2]), "depth_l1": div(c[5] / VIEW_FIX, c[3]),
+            "depth_within_tau": div(c[4], c[3]), "psnr": psnr(c[6], c[0]), "psnr_covered": psnr(c[7], c[1]), "ssim": div(c[9] / VIEW_FIX, c[8])}
+
+
+def view_metrics(counts) -> dict:
+    """From counters to scores, without a GPU.  counts: (n_frames, n_groups, 10), view_counts' result.  Per row of counters:
+      coverage = c1 / c0, depth_coverage = c3 / c2, depth_l1 (m) = c5 / 2^24 / c3, depth_within_tau = c4 / c3,
+      psnr = 10 log10(255^2 3 c0 / c6), psnr_covered the same from c7 and c1, ssim = c9 / 2^24 / c8;
+    None for a zero denominator and, for the two PSNRs, a zero error sum.
+    Returns {"frames", "groups", "summary"}.  frames[f][g]: the scores of frame f and group g.  groups[g]: {"group", "pixels", "frames" (those
+    in which the group has a pixel), the scores POOLED over the frames (from the counters summed over the frames), and under "mean" the
+    mean of each per-frame score over the frames where it is defined (None: nowhere)}.  summary: the same two for all groups together (the
+    counters summed over the groups: every pixel that is not void)."""
+    c = np.asarray(counts)
+    if c.ndim != 3 or c.shape[2] != VIEW_COUNTERS:
+        raise ValueError("counts must have the shape (n_frames, n_groups, 10)")
+    c = np.ascontiguousarray(c.astype(np.uint64)).view(np.int64).astype(object)      # Python integers: sums over long runs cannot wrap
+
+    def sequence(rows):
+        per_frame = [_view_scores(r) for r in rows]
+        pooled = _view_scores(rows.sum(0)) if len(rows) else _view_scores([0] * VIEW_COUNTERS)
+        mean = {}
+        for k in VIEW_KEYS:
+            vals = [s[k] for s in per_frame if s[k] is not None]
+            mean[k] = float(np.mean(vals)) if vals else None
+        return per_frame, dict(pooled, mean=mean)
+
+    n_frames, n_groups = c.shape[:2]
+    frames = [[None] * n_groups for _ in range(n_frames)]
+    groups = []
+    for g in range(n_groups):
+        per_frame, scores = sequence(c[:, g])
+        for f in range(n_frames):
+            frames[f][g] = per_frame[f]
+        groups.append(dict(group=g, pixels=int(c[:, g, 0].sum()), frames=int(np.count_nonzero(c[:, g, 0])), **scores))
+    _, summary = sequence(c.sum(1))
+    return {"frames": frames, "groups": groups, "summary": dict(summary, frames=int(n_frames))}
+
+
+def _torch_ready():
+    """torch's side of the GPU, opened now.  torch brings a HIP runtime of its own, and in a process where the library's context exists
+    first that runtime finds no device: whoever uses a live context together with torch opens torch's side BEFORE MaskFusion() -- creating
+    the ViewScorer first does it."""
+    import torch
+    from .lib import MFError, torch_device
+    if torch_device() != "cuda" or torch.cuda.is_initialized():
+        return
+    try:
+        torch.cuda.init()
+    except RuntimeError as e:
+        raise MFError("torch cannot open the GPU once the library's context exists: create the ViewScorer (or call torch.cuda.init()) "
+                      "before MaskFusion()") from e
+
+
+class ViewScorer:
+    """Scores the map's renders against the frames of a run (SegmentationScorer's counterpart for view_counts / view_metrics).  add() takes
+    the five images of one or more frames; add_from() renders a live context from the camera that just saw the frame and compares on the
+    device: nothing is downloaded but the counters, and those in result().
+
+    Create the scorer before the context it will score (see _torch_ready).
+
+    Groups: add() takes them as given.  add_from() counts every pixel under the model that drew it: group 0 is "nothing drawn", a model id
+    gets the next free group when it is first seen and keeps it; ids past group 63 are void."""
+
+    def __init__(self, max_depth=math.inf, tau=0.01):
+        self.max_depth, self.tau = float(max_depth), float(tau)
+        _torch_ready()
+        self._counts = []
+        self._group_of = {}              # model id -> group
+        self._buffers = None
+        self._keep = None
+
+    def add(self, render_rgba, render_depth, rgb, depth, group=None):
+        """one frame or a batch of the five images, numpy arrays or device tensors (view_counts' arguments; group values 0..63, others void)"""
+        import torch
+        r, rd = _device_frames(render_rgba, np.uint8, 4, "render_rgba"), _device_frames(render_depth, np.float32, 0, "render_depth")
+        c, d = _device_frames(rgb, np.uint8, 3, "rgb"), _device_frames(depth, np.float32, 0, "depth")
+        g = None if group is None else _device_frames(group, np.uint8, 0, "group")
+        stream = torch.cuda.current_stream().cuda_stream if rd.device.type == "cuda" else None
+        self._counts.append(_view_call(r, rd, c, d, g, VIEW_GROUPS, self.max_depth, self.tau, stream))
+
+    def _groups_for(self, ids):
+        """the group of every model list index, shifted by one: entry 0 is "no model" """
+        table = [0]
+        for i in ids:
+            if i not in self._group_of:
+                self._group_of[i] = len(self._group_of) + 1
+            table.append(self._group_of[i] if self._group_of[i] < VIEW_GROUPS else VOID)
+        return table
+
+    def add_from(self, mf, rgb, depth, view=None):
+        """the frame `mf` (a MaskFusion context) processed last, rgb (H, W, 3) uint8 and depth (H, W) float32 in metres, against the render of
+        the context's maps from view (default: mf.sensorRenderView()).  Render, group look-up and comparison are enqueued on the
+        context's stream; the call does not wait for them."""
+        import contextlib
+        import torch
+        from .lib import torch_device
+        if view is None:
+            view = mf.sensorRenderView()
+        H, W = int(view.height), int(view.width)
+        dev = torch_device()
+        on_stream = contextlib.nullcontext()
+        if dev == "cuda":
+            torch.cuda.current_stream().synchronize()          # inputs that torch's stream is still writing
+            on_stream = torch.cuda.stream(torch.cuda.ExternalStream(mf.stream()))
+        with on_stream:
+            c, d = _device_frames(rgb, np.uint8, 3, "rgb"), _device_frames(depth, np.float32, 0, "depth")
+            if tuple(d.shape) != (1, H, W):
+                raise ValueError(f"a frame of {tuple(d.shape[1:])} against a view of {(H, W)}")
+            if self._buffers is None or tuple(self._buffers[1].shape) != (1, H, W):
+                self._buffers = (torch.empty((1, H, W, 4), dtype=torch.uint8, device=dev), torch.empty((1, H, W), dtype=torch.float32, device=dev),
+                                 torch.empty((1, H, W), dtype=torch.int32, device=dev))
+            r, rd, model = self._buffers
+            mf.renderViewDevice(view, r.data_ptr(), rd.data_ptr(), model.data_ptr())
+            table = torch.as_tensor(self._groups_for(mf.modelIDs()), dtype=torch.uint8).to(dev)
+            g = table[(model + 1).long()].contiguous()
+            self._counts.append(_view_call(r, rd, c, d, g, VIEW_GROUPS, self.max_depth, self.tau, mf.stream() or None))
+        self._keep = (c, d, g)             # alive until the kernel has read them: the next call's view waits for the context's stream
+
+    @property
+    def frames(self) -> int:
+        return sum(int(t.shape[0]) for t in self._counts)
+
+    def counts(self) -> np.ndarray:
+        """uint64 (n_frames, 64, 10) of everything added so far; waits for the device"""
+        import torch
+        if not self._counts:
+            raise ValueError("no frames were added")
+        if self._counts[0].device.type == "cuda":
+            torch.cuda.synchronize()
+        if len(self._counts) > 1:
+            self._counts = [torch.cat(self._counts)]
+        return self._counts[0].cpu().numpy().view(np.uint64)
+
+    def result(self) -> dict:
+        """{"groups", "summary", "frames", "counts"}: view_metrics' groups (pooled scores and "mean") for the groups that were assigned to a
+        model or hold a pixel, each with the "model_id" it stands for (None: group 0 of add_from, "nothing drawn", and every group of add());
+        view_metrics' summary with tau; the number of frames; the counters (n_frames, 64, 10)"""
+        counts = self.counts()
+        m = view_metrics(counts)
+        id_of = {g: i for i, g in self._group_of.items()}
+        groups = [dict(o, model_id=id_of.get(o["group"])) for o in m["groups"] if o["pixels"] or o["group"] in id_of]
+        return {"groups": groups, "summary": dict(m["summary"], tau=self.tau), "frames": int(counts.shape[0]), "counts": counts}
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

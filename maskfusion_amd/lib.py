@@ -157,6 +157,7 @@ SYMBOLS = {
                                      C.c_int32, C.c_void_p]),
     "mf_k_gn_solve": (C.c_int, [C.c_void_p] * 10 + [C.c_void_p]),
     "mf_default_render_view": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "mf_sensor_render_view": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mf_default_palette": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "mf_render_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_render_view_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -179,6 +180,8 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p]),
     "mf_label_boundary_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mf_view_score_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "mf_k_icp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                 C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
                                 C.c_int32, C.c_void_p, C.c_void_p]),
