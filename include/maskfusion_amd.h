@@ -277,7 +277,7 @@ int mf_cloud_fpfh_dev(const float* d_points, int32_t stride, int32_t normal_offs
  * rows or a null pointer.  Enqueued on `stream`, which the call synchronises before it returns. */
 int mf_feature_match_dev(const float* d_target, int64_t n_target, const float* d_query, int64_t n_query, int32_t dim, int32_t* d_idx,
                          float* d_d2, void* stream);
-/* Segmentation scores on the GPU (kernels: mf_eval.hip; DESIGN.md "Segmentation evaluation"; the metrics built on them:
+/* Segmentation scores on the GPU (kernels: mf_eval_image.hip; DESIGN.md "Segmentation evaluation"; the metrics built on them:
  * maskfusion_amd.eval.seg_metrics).  Both calls compare two label streams d_est, d_gt (DEVICE, uint8 [n_frames][height][width], any byte
  * alignment).  lut_est and lut_gt (HOST, 256 entries each) map a raw label value to a compact class index < n_est (< n_gt), or to 255: void.
  * n_est and n_gt are 1..64; by the callers' convention class 0 is the background.  The tables are copied into the launch's argument block when
@@ -300,7 +300,7 @@ int mf_label_confusion_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_
                            int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, uint32_t* d_counts, void* stream);
 int mf_label_boundary_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_frames, int32_t height, int32_t width, const uint8_t* lut_est,
                           int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, const uint8_t* pair, int32_t radius, uint32_t* d_out, void* stream);
-/* View scores on the GPU (kernel: mf_eval.hip; DESIGN.md "View evaluation"; the metrics built on them: maskfusion_amd.eval.view_metrics):
+/* View scores on the GPU (kernel: mf_eval_image.hip; DESIGN.md "View evaluation"; the metrics built on them: maskfusion_amd.eval.view_metrics):
  * a render of the map from the camera that saw a frame -- mf_render_view_dev's colour and camera z from mf_sensor_render_view -- compared
  * with that frame.  d_render_rgba (DEVICE, uint8 [n_frames][height][width][4]; channel 3 is not read) and d_render_depth (DEVICE, float, same
  * frames) are the render, d_rgb (DEVICE, uint8 [n_frames][height][width][3]) and d_depth (DEVICE, float, metres) the input; the uint8 inputs

@@ -1,9 +1,11 @@
-// mf_eval.hip -- run evaluation: fixed-radius nearest neighbour between two point clouds (mf_cloud_nn_dev, mf_model_cloud_nn_dev) and one
-// Gauss-Newton step of a rigid registration on those correspondences (mf_cloud_icp_build_dev / mf_cloud_icp_step_dev, below).  No upstream
-// twin: the reference writes its clouds (savePly) and poses (exportPoses) and leaves their evaluation to outside tools.
-// Further down: the segmentation scores, region and boundary counts of two label streams (mf_label_confusion_dev, mf_label_boundary_dev).
+// mf_eval.hip -- run evaluation on point clouds, all of it over one hashed grid: the fixed-radius nearest neighbour between two clouds
+// (mf_cloud_nn_dev, mf_model_cloud_nn_dev), one Gauss-Newton step of a rigid registration on those correspondences (mf_cloud_icp_build_dev /
+// mf_cloud_icp_step_dev), a cloud's normals (mf_cloud_normals_dev) and FPFH descriptors (mf_cloud_fpfh_dev), and the brute-force descriptor
+// matcher (mf_feature_match_dev).  No upstream twin: the reference writes its clouds (savePly) and poses (exportPoses) and leaves their
+// evaluation to outside tools.  The image scores of the evaluation are mf_eval_image.hip.
+// Every consumer of the grid goes through the two walks below (nn_walk_cells, nn_walk_records), which own the rounding argument.
 //
-// Result (DESIGN.md "Cloud evaluation"): for query i, the target j with the smallest fp32 d2 = dx*dx + dy*dy + dz*dz (d = q - p, no
+// Nearest neighbour (DESIGN.md "Cloud evaluation"): for query i, the target j with the smallest fp32 d2 = dx*dx + dy*dy + dz*dz (d = q - p, no
 // contraction: this file is compiled with -ffp-contract=off) among the finite targets with d2 <= fl(radius * radius); ties go to the smallest j.
 // dist[i] = sqrtf(d2), idx[i] = j, or +inf / -1 when there is none or the query is not finite.
 //
@@ -60,19 +62,59 @@ __device__ __forceinline__ bool nn_in_range(const NnGrid& g, float x, float y, f
 }
 __device__ __forceinline__ int nn_cell(const NnGrid& g, float x) { return (int)floor((double)x * g.inv_h); }
 
-// The cells of one axis that can hold a target p the radius test accepts for query coordinate x.  The test passing means
-// fl(fl(q - p)^2 ...) <= fl(r^2), hence |q - p| <= r (1 + 4 eps) < reach; rounding is monotone and p is representable, so
-// fl(x - reach) <= p <= fl(x + reach) and the cells of the two bounds (the same fp64 product as nn_cell) enclose p's cell.
+// ---------------- the walk over the grid: which cells a point has to visit ----------------
+// The rounding argument, stated here once for every consumer of the grid (nn_find, the normals, both FPFH passes).
+//   The bounds enclose the cell.  A target p passes the radius test of point x when fl(fl(x - p)^2 ...) <= fl(r^2), hence |x - p| <=
+//   r (1 + 4 eps) < reach per axis; rounding is monotone and p is representable, so fl(x - reach) <= p <= fl(x + reach), and the cells of the
+//   two bounds (nn_cell_range: the same fp64 product as nn_cell) enclose p's cell.
+//   A cell beyond the gap can be skipped.  nn_box_gap is the squared distance from x to the cell's box, the box widened by 2^-20 of a cell
+//   on each side for the fp64 rounding of the cell assignment, so every target the build put into the cell lies in the widened box; the
+//   fp32 d2 of such a target is at least (1 - 2^-18) of the three axes' gaps added.  When that exceeds the limit -- what d2 may still be
+//   of use: the radius test's r2, or the best d2 of a minimum so far -- no record of the cell can count.
+// Two cells of one walk may share a bucket.  A minimum may meet a record twice; a sum must not, so nn_walk_records lets a record count only
+// in the visit of its OWN cell (nn_cell of its coordinates, the build's product).
 __device__ __forceinline__ void nn_cell_range(const NnGrid& g, float x, int& lo, int& hi) {
     lo = (int)floor(((double)x - g.reach) * g.inv_h);
     hi = (int)floor(((double)x + g.reach) * g.inv_h);
 }
-// Squared distance from x to the cell's box, lowered for the fp64 rounding of the cell assignment (2^-20 of a cell on each side).
 __device__ __forceinline__ double nn_box_gap(const NnGrid& g, double x, int c) {
     const double pad = g.h * 9.5367431640625e-07;
     const double lo = (double)c * g.h - pad, hi = (double)(c + 1) * g.h + pad;
     const double d = x < lo ? lo - x : (x > hi ? x - hi : 0.0);
     return d * d;
+}
+// cell(cx, cy, cz) for every cell of the ranges of (x, y, z), finite and in range, whose gap is not beyond limit() -- asked anew for every cell
+template <class Limit, class Cell>
+__device__ __forceinline__ void nn_walk_cells(const NnGrid& g, float x, float y, float z, Limit&& limit, Cell&& cell) {
+    int x0, x1, y0, y1, z0, z1;
+    nn_cell_range(g, x, x0, x1); nn_cell_range(g, y, y0, y1); nn_cell_range(g, z, z0, z1);
+    for (int cz = z0; cz <= z1; ++cz) {
+        const double gz = nn_box_gap(g, z, cz);
+        for (int cy = y0; cy <= y1; ++cy) {
+            const double gy = nn_box_gap(g, y, cy);
+            for (int cx = x0; cx <= x1; ++cx) {
+                const double gap = (gz + gy + nn_box_gap(g, x, cx)) * (1.0 - 3.814697265625e-06);
+                if (gap > (double)limit()) continue;
+                cell(cx, cy, cz);
+            }
+        }
+    }
+}
+// f(record) for every record that passes mf_cloud_nn_dev's radius test for (x, y, z), each exactly once
+template <class F>
+__device__ __forceinline__ void nn_walk_records(const NnGrid& g, float x, float y, float z, F&& f) {
+    nn_walk_cells(g, x, y, z, [&] { return g.r2; }, [&](int cx, int cy, int cz) {
+        const unsigned b = nn_hash(cx, cy, cz) & g.mask;
+        const unsigned e = g.start[b + 1];
+        for (unsigned r = g.start[b]; r < e; ++r) {
+            const float4 p = g.rec[r];
+            const float fx = p.x - x, fy = p.y - y, fz = p.z - z;
+            const float d2 = fx * fx + fy * fy + fz * fz;
+            if (!(d2 <= g.r2)) continue;
+            if (nn_cell(g, p.x) != cx || nn_cell(g, p.y) != cy || nn_cell(g, p.z) != cz) continue;   // another cell's record in a shared bucket
+            f(p);
+        }
+    });
 }
 
 // 1.  grid-stride over the targets
@@ -186,22 +228,11 @@ __device__ __forceinline__ void nn_find(const NnGrid& g, int n_target, float x, 
     if (n_target <= 0) return;
     const int ox = nn_cell(g, x), oy = nn_cell(g, y), oz = nn_cell(g, z);
     nn_scan_bucket(g, ox, oy, oz, x, y, z, bd2, bj, bk);
-    int x0, x1, y0, y1, z0, z1;
-    nn_cell_range(g, x, x0, x1); nn_cell_range(g, y, y0, y1); nn_cell_range(g, z, z0, z1);
-    for (int cz = z0; cz <= z1; ++cz) {
-        const double gz = nn_box_gap(g, z, cz);
-        for (int cy = y0; cy <= y1; ++cy) {
-            const double gy = nn_box_gap(g, y, cy);
-            for (int cx = x0; cx <= x1; ++cx) {
-                if (cx == ox && cy == oy && cz == oz) continue;
-                // the fp32 d2 of any target in the cell is at least (1 - 2^-18) of the box gap: skip the cell when that exceeds
-                // what can still win (the best d2 so far, or the radius test)
-                const double gap = (gz + gy + nn_box_gap(g, x, cx)) * (1.0 - 3.814697265625e-06);
-                if (gap > (double)(bj >= 0 ? bd2 : g.r2)) continue;
-                nn_scan_bucket(g, cx, cy, cz, x, y, z, bd2, bj, bk);
-            }
-        }
-    }
+    // the limit of the walk: what can still win (the best d2 so far, or the radius test).  A minimum may meet a record twice: no own-cell test.
+    nn_walk_cells(g, x, y, z, [&] { return bj >= 0 ? bd2 : g.r2; }, [&](int cx, int cy, int cz) {
+        if (cx == ox && cy == oy && cz == oz) return;
+        nn_scan_bucket(g, cx, cy, cz, x, y, z, bd2, bj, bk);
+    });
 }
 __global__ __launch_bounds__(kNnThreads) void k_nn_query(NnGrid g, NnQuery a, int n_target) {
     for (int i = blockIdx.x * kNnThreads + threadIdx.x; i < a.n; i += gridDim.x * kNnThreads) {
@@ -310,15 +341,13 @@ __global__ __launch_bounds__(64) void k_icp_sum(const double* __restrict__ parti
 
 // ---------------- normals of a cloud (mf_cloud_normals_dev; DESIGN.md "Cloud normals") ----------------
 // The cloud is target and query at once.  Two launches over the grid nn_build makes of it.
-// k_normals_walk: one lane per point i, grid-stride as k_nn_query.  The walk visits every cell nn_cell_range names and adds, for every record j
-// that passes mf_cloud_nn_dev's radius test (i itself does: d2 = 0), d = p_j - p_i in fp64 to ten accumulators -- the count, sum d and the upper
-// triangle of sum d d^T.  Two cells of the walk may share a bucket, and a sum, unlike a minimum, must not meet a record twice: a record counts
-// only in the visit of its OWN cell (nn_cell of its coordinates, the build's product).  A cell whose box lies beyond the radius is skipped
-// by nn_find's bound.  The nine sums go to a scratch record behind the grid (component-major, [9][n] doubles), the count to d_count.
+// k_normals_walk: one lane per point i, grid-stride as k_nn_query.  nn_walk_records hands it every record j that passes mf_cloud_nn_dev's
+// radius test (i itself does: d2 = 0), each once, and it adds d = p_j - p_i in fp64 to ten accumulators -- the count, sum d and the upper
+// triangle of sum d d^T.  The nine sums go to a scratch record behind the grid (component-major, [9][n] doubles), the count to d_count.
 // k_normals_solve: C = sum d d^T / k - m m^T, m = sum d / k, decomposed per lane by cyclic Jacobi rotations in fp64 (not the trigonometric
 // closed form, which loses the small eigenvalue to cancellation), then the rules of the header.
 // Why two, as k_icp_find / k_icp_accum: the walk lives on occupancy.  In one kernel the rotations' nine-double V and six-double C overlap the
-// walk's registers only in part: 72 VGPRs, 7 wavefronts per SIMD.  Apart, the walk takes 64 -- the 8 wavefronts k_nn_query (46) has -- and
+// walk's registers only in part: 72 VGPRs, 7 wavefronts per SIMD.  Apart, the walk takes 64 -- the 8 wavefronts k_nn_query (47) has -- and
 // the solve 62.  The price is 72 B per point written and read once.
 // kNrmSweeps: Jacobi converges quadratically once the off-diagonal is small, and a 3 x 3 gets there in few sweeps; see DESIGN.md "Cloud
 // normals" for how the count was chosen on the test clouds.
@@ -346,36 +375,14 @@ __device__ __forceinline__ void nrm_rotate(double& app, double& aqq, double& apq
         vp[k] = c * a - s * b; vq[k] = s * a + c * b;
     }
 }
-__device__ __forceinline__ void nrm_add_bucket(const NnGrid& g, int cx, int cy, int cz, float x, float y, float z, double (&s)[9], int& k) {
-    const unsigned b = nn_hash(cx, cy, cz) & g.mask;
-    const unsigned e = g.start[b + 1];
-    for (unsigned r = g.start[b]; r < e; ++r) {
-        const float4 p = g.rec[r];
-        const float fx = p.x - x, fy = p.y - y, fz = p.z - z;
-        const float d2 = fx * fx + fy * fy + fz * fz;
-        if (!(d2 <= g.r2)) continue;
-        if (nn_cell(g, p.x) != cx || nn_cell(g, p.y) != cy || nn_cell(g, p.z) != cz) continue;   // another cell's record in a shared bucket
+// the ten sums of point (x, y, z), finite and in range: k and s = {sum d (3), the upper triangle of sum d d^T (6)}
+__device__ __forceinline__ void nrm_walk(const NnGrid& g, float x, float y, float z, double (&s)[9], int& k) {
+    nn_walk_records(g, x, y, z, [&](const float4& p) {
         const double dx = (double)p.x - (double)x, dy = (double)p.y - (double)y, dz = (double)p.z - (double)z;
         s[0] += dx; s[1] += dy; s[2] += dz;
         s[3] += dx * dx; s[4] += dx * dy; s[5] += dx * dz; s[6] += dy * dy; s[7] += dy * dz; s[8] += dz * dz;
         ++k;
-    }
-}
-// the ten sums of point (x, y, z), finite and in range: k and s = {sum d (3), the upper triangle of sum d d^T (6)}
-__device__ __forceinline__ void nrm_walk(const NnGrid& g, float x, float y, float z, double (&s)[9], int& k) {
-    int x0, x1, y0, y1, z0, z1;
-    nn_cell_range(g, x, x0, x1); nn_cell_range(g, y, y0, y1); nn_cell_range(g, z, z0, z1);
-    for (int cz = z0; cz <= z1; ++cz) {
-        const double gz = nn_box_gap(g, z, cz);
-        for (int cy = y0; cy <= y1; ++cy) {
-            const double gy = nn_box_gap(g, y, cy);
-            for (int cx = x0; cx <= x1; ++cx) {
-                const double gap = (gz + gy + nn_box_gap(g, x, cx)) * (1.0 - 3.814697265625e-06);   // (nn_find's bound)
-                if (gap > (double)g.r2) continue;
-                nrm_add_bucket(g, cx, cy, cz, x, y, z, s, k);
-            }
-        }
-    }
+    });
 }
 // sums -> (normal, surface variation), NaN where the rules give no normal
 __device__ __forceinline__ float4 nrm_solve(const NrmArgs& a, float x, float y, float z, const double (&s)[9], int k) {
@@ -442,8 +449,8 @@ __global__ __launch_bounds__(kNnThreads) void k_normals_solve(NrmArgs a, const d
 // k_fpfh_prep: one lane per point: the eligible points (position and normal finite, the normal not zero) as float4 -- the others as NaN, which
 //   the grid does not hold -- and the normals normalised in fp64, [n][4] doubles.  The grid is built of that copy, so a point that is not
 //   eligible is nobody's neighbour and the grid code stays as it is.
-// k_fpfh_spfh: one lane per point i, grid-stride as k_normals_walk.  Every record j != i that passes the radius test in the visit of its own
-//   cell (nrm_add_bucket's rule) gives one pair: its three bins from fpfh_pair, in fp64.  The 33 counters of a lane live in LDS, bin-major
+// k_fpfh_spfh: one lane per point i, grid-stride as k_normals_walk.  Every record j != i that nn_walk_records hands over (the radius test, each
+//   record once) gives one pair: its three bins from fpfh_pair, in fp64.  The 33 counters of a lane live in LDS, bin-major
 //   (s_h[bin][lane]: a lane's column, no two lanes on one bank), because a histogram indexed by a computed bin cannot live in registers.
 //   Integer counts: the SPFH does not depend on the order of a bucket's records.
 // k_fpfh_sum: one wavefront per point, lane b < 33 owns bin b.  The wavefront walks the same cells in step (every lane tests the same
@@ -472,32 +479,6 @@ __global__ __launch_bounds__(kNnThreads) void k_fpfh_prep(FpfhArgs a) {
         a.pts[i] = ok ? make_float4(x, y, z, 0.f) : make_float4(NAN, NAN, NAN, 0.f);
         double* o = a.nrm + (size_t)i * 4;
         o[0] = ux; o[1] = uy; o[2] = uz; o[3] = 0.0;
-    }
-}
-// f(record) for every record within the radius of (x, y, z), each once: nrm_walk's cells and nrm_add_bucket's two tests
-template <class F>
-__device__ __forceinline__ void fpfh_walk(const NnGrid& g, float x, float y, float z, F&& f) {
-    int x0, x1, y0, y1, z0, z1;
-    nn_cell_range(g, x, x0, x1); nn_cell_range(g, y, y0, y1); nn_cell_range(g, z, z0, z1);
-    for (int cz = z0; cz <= z1; ++cz) {
-        const double gz = nn_box_gap(g, z, cz);
-        for (int cy = y0; cy <= y1; ++cy) {
-            const double gy = nn_box_gap(g, y, cy);
-            for (int cx = x0; cx <= x1; ++cx) {
-                const double gap = (gz + gy + nn_box_gap(g, x, cx)) * (1.0 - 3.814697265625e-06);   // (nn_find's bound)
-                if (gap > (double)g.r2) continue;
-                const unsigned b = nn_hash(cx, cy, cz) & g.mask;
-                const unsigned e = g.start[b + 1];
-                for (unsigned r = g.start[b]; r < e; ++r) {
-                    const float4 p = g.rec[r];
-                    const float fx = p.x - x, fy = p.y - y, fz = p.z - z;
-                    const float d2 = fx * fx + fy * fy + fz * fz;
-                    if (!(d2 <= g.r2)) continue;
-                    if (nn_cell(g, p.x) != cx || nn_cell(g, p.y) != cy || nn_cell(g, p.z) != cz) continue;   // another cell's record in a shared bucket
-                    f(p);
-                }
-            }
-        }
     }
 }
 __device__ __forceinline__ int fpfh_bin(double t) { return t >= 10.0 ? 10 : (t > 0.0 ? (int)t : 0); }   // floor, clamped to 0..10
@@ -538,7 +519,7 @@ __global__ __launch_bounds__(kNnThreads) void k_fpfh_spfh(NnGrid g, FpfhArgs a) 
             else {
                 const double* ni = a.nrm + (size_t)i * 4;
                 const double nix = ni[0], niy = ni[1], niz = ni[2];
-                fpfh_walk(g, pi.x, pi.y, pi.z, [&](const float4& pj) {
+                nn_walk_records(g, pi.x, pi.y, pi.z, [&](const float4& pj) {
                     const int j = __float_as_int(pj.w);
                     if (j == i) return;
                     const double* nj = a.nrm + (size_t)j * 4;
@@ -566,7 +547,7 @@ __global__ __launch_bounds__(kNnThreads) void k_fpfh_sum(NnGrid g, FpfhArgs a) {
         double acc = 0.0;
         const float4 pi = a.pts[i];
         if (nn_finite(pi.x, pi.y, pi.z) && nn_in_range(g, pi.x, pi.y, pi.z)) {
-            fpfh_walk(g, pi.x, pi.y, pi.z, [&](const float4& pj) {
+            nn_walk_records(g, pi.x, pi.y, pi.z, [&](const float4& pj) {
                 const int j = __float_as_int(pj.w);
                 if (j == i) return;
                 const int* sj = a.spfh + (size_t)j * kFpfhRow;
@@ -669,6 +650,10 @@ static uint64_t nn_buckets(int64_t n) {
     return b;
 }
 static uint64_t nn_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
+// the three checks every entry point shares
+static bool nn_radius_ok(float radius) { return std::isfinite(radius) && radius > 0.f; }
+static bool nn_count_ok(int64_t n) { return n >= 0 && n <= (int64_t)1 << 30; }
+static bool nn_ws_ok(const void* d_ws, uint64_t bytes, uint64_t need) { return d_ws && ((uintptr_t)d_ws & 15) == 0 && bytes >= need; }
 // workspace: rec [N] float4 | start [B + 1] | rank [N] | sums [kNnScanBlocks] | flag
 uint64_t nn_workspace_bytes(int64_t n_target) {
     const uint64_t n = (uint64_t)std::max<int64_t>(n_target, 0);
@@ -690,11 +675,16 @@ static NnGrid nn_layout(void* d_ws, int64_t n_target, float radius) {
     g.flag = (int*)w;
     return g;
 }
+static int nn_fail(const char** why, const char* text, int rc) {
+    if (why) *why = text;
+    return rc;
+}
 // clears the flag and fills the grid (count, scan, scatter); normal_offset >= 0: the normals go to nrm by record slot
+// (why, here and in nn_finish: where the text of a failure goes, or null -- only nn_run's caller reads it)
 static int nn_build(const NnGrid& g, const float* d_target, int target_stride, int normal_offset, float4* nrm, int64_t n_target, hipStream_t s,
-                    const char** why) {
+                    const char** why = nullptr) {
     const uint64_t B = (uint64_t)g.mask + 1;
-    if (hipMemsetAsync(g.start, 0, (B + 1) * 4, s) != hipSuccess || hipMemsetAsync(g.flag, 0, sizeof(int), s) != hipSuccess) { *why = "hipMemsetAsync failed"; return MF_EHIP; }
+    if (hipMemsetAsync(g.start, 0, (B + 1) * 4, s) != hipSuccess || hipMemsetAsync(g.flag, 0, sizeof(int), s) != hipSuccess) return nn_fail(why, "hipMemsetAsync failed", MF_EHIP);
     if (n_target > 0) {
         const int nb = nn_grid_blocks(n_target);
         hipLaunchKernelGGL(k_nn_count, dim3(nb), dim3(kNnThreads), 0, s, d_target, target_stride, normal_offset, (int)n_target, g);
@@ -715,25 +705,23 @@ static bool nn_transform_finite(const float* T16) {
     return true;
 }
 // waits for the stream and reports the range flag
-static int nn_finish(const NnGrid& g, hipStream_t s, const char** why) {
-    if (hipGetLastError() != hipSuccess) { *why = "kernel launch failed"; return MF_EHIP; }
+static int nn_finish(const NnGrid& g, hipStream_t s, const char** why = nullptr) {
+    if (hipGetLastError() != hipSuccess) return nn_fail(why, "kernel launch failed", MF_EHIP);
     int flag = 0;
-    if (hipMemcpyAsync(&flag, g.flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        *why = "HIP error during the nearest-neighbour kernels"; return MF_EHIP;
-    }
-    if (flag) { *why = "a coordinate has |x / radius| >= 2^30"; return MF_EINVAL; }
+    if (hipMemcpyAsync(&flag, g.flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return nn_fail(why, "HIP error during the nearest-neighbour kernels", MF_EHIP);
+    if (flag) return nn_fail(why, "a coordinate has |x / radius| >= 2^30", MF_EINVAL);
     return MF_OK;
 }
 
 int nn_run(const float* d_target, int target_stride, int64_t n_target, const float* d_query, int query_stride, int64_t n_query,
            const float* T16, float radius, float* d_dist, int32_t* d_idx, void* d_ws, uint64_t ws_bytes, hipStream_t s, const char** why) {
-    *why = nullptr;
-    if (!(std::isfinite(radius) && radius > 0.f)) { *why = "radius must be finite and > 0"; return MF_EINVAL; }
-    if (target_stride < 3 || query_stride < 3) { *why = "strides must be >= 3 floats"; return MF_EINVAL; }
-    if (n_target < 0 || n_query < 0 || n_target > (int64_t)1 << 30 || n_query > (int64_t)1 << 30) { *why = "point count out of range"; return MF_EINVAL; }
-    if ((n_target > 0 && !d_target) || (n_query > 0 && (!d_query || !d_dist || !d_idx))) { *why = "null pointer"; return MF_EINVAL; }
-    if (!d_ws || ((uintptr_t)d_ws & 15) != 0 || ws_bytes < nn_workspace_bytes(n_target)) { *why = "workspace missing, misaligned or too small"; return MF_EINVAL; }
-    if (T16 && !nn_transform_finite(T16)) { *why = "transform is not finite"; return MF_EINVAL; }
+    if (!nn_radius_ok(radius)) return nn_fail(why, "radius must be finite and > 0", MF_EINVAL);
+    if (target_stride < 3 || query_stride < 3) return nn_fail(why, "strides must be >= 3 floats", MF_EINVAL);
+    if (!nn_count_ok(n_target) || !nn_count_ok(n_query)) return nn_fail(why, "point count out of range", MF_EINVAL);
+    if ((n_target > 0 && !d_target) || (n_query > 0 && (!d_query || !d_dist || !d_idx))) return nn_fail(why, "null pointer", MF_EINVAL);
+    if (!nn_ws_ok(d_ws, ws_bytes, nn_workspace_bytes(n_target))) return nn_fail(why, "workspace missing, misaligned or too small", MF_EINVAL);
+    if (T16 && !nn_transform_finite(T16)) return nn_fail(why, "transform is not finite", MF_EINVAL);
     const NnGrid g = nn_layout(d_ws, n_target, radius);
     const int rc = nn_build(g, d_target, target_stride, -1, nullptr, n_target, s, why);
     if (rc != MF_OK) return rc;
@@ -756,23 +744,21 @@ static uint64_t icp_slots_at(int64_t n_target) { return icp_partials_at(n_target
 static uint64_t icp_workspace_bytes(int64_t n_target, int64_t n_query) {
     return icp_slots_at(n_target) + nn_align((uint64_t)std::max<int64_t>(n_query, 0) * 4);
 }
-static bool icp_ws_ok(const void* d_ws, uint64_t bytes, uint64_t need) { return d_ws && ((uintptr_t)d_ws & 15) == 0 && bytes >= need; }
 
 static int icp_build(const float* d_target, int target_stride, int normal_offset, int64_t n_target, float radius, void* d_ws, uint64_t ws_bytes,
                      hipStream_t s) {
-    const char* why = nullptr;
-    if (!(std::isfinite(radius) && radius > 0.f)) return MF_EINVAL;
+    if (!nn_radius_ok(radius)) return MF_EINVAL;
     if (target_stride < 3 || (normal_offset >= 0 && (normal_offset < 3 || normal_offset + 3 > target_stride))) return MF_EINVAL;
-    if (n_target < 0 || n_target > (int64_t)1 << 30 || (n_target > 0 && !d_target)) return MF_EINVAL;
-    if (!icp_ws_ok(d_ws, ws_bytes, icp_workspace_bytes(n_target, 0))) return MF_EINVAL;
+    if (!nn_count_ok(n_target) || (n_target > 0 && !d_target)) return MF_EINVAL;
+    if (!nn_ws_ok(d_ws, ws_bytes, icp_workspace_bytes(n_target, 0))) return MF_EINVAL;
     char* w = (char*)d_ws;
     // not a built workspace until the build has gone through
     if (hipMemsetAsync(w, 0, 256, s) != hipSuccess) return MF_EHIP;
     const NnGrid g = nn_layout(w + 256, n_target, radius);
     float4* nrm = (float4*)(w + 256 + nn_workspace_bytes(n_target));
-    int rc = nn_build(g, d_target, target_stride, normal_offset < 0 ? -1 : normal_offset, nrm, n_target, s, &why);
+    int rc = nn_build(g, d_target, target_stride, normal_offset < 0 ? -1 : normal_offset, nrm, n_target, s);
     if (rc != MF_OK) return rc;
-    rc = nn_finish(g, s, &why);
+    rc = nn_finish(g, s);
     if (rc != MF_OK) return rc;
     const IcpHeader h = {kIcpMagic, n_target, radius, normal_offset >= 0 ? 1 : 0};
     if (hipMemcpyAsync(w, &h, sizeof(h), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return MF_EHIP;
@@ -781,14 +767,13 @@ static int icp_build(const float* d_target, int target_stride, int normal_offset
 
 static int icp_step(void* d_ws, uint64_t ws_bytes, const float* d_query, int query_stride, int64_t n_query, const float* T16, double* d_out29,
                     hipStream_t s) {
-    const char* why = nullptr;
-    if (query_stride < 3 || n_query < 0 || n_query > (int64_t)1 << 30 || (n_query > 0 && !d_query) || !d_out29) return MF_EINVAL;
-    if (!icp_ws_ok(d_ws, ws_bytes, 256)) return MF_EINVAL;
+    if (query_stride < 3 || !nn_count_ok(n_query) || (n_query > 0 && !d_query) || !d_out29) return MF_EINVAL;
+    if (!nn_ws_ok(d_ws, ws_bytes, 256)) return MF_EINVAL;
     if (T16 && !nn_transform_finite(T16)) return MF_EINVAL;
     char* w = (char*)d_ws;
     IcpHeader h;
     if (hipMemcpyAsync(&h, w, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return MF_EHIP;
-    if (h.magic != kIcpMagic || h.n_target < 0 || h.n_target > (int64_t)1 << 30 || !(std::isfinite(h.radius) && h.radius > 0.f)) return MF_EINVAL;
+    if (h.magic != kIcpMagic || !nn_count_ok(h.n_target) || !nn_radius_ok(h.radius)) return MF_EINVAL;
     if (ws_bytes < icp_workspace_bytes(h.n_target, n_query)) return MF_EINVAL;
     const NnGrid g = nn_layout(w + 256, h.n_target, h.radius);
     if (hipMemsetAsync(g.flag, 0, sizeof(int), s) != hipSuccess) return MF_EHIP;
@@ -804,20 +789,19 @@ static int icp_step(void* d_ws, uint64_t ws_bytes, const float* d_query, int que
     if (h.plane) hipLaunchKernelGGL(k_icp_accum<true>, dim3(nb), dim3(kNnThreads), 0, s, g, a);
     else hipLaunchKernelGGL(k_icp_accum<false>, dim3(nb), dim3(kNnThreads), 0, s, g, a);
     hipLaunchKernelGGL(k_icp_sum, dim3(1), dim3(64), 0, s, (const double*)a.partial, nb, d_out29);
-    return nn_finish(g, s, &why);
+    return nn_finish(g, s);
 }
 
 // ---------------- normals: workspace = the grid's workspace | sums [9][n] double ----------------
 static uint64_t normals_workspace_bytes(int64_t n) { return nn_workspace_bytes(n) + nn_align((uint64_t)std::max<int64_t>(n, 0) * 72); }
 static int normals_run(const float* d_points, int stride, int64_t n, float radius, int min_neighbours, const float* viewpoint3, float4* d_normals,
                        int32_t* d_count, void* d_ws, uint64_t ws_bytes, hipStream_t s) {
-    const char* why = nullptr;
-    if (!(std::isfinite(radius) && radius > 0.f) || stride < 3 || min_neighbours < 3) return MF_EINVAL;
-    if (n < 0 || n > (int64_t)1 << 30 || (n > 0 && (!d_points || !d_normals || !d_count))) return MF_EINVAL;
-    if (!d_ws || ((uintptr_t)d_ws & 15) != 0 || ws_bytes < normals_workspace_bytes(n)) return MF_EINVAL;
+    if (!nn_radius_ok(radius) || stride < 3 || min_neighbours < 3) return MF_EINVAL;
+    if (!nn_count_ok(n) || (n > 0 && (!d_points || !d_normals || !d_count))) return MF_EINVAL;
+    if (!nn_ws_ok(d_ws, ws_bytes, normals_workspace_bytes(n))) return MF_EINVAL;
     if (viewpoint3 && !(std::isfinite(viewpoint3[0]) && std::isfinite(viewpoint3[1]) && std::isfinite(viewpoint3[2]))) return MF_EINVAL;
     const NnGrid g = nn_layout(d_ws, n, radius);
-    const int rc = nn_build(g, d_points, stride, -1, nullptr, n, s, &why);
+    const int rc = nn_build(g, d_points, stride, -1, nullptr, n, s);
     if (rc != MF_OK) return rc;
     if (n > 0) {
         NrmArgs a;
@@ -828,7 +812,7 @@ static int normals_run(const float* d_points, int stride, int64_t n, float radiu
         hipLaunchKernelGGL(k_normals_walk, dim3(nn_grid_blocks(n)), dim3(kNnThreads), 0, s, g, a, sums);
         hipLaunchKernelGGL(k_normals_solve, dim3(nn_grid_blocks(n)), dim3(kNnThreads), 0, s, a, (const double*)sums);
     }
-    return nn_finish(g, s, &why);
+    return nn_finish(g, s);
 }
 
 // ---------------- FPFH: workspace = points [n] float4 | normals [n][4] double | the grid's workspace | counts [n][34] int ----------------
@@ -838,10 +822,9 @@ static uint64_t fpfh_workspace_bytes(int64_t n) {
 }
 static int fpfh_run(const float* d_points, int stride, int normal_offset, int64_t n, float radius, float* d_fpfh, int32_t* d_spfh, void* d_ws,
                     uint64_t ws_bytes, hipStream_t s) {
-    const char* why = nullptr;
-    if (!(std::isfinite(radius) && radius > 0.f) || stride < 6 || normal_offset < 3 || normal_offset + 3 > stride) return MF_EINVAL;
-    if (n < 0 || n > (int64_t)1 << 30 || (n > 0 && (!d_points || !d_fpfh))) return MF_EINVAL;
-    if (!d_ws || ((uintptr_t)d_ws & 15) != 0 || ws_bytes < fpfh_workspace_bytes(n)) return MF_EINVAL;
+    if (!nn_radius_ok(radius) || stride < 6 || normal_offset < 3 || normal_offset + 3 > stride) return MF_EINVAL;
+    if (!nn_count_ok(n) || (n > 0 && (!d_points || !d_fpfh))) return MF_EINVAL;
+    if (!nn_ws_ok(d_ws, ws_bytes, fpfh_workspace_bytes(n))) return MF_EINVAL;
     char* w = (char*)d_ws;
     FpfhArgs a;
     memset(&a, 0, sizeof(a));
@@ -851,20 +834,20 @@ static int fpfh_run(const float* d_points, int stride, int normal_offset, int64_
     a.spfh = d_spfh ? d_spfh : (int*)(w + fpfh_grid_at(n) + nn_workspace_bytes(n));
     const NnGrid g = nn_layout(w + fpfh_grid_at(n), n, radius);
     if (n > 0) hipLaunchKernelGGL(k_fpfh_prep, dim3(nn_grid_blocks(n)), dim3(kNnThreads), 0, s, a);
-    const int rc = nn_build(g, (const float*)a.pts, 4, -1, nullptr, n, s, &why);
+    const int rc = nn_build(g, (const float*)a.pts, 4, -1, nullptr, n, s);
     if (rc != MF_OK) return rc;
     if (n > 0) {
         hipLaunchKernelGGL(k_fpfh_spfh, dim3(nn_grid_blocks(n)), dim3(kNnThreads), 0, s, g, a);
         const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((n + kFpfhWaves - 1) / kFpfhWaves, kNnMaxGrid));
         hipLaunchKernelGGL(k_fpfh_sum, dim3(nb), dim3(kNnThreads), 0, s, g, a);
     }
-    return nn_finish(g, s, &why);
+    return nn_finish(g, s);
 }
 
 static int feature_match(const float* d_target, int64_t n_target, const float* d_query, int64_t n_query, int dim, int32_t* d_idx, float* d_d2,
                          hipStream_t s) {
     if (dim < 1 || dim > kMatchMaxDim) return MF_EINVAL;
-    if (n_target < 0 || n_query < 0 || n_target > (int64_t)1 << 30 || n_query > (int64_t)1 << 30) return MF_EINVAL;
+    if (!nn_count_ok(n_target) || !nn_count_ok(n_query)) return MF_EINVAL;
     if ((n_target > 0 && !d_target) || (n_query > 0 && (!d_query || !d_idx || !d_d2))) return MF_EINVAL;
     if (n_query > 0) {
         MatchArgs a;
@@ -876,479 +859,12 @@ static int feature_match(const float* d_target, int64_t n_target, const float* d
     return MF_OK;
 }
 
-// ---------------- segmentation scores (mf_label_confusion_dev, mf_label_boundary_dev; DESIGN.md "Segmentation evaluation") ----------------
-// Two label streams uint8 [n_frames][H][W]; a 256-entry table per stream maps a raw value to a compact class (< 64) or to kLabVoid.  The
-// tables (and the boundary pass's pairing) travel BY VALUE in the kernel's argument block; the first thing a workgroup does is to copy
-// them to LDS, where the per-pixel lookups go.  Every counter is an integer: the results do not depend on the order of execution.
-constexpr int kLabMaxClasses = 64;
-constexpr unsigned kLabVoid = 255u;          // a table entry: the raw value belongs to no class
-constexpr unsigned kLabOutside = 254u;       // boundary pass, in LDS only: a position outside the image
-constexpr int kLabThreads = 256;
-
-// ---- region counts ----
-// One workgroup takes one chunk of kConfChunk pixels of ONE frame (the last chunk of a frame is short), so a workgroup never spans two frames:
-// histogram [n_gt][n_est] in LDS, non-zero bins flushed with one global atomic each.  A lane reads 16 pixels of either stream with one 16-byte
-// load and adds runs of equal (gt, est) pairs with one LDS atomic per run -- label images are piecewise constant, and without this the 64
-// lanes of a wavefront serialise on the background's bin.  A frame need not start at a multiple of 16 bytes (W H odd, a view into a larger
-// buffer): the wide loads cover the 16-byte-aligned middle of the chunk when both streams are misaligned by the same amount, the pixels before
-// and after it are read byte by byte; when the two misalignments differ, the whole chunk is.
-constexpr int kConfChunk = 32768;
-struct ConfArgs {
-    const uint8_t* est; const uint8_t* gt;
-    unsigned* counts;                         // [n_frames][n_gt][n_est]
-    int P;                                    // W H
-    int chunks;                               // per frame
-    int n_est, n_gt;
-    uint8_t lut_est[256], lut_gt[256];
-};
-__device__ __forceinline__ unsigned conf_key(const uint8_t* s_le, const uint8_t* s_lg, unsigned e, unsigned g, int n_est) {
-    const unsigned ce = s_le[e], cg = s_lg[g];
-    return (ce == kLabVoid || cg == kLabVoid) ? 0xFFFFFFFFu : cg * (unsigned)n_est + ce;
-}
-__device__ __forceinline__ void conf_flush(unsigned* s_hist, unsigned key, unsigned n) {
-    if (key != 0xFFFFFFFFu && n) atomicAdd(&s_hist[key], n);
-}
-__device__ __forceinline__ void conf_add(unsigned* s_hist, unsigned key, unsigned n, unsigned& cur, unsigned& run) {
-    if (key == cur) { run += n; return; }
-    conf_flush(s_hist, cur, run);
-    cur = key; run = n;
-}
-__global__ __launch_bounds__(kLabThreads) void k_label_confusion(ConfArgs a) {
-    __shared__ unsigned s_hist[kLabMaxClasses * kLabMaxClasses];
-    __shared__ uint8_t s_le[256], s_lg[256];
-    const int tid = threadIdx.x;
-    const int frame = blockIdx.x / a.chunks, chunk = blockIdx.x - frame * a.chunks;
-    const int bins = a.n_gt * a.n_est;
-    s_le[tid] = a.lut_est[tid];
-    s_lg[tid] = a.lut_gt[tid];
-    for (int b = tid; b < bins; b += kLabThreads) s_hist[b] = 0u;
-    __syncthreads();
-    const uint8_t* pe = a.est + (size_t)frame * a.P;
-    const uint8_t* pg = a.gt + (size_t)frame * a.P;
-    const int beg = chunk * kConfChunk, end = min(a.P, beg + kConfChunk);
-    // [v0, v1): whole 16-byte groups at 16-byte-aligned addresses of both streams
-    const unsigned me = (unsigned)(((uintptr_t)pe + (unsigned)beg) & 15u), mg = (unsigned)(((uintptr_t)pg + (unsigned)beg) & 15u);
-    int v0 = end, v1 = end;
-    if (me == mg) {
-        v0 = min(end, beg + (int)((16u - me) & 15u));
-        v1 = v0 + ((end - v0) & ~15);
-    }
-    unsigned cur = 0xFFFFFFFFu, run = 0u;
-    for (int i = v0 + tid * 16; i < v1; i += kLabThreads * 16) {
-        const uint4 e4 = *(const uint4*)(pe + i), g4 = *(const uint4*)(pg + i);
-        const unsigned ew[4] = {e4.x, e4.y, e4.z, e4.w}, gw[4] = {g4.x, g4.y, g4.z, g4.w};
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const unsigned e = ew[w], g = gw[w];
-            if (e == (e & 255u) * 0x01010101u && g == (g & 255u) * 0x01010101u) {   // four equal pixels: one lookup
-                conf_add(s_hist, conf_key(s_le, s_lg, e & 255u, g & 255u, a.n_est), 4u, cur, run);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    conf_add(s_hist, conf_key(s_le, s_lg, (e >> (8 * k)) & 255u, (g >> (8 * k)) & 255u, a.n_est), 1u, cur, run);
-            }
-        }
-    }
-    conf_flush(s_hist, cur, run);
-    // the pixels before and after the aligned middle (at most 15 each), or the whole chunk
-    const int head = v0 - beg, rest = head + (end - v1);
-    for (int k = tid; k < rest; k += kLabThreads) {
-        const int i = k < head ? beg + k : v1 + (k - head);
-        conf_flush(s_hist, conf_key(s_le, s_lg, pe[i], pg[i], a.n_est), 1u);
-    }
-    __syncthreads();
-    unsigned* out = a.counts + (size_t)frame * bins;
-    for (int b = tid; b < bins; b += kLabThreads) {
-        const unsigned v = s_hist[b];
-        if (v) atomicAdd(&out[b], v);
-    }
-}
-
-// ---- boundary counts ----
-// One workgroup per tile of kBndTW x kBndTH pixels of one frame.  h = radius + 1.
-//   1. the compact labels of the tile and a halo of h pixels -> LDS, one byte per pixel and stream (kLabOutside beyond the image);
-//   2. two boundary planes over the tile and a halo of `radius`: the class whose boundary the pixel is, or kLabVoid for none (a pixel is a
-//      boundary pixel of its class k when a 4-neighbour inside the image has another label; void and outside pixels are boundaries of nothing).
-//      The boundary pixels INSIDE the tile are appended to a list (one LDS atomic each), so that
-//   3. the threads share the boundary pixels evenly: each walks the disc dx^2 + dy^2 <= radius^2 over the OTHER stream's plane, rows in the
-//      order 0, -1, +1, -2, ..., and stops at the first hit.  An estimate's boundary pixel of class e serves every ground-truth class g with
-//      pair[g] = e (s_gmask[e], one bit per g: the pairing need not be one to one);
-//   4. counters [n_gt][4] in LDS, one global atomic per non-zero counter.
-constexpr int kBndTW = 64, kBndTH = 32, kBndMaxRadius = 16;
-constexpr int kBndLabMax = (kBndTW + 2 * (kBndMaxRadius + 1)) * (kBndTH + 2 * (kBndMaxRadius + 1));   // 98 x 66
-constexpr int kBndPlaneMax = (kBndTW + 2 * kBndMaxRadius) * (kBndTH + 2 * kBndMaxRadius);             // 96 x 64
-struct BndArgs {
-    const uint8_t* est; const uint8_t* gt;
-    unsigned* out;                            // [n_frames][n_gt][4]
-    int W, H, radius;
-    int tiles_x, tiles_y;
-    int n_gt;
-    uint8_t lut_est[256], lut_gt[256], pair[kLabMaxClasses];
-};
-// the class whose boundary pixel (x, y) of the label plane is (pitch lp), or kLabVoid
-__device__ __forceinline__ unsigned bnd_class(const uint8_t* s_lab, int lp, int x, int y) {
-    const uint8_t* p = s_lab + y * lp + x;
-    const unsigned k = p[0];
-    if (k >= (unsigned)kLabMaxClasses) return kLabVoid;
-    const unsigned l = p[-1], r = p[1], u = p[-lp], d = p[lp];
-    const bool edge = (l != kLabOutside && l != k) || (r != kLabOutside && r != k) || (u != kLabOutside && u != k) || (d != kLabOutside && d != k);
-    return edge ? k : kLabVoid;
-}
-__global__ __launch_bounds__(kLabThreads) void k_label_boundary(BndArgs a) {
-    __shared__ uint8_t s_le[kBndLabMax], s_lg[kBndLabMax];          // compact labels, halo radius + 1
-    __shared__ uint8_t s_be[kBndPlaneMax], s_bg[kBndPlaneMax];      // boundary planes, halo radius
-    __shared__ uint16_t s_list[2 * kBndTW * kBndTH];                // boundary pixels of the tile: (side << 15) | (ty * kBndTW + tx)
-    __shared__ unsigned long long s_gmask[kLabMaxClasses];          // estimate class e -> the g with pair[g] = e
-    __shared__ unsigned s_cnt[kLabMaxClasses * 4];
-    __shared__ uint8_t s_lut_e[256], s_lut_g[256], s_pair[kLabMaxClasses];
-    __shared__ int s_halfw[kBndMaxRadius + 1];                      // |dy| -> the largest dx with dx^2 + dy^2 <= radius^2
-    __shared__ unsigned s_n;
-    const int tid = threadIdx.x;
-    const int R = a.radius, h = R + 1;
-    const int tile = blockIdx.x % (a.tiles_x * a.tiles_y), frame = blockIdx.x / (a.tiles_x * a.tiles_y);
-    const int x0 = (tile % a.tiles_x) * kBndTW, y0 = (tile / a.tiles_x) * kBndTH;
-    const int lp = kBndTW + 2 * h, lrows = kBndTH + 2 * h;          // label planes
-    const int bp = kBndTW + 2 * R, brows = kBndTH + 2 * R;          // boundary planes
-    s_lut_e[tid] = a.lut_est[tid];
-    s_lut_g[tid] = a.lut_gt[tid];
-    if (tid < kLabMaxClasses) {
-        s_pair[tid] = tid < a.n_gt ? a.pair[tid] : (uint8_t)kLabVoid;
-        unsigned long long m = 0ull;
-        for (int g = 0; g < a.n_gt; ++g) if (a.pair[g] == tid) m |= 1ull << g;
-        s_gmask[tid] = m;
-    }
-    if (tid <= R) {
-        int w = 0;
-        while ((w + 1) * (w + 1) + tid * tid <= R * R) ++w;
-        s_halfw[tid] = w;
-    }
-    for (int k = tid; k < a.n_gt * 4; k += kLabThreads) s_cnt[k] = 0u;
-    if (tid == 0) s_n = 0u;
-    __syncthreads();
-    // 1.
-    const uint8_t* pe = a.est + (size_t)frame * a.W * a.H;
-    const uint8_t* pg = a.gt + (size_t)frame * a.W * a.H;
-    for (int k = tid; k < lp * lrows; k += kLabThreads) {
-        const int ly = k / lp, lx = k - ly * lp;
-        const int x = x0 - h + lx, y = y0 - h + ly;
-        unsigned e = kLabOutside, g = kLabOutside;
-        if (x >= 0 && x < a.W && y >= 0 && y < a.H) {
-            const size_t at = (size_t)y * a.W + x;
-            e = s_lut_e[pe[at]];
-            g = s_lut_g[pg[at]];
-        }
-        s_le[k] = (uint8_t)e;
-        s_lg[k] = (uint8_t)g;
-    }
-    __syncthreads();
-    // 2.  (plane position (bx, by) is label position (bx + 1, by + 1): never on the label planes' rim)
-    for (int k = tid; k < bp * brows; k += kLabThreads) {
-        const int by = k / bp, bx = k - by * bp;
-        const unsigned ce = bnd_class(s_le, lp, bx + 1, by + 1), cg = bnd_class(s_lg, lp, bx + 1, by + 1);
-        s_be[k] = (uint8_t)ce;
-        s_bg[k] = (uint8_t)cg;
-        const int tx = bx - R, ty = by - R;
-        if (tx >= 0 && tx < kBndTW && ty >= 0 && ty < kBndTH) {
-            const unsigned id = (unsigned)(ty * kBndTW + tx);
-            if (ce != kLabVoid && s_gmask[ce] != 0ull) s_list[atomicAdd(&s_n, 1u)] = (uint16_t)id;
-            if (cg != kLabVoid) s_list[atomicAdd(&s_n, 1u)] = (uint16_t)(0x8000u | id);
-        }
-    }
-    __syncthreads();
-    // 3.
-    const unsigned n = s_n;
-    for (unsigned k = tid; k < n; k += kLabThreads) {
-        const unsigned item = s_list[k];
-        const bool gt_side = (item & 0x8000u) != 0u;
-        const int id = (int)(item & 0x7FFFu);
-        const int at = (id / kBndTW + R) * bp + (id % kBndTW + R);       // the pixel in the boundary planes
-        if (gt_side) {
-            const unsigned g = s_bg[at], e = s_pair[g];
-            atomicAdd(&s_cnt[g * 4 + 2], 1u);
-            if (e == kLabVoid) continue;
-            bool hit = false;
-            for (int j = 0; j <= 2 * R && !hit; ++j) {
-                const int dy = (j & 1) ? -((j + 1) >> 1) : (j >> 1);
-                const int w = s_halfw[dy < 0 ? -dy : dy];
-                const uint8_t* row = s_be + at + dy * bp;
-                for (int dx = -w; dx <= w; ++dx)
-                    if (row[dx] == e) { hit = true; break; }
-            }
-            if (hit) atomicAdd(&s_cnt[g * 4 + 3], 1u);
-        } else {
-            const unsigned e = s_be[at];
-            const unsigned long long want = s_gmask[e];
-            unsigned long long found = 0ull;
-            for (int j = 0; j <= 2 * R && found != want; ++j) {
-                const int dy = (j & 1) ? -((j + 1) >> 1) : (j >> 1);
-                const int w = s_halfw[dy < 0 ? -dy : dy];
-                const uint8_t* row = s_bg + at + dy * bp;
-                for (int dx = -w; dx <= w; ++dx) {
-                    const unsigned g = row[dx];
-                    if (g != kLabVoid) found |= (1ull << g) & want;
-                }
-            }
-            for (unsigned long long m = want; m; m &= m - 1) {
-                const int g = __ffsll(m) - 1;
-                atomicAdd(&s_cnt[g * 4 + 0], 1u);
-                if ((found >> g) & 1ull) atomicAdd(&s_cnt[g * 4 + 1], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    // 4.
-    unsigned* out = a.out + (size_t)frame * a.n_gt * 4;
-    for (int k = tid; k < a.n_gt * 4; k += kLabThreads) {
-        const unsigned v = s_cnt[k];
-        if (v) atomicAdd(&out[k], v);
-    }
-}
-
-// the checks the two calls share; the frame's pixel count -> *P
-static int lab_check(const uint8_t* d_est, const uint8_t* d_gt, const void* d_out, int32_t n_frames, int32_t height, int32_t width,
-                     const uint8_t* lut_est, int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, int64_t* P) {
-    if (!d_est || !d_gt || !d_out || !lut_est || !lut_gt) return MF_EINVAL;
-    if (width < 1 || height < 1 || n_frames < 1) return MF_EINVAL;
-    if (n_est < 1 || n_est > kLabMaxClasses || n_gt < 1 || n_gt > kLabMaxClasses) return MF_EINVAL;
-    *P = (int64_t)width * height;
-    if (*P > (int64_t)1 << 30) return MF_EINVAL;                      // (a frame's counters and indices stay within 32 bits)
-    for (int v = 0; v < 256; ++v)
-        if ((lut_est[v] >= n_est && lut_est[v] != kLabVoid) || (lut_gt[v] >= n_gt && lut_gt[v] != kLabVoid)) return MF_EINVAL;
-    return MF_OK;
-}
-
-static int label_confusion(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_frames, int32_t height, int32_t width, const uint8_t* lut_est,
-                           int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, uint32_t* d_counts, hipStream_t s) {
-    int64_t P = 0;
-    const int rc = lab_check(d_est, d_gt, d_counts, n_frames, height, width, lut_est, n_est, lut_gt, n_gt, &P);
-    if (rc != MF_OK) return rc;
-    ConfArgs a;
-    memset(&a, 0, sizeof(a));
-    a.est = d_est; a.gt = d_gt; a.counts = d_counts; a.P = (int)P; a.n_est = n_est; a.n_gt = n_gt;
-    a.chunks = (int)((P + kConfChunk - 1) / kConfChunk);
-    memcpy(a.lut_est, lut_est, 256);
-    memcpy(a.lut_gt, lut_gt, 256);
-    const int64_t blocks = (int64_t)n_frames * a.chunks;
-    if (blocks > 0x7FFFFFFF) return MF_EINVAL;
-    if (hipMemsetAsync(d_counts, 0, (size_t)n_frames * n_gt * n_est * sizeof(uint32_t), s) != hipSuccess) return MF_EHIP;
-    hipLaunchKernelGGL(k_label_confusion, dim3((unsigned)blocks), dim3(kLabThreads), 0, s, a);
-    return hipGetLastError() == hipSuccess ? MF_OK : MF_EHIP;
-}
-
-static int label_boundary(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_frames, int32_t height, int32_t width, const uint8_t* lut_est,
-                          int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, const uint8_t* pair, int32_t radius, uint32_t* d_out, hipStream_t s) {
-    int64_t P = 0;
-    const int rc = lab_check(d_est, d_gt, d_out, n_frames, height, width, lut_est, n_est, lut_gt, n_gt, &P);
-    if (rc != MF_OK) return rc;
-    if (!pair || radius < 0 || radius > kBndMaxRadius) return MF_EINVAL;
-    for (int g = 0; g < n_gt; ++g)
-        if (pair[g] >= n_est && pair[g] != kLabVoid) return MF_EINVAL;
-    BndArgs a;
-    memset(&a, 0, sizeof(a));
-    a.est = d_est; a.gt = d_gt; a.out = d_out; a.W = width; a.H = height; a.radius = radius; a.n_gt = n_gt;
-    a.tiles_x = (width + kBndTW - 1) / kBndTW;
-    a.tiles_y = (height + kBndTH - 1) / kBndTH;
-    memcpy(a.lut_est, lut_est, 256);
-    memcpy(a.lut_gt, lut_gt, 256);
-    memset(a.pair, (int)kLabVoid, sizeof(a.pair));
-    memcpy(a.pair, pair, (size_t)n_gt);
-    const int64_t blocks = (int64_t)n_frames * a.tiles_x * a.tiles_y;
-    if (blocks > 0x7FFFFFFF) return MF_EINVAL;
-    if (hipMemsetAsync(d_out, 0, (size_t)n_frames * n_gt * 4 * sizeof(uint32_t), s) != hipSuccess) return MF_EHIP;
-    hipLaunchKernelGGL(k_label_boundary, dim3((unsigned)blocks), dim3(kLabThreads), 0, s, a);
-    return hipGetLastError() == hipSuccess ? MF_OK : MF_EHIP;
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------------
-// view scores: the map's render against the input frame (mf_view_score_dev; DESIGN.md "View evaluation")
-// ------------------------------------------------------------------------------------------------------------------------------------
-// One workgroup per tile of kViewTW x kViewTH pixels of one frame; thread (tx, ty0) owns the tile's pixels (tx, ty0) and (tx, ty0 + 8).
-//   1. the R, G, B bytes of both images over the tile and a halo of 5 -> LDS, one plane per channel and image (0 beyond the image: such a
-//      position only enters windows that do not lie wholly inside the image, and those are not counted);
-//   2. the counters that need no window (0..8) of the thread's pixels into registers: depths and group from global memory, bytes from LDS;
-//   3. per channel: the row pass -- the five quantities x, y, xx, xy, yy filtered along the row for every row of the tile and its halo --
-//      into LDS as fp64, then the column pass of the thread's pixels from it; the channel's SSIM value is added to the pixel's sum;
-//   4. the pixel's counters -> the group's ten 64-bit counters in LDS (a thread whose two pixels share a group adds them once), and one
-//      global 64-bit atomic per non-zero counter.
-// Everything that is summed is an integer, so the result does not depend on the order of execution; the fp64 arithmetic is rounded
-// operation by operation (no contraction in this file) in the order the header gives.
-constexpr int kViewTW = 32, kViewTH = 16, kViewHalo = 5, kViewTaps = 2 * kViewHalo + 1;
-constexpr int kViewThreads = 256;
-constexpr int kViewPW = kViewTW + 2 * kViewHalo, kViewPH = kViewTH + 2 * kViewHalo;     // the staged planes: 42 x 26
-constexpr int kViewMaxGroups = 64, kViewCounters = 10;
-constexpr double kViewFix = 16777216.0;      // 2^24: the fixed point of counters 5 and 9
-static_assert(kViewTW * kViewTH == 2 * kViewThreads && kViewThreads / kViewTW * 2 == kViewTH, "a thread owns two pixels, 8 rows apart");
-struct ViewArgs {
-    const uint8_t* render; const float* render_depth;     // [n_frames][H][W][4], [n_frames][H][W]
-    const uint8_t* rgb; const float* depth;               // [n_frames][H][W][3], [n_frames][H][W]
-    const uint8_t* group;                                 // [n_frames][H][W] or null
-    unsigned long long* counts;                           // [n_frames][n_groups][10]
-    int W, H, tiles_x, tiles_y, n_groups;
-    float max_depth, tau;
-    double w[kViewTaps];
-};
-__device__ __forceinline__ bool view_depth_ok(float z) { return z - z == 0.f && z > 0.f; }   // finite and positive
-__global__ __launch_bounds__(kViewThreads) void k_view_score(ViewArgs a) {
-    __shared__ uint8_t s_x[3][kViewPW * kViewPH], s_y[3][kViewPW * kViewPH];      // render, input
-    __shared__ double s_row[5][kViewPH * kViewTW];
-    __shared__ unsigned long long s_cnt[kViewMaxGroups * kViewCounters];
-    const int tid = threadIdx.x;
-    const int tiles = a.tiles_x * a.tiles_y;
-    const int frame = blockIdx.x / tiles, tile = blockIdx.x - frame * tiles;
-    const int x0 = (tile % a.tiles_x) * kViewTW, y0 = (tile / a.tiles_x) * kViewTH;
-    const size_t P = (size_t)a.W * a.H, fbase = (size_t)frame * P;
-    for (int k = tid; k < a.n_groups * kViewCounters; k += kViewThreads) s_cnt[k] = 0ull;
-    // 1.
-    for (int k = tid; k < kViewPW * kViewPH; k += kViewThreads) {
-        const int ly = k / kViewPW, lx = k - ly * kViewPW;
-        const int x = x0 - kViewHalo + lx, y = y0 - kViewHalo + ly;
-        unsigned r[3] = {0u, 0u, 0u}, i[3] = {0u, 0u, 0u};
-        if (x >= 0 && x < a.W && y >= 0 && y < a.H) {
-            const size_t at = fbase + (size_t)y * a.W + x;
-            const uint8_t* pr = a.render + at * 4;
-            const uint8_t* pi = a.rgb + at * 3;
-            r[0] = pr[0]; r[1] = pr[1]; r[2] = pr[2];
-            i[0] = pi[0]; i[1] = pi[1]; i[2] = pi[2];
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { s_x[c][k] = (uint8_t)r[c]; s_y[c][k] = (uint8_t)i[c]; }
-    }
-    __syncthreads();
-    // 2.
-    const int tx = tid & (kViewTW - 1), ty0 = tid / kViewTW;
-    const int x = x0 + tx;
-    int grp[2];                                   // -1: outside the image, or void
-    bool window[2];                               // the 11 x 11 window lies inside the image
-    unsigned long long cnt[2][kViewCounters - 1]; // counters 0..8 of the two pixels
-    double ssum[2] = {0.0, 0.0};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int y = y0 + ty0 + j * (kViewTH / 2);
-        grp[j] = -1; window[j] = false;
-#pragma unroll
-        for (int q = 0; q < kViewCounters - 1; ++q) cnt[j][q] = 0ull;
-        if (x >= a.W || y >= a.H) continue;
-        const size_t at = fbase + (size_t)y * a.W + x;
-        const int g = a.group ? (int)a.group[at] : 0;
-        if (g >= a.n_groups) continue;
-        grp[j] = g;
-        const float zr = a.render_depth[at], zi = a.depth[at];
-        const bool covered = view_depth_ok(zr), valid = view_depth_ok(zi) && zi <= a.max_depth;
-        cnt[j][0] = 1ull; cnt[j][1] = covered ? 1ull : 0ull; cnt[j][2] = valid ? 1ull : 0ull;
-        if (covered && valid) {
-            const float dz = fabsf(zr - zi);
-            cnt[j][3] = 1ull;
-            cnt[j][4] = dz <= a.tau ? 1ull : 0ull;
-            cnt[j][5] = (unsigned long long)llrint((double)dz * kViewFix);
-        }
-        const int lk = (ty0 + j * (kViewTH / 2) + kViewHalo) * kViewPW + tx + kViewHalo;
-        unsigned sq = 0u;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { const int d = (int)s_x[c][lk] - (int)s_y[c][lk]; sq += (unsigned)(d * d); }
-        cnt[j][6] = sq; cnt[j][7] = covered ? sq : 0u;
-        window[j] = x >= kViewHalo && x < a.W - kViewHalo && y >= kViewHalo && y < a.H - kViewHalo;
-        cnt[j][8] = window[j] ? 1ull : 0ull;
-    }
-    // 3.
-    for (int c = 0; c < 3; ++c) {
-        for (int k = tid; k < kViewPH * kViewTW; k += kViewThreads) {
-            const int row = k / kViewTW, col = k - row * kViewTW;
-            const uint8_t* px = &s_x[c][row * kViewPW + col];
-            const uint8_t* py = &s_y[c][row * kViewPW + col];
-            double ax = 0.0, ay = 0.0, axx = 0.0, axy = 0.0, ayy = 0.0;
-#pragma unroll
-            for (int t = 0; t < kViewTaps; ++t) {
-                const double xv = (double)px[t], yv = (double)py[t], wt = a.w[t];
-                ax = ax + wt * xv;
-                ay = ay + wt * yv;
-                axx = axx + wt * (xv * xv);
-                axy = axy + wt * (xv * yv);
-                ayy = ayy + wt * (yv * yv);
-            }
-            s_row[0][k] = ax; s_row[1][k] = ay; s_row[2][k] = axx; s_row[3][k] = axy; s_row[4][k] = ayy;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (!window[j]) continue;
-            const int k0 = (ty0 + j * (kViewTH / 2)) * kViewTW + tx;      // the window's first row of the row pass
-            double mx = 0.0, my = 0.0, exx = 0.0, exy = 0.0, eyy = 0.0;
-#pragma unroll
-            for (int t = 0; t < kViewTaps; ++t) {
-                const double wt = a.w[t];
-                mx = mx + wt * s_row[0][k0 + t * kViewTW];
-                my = my + wt * s_row[1][k0 + t * kViewTW];
-                exx = exx + wt * s_row[2][k0 + t * kViewTW];
-                exy = exy + wt * s_row[3][k0 + t * kViewTW];
-                eyy = eyy + wt * s_row[4][k0 + t * kViewTW];
-            }
-            const double vx = exx - mx * mx, vy = eyy - my * my, cxy = exy - mx * my;
-            const double num = (2.0 * mx * my + 6.5025) * (2.0 * cxy + 58.5225);
-            const double den = (mx * mx + my * my + 6.5025) * (vx + vy + 58.5225);
-            ssum[j] = ssum[j] + num / den;
-        }
-        __syncthreads();
-    }
-    // 4.
-    long long fix[2] = {0ll, 0ll};
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-        if (window[j]) fix[j] = llrint(ssum[j] / 3.0 * kViewFix);
-    if (grp[0] >= 0 && grp[0] == grp[1]) {
-#pragma unroll
-        for (int q = 0; q < kViewCounters - 1; ++q) cnt[0][q] += cnt[1][q];
-        fix[0] += fix[1];
-        grp[1] = -1;
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        if (grp[j] < 0) continue;
-        unsigned long long* to = s_cnt + grp[j] * kViewCounters;
-#pragma unroll
-        for (int q = 0; q < kViewCounters - 1; ++q)
-            if (cnt[j][q]) atomicAdd(&to[q], cnt[j][q]);
-        if (fix[j]) atomicAdd(&to[9], (unsigned long long)fix[j]);
-    }
-    __syncthreads();
-    unsigned long long* out = a.counts + (size_t)frame * a.n_groups * kViewCounters;
-    for (int k = tid; k < a.n_groups * kViewCounters; k += kViewThreads) {
-        const unsigned long long v = s_cnt[k];
-        if (v) atomicAdd(&out[k], v);
-    }
-}
-
-static int view_score(const uint8_t* d_render_rgba, const float* d_render_depth, const uint8_t* d_rgb, const float* d_depth, const uint8_t* d_group,
-                      int32_t n_frames, int32_t height, int32_t width, int32_t n_groups, float max_depth, float tau, uint64_t* d_counts, hipStream_t s) {
-    if (!d_render_rgba || !d_render_depth || !d_rgb || !d_depth || !d_counts) return MF_EINVAL;
-    if (width < 1 || height < 1 || n_frames < 1 || (int64_t)width * height > (int64_t)1 << 24) return MF_EINVAL;
-    if (n_groups < 1 || n_groups > kViewMaxGroups) return MF_EINVAL;
-    if (!(max_depth > 0.f) || !(tau >= 0.f) || !std::isfinite(tau)) return MF_EINVAL;
-    ViewArgs a;
-    memset(&a, 0, sizeof(a));
-    a.render = d_render_rgba; a.render_depth = d_render_depth; a.rgb = d_rgb; a.depth = d_depth; a.group = d_group;
-    a.counts = reinterpret_cast<unsigned long long*>(d_counts);
-    a.W = width; a.H = height; a.n_groups = n_groups; a.max_depth = max_depth; a.tau = tau;
-    a.tiles_x = (width + kViewTW - 1) / kViewTW;
-    a.tiles_y = (height + kViewTH - 1) / kViewTH;
-    double g[kViewTaps], sum = 0.0;
-    for (int k = 0; k < kViewTaps; ++k) {
-        g[k] = std::exp(-(double)((k - kViewHalo) * (k - kViewHalo)) / 4.5);
-        sum = sum + g[k];
-    }
-    for (int k = 0; k < kViewTaps; ++k) a.w[k] = g[k] / sum;
-    const int64_t blocks = (int64_t)n_frames * a.tiles_x * a.tiles_y;
-    if (blocks > 0x7FFFFFFF) return MF_EINVAL;
-    if (hipMemsetAsync(d_counts, 0, (size_t)n_frames * n_groups * kViewCounters * sizeof(uint64_t), s) != hipSuccess) return MF_EHIP;
-    hipLaunchKernelGGL(k_view_score, dim3((unsigned)blocks), dim3(kViewThreads), 0, s, a);
-    return hipGetLastError() == hipSuccess ? MF_OK : MF_EHIP;
-}
-
 }  // namespace mf
 
 using namespace mf;
 
 extern "C" int mf_cloud_nn_workspace(int64_t n_target, uint64_t* bytes) {
-    if (!bytes || n_target < 0 || n_target > (int64_t)1 << 30) return MF_EINVAL;
+    if (!bytes || !nn_count_ok(n_target)) return MF_EINVAL;
     *bytes = nn_workspace_bytes(n_target);
     return MF_OK;
 }
@@ -1356,13 +872,12 @@ extern "C" int mf_cloud_nn_workspace(int64_t n_target, uint64_t* bytes) {
 extern "C" int mf_cloud_nn_dev(const float* d_target, int32_t target_stride, int64_t n_target, const float* d_query, int32_t query_stride, int64_t n_query,
                                const float* query_to_target16, float radius, float* d_dist, int32_t* d_idx, void* d_workspace, uint64_t workspace_bytes,
                                void* stream) {
-    const char* why = nullptr;
     return nn_run(d_target, target_stride, n_target, d_query, query_stride, n_query, query_to_target16, radius, d_dist, d_idx, d_workspace,
-                  workspace_bytes, (hipStream_t)stream, &why);
+                  workspace_bytes, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int mf_cloud_icp_workspace(int64_t n_target, int64_t n_query, uint64_t* bytes) {
-    if (!bytes || n_target < 0 || n_target > (int64_t)1 << 30 || n_query < 0 || n_query > (int64_t)1 << 30) return MF_EINVAL;
+    if (!bytes || !nn_count_ok(n_target) || !nn_count_ok(n_query)) return MF_EINVAL;
     *bytes = icp_workspace_bytes(n_target, n_query);
     return MF_OK;
 }
@@ -1378,7 +893,7 @@ extern "C" int mf_cloud_icp_step_dev(void* d_workspace, uint64_t workspace_bytes
 }
 
 extern "C" int mf_cloud_normals_workspace(int64_t n, uint64_t* bytes) {
-    if (!bytes || n < 0 || n > (int64_t)1 << 30) return MF_EINVAL;
+    if (!bytes || !nn_count_ok(n)) return MF_EINVAL;
     *bytes = normals_workspace_bytes(n);
     return MF_OK;
 }
@@ -1389,7 +904,7 @@ extern "C" int mf_cloud_normals_dev(const float* d_points, int32_t stride, int64
 }
 
 extern "C" int mf_cloud_fpfh_workspace(int64_t n, uint64_t* bytes) {
-    if (!bytes || n < 0 || n > (int64_t)1 << 30) return MF_EINVAL;
+    if (!bytes || !nn_count_ok(n)) return MF_EINVAL;
     *bytes = fpfh_workspace_bytes(n);
     return MF_OK;
 }
@@ -1402,22 +917,4 @@ extern "C" int mf_cloud_fpfh_dev(const float* d_points, int32_t stride, int32_t 
 extern "C" int mf_feature_match_dev(const float* d_target, int64_t n_target, const float* d_query, int64_t n_query, int32_t dim, int32_t* d_idx,
                                     float* d_d2, void* stream) {
     return feature_match(d_target, n_target, d_query, n_query, dim, d_idx, d_d2, (hipStream_t)stream);
-}
-
-extern "C" int mf_label_confusion_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_frames, int32_t height, int32_t width,
-                                      const uint8_t* lut_est, int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, uint32_t* d_counts, void* stream) {
-    return label_confusion(d_est, d_gt, n_frames, height, width, lut_est, n_est, lut_gt, n_gt, d_counts, (hipStream_t)stream);
-}
-
-extern "C" int mf_label_boundary_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_frames, int32_t height, int32_t width,
-                                     const uint8_t* lut_est, int32_t n_est, const uint8_t* lut_gt, int32_t n_gt, const uint8_t* pair, int32_t radius,
-                                     uint32_t* d_out, void* stream) {
-    return label_boundary(d_est, d_gt, n_frames, height, width, lut_est, n_est, lut_gt, n_gt, pair, radius, d_out, (hipStream_t)stream);
-}
-
-extern "C" int mf_view_score_dev(const uint8_t* d_render_rgba, const float* d_render_depth, const uint8_t* d_rgb, const float* d_depth,
-                                 const uint8_t* d_group, int32_t n_frames, int32_t height, int32_t width, int32_t n_groups, float max_depth, float tau,
-                                 uint64_t* d_counts, void* stream) {
-    return view_score(d_render_rgba, d_render_depth, d_rgb, d_depth, d_group, n_frames, height, width, n_groups, max_depth, tau, d_counts,
-                      (hipStream_t)stream);
 }

@@ -236,17 +236,41 @@ def read_ply(path: str, normals: bool = False):
     raise ValueError(f"{path}: format {fmt} is not supported")
 
 
-def _device_points(a):
-    """(tensor on the library's device, stride in floats)"""
+def _device_points(a, min_cols: int = 3, what: str = "points must be (n, >= 3) float32"):
+    """(n, >= min_cols) float32 as a contiguous tensor on the library's device"""
     import torch
     from .lib import torch_device
-    if isinstance(a, torch.Tensor):
-        t = a
-    else:
-        t = torch.as_tensor(np.ascontiguousarray(np.asarray(a, np.float32)))
-    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < 3:
-        raise ValueError("points must be (n, >= 3) float32")
+    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(a, np.float32)))
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < min_cols:
+        raise ValueError(what)
     return t.to(torch_device()).contiguous()
+
+
+def _stream_of(device):
+    """the handle of torch's current stream on `device` as the library takes it: None off the GPU"""
+    import torch
+    return torch.cuda.current_stream().cuda_stream if device.type == "cuda" else None
+
+
+def _pack_T(T):
+    """a 4 x 4 transform as the 16 column-major floats the library takes, or None"""
+    return None if T is None else np.ascontiguousarray(np.asarray(T, np.float32).T.reshape(16))
+
+
+def _workspace(L, name: str, device, *counts):
+    """(uint8 tensor on `device`, its size in bytes): what the library's function `name` asks for `counts` points"""
+    import torch
+    from .lib import MFError
+    need = C.c_uint64(0)
+    if getattr(L, name)(*counts, C.byref(need)) != 0:
+        raise MFError(f"{name} failed")
+    return torch.empty(int(need.value), dtype=torch.uint8, device=device), int(need.value)
+
+
+def _check(rc: int, name: str, hint: str):
+    from .lib import MFError
+    if rc != 0:
+        raise MFError(f"{name} failed with code {rc} ({hint})")
 
 
 def nearest(target, query, radius: float, T=None):
@@ -254,23 +278,18 @@ def nearest(target, query, radius: float, T=None):
     float32 numpy arrays or device tensors (x, y, z first); T: 4 x 4 applied to the queries first.  Returns numpy (dist float32, +inf: none
     in range; idx int32, -1: none)."""
     import torch
-    from .lib import load, MFError
+    from .lib import load
     L = load()
     t, q = _device_points(target), _device_points(query)
     nt, nq = int(t.shape[0]), int(q.shape[0])
-    need = C.c_uint64(0)
-    if L.mf_cloud_nn_workspace(nt, C.byref(need)) != 0:
-        raise MFError("mf_cloud_nn_workspace failed")
-    ws = torch.empty(int(need.value), dtype=torch.uint8, device=q.device)
+    ws, need = _workspace(L, "mf_cloud_nn_workspace", q.device, nt)
     dist = torch.empty(max(nq, 1), dtype=torch.float32, device=q.device)
     idx = torch.empty(max(nq, 1), dtype=torch.int32, device=q.device)
-    T16 = None if T is None else np.ascontiguousarray(np.asarray(T, np.float32).T.reshape(16))
-    stream = torch.cuda.current_stream().cuda_stream if q.device.type == "cuda" else None
+    T16 = _pack_T(T)
     rc = L.mf_cloud_nn_dev(t.data_ptr() if nt else None, int(t.shape[1]), nt, q.data_ptr() if nq else None, int(q.shape[1]), nq,
                            T16.ctypes.data if T16 is not None else None, float(radius), dist.data_ptr(), idx.data_ptr(), ws.data_ptr(),
-                           int(need.value), stream)
-    if rc != 0:
-        raise MFError(f"mf_cloud_nn_dev failed with code {rc} (radius must be finite and > 0, coordinates |x / radius| < 2^30)")
+                           need, _stream_of(q.device))
+    _check(rc, "mf_cloud_nn_dev", "radius must be finite and > 0, coordinates |x / radius| < 2^30")
     return dist[:nq].cpu().numpy(), idx[:nq].cpu().numpy()
 
 
@@ -320,7 +339,7 @@ class Registration:
 
     def __init__(self, ref, radius: float, normals=None, n_query: int = 0):
         import torch
-        from .lib import load, MFError
+        from .lib import load
         self._L = load()
         t = _device_points(ref)
         if normals is None:
@@ -334,19 +353,13 @@ class Registration:
             t, off = torch.cat([t[:, :3], nr[:, :3]], 1).contiguous(), 3
         self.target, self.plane, self.radius = t, off >= 0, float(radius)
         self.n_query = int(n_query)
-        need = C.c_uint64(0)
-        if self._L.mf_cloud_icp_workspace(int(t.shape[0]), self.n_query, C.byref(need)) != 0:
-            raise MFError("mf_cloud_icp_workspace failed")
-        self._need = int(need.value)
-        self._ws = torch.empty(self._need, dtype=torch.uint8, device=t.device)
-        self._out = torch.zeros(29, dtype=torch.float64, device=t.device)
-        self._stream = (lambda: torch.cuda.current_stream().cuda_stream) if t.device.type == "cuda" else (lambda: None)
         nt = int(t.shape[0])
+        self._ws, self._need = _workspace(self._L, "mf_cloud_icp_workspace", t.device, nt, self.n_query)
+        self._out = torch.zeros(29, dtype=torch.float64, device=t.device)
+        self._stream = lambda: _stream_of(t.device)
         rc = self._L.mf_cloud_icp_build_dev(t.data_ptr() if nt else None, int(t.shape[1]), off, nt, self.radius, self._ws.data_ptr(), self._need,
                                             self._stream())
-        if rc != 0:
-            raise MFError(f"mf_cloud_icp_build_dev failed with code {rc} (radius must be finite and > 0, coordinates |x / radius| < 2^30, "
-                          "normals inside the record)")
+        _check(rc, "mf_cloud_icp_build_dev", "radius must be finite and > 0, coordinates |x / radius| < 2^30, normals inside the record")
 
     def step(self, query, T=None) -> np.ndarray:
         """sys29 (float64 [29], see unpack_sys29) of `query` (device tensor or array, at most n_query points) mapped by T (4 x 4 or None)"""
@@ -355,12 +368,10 @@ class Registration:
         nq = int(q.shape[0])
         if nq > self.n_query:
             raise MFError(f"{nq} queries, but the workspace was sized for {self.n_query}")
-        T16 = None if T is None else np.ascontiguousarray(np.asarray(T, np.float32).T.reshape(16))
+        T16 = _pack_T(T)
         rc = self._L.mf_cloud_icp_step_dev(self._ws.data_ptr(), self._need, q.data_ptr() if nq else None, int(q.shape[1]), nq,
                                            T16.ctypes.data if T16 is not None else None, self._out.data_ptr(), self._stream())
-        if rc != 0:
-            raise MFError(f"mf_cloud_icp_step_dev failed with code {rc} (finite transform, at most {self.n_query} queries, "
-                          "coordinates |x / radius| < 2^30)")
+        _check(rc, "mf_cloud_icp_step_dev", f"finite transform, at most {self.n_query} queries, coordinates |x / radius| < 2^30")
         return self._out.cpu().numpy().copy()
 
 
@@ -517,23 +528,17 @@ def estimate_normals(points, radius: float, min_neighbours: int = 5, viewpoint=N
     number of neighbours within `radius`, the point itself included.  A row is NaN (its count still true) where the point is not finite, has
     fewer than min_neighbours (>= 3) neighbours, or its neighbours lie on a line or in one place."""
     import torch
-    from .lib import load, MFError
+    from .lib import load
     L = load()
     p = _device_points(points)
     n = int(p.shape[0])
-    need = C.c_uint64(0)
-    if L.mf_cloud_normals_workspace(n, C.byref(need)) != 0:
-        raise MFError("mf_cloud_normals_workspace failed")
-    ws = torch.empty(int(need.value), dtype=torch.uint8, device=p.device)
+    ws, need = _workspace(L, "mf_cloud_normals_workspace", p.device, n)
     out = torch.empty((max(n, 1), 4), dtype=torch.float32, device=p.device)
     cnt = torch.empty(max(n, 1), dtype=torch.int32, device=p.device)
     v = None if viewpoint is None else np.ascontiguousarray(np.asarray(viewpoint, np.float32).reshape(3))
-    stream = torch.cuda.current_stream().cuda_stream if p.device.type == "cuda" else None
     rc = L.mf_cloud_normals_dev(p.data_ptr() if n else None, int(p.shape[1]), n, float(radius), int(min_neighbours),
-                                v.ctypes.data if v is not None else None, out.data_ptr(), cnt.data_ptr(), ws.data_ptr(), int(need.value), stream)
-    if rc != 0:
-        raise MFError(f"mf_cloud_normals_dev failed with code {rc} (radius must be finite and > 0, min_neighbours >= 3, a finite viewpoint, "
-                      "coordinates |x / radius| < 2^30)")
+                                v.ctypes.data if v is not None else None, out.data_ptr(), cnt.data_ptr(), ws.data_ptr(), need, _stream_of(p.device))
+    _check(rc, "mf_cloud_normals_dev", "radius must be finite and > 0, min_neighbours >= 3, a finite viewpoint, coordinates |x / radius| < 2^30")
     o = out[:n].cpu().numpy()
     return np.ascontiguousarray(o[:, :3]), np.ascontiguousarray(o[:, 3]), cnt[:n].cpu().numpy()
 
@@ -594,24 +599,19 @@ def fpfh(points, normals, radius: float):
     pair histogram and k, the number of counted pairs).  A row of fpfh is NaN where the point or its normal is not finite, the normal is
     zero, or no neighbour within `radius` has a counted pair."""
     import torch
-    from .lib import load, MFError
+    from .lib import load
     L = load()
     p, nr_ = _device_points(points), _device_points(normals)
     if nr_.shape[0] != p.shape[0]:
         raise ValueError("normals must have one row per point")
     rec = torch.cat([p[:, :3], nr_[:, :3]], 1).contiguous()
     n = int(rec.shape[0])
-    need = C.c_uint64(0)
-    if L.mf_cloud_fpfh_workspace(n, C.byref(need)) != 0:
-        raise MFError("mf_cloud_fpfh_workspace failed")
-    ws = torch.empty(int(need.value), dtype=torch.uint8, device=rec.device)
+    ws, need = _workspace(L, "mf_cloud_fpfh_workspace", rec.device, n)
     out = torch.empty((max(n, 1), FPFH_DIM), dtype=torch.float32, device=rec.device)
     cnt = torch.empty((max(n, 1), FPFH_DIM + 1), dtype=torch.int32, device=rec.device)
-    stream = torch.cuda.current_stream().cuda_stream if rec.device.type == "cuda" else None
-    rc = L.mf_cloud_fpfh_dev(rec.data_ptr() if n else None, 6, 3, n, float(radius), out.data_ptr(), cnt.data_ptr(), ws.data_ptr(),
-                             int(need.value), stream)
-    if rc != 0:
-        raise MFError(f"mf_cloud_fpfh_dev failed with code {rc} (radius must be finite and > 0, coordinates |x / radius| < 2^30)")
+    rc = L.mf_cloud_fpfh_dev(rec.data_ptr() if n else None, 6, 3, n, float(radius), out.data_ptr(), cnt.data_ptr(), ws.data_ptr(), need,
+                             _stream_of(rec.device))
+    _check(rc, "mf_cloud_fpfh_dev", "radius must be finite and > 0, coordinates |x / radius| < 2^30")
     return out[:n].cpu().numpy(), cnt[:n].cpu().numpy()
 
 
@@ -620,25 +620,17 @@ def match_features(target, query):
     or device tensors.  Returns numpy (idx int32, -1: none; d2 float32, the squared distance, +inf: none).  Ties go to the smallest index;
     a row with a NaN matches nothing and is nobody's match."""
     import torch
-    from .lib import load, MFError, torch_device
+    from .lib import load
     L = load()
-
-    def dev(a):
-        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(a, np.float32)))
-        if t.dtype != torch.float32 or t.dim() != 2:
-            raise ValueError("descriptors must be (n, dim) float32")
-        return t.to(torch_device()).contiguous()
-    t, q = dev(target), dev(query)
+    t, q = (_device_points(a, 0, "descriptors must be (n, dim) float32") for a in (target, query))
     if t.shape[1] != q.shape[1]:
         raise ValueError(f"target descriptors have {t.shape[1]} values, query descriptors {q.shape[1]}")
     nt, nq = int(t.shape[0]), int(q.shape[0])
     idx = torch.empty(max(nq, 1), dtype=torch.int32, device=q.device)
     d2 = torch.empty(max(nq, 1), dtype=torch.float32, device=q.device)
-    stream = torch.cuda.current_stream().cuda_stream if q.device.type == "cuda" else None
     rc = L.mf_feature_match_dev(t.data_ptr() if nt else None, nt, q.data_ptr() if nq else None, nq, int(q.shape[1]), idx.data_ptr(),
-                                d2.data_ptr(), stream)
-    if rc != 0:
-        raise MFError(f"mf_feature_match_dev failed with code {rc} (1 to 64 values per descriptor)")
+                                d2.data_ptr(), _stream_of(q.device))
+    _check(rc, "mf_feature_match_dev", "1 to 64 values per descriptor")
     return idx[:nq].cpu().numpy(), d2[:nq].cpu().numpy()
 
 
@@ -815,27 +807,23 @@ def _lut_arg(lut, n):
 
 
 def _label_call(est, gt, lut_est, lut_gt, n_est, n_gt):
-    import torch
     from .lib import load
     e, g = _device_labels(est), _device_labels(gt)
     if e.shape != g.shape:
         raise ValueError(f"estimate {tuple(e.shape)} and ground truth {tuple(g.shape)} differ in shape")
     le, n_est = _lut_arg(lut_est, n_est)
     lg, n_gt = _lut_arg(lut_gt, n_gt)
-    stream = torch.cuda.current_stream().cuda_stream if e.device.type == "cuda" else None
-    return load(), e, g, le, n_est, lg, n_gt, stream
+    return load(), e, g, le, n_est, lg, n_gt, _stream_of(e.device)
 
 
 def label_confusion_dev(est, gt, lut_est, lut_gt, n_est=None, n_gt=None):
     """label_confusion() with the result left on the device: an int32 tensor (n_frames, n_gt, n_est) holding the uint32 counts"""
     import torch
-    from .lib import MFError
     L, e, g, le, n_est, lg, n_gt, stream = _label_call(est, gt, lut_est, lut_gt, n_est, n_gt)
     out = torch.empty((e.shape[0], n_gt, n_est), dtype=torch.int32, device=e.device)
     rc = L.mf_label_confusion_dev(e.data_ptr(), g.data_ptr(), int(e.shape[0]), int(e.shape[1]), int(e.shape[2]), le.ctypes.data, n_est,
                                   lg.ctypes.data, n_gt, out.data_ptr(), stream)
-    if rc != 0:
-        raise MFError(f"mf_label_confusion_dev failed with code {rc} (1..64 classes per side; table entries below the class count, or 255)")
+    _check(rc, "mf_label_confusion_dev", "1..64 classes per side; table entries below the class count, or 255")
     return out
 
 
@@ -851,7 +839,6 @@ def label_boundary(est, gt, lut_est, lut_gt, pair, radius: int, n_est=None, n_gt
     ground-truth class, the estimate class matched to it or 255; its length is n_gt unless n_gt is given.  radius: 0..16 pixels.
     Returns uint32 (n_frames, n_gt, 4) = n_est_boundary, est_hit, n_gt_boundary, gt_hit."""
     import torch
-    from .lib import MFError
     pr = np.ascontiguousarray(np.asarray(pair, np.uint8).reshape(-1))
     L, e, g, le, n_est, lg, n_gt, stream = _label_call(est, gt, lut_est, lut_gt, n_est, len(pr) if n_gt is None else n_gt)
     if len(pr) != n_gt:
@@ -859,9 +846,7 @@ def label_boundary(est, gt, lut_est, lut_gt, pair, radius: int, n_est=None, n_gt
     out = torch.empty((e.shape[0], n_gt, 4), dtype=torch.int32, device=e.device)
     rc = L.mf_label_boundary_dev(e.data_ptr(), g.data_ptr(), int(e.shape[0]), int(e.shape[1]), int(e.shape[2]), le.ctypes.data, n_est,
                                  lg.ctypes.data, n_gt, pr.ctypes.data, int(radius), out.data_ptr(), stream)
-    if rc != 0:
-        raise MFError(f"mf_label_boundary_dev failed with code {rc} (1..64 classes per side; table and pair entries below the class count, "
-                      "or 255; radius 0..16)")
+    _check(rc, "mf_label_boundary_dev", "1..64 classes per side; table and pair entries below the class count, or 255; radius 0..16")
     return out.cpu().numpy().view(np.uint32)
 
 
@@ -1127,7 +1112,7 @@ def _device_frames(a, dtype, channels, what):
 def _view_call(r, rd, c, d, g, n_groups, max_depth, tau, stream):
     """mf_view_score_dev on device tensors that are already in shape -> the counters as an int64 tensor (n_frames, n_groups, 10)"""
     import torch
-    from .lib import MFError, load
+    from .lib import load
     shape = tuple(rd.shape)
     if tuple(r.shape) != shape + (4,) or tuple(c.shape) != shape + (3,) or tuple(d.shape) != shape or (g is not None and tuple(g.shape) != shape):
         raise ValueError(f"render {tuple(r.shape)} / {tuple(rd.shape)}, frame {tuple(c.shape)} / {tuple(d.shape)}"
@@ -1136,8 +1121,7 @@ def _view_call(r, rd, c, d, g, n_groups, max_depth, tau, stream):
     md = min(float(max_depth), _FLT_MAX)          # "no limit" is FLT_MAX
     rc = load().mf_view_score_dev(r.data_ptr(), rd.data_ptr(), c.data_ptr(), d.data_ptr(), g.data_ptr() if g is not None else None, shape[0], shape[1],
                                   shape[2], int(n_groups), md, float(tau), out.data_ptr(), stream)
-    if rc != 0:
-        raise MFError(f"mf_view_score_dev failed with code {rc} (1..64 groups, at most 2^24 pixels per frame, max_depth > 0, tau >= 0 and finite)")
+    _check(rc, "mf_view_score_dev", "1..64 groups, at most 2^24 pixels per frame, max_depth > 0, tau >= 0 and finite")
     return out
 
 
@@ -1147,12 +1131,10 @@ def view_counts(render_rgba, render_depth, rgb, depth, group=None, n_groups=1, m
     uint8 (n_frames, H, W, 3), depth float32 in metres.  group: uint8 per pixel, the group the pixel is counted in (None: all in group 0;
     a value >= n_groups: nowhere).  Inputs are numpy arrays or device tensors; a single image is one frame.
     Returns uint64 (n_frames, n_groups, 10); counter 9 is a two's-complement int64."""
-    import torch
     r, rd = _device_frames(render_rgba, np.uint8, 4, "render_rgba"), _device_frames(render_depth, np.float32, 0, "render_depth")
     c, d = _device_frames(rgb, np.uint8, 3, "rgb"), _device_frames(depth, np.float32, 0, "depth")
     g = None if group is None else _device_frames(group, np.uint8, 0, "group")
-    stream = torch.cuda.current_stream().cuda_stream if rd.device.type == "cuda" else None
-    return _view_call(r, rd, c, d, g, n_groups, max_depth, tau, stream).cpu().numpy().view(np.uint64)
+    return _view_call(r, rd, c, d, g, n_groups, max_depth, tau, _stream_of(rd.device)).cpu().numpy().view(np.uint64)
 
 
 def _view_scores(c) -> dict:
@@ -1234,12 +1216,10 @@ class ViewScorer:
 
     def add(self, render_rgba, render_depth, rgb, depth, group=None):
         """one frame or a batch of the five images, numpy arrays or device tensors (view_counts' arguments; group values 0..63, others void)"""
-        import torch
         r, rd = _device_frames(render_rgba, np.uint8, 4, "render_rgba"), _device_frames(render_depth, np.float32, 0, "render_depth")
         c, d = _device_frames(rgb, np.uint8, 3, "rgb"), _device_frames(depth, np.float32, 0, "depth")
         g = None if group is None else _device_frames(group, np.uint8, 0, "group")
-        stream = torch.cuda.current_stream().cuda_stream if rd.device.type == "cuda" else None
-        self._counts.append(_view_call(r, rd, c, d, g, VIEW_GROUPS, self.max_depth, self.tau, stream))
+        self._counts.append(_view_call(r, rd, c, d, g, VIEW_GROUPS, self.max_depth, self.tau, _stream_of(rd.device)))
 
     def _groups_for(self, ids):
         """the group of every model list index, shifted by one: entry 0 is "no model" """

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU = os.environ.get("MF_EMU") == "1"
-TILE_W, TILE_H = 64, 32          # the boundary kernel's tile (kBndTW x kBndTH in csrc/mf_eval.hip); its halo is radius + 1
+TILE_W, TILE_H = 64, 32          # the boundary kernel's tile (kBndTW x kBndTH in csrc/mf_eval_image.hip); its halo is radius + 1
 RADII = (0, 1, 6, 16)
 
 

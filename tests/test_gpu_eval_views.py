@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU = os.environ.get("MF_EMU") == "1"
-TILE_W, TILE_H = 32, 16          # the kernel's tile (kViewTW x kViewTH in csrc/mf_eval.hip); its halo is 5
+TILE_W, TILE_H = 32, 16          # the kernel's tile (kViewTW x kViewTH in csrc/mf_eval_image.hip); its halo is 5
 # exactly one SSIM pixel; none at all; odd sizes with no frame start aligned; windows across tile borders and partial last tiles
 SHAPES = [(1, 11, 11), (1, 10, 40), (2, 23, 37), (1, 2 * TILE_H + 5, 2 * TILE_W + 6)]
 MAX_DEPTH = 4.0
