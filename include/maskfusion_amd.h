@@ -329,6 +329,34 @@ int mf_label_boundary_dev(const uint8_t* d_est, const uint8_t* d_gt, int32_t n_f
 int mf_view_score_dev(const uint8_t* d_render_rgba, const float* d_render_depth, const uint8_t* d_rgb, const float* d_depth,
                       const uint8_t* d_group, int32_t n_frames, int32_t height, int32_t width, int32_t n_groups, float max_depth, float tau,
                       uint64_t* d_counts, void* stream);
+/* Cloud visibility on the GPU (kernel: mf_eval_visibility.hip; DESIGN.md "Cloud visibility"; what is built on it: maskfusion_amd.eval.Visibility,
+ * observed): every point of a cloud classified against every depth frame of a sequence, so that a reference model can be culled to what the
+ * sensor observed before completeness is taken over it.  Points are read as x, y, z at d_points + i * stride floats (3: xyz, 4: float4, 12:
+ * mf_download_map's records).  d_depth (DEVICE, float [n_frames][height][width], metres) are the frames, d_cam_from_cloud (DEVICE, float
+ * [n_frames][12]) the rows of each frame's 3 x 4 M, row-major, from the cloud's frame into the camera's.  The call follows the label and view
+ * calls: it needs no context, validates the host arguments, enqueues one kernel on `stream` and returns without waiting; it reads the points,
+ * the frames and the poses and writes only the two outputs.
+ * Per point (x, y, z) and frame, in fp32 with every operation rounded on its own, in this order:
+ *   xc = ((M00 x + M01 y) + M02 z) + M03, and yc, zc likewise from rows 1 and 2;
+ *   IN FRONT: zc > near_z and zc <= far_z;
+ *   u = fx * (xc / zc) + cx, v = fy * (yc / zc) + cy, col = floorf(u + 0.5f), row = floorf(v + 0.5f): the pixel centre is the integer coordinate;
+ *   IN FRUSTUM: in front, 0 <= col < width and 0 <= row < height, compared as floats before any conversion: a NaN or an infinite coordinate
+ *     fails every test, and a point that is not finite is in no frustum;
+ *   d = depth[frame][row][col], VALID when it is finite and > 0; tol = tol_abs + tol_rel * d, dz = zc - d;
+ *   an in-frustum point with a valid sample gets exactly one class: ON SURFACE |dz| <= tol; SEEN THROUGH dz < -tol (the sensor measured
+ *     something farther along that pixel); OCCLUDED dz > tol.  An in-frustum point whose sample is not valid is a hole and gets no class.
+ * d_counts (DEVICE, uint32 [n][4]) = {frames in frustum, on surface, seen through, occluded}; d_first (DEVICE, int32 [n]) = the smallest
+ * frame_base + f with ON SURFACE, or -1.  accumulate == 0: both are overwritten (no zeroed buffer is needed).  accumulate != 0: the counts are
+ * added to what is there, and d_first keeps a value >= 0 and is otherwise set: a sequence of any length can be streamed through in chunks of
+ * frames with a running frame_base, and the result is the one call's.  All outputs are integers: the result is exact, independent of the
+ * order of execution and the same for every call.  n == 0: MF_OK, nothing enqueued.  MF_EINVAL, with nothing enqueued and nothing written,
+ * for a null pointer with n > 0, stride < 3, n < 0 or n > 2^30, n_frames, width or height < 1, width * height > 2^24, fx or fy not finite or
+ * zero, cx or cy not finite, near_z not finite or <= 0, far_z <= near_z or NaN (FLT_MAX and +inf mean no limit), tol_abs or tol_rel negative or
+ * not finite, frame_base < 0. */
+int mf_cloud_visibility_dev(const float* d_points, int32_t stride, int64_t n, const float* d_depth, const float* d_cam_from_cloud,
+                            int32_t n_frames, int32_t height, int32_t width, float fx, float fy, float cx, float cy, float near_z, float far_z,
+                            float tol_abs, float tol_rel, int32_t frame_base, int32_t accumulate, uint32_t* d_counts /* [n][4] */,
+                            int32_t* d_first /* [n] */, void* stream);
 /* whether the last tracking step used the fill-in maps (MaskFusion::requiresFillIn, MaskFusion.cpp:630-648) */
 int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
 

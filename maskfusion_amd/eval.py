@@ -13,11 +13,16 @@ seeded RANSAC over the matches in numpy, then register().
                                   [--register [--register-radius R0,R1,...] [--register-iterations N] [--point-to-point]]
                                   [--register-global[=VOXEL]] [--ref-cloud FILE [--init FILE]] [--estimate-normals[=R]] [--normals]
                                   [--seg-gt DIR [--seg-gt-prefix Mask] [--seg-index-width 4] [--seg-radius R] [--seg-void V]]
+                                  [--observed-from SEQ [--observed-poses FILE] [--observed-cal FILE] [--observed-tol A[,R]]
+                                   [--observed-rule seen|surface] [--observed-min-frames K] [--observed-stride S] [--observed-max-depth D]
+                                   [--observed-time-scale S]]
 
 prints one JSON object per model on stdout (INTEGRATION.md "Evaluating a run"); with --seg-gt, one per ground-truth object of the
 segmentation and a summary (region similarity J and boundary accuracy F of the -es label images, counted on the GPU:
 mf_label_confusion_dev / mf_label_boundary_dev).  ViewScorer scores what needs nothing from outside the run: the map's render from the
 sensor's own view against the frame it just saw (mf_view_score_dev; the driver's -evalviews flag writes its result as views.json).
+With --observed-from, completeness and F-score are also reported over the part of the reference the sequence observed: every reference point
+is classified against every depth frame on the GPU (mf_cloud_visibility_dev; Visibility, observed, observe_sequence).
 """
 from __future__ import annotations
 
@@ -314,12 +319,24 @@ def transform_f32(T, pts) -> np.ndarray:
     return np.stack([T[r, 0] * x + T[r, 1] * y + T[r, 2] * z + T[r, 3] for r in range(3)], 1)
 
 
-def compare_clouds(est, ref, radius: float = 0.05, taus=(0.01, 0.02, 0.05), T=None) -> dict:
+def compare_clouds(est, ref, radius: float = 0.05, taus=(0.01, 0.02, 0.05), T=None, ref_keep=None) -> dict:
     """accuracy = est -> ref distances, completeness = ref -> est, and F-score(tau) = 2 P R / (P + R) with P, R their fractions <= tau.
-    T (4 x 4, est -> ref; e.g. register()'s): est is moved by it first (transform_f32), for both directions."""
+    T (4 x 4, est -> ref; e.g. register()'s): est is moved by it first (transform_f32), for both directions.
+    ref_keep (bool per reference point, e.g. observed()'s; None: all): completeness is taken over ref[ref_keep] only -- the part of the
+    reference the sensor observed.  Accuracy is still measured against the whole reference: an estimate point that lies on reference surface
+    the mask leaves out is not an error."""
     if T is not None:
         est = transform_f32(T, est.cpu().numpy() if hasattr(est, "cpu") else est)
     acc = cloud_stats(nearest(ref, est, radius)[0], radius, taus)
+    if ref_keep is not None:
+        keep = np.asarray(ref_keep)
+        if keep.dtype != np.bool_ or keep.shape != (len(ref),):
+            raise ValueError("ref_keep must be one bool per reference point")
+        if hasattr(ref, "cpu"):
+            import torch
+            ref = ref[torch.as_tensor(keep).to(ref.device)]
+        else:
+            ref = np.asarray(ref)[keep]
     comp = cloud_stats(nearest(est, ref, radius)[0], radius, taus)
     f = {}
     for t in taus:
@@ -1286,6 +1303,161 @@ class ViewScorer:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
+# cloud visibility: which part of a reference the sequence observed
+# ------------------------------------------------------------------------------------------------------------------------------------
+VISIBILITY_CHUNK = 16     # frames per call of observe_sequence: 20 MB of depth at 640 x 480, never the whole stack
+OBSERVED_NEAR = 0.01      # the near plane of the command's frusta (m); what a sensor cannot measure is a hole in its depth already
+
+
+def cam_from_cloud(cam_to_world, cloud_to_world=None) -> np.ndarray:
+    """The (n_frames, 12) float32 array mf_cloud_visibility_dev takes -- the rows of every frame's 3 x 4 from the cloud's frame into the
+    camera's -- from 4 x 4 camera -> world poses (one, or a stack) and, when the cloud is not in the world frame, its own frame -> world.
+    Inverse and product in fp64, rounded once at the end."""
+    T = np.asarray(cam_to_world, np.float64).reshape(-1, 4, 4)
+    M = np.linalg.inv(T)
+    if cloud_to_world is not None:
+        M = M @ np.asarray(cloud_to_world, np.float64).reshape(4, 4)
+    return np.ascontiguousarray(M[:, :3, :].reshape(-1, 12).astype(np.float32))
+
+
+class Visibility:
+    """Classifies the points of one cloud against the depth frames of a sequence, chunk of frames by chunk, on the device
+    (mf_cloud_visibility_dev; the rule: include/maskfusion_amd.h).  points: (n, >= 3) float32 numpy or a device tensor, x y z first;
+    fx, fy, cx, cy: the frames' intrinsics; near, far: the frustum's depth range (far inf: no limit); a point is ON SURFACE in a frame when
+    its camera z is within tol_abs + tol_rel * d of the depth d measured at its pixel.  add() uploads a chunk and enqueues; nothing is
+    downloaded before result()."""
+
+    def __init__(self, points, fx: float, fy: float, cx: float, cy: float, near: float = OBSERVED_NEAR, far: float = math.inf,
+                 tol_abs: float = 0.05, tol_rel: float = 0.0):
+        import torch
+        self._p = _device_points(points)
+        self.intrinsics = (float(fx), float(fy), float(cx), float(cy))
+        self.near, self.far, self.tol_abs, self.tol_rel = float(near), float(far), float(tol_abs), float(tol_rel)
+        n = int(self._p.shape[0])
+        self._counts = torch.empty((max(n, 1), 4), dtype=torch.int32, device=self._p.device)      # uint32 on the device
+        self._first = torch.empty(max(n, 1), dtype=torch.int32, device=self._p.device)
+        self.frames = 0
+        self.shape = None
+
+    def add(self, depth_frames, cam_from_cloud):
+        """one chunk: depth float32 (n_frames, H, W) in metres (a single image is one frame) and cam_from_cloud()'s (n_frames, 12)"""
+        import torch
+        from .lib import load
+        d = _device_frames(depth_frames, np.float32, 0, "depth_frames")
+        m = cam_from_cloud if isinstance(cam_from_cloud, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(cam_from_cloud, np.float32)))
+        if m.dtype != torch.float32 or m.numel() != 12 * int(d.shape[0]):
+            raise ValueError(f"{int(d.shape[0])} frames need a float32 cam_from_cloud of shape ({int(d.shape[0])}, 12)")
+        if self.shape is not None and tuple(d.shape[1:]) != self.shape:
+            raise ValueError(f"frames of {tuple(d.shape[1:])} after frames of {self.shape}")
+        m = m.to(d.device).contiguous()
+        n = int(self._p.shape[0])
+        fx, fy, cx, cy = self.intrinsics
+        rc = load().mf_cloud_visibility_dev(self._p.data_ptr() if n else None, int(self._p.shape[1]), n, d.data_ptr(), m.data_ptr(), int(d.shape[0]),
+                                            int(d.shape[1]), int(d.shape[2]), fx, fy, cx, cy, self.near, min(self.far, _FLT_MAX), self.tol_abs,
+                                            self.tol_rel, self.frames, int(self.frames > 0), self._counts.data_ptr(), self._first.data_ptr(),
+                                            _stream_of(d.device))
+        _check(rc, "mf_cloud_visibility_dev", "at most 2^30 points and 2^24 pixels per frame, fx and fy finite and not 0, 0 < near < far, "
+               "tolerances >= 0 and finite")
+        self.shape = tuple(d.shape[1:])
+        self.frames += int(d.shape[0])
+
+    def result(self):
+        """(counts uint32 (n, 4) = {frames in frustum, on surface, seen through, occluded}, first int32 (n,) = the first frame, counted over all
+        add() calls, in which the point was on the surface, or -1) as numpy; waits for the device"""
+        n = int(self._p.shape[0])
+        if self.frames == 0 or n == 0:
+            return np.zeros((n, 4), np.uint32), np.full(n, -1, np.int32)
+        return self._counts[:n].cpu().numpy().view(np.uint32), self._first[:n].cpu().numpy()
+
+
+def observed(counts, rule: str = "seen", min_frames: int = 1) -> np.ndarray:
+    """bool per point from Visibility's counts: did the sequence observe the point?
+      "seen": on surface + seen through >= min_frames -- the sensor's ray reached the point's depth, whether it found the point there or
+              measured something farther;
+      "surface": on surface >= min_frames."""
+    c = np.asarray(counts).astype(np.int64)
+    if c.ndim != 2 or c.shape[1] != 4:
+        raise ValueError("counts must have the shape (n, 4)")
+    if int(min_frames) < 1:
+        raise ValueError("min_frames must be at least 1")
+    if rule == "seen":
+        k = c[:, 1] + c[:, 2]
+    elif rule == "surface":
+        k = c[:, 1]
+    else:
+        raise ValueError(f"rule {rule!r}: 'seen' or 'surface'")
+    return k >= int(min_frames)
+
+
+def visibility_summary(counts, keep, frames=None) -> dict:
+    """What became of the points, from Visibility's counts and observed()'s mask: {"frames" (as given), "points", "never_in_frustum",
+    "only_holes" (in a frustum, never with a valid depth sample), "occluded_only" (classified, and occluded every time), "reached" (on surface
+    or seen through at least once), "on_surface", "seen_through" (each at least once; a point can be both), "kept"}.  The first four counts
+    after "points" partition the points."""
+    c = np.asarray(counts).astype(np.int64)
+    keep = np.asarray(keep)
+    if c.ndim != 2 or c.shape[1] != 4 or keep.shape != (len(c),):
+        raise ValueError("counts must have the shape (n, 4) and keep one entry per point")
+    classified = c[:, 1] + c[:, 2] + c[:, 3]
+    reached = (c[:, 1] + c[:, 2]) > 0
+    return {"frames": None if frames is None else int(frames), "points": int(len(c)),
+            "never_in_frustum": int(np.count_nonzero(c[:, 0] == 0)),
+            "only_holes": int(np.count_nonzero((c[:, 0] > 0) & (classified == 0))),
+            "occluded_only": int(np.count_nonzero((classified > 0) & ~reached)),
+            "reached": int(np.count_nonzero(reached)),
+            "on_surface": int(np.count_nonzero(c[:, 1])), "seen_through": int(np.count_nonzero(c[:, 2])),
+            "kept": int(np.count_nonzero(keep))}
+
+
+def observe_sequence(points, log, pose_log, intrinsics, pose_to_cloud=None, tol_abs: float = 0.05, tol_rel: float = 0.0, near: float = OBSERVED_NEAR,
+                     max_depth=None, stride: int = 1, time_scale: float = 1e-6, max_dt: float = 0.02, chunk: int = VISIBILITY_CHUNK):
+    """Visibility of `points` over a recorded sequence.  log: a sequence directory or a .klg (io.readers.open_log; depth only is used, read
+    and uploaded `chunk` frames at a time); pose_log: read_tum()'s (timestamps in seconds, camera -> world poses); pose_to_cloud: 4 x 4 from
+    the poses' world into the frame of `points` (None: the same frame); intrinsics: (fx, fy, cx, cy) or load_calibration()'s six values.
+    Every stride-th frame is paired with a pose by associate(frame timestamp * time_scale, pose timestamps, max_dt); a frame without a pose
+    is skipped.  max_depth: depth samples beyond it are holes and the frusta end there -- with the run's depth cutoff, only what the run was
+    allowed to fuse counts as observed.  Returns (counts, first, {"frames_used", "frames_skipped"}); ValueError when no frame has a pose."""
+    from .io.readers import open_log
+    fx, fy, cx, cy = (float(v) for v in intrinsics[:4])
+    size = tuple(intrinsics[4:6]) if len(intrinsics) >= 6 and intrinsics[4] is not None else None
+    reader = open_log(log, *(size or ()))
+    try:
+        stamps = np.asarray(reader.timestamps(), np.float64)
+        chosen = np.arange(0, len(stamps), max(1, int(stride)))
+        pairs = associate(stamps[chosen] * float(time_scale), pose_log[0], max_dt)
+        if len(pairs) == 0:
+            raise ValueError(f"none of the {len(chosen)} frames of {log} has a pose within {max_dt} s (frame timestamps are multiplied by {time_scale:g})")
+        pose_of = {int(chosen[i]): int(j) for i, j in pairs}
+        to_cloud = np.eye(4) if pose_to_cloud is None else np.asarray(pose_to_cloud, np.float64)
+        far = math.inf if max_depth is None else float(max_depth)
+        vis = Visibility(points, fx, fy, cx, cy, near, far, tol_abs, tol_rel)
+        frames = (reader.load(k) for k in sorted(pose_of)) if hasattr(reader, "load") else (f for f in reader if f.index in pose_of)
+        depth, poses = [], []
+
+        def flush():
+            if depth:
+                vis.add(np.stack(depth), cam_from_cloud(np.stack(poses)))
+                depth.clear()
+                poses.clear()
+        for f in frames:
+            d = np.asarray(f.depth, np.float32)
+            if size is not None and d.shape != (size[1], size[0]):
+                raise ValueError(f"the calibration names frames of {size[0]} x {size[1]}, {log} holds {d.shape[1]} x {d.shape[0]}")
+            if max_depth is not None:
+                d = np.where(d > np.float32(max_depth), np.float32(0), d)
+            depth.append(d)
+            poses.append(to_cloud @ pose_log[1][pose_of[f.index]])
+            if len(depth) == max(1, int(chunk)):
+                flush()
+        flush()
+    finally:
+        if hasattr(reader, "close"):
+            reader.close()
+    counts, first = vis.result()
+    return counts, first, {"frames_used": int(vis.frames), "frames_skipped": int(len(chosen) - len(pairs))}
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
 # the command
 # ------------------------------------------------------------------------------------------------------------------------------------
 def _run_files(d: str):
@@ -1353,7 +1525,45 @@ def main(argv=None) -> int:
     ap.add_argument("--seg-index-width", type=int, default=4, help="digits of the masks' file index (default 4)")
     ap.add_argument("--seg-radius", type=int, help="pixel radius of the boundary measure, 0..16 (default: 0.008 of the image diagonal)")
     ap.add_argument("--seg-void", type=int, help="ground-truth value that marks pixels to leave out (default: none)")
+    ap.add_argument("--observed-from", metavar="SEQ", help="the sequence the run saw (a directory or a .klg): adds cloud_observed -- completeness and "
+                    "F-score over the reference points the sensor observed (inside a frustum and not behind the measured depth) -- and observed, "
+                    "to the background pair 0:0; cloud stays as without the flag.  Only the depth is read, in chunks of frames")
+    ap.add_argument("--observed-poses", metavar="FILE", help="TUM file, camera -> reference frame (default: poses-0.txt of --est, carried into the "
+                    "reference frame by the est -> ref transform in force: --init or identity, and the registered one for cloud_registered_observed)")
+    ap.add_argument("--observed-cal", metavar="FILE", help="calibration file 'fx fy cx cy [w h]' of the sequence (default 528 528 320 240)")
+    ap.add_argument("--observed-tol", metavar="A[,R]", help="a point is on the measured surface within A + R * depth metres (default A = --radius, "
+                    "R = 0: a reference point farther than the radius behind the surface could not have been paired anyway)")
+    ap.add_argument("--observed-rule", choices=("seen", "surface"), help="seen (default): the sensor's ray reached the point's depth in at least K "
+                    "frames, on the surface or through it; surface: the point was on the measured surface in at least K frames")
+    ap.add_argument("--observed-min-frames", type=int, metavar="K", help="K of --observed-rule (default 1)")
+    ap.add_argument("--observed-stride", type=int, metavar="S", help="use every S-th frame (default 1)")
+    ap.add_argument("--observed-max-depth", type=float, metavar="D", help="depth beyond D metres is a hole and the frusta end at D (default: no "
+                    "limit); with the run's -d, only what the run was allowed to fuse counts as observed")
+    ap.add_argument("--observed-time-scale", type=float, metavar="S", help="a frame's timestamp in the sequence times S is the pose file's seconds "
+                    "(default 1e-6, what mf_export_poses writes)")
     a = ap.parse_args(argv)
+    obs = None
+    given = [k for k in ("poses", "cal", "tol", "rule", "min_frames", "stride", "max_depth", "time_scale") if getattr(a, "observed_" + k) is not None]
+    if a.observed_from:
+        if not (a.ref or a.ref_cloud):
+            ap.error("--observed-from needs --ref or --ref-cloud")
+        try:
+            tol = [float(x) for x in (a.observed_tol or str(a.radius)).split(",")]
+        except ValueError:
+            ap.error("--observed-tol takes A or A,R")
+        if len(tol) not in (1, 2) or not all(math.isfinite(t) and t >= 0 for t in tol):
+            ap.error("--observed-tol takes A or A,R, both finite and not negative")
+        obs = {"tol_abs": tol[0], "tol_rel": tol[1] if len(tol) == 2 else 0.0, "rule": a.observed_rule or "seen",
+               "min_frames": 1 if a.observed_min_frames is None else a.observed_min_frames, "stride": 1 if a.observed_stride is None else a.observed_stride,
+               "max_depth": a.observed_max_depth, "time_scale": 1e-6 if a.observed_time_scale is None else a.observed_time_scale}
+        if obs["min_frames"] < 1 or obs["stride"] < 1:
+            ap.error("--observed-min-frames and --observed-stride take at least 1")
+        if obs["max_depth"] is not None and not (math.isfinite(obs["max_depth"]) and obs["max_depth"] > OBSERVED_NEAR):
+            ap.error(f"--observed-max-depth takes a finite depth above {OBSERVED_NEAR} m")
+        if not (math.isfinite(obs["time_scale"]) and obs["time_scale"] > 0):
+            ap.error("--observed-time-scale takes a positive factor")
+    elif given:
+        ap.error("--observed-" + given[0].replace("_", "-") + " needs --observed-from")
     if a.register_seed != 0 and a.register_global is None:
         ap.error("--register-seed needs --register-global")
     if not a.seg_gt and (a.seg_radius is not None or a.seg_void is not None):
@@ -1420,10 +1630,44 @@ def main(argv=None) -> int:
         if global_voxel is not None:
             o["registration"]["coarse"] = coarse_summary(res["coarse"])
         consistency(o, ce, ne, cr, nr, res["T"])
+        return observed_part(o, ce, cr, res["T"], "_registered")
+
+    def observed_part(o, ce, cr, T, suffix=""):
+        """With --observed-from and for the background pair 0:0 (object models move: they are not culled), adds cloud<suffix>_observed to o: cr
+        culled to what the sequence observed, est -> ref being T (None: identity).  The visibility is computed once when the poses are given in
+        the reference frame, and once per transform when they are the estimate's.  False (after a message) when it cannot be computed."""
+        if obs is None or o["model"] != 0 or o.get("ref_model", 0) != 0:
+            return True
+        if obs.get("keep") is None or (obs["own_poses"] and suffix):
+            try:
+                counts, _, info = observe_sequence(cr, a.observed_from, obs["pose_log"], obs["cal"], pose_to_cloud=T if obs["own_poses"] else None,
+                                                   tol_abs=obs["tol_abs"], tol_rel=obs["tol_rel"], max_depth=obs["max_depth"], stride=obs["stride"],
+                                                   time_scale=obs["time_scale"], max_dt=a.max_dt)
+            except (OSError, ValueError, EOFError) as e:
+                sys.stderr.write(f"eval: --observed-from: {e}\n")
+                return False
+            obs["keep"] = observed(counts, obs["rule"], obs["min_frames"])
+            summary = dict(visibility_summary(counts, obs["keep"], info["frames_used"]), frames_skipped=info["frames_skipped"], rule=obs["rule"],
+                           min_frames=obs["min_frames"], tol_abs=obs["tol_abs"], tol_rel=obs["tol_rel"], max_depth=obs["max_depth"],
+                           poses=a.observed_poses or "estimate")
+            o["observed" + suffix] = summary
+        o["cloud" + suffix + "_observed"] = compare_clouds(ce, cr, a.radius, taus, T=T, ref_keep=obs["keep"])
         return True
 
     est = _run_files(a.est)
     results = []
+    if obs is not None:
+        from .io.readers import load_calibration
+        obs["own_poses"] = a.observed_poses is None
+        if obs["own_poses"] and (0 not in est or "poses" not in est[0]):
+            sys.stderr.write(f"eval: --observed-from: {a.est} holds no poses-0.txt; give --observed-poses\n")
+            return 2
+        try:
+            obs["pose_log"] = read_tum(a.observed_poses or est[0]["poses"])
+            obs["cal"] = load_calibration(a.observed_cal) if a.observed_cal else (528.0, 528.0, 320.0, 240.0)
+        except (OSError, ValueError) as e:
+            sys.stderr.write(f"eval: --observed-poses / --observed-cal: {e}\n")
+            return 2
     if a.gt:
         gt = read_tum(a.gt)
         if 0 not in est or "poses" not in est[0]:
@@ -1463,6 +1707,8 @@ def main(argv=None) -> int:
                         o["cloud_pose_time"] = w[2]
                 if "cloud_error" not in o:
                     o["cloud"] = compare_clouds(ce, cr, a.radius, taus)
+                    if not observed_part(o, ce, cr, None):
+                        return 2
                     nr = ref_normals(o, cr, nr)
                     if a.register:
                         if not registered(o, ce, ne, cr, nr, None):
@@ -1483,6 +1729,8 @@ def main(argv=None) -> int:
             return 2
         (ce, ne), (cr, nr) = read_ply(est[0]["cloud"], normals=True), read_ply(a.ref_cloud, normals=True)
         o = {"model": 0, "ref_cloud": a.ref_cloud, "cloud": compare_clouds(ce, cr, a.radius, taus, T=T0)}
+        if not observed_part(o, ce, cr, T0):
+            return 2
         nr = ref_normals(o, cr, nr)
         if a.register:
             if not registered(o, ce, ne, cr, nr, T0):

@@ -107,6 +107,20 @@ class KlgLogReader:
     def close(self):
         self.fp.close()
 
+    def timestamps(self) -> List[int]:
+        """the timestamps of the frames iteration delivers (all but the last, see hasMore), read from the frame headers alone"""
+        out = []
+        with open(self.file, "rb") as fp:
+            fp.seek(4)
+            for _ in range(max(self.numFrames - 1, 0)):
+                hdr = fp.read(16)
+                if len(hdr) != 16:
+                    raise EOFError("truncated .klg frame header")
+                ts, dsz, isz = struct.unpack("<qii", hdr)
+                out.append(ts)
+                fp.seek(dsz + max(isz, 0), 1)
+        return out
+
     def __iter__(self):
         while self.hasMore():   # MainController::run: "if (logReader->hasMore()) getNext()" -- upstream never delivers the last frame
             yield self.getNext()
@@ -240,6 +254,10 @@ class ImageLogReader:
     def getNext(self) -> FrameData:
         self.currentFrame += 1
         return self.load(self.currentFrame)
+
+    def timestamps(self) -> List[int]:
+        """the timestamps of all frames, as load() stamps them, without reading an image"""
+        return [int(index * 1000.0 / self.rateHz) for index in range(self.numFrames)]
 
     def __iter__(self):
         while self.hasMore():
