@@ -369,6 +369,12 @@ int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
  * Implementation switches (defaults are the product; the alternatives exist for A/B measurements and as executable specifications):
  * "splatTiles" (1), "globalTiles" (1: GlobalProjection of the background through tile lists), "gpuLabels" (1: label stage on the
  * device), "batchTracking" (1: one Gauss-Newton launch serves every tracked model), "earlyBackgroundFusion" (1),
+ * "cleanTap16" (1: inside mf_process_frame the index pass that feeds Model::clean writes one 16-byte tap per texel -- {x, y, z', initTime}, z' = NaN
+ * unless index > 0, confidence > the model's threshold and z > 0, its sign bit set when lastTime == tick: everything the pass's window uses of a
+ * tap, so the results are bit-identical -- and the filtered depth into a plane of its own; 0: the 32-byte record, which the model-level calls
+ * mf_model_predict_indices -> mf_model_clean always use), "fuseLanes" (4: the data association handles a candidate on a quad of lanes, one window
+ * column per lane, merged in the serial order; 1: one lane per candidate -- same results), read-only "indexPackedTexelBytes" (16 or 32: the form the
+ * debug tap "index_packed" holds),
  * "cleanLiteralWindow" (1: Model::clean walks its window with copy_unstable.vert's own fp32 trip count, 4 or 5 taps per axis;
  * 0: 4 x 4), "timings", "passTimings" (mf_get_pass_timings), "icpProfile", "objectSmallGrids" (1; 1: the grid-stride
  * surfel kernels of an object model run on a grid sized from its last known surfel count instead of 2048 workgroups), "objectScatterSplat" (1;
@@ -465,7 +471,8 @@ void* mf_get_input_stream(mf_ctx* ctx);
  *       Rcurr [48..56], tcurr [57..59] as iteration r used them; row 19 = the state after the last update),
  *       "edge_map" (H*W f32), "edge_binary" (H*W u8), "projected_ids" (H*W u8);
  *       index map of the last (pre-fusion) index pass, index_map.frag's attachments: "index" (H*W i32), "index_vc", "index_nr",
- *       "index_ct" (H*W*4 f32), "index_packed" (post-fusion pass: 2 float4 per texel, column-major texel order);
+ *       "index_ct" (H*W*4 f32), "index_packed" (post-fusion pass, column-major texel order: 2 float4 per texel, or -- when the last frame ran
+ *       with "cleanTap16" -- 1 float4 per texel {x, y, z', initTime}; "indexPackedTexelBytes" tells which);
  *       Model::fuse / clean intermediates (variable length: as many bytes as asked for, at most the buffer): "cand_op" (u8 per
  *       quarter-rate pixel in column-major order: 0 none, 1 merge, 2 new), "cand_rec" (3 float4 per candidate), "clean_flags"
  *       (u8 keep flag per old surfel, then per candidate), "clean_newconf" (f32, same indexing). */

@@ -168,6 +168,9 @@ struct mf_ctx {
     int W, H, P;
     Intr K;
     hipStream_t stream = nullptr;      // the frame's chain: preprocessing, tracking, fusion, prediction
+    bool clean_tap16 = true;                           // the pass that feeds clean() inside a frame writes 16-byte window taps ("cleanTap16"; 0: the 32-byte record)
+    bool iclean_is_tap16 = false;                      // the form d_iclean holds (debug tap "index_packed")
+    int fuse_lanes = 4;                                // lanes per candidate of the data association ("fuseLanes": 1 or 4)
     bool clean_literal = true;                         // Model::clean walks its window with the shader text's fp32 trip count ("cleanLiteralWindow")
     bool global_tiles = true;                          // A/B + test knob ("globalTiles"): 0 = every model through k_global_scatter
     bool early_bg_fusion = true;                       // A/B knob ("earlyBackgroundFusion"): 0 = the host visit drains the stream
@@ -206,6 +209,8 @@ struct mf_ctx {
     hipStream_t stream_obj = nullptr, obj_s = nullptr;
     hipEvent_t ev_obj_dep = nullptr, ev_obj_done = nullptr;
     bool obj_dep_main = false;
+    float* d_depthT = nullptr;                         // the filtered depth in d_maskT's order (16-byte taps: the 32-byte record carries it in its spare word)
+    float* d_depthT_obj = nullptr;                     // the object chain's own copy, as d_maskT_obj
     uint8_t* d_maskT_obj = nullptr;                    // the object chain's own copy of d_maskT (every packed resolve pass writes the whole plane)
     bool ftf_rgb = false;                              // MaskFusion::frameToFrameRGB ("-ftf"; Model.cpp:399-400,981): the photometric term tracks against the previous RAW frame
     double host_us[5] = {0, 0, 0, 0, 0}; long host_calls = 0;   // mf_process_frame's host time: wait for the slot + staging copy | upload enqueue | frame enqueue | whole call | the wait alone ("hostStageUs" ... "hostWaitUs")
@@ -266,7 +271,8 @@ struct mf_ctx {
     std::vector<std::unique_ptr<ModelState>> pool;   // MaskFusion::preallocatedModels (buffers allocated ahead of the spawn)
     unsigned long long* d_keys = nullptr;
     int* d_index = nullptr; float4* d_ivc = nullptr; float4* d_ict = nullptr; float4* d_inr = nullptr;
-    float4* d_iclean = nullptr;            // packed column-major index map of the clean pass: 2 x float4 per texel (the spare word carries the filtered depth)
+    float4* d_iclean = nullptr;            // packed column-major index map of the clean pass: 2 x float4 per texel (the spare word carries the filtered depth),
+                                           // or one float4 per texel (16-byte taps, "cleanTap16") in its first half
     uint8_t* d_maskT = nullptr;            // the frame's mask in the same column-major order (launch_index_resolve writes it, clean reads it)
     uint8_t* d_cand_op = nullptr; float4* d_cand_rec = nullptr; int* d_upd_first = nullptr;
     uint8_t* d_flags = nullptr; float* d_newconf = nullptr; int* d_block_counts = nullptr;
@@ -597,6 +603,8 @@ extern "C" int mf_create(const mf_config* cfg, mf_ctx** out) {
     A(dev_alloc(c, c->allocs, &c->d_iclean, (size_t)P * 2));
     A(dev_alloc(c, c->allocs, &c->d_maskT, (size_t)P));
     A(dev_alloc(c, c->allocs, &c->d_maskT_obj, (size_t)P));
+    A(dev_alloc(c, c->allocs, &c->d_depthT, (size_t)P));
+    A(dev_alloc(c, c->allocs, &c->d_depthT_obj, (size_t)P));
     A(dev_alloc(c, c->allocs, &c->d_inr, (size_t)P));
     A(dev_alloc(c, c->allocs, &c->d_cand_op, (size_t)P));
     A(dev_alloc(c, c->allocs, &c->d_cand_rec, (size_t)P * 3));
@@ -1111,6 +1119,12 @@ extern "C" int mf_set_param(mf_ctx* c, const char* key, double value) {
         c->vis_tag.model = nullptr;
         return check_launch(c);
     }
+    if (!strcmp(key, "cleanTap16")) { c->clean_tap16 = value != 0; return MF_OK; }   // 0: the 32-byte record in every clean pass
+    if (!strcmp(key, "fuseLanes")) {
+        if ((int)value != 1 && (int)value != 4) { c->err = "fuseLanes: 1 or 4"; return MF_EINVAL; }
+        c->fuse_lanes = (int)value;
+        return MF_OK;
+    }
     if (!strcmp(key, "cleanLiteralWindow")) { c->clean_literal = value != 0; return MF_OK; }   // 0: the exact-arithmetic 4 x 4 window
     if (!strcmp(key, "earlyBackgroundFusion")) { c->early_bg_fusion = value != 0; return MF_OK; }
     if (!strcmp(key, "modelApiPackedIndex")) { c->model_api_packed = value != 0; return MF_OK; }   // 0: scatter + resolve form (specification)
@@ -1140,6 +1154,9 @@ extern "C" int mf_get_param(mf_ctx* c, const char* key, double* value) {
     if (!strcmp(key, "confidenceThreshold")) { *value = c->models[0]->confThr; return MF_OK; }
     if (!strcmp(key, "splatTileEntries")) { *value = c->tile_entries_cap; return MF_OK; }
     if (!strcmp(key, "cullRuns")) { *value = c->cull_runs ? 1 : 0; return MF_OK; }
+    if (!strcmp(key, "cleanTap16")) { *value = c->clean_tap16 ? 1 : 0; return MF_OK; }
+    if (!strcmp(key, "fuseLanes")) { *value = c->fuse_lanes; return MF_OK; }
+    if (!strcmp(key, "indexPackedTexelBytes")) { *value = c->iclean_is_tap16 ? 16 : 32; return MF_OK; }   // the form "index_packed" holds
     if (!strcmp(key, "densifyCount")) { *value = (float)c->densify_count; return MF_OK; }
     if (!strcmp(key, "unstampedRuns")) {   // test tap: live runs of the background's table that carry "holds a time stamp <= 0" (k_cull_clean lists them)
         MF_HIP(c, hipStreamSynchronize(c->stream));
@@ -1242,7 +1259,7 @@ static int debug_read_impl(mf_ctx* c, ModelState& mdl, const char* what, void* o
     else if (w == "index_vc") { src = c->d_ivc; bytes = P * 16; }
     else if (w == "index_nr") { src = c->d_inr; bytes = P * 16; }
     else if (w == "index_ct") { src = c->d_ict; bytes = P * 16; }
-    else if (w == "index_packed") { src = c->d_iclean; bytes = P * 32; }
+    else if (w == "index_packed") { src = c->d_iclean; bytes = c->iclean_is_tap16 ? P * 16 : P * 32; variable = true; }
     else if (w == "cand_op") { src = c->d_cand_op; bytes = P; variable = true; }
     else if (w == "cand_rec") { src = c->d_cand_rec; bytes = P * 48; variable = true; }
     else if (w == "clean_flags") { src = c->d_flags; bytes = (size_t)c->cap_max + P; variable = true; }
@@ -1263,7 +1280,8 @@ static int debug_read_impl(mf_ctx* c, ModelState& mdl, const char* what, void* o
     MF_HIP(c, hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
     // "index" / "index_vc" / "index_nr" / "index_ct" are the row-major images of the pre-fusion index pass (and of
     // mf_model_predict_indices); inside mf_process_frame the post-fusion pass that feeds clean() lives in "index_packed"
-    // (column-major texel order, two float4 per texel: {vertConf | initTime, lastTime, index bits, 0})
+    // (column-major texel order, two float4 per texel: {vertConf | initTime, lastTime, index bits, 0}; with "cleanTap16" one float4 per texel,
+    // {x, y, z', initTime}, in the first half of the buffer)
     return MF_OK;
 }
 extern "C" int mf_debug_read(mf_ctx* c, const char* what, void* out, uint64_t out_bytes) {

@@ -327,11 +327,13 @@ static void after_clean(mf_ctx* c, ModelState& m, bool in_place, int live) {
     else m.became_dense(live);
 }
 // the arguments every clean form of model m shares (shared scratch of the single-model path)
-static CleanIn clean_in(mf_ctx* c, ModelState& m, int time_delta, bool packed, const float* depthF, const uint8_t* mask) {
+// tap16: the packed map holds the 16-byte taps a resolve pass of the SAME enqueue wrote with this model's threshold and tick
+static CleanIn clean_in(mf_ctx* c, ModelState& m, int time_delta, bool packed, const float* depthF, const uint8_t* mask, bool tap16 = false) {
     CleanIn in;
     in.frame = m.d_frame; in.pose = m.d_pose; in.W = c->W; in.H = c->H; in.k = c->K; in.timeDelta = time_delta; in.confThreshold = m.confThr;
     in.outlierCoeff = c->cfg.outlier_coefficient; in.maskID = m.id;
     in.index = c->d_index; in.vc = c->d_ivc; in.ct = c->d_ict; in.packed = packed ? c->d_iclean : nullptr; in.maskT = c->d_maskT;
+    in.depthT = packed && tap16 ? c->d_depthT : nullptr;
     in.depthF = depthF; in.mask = mask; in.cand_op = c->d_cand_op; in.cand_rec = c->d_cand_rec;
     in.flags = c->d_flags; in.newconf = c->d_newconf; in.block_counts = c->d_block_counts; in.host_count = m.h_count;
     in.host_append = append_mirror_fits(c, m) ? m.h_append : nullptr; in.seq = m.clean_seq + 1;     // (after_clean counts the pass)
@@ -368,6 +370,10 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
     const int src = m.cur, dst = 1 - m.cur;
     const int blocks = surfel_blocks(c, m);
     const bool timed = m.id == 0;       // "passTimings": the background's passes one by one
+    // the pass that feeds clean writes 16-byte taps: resolve and clean are enqueued here, with one tick and one threshold
+    const bool tap16 = c->clean_tap16 && secondIndexPass;
+    float* const depthT = tap16 ? c->d_depthT : nullptr;
+    if (secondIndexPass) c->iclean_is_tap16 = tap16;
     VisList vl;
     const VisList* vis = nullptr;
     {
@@ -383,7 +389,7 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
     {
         PassTimer t(c, timed ? MF_PASS_BG_FUSE_DATA : -1);
         launch_fuse_data(d_rgb, d_depth, depthF, mask, m.id, m.d_frame, m.d_pose, weightMultiplier, fminf(fuseDepthCutoff, m.maxDepth), W, H,
-                         c->K, c->d_index, c->d_ivc, c->d_inr, c->d_cand_op, c->d_cand_rec, c->d_upd_first, c->d_cand_best, s, c->bbox_limit ? 1 : 0);
+                         c->K, c->d_index, c->d_ivc, c->d_inr, c->d_cand_op, c->d_cand_rec, c->d_upd_first, c->d_cand_best, s, c->bbox_limit ? 1 : 0, c->fuse_lanes);
     }
     if (marks) mark(c, 5);
     // the in-place clean of the background visits only the runs its rules can touch (k_cull_clean); the resolve pass that feeds clean gathers
@@ -402,7 +408,8 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
         if (marks) mark(c, 6);
         if (secondIndexPass) {
             PassTimer t(c, timed ? MF_PASS_BG_INDEX2 : -1);
-            launch_index_resolve(m.surf[live], m.d_frame, m.d_pose, c->d_keys, W, H, nullptr, nullptr, nullptr, nullptr, c->d_iclean, depthF, mask, c->d_maskT, true, s);
+            launch_index_resolve(m.surf[live], m.d_frame, m.d_pose, c->d_keys, W, H, nullptr, nullptr, nullptr, nullptr, c->d_iclean, depthF, mask, c->d_maskT, true, s,
+                                 nullptr, 0, depthT, m.confThr);
         }
     } else {
         // update.vert in place -- only the surfels a candidate merged into are touched (the reference copies the whole buffer,
@@ -416,11 +423,11 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
             PassTimer t(c, timed ? MF_PASS_BG_INDEX2 : -1);
             launch_index_scatter(m.surf[src], m.d_frame, m.d_pose, W, H, c->K, g.max_depth_processed, g.time_delta, c->d_keys, true, s, blocks, vis);
             launch_index_resolve(m.surf[src], m.d_frame, m.d_pose, c->d_keys, W, H, nullptr, nullptr, nullptr, nullptr, c->d_iclean, depthF, mask, c->d_maskT, true, s,
-                                 cull_clean ? c->d_decay_stats : nullptr, m.id);
+                                 cull_clean ? c->d_decay_stats : nullptr, m.id, depthT, m.confThr);
         }
     }
     // clean: two launches live -> the other buffer (a dense copy) below big_map_elements; from there on in place, run by run
-    const CleanIn in = clean_in(c, m, g.time_delta, secondIndexPass, depthF, mask);
+    const CleanIn in = clean_in(c, m, g.time_delta, secondIndexPass, depthF, mask, tap16);
     if (in_place) {
         enqueue_clean_in_place(c, m, in, cull_clean, timed);
     } else {
@@ -494,7 +501,8 @@ static int make_obj_batch(mf_ctx* c, const std::vector<ModelState*>& ms, const s
     b.outlierCoeff = g.outlier_coefficient; b.cleanLiteral = c->clean_literal ? 1 : 0; b.bboxLimit = c->bbox_limit ? 1 : 0; b.cleanSmall = 0; b.updateCopy = 0;
     b.denseSprites = 0;
     for (ModelState* m : ms) if ((long)*m->h_count >= (long)c->in_place_elements) b.denseSprites = 1;
-    b.rgb = d_rgb; b.depthRaw = d_depth; b.depthF = depthF; b.mask = mask; b.maskT = s == c->stream ? c->d_maskT : c->d_maskT_obj; b.bg_pose = c->models[0]->d_pose; b.global_keys = c->d_keys;
+    b.rgb = d_rgb; b.depthRaw = d_depth; b.depthF = depthF; b.mask = mask; b.maskT = s == c->stream ? c->d_maskT : c->d_maskT_obj;
+    b.depthT = !c->clean_tap16 ? nullptr : s == c->stream ? c->d_depthT : c->d_depthT_obj; b.fuseLanes = c->fuse_lanes; b.bg_pose = c->models[0]->d_pose; b.global_keys = c->d_keys;
     return MF_OK;
 }
 // every object model of the list, with its position in the list (the GlobalProjection payload)

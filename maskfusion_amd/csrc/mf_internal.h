@@ -278,11 +278,15 @@ void launch_cull(Surfels s, const FrameDev* frame, const PoseDev* pose, int W, i
 void launch_index_resolve(Surfels src, const FrameDev* frame, const PoseDev* pose, unsigned long long* keys, int W, int H, int* index,
                           float4* vc, float4* nr, float4* ct /*or null*/, float4* packed /*or null: the packed column-major map instead of the row-major maps*/,
                           const float* depthF, const uint8_t* mask, uint8_t* maskT /* with packed: the frame planes that travel with it */,
-                          bool keys_transposed /* the order the scatter used */, hipStream_t s, int* decay_stats = nullptr, int maskID = 0);
+                          bool keys_transposed /* the order the scatter used */, hipStream_t s, int* decay_stats = nullptr, int maskID = 0,
+                          float* depthT = nullptr /* with packed: the 16-byte tap {x, y, z', initTime} per texel instead (z' = NaN unless index > 0, confidence >
+                          tapThreshold and z > 0, sign bit = lastTime == tick), the filtered depth in this column-major plane -- only for a clean pass enqueued
+                          with it, with the same tick and threshold */, float tapThreshold = 0.f);
 void launch_fuse_data(const uint8_t* rgb, const float* depthRaw, const float* depthF, const uint8_t* mask,
                       int maskID, const FrameDev* frame, const PoseDev* pose, float weightMultiplier, float maxDepth,
                       int W, int H, Intr k, const int* index, const float4* vc, const float4* nr, uint8_t* cand_op,
-                      float4* cand_rec, int* upd_first, int* cand_best, hipStream_t s, int bboxLimit = 1);
+                      float4* cand_rec, int* upd_first, int* cand_best, hipStream_t s, int bboxLimit = 1,
+                      int lanes = 4 /* lanes per candidate: 1 or 4 (a quad shares the 3 x 3 window, one column per lane) */);
 // update.vert IN PLACE: one thread per candidate, the winning candidate of a surfel (upd_first) merges into it where it stands
 void launch_fuse_update(Surfels s, const FrameDev* frame, int* upd_first, const uint8_t* cand_op, const int* cand_best, const float4* cand_rec,
                         int W, int H, hipStream_t st);
@@ -297,6 +301,7 @@ struct CleanIn {
     FrameDev* frame; const PoseDev* pose; int W, H; Intr k; int timeDelta; float confThreshold, outlierCoeff; int maskID;
     const int* index; const float4* vc; const float4* ct;    // the index map as separate images, or
     const float4* packed; const uint8_t* maskT;              // ... the packed column-major map with the mask beside it
+    const float* depthT = nullptr;                           // != nullptr: `packed` holds 16-byte taps and this plane the filtered depth (launch_index_resolve)
     const float* depthF; const uint8_t* mask;
     const uint8_t* cand_op; const float4* cand_rec;
     uint8_t* flags; float* newconf; int* block_counts;       // [elements], [elements], [kCompactBlocks]
@@ -385,6 +390,8 @@ struct ObjBatch {
     int cleanSmall;                    // 1: the two-launch clean form src -> dst; 0: every model of the batch has a run table -- clean in place
     const uint8_t* rgb; const float* depthRaw; const float* depthF; const uint8_t* mask; const PoseDev* bg_pose;
     uint8_t* maskT;                    // the mask in column-major order, beside the packed maps (every model's resolve writes the same bytes)
+    float* depthT;                     // != nullptr: the packed maps hold 16-byte taps, and this plane the filtered depth in column-major order (as maskT)
+    int fuseLanes;                     // lanes per candidate of the association pass: 1 or 4
     unsigned long long* global_keys;
 };
 void launch_obj_global_scatter(const ObjBatch& b, int blocks, hipStream_t s);          // GlobalProjection of every object model (mf_segment.hip)

@@ -163,6 +163,7 @@ extern "C" int mf_model_predict_indices(mf_ctx* c, int32_t model, int32_t time, 
         launch_index_scatter(m->surf[m->cur], m->d_frame, m->d_pose, c->W, c->H, c->K, max_depth, time_delta, c->d_keys, true, s);
         launch_index_resolve(m->surf[m->cur], m->d_frame, m->d_pose, c->d_keys, c->W, c->H, nullptr, nullptr, nullptr, nullptr, c->d_iclean, c->d_depthF[staged_frame(c) % 3],
                              current_mask(c), c->d_maskT, true, s);
+        c->iclean_is_tap16 = false;   // (the 32-byte record: tick and threshold may change before mf_model_clean)
     }
     return check_launch(c);
 }
@@ -178,7 +179,7 @@ extern "C" int mf_model_fuse(mf_ctx* c, int32_t model, int32_t time, float depth
     set_model_tick(c, *m, time);
     launch_fuse_data(c->cur_rgb, c->cur_depth, c->d_depthF[k % 3], current_mask(c), m->id, m->d_frame, m->d_pose, weight_multiplier,
                      fminf(depth_cutoff, m->maxDepth), c->W, c->H, c->K, c->d_index, c->d_ivc, c->d_inr, c->d_cand_op, c->d_cand_rec,
-                     c->d_upd_first, c->d_cand_best, s, c->bbox_limit ? 1 : 0);
+                     c->d_upd_first, c->d_cand_best, s, c->bbox_limit ? 1 : 0, c->fuse_lanes);
     launch_fuse_update(m->surf[m->cur], m->d_frame, c->d_upd_first, c->d_cand_op, c->d_cand_best, c->d_cand_rec, c->W, c->H, s);   // in place
     // merged surfels moved and were seen now: the boxes and time stamps of their runs are refreshed (inside mf_process_frame the clean pass that
     // follows rewrites the entries of every run it visits -- and it visits every run a merge can have touched)

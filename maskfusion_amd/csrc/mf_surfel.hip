@@ -396,11 +396,21 @@ void launch_cull(Surfels s, const FrameDev* frame, const PoseDev* pose, int W, i
 // workgroup handles a 16 x 16-pixel tile and transposes it through the LDS: keys are read and records written in pieces of 128-512 bytes.
 // Every form also resets the key it read (ready for the next scatter: saves a separate clear pass).
 struct ResolvedTexel { int index; float4 vc, nr, ct, p0, p1; };
+// The 16-byte tap of the pass that feeds clean ("cleanTap16"): clean_test's window uses a tap only through x, y, z, initTime, "live" (index > 0,
+// confidence above the model's threshold, z > 0 -- both counting rules hold `idx > 0 && v.w > thr && v.z > lp.z` under lp.z > 0) and "updated in
+// this frame" (lastTime == tick).  One float4 {x, y, z', initTime}: z' = NaN for a tap that is not live, else z with the sign bit = updated.
+struct Tap16 { float thr, time; };     // the model's confidence threshold, (float)frame->tick -- the values the clean pass of the same enqueue tests with
+__device__ __forceinline__ float4 tap16_encode(float3 h, float conf, float initTime, float lastTime, int id, Tap16 t) {
+    const bool live = id > 0 && conf > t.thr && h.z > 0;
+    return make_float4(h.x, h.y, live ? (lastTime == t.time ? -h.z : h.z) : __int_as_float(0x7fc00000), initTime);
+}
 template <bool kPacked>
-__device__ __forceinline__ ResolvedTexel resolve_texel(const Surfels& src, const PoseDev* __restrict__ pose, unsigned long long key, bool want_ct, int first) {
+__device__ __forceinline__ ResolvedTexel resolve_texel(const Surfels& src, const PoseDev* __restrict__ pose, unsigned long long key, bool want_ct, int first,
+                                                       const Tap16* tap16 = nullptr) {
     ResolvedTexel r;
     r.index = 0;
     r.vc = r.nr = r.ct = r.p0 = r.p1 = make_float4(0, 0, 0, 0);
+    if (kPacked && tap16) r.p0.z = __int_as_float(0x7fc00000);    // an empty texel is no live tap
     if (key == kEmptyKey) return r;
     const int i = (int)(unsigned)(key & 0xFFFFFFFFull);
     // The index image holds the VERTEX ID of the winner (index_map.frag), and vertex 0 -- the first surfel of the buffer -- cannot be told from
@@ -411,7 +421,7 @@ __device__ __forceinline__ ResolvedTexel resolve_texel(const Surfels& src, const
     const float3 h = mul33(pose->Ri, f3(pc.x, pc.y, pc.z)) + f3(pose->ti[0], pose->ti[1], pose->ti[2]);
     if (kPacked) {
         const float4 c4 = src.ct[i];
-        r.p0 = make_float4(h.x, h.y, h.z, pc.w);
+        r.p0 = tap16 ? tap16_encode(h, pc.w, c4.z, c4.w, id, *tap16) : make_float4(h.x, h.y, h.z, pc.w);
         r.p1 = make_float4(c4.z, c4.w, __int_as_float(id), 0.f);
     } else {
         const float4 n4 = src.nr[i];
@@ -425,9 +435,10 @@ __device__ __forceinline__ ResolvedTexel resolve_texel(const Surfels& src, const
 }
 // frame planes that travel with the packed map (copy_unstable.vert:139-156 looks the filtered depth and the mask up at the surfel's own texel: in the
 // packed, column-major order these are neighbours of its window taps; in the row-major images every lane pulled a sector of its own):
-// depthF -> the packed record's spare word, mask -> maskT (column-major bytes)
+// depthF -> the packed record's spare word (32-byte record) or depthT (16-byte tap: column-major floats), mask -> maskT (column-major bytes)
 struct ResolveOut {
     int* index; float4* vc; float4* nr; float4* ct; float4* packed; const float* depthF; const uint8_t* mask; uint8_t* maskT;
+    float* depthT; float tapThreshold;    // depthT != nullptr: the 16-byte tap (one float4 per texel), live against this confidence threshold
     const FrameDev* frame;    // the buffer's frame state (`first`)
     // with `packed`, optional: what Model::clean's mask-disagreement rule (copy_unstable.vert:139-156) can meet in this frame, for the run culling of
     // the in-place clean (k_cull_clean): order-preserving ints -- {min, max} filtered depth over the texels of the LEFT column, the RIGHT column, the
@@ -478,13 +489,15 @@ __device__ __forceinline__ void index_resolve_transposing_body(Surfels src, cons
     {   // read the keys in THEIR order: packed output <- row-major keys (x fast), maps <- column-major keys (y fast)
         const int lx = kPacked ? f : g, ly = kPacked ? g : f;
         const int x = x0 + lx, y = y0 + ly;
-        ResolvedTexel r = resolve_texel<kPacked>(src, pose, kEmptyKey, false, 0);
+        const Tap16 t16{o.tapThreshold, (float)o.frame->tick};
+        const Tap16* tap = (kPacked && o.depthT) ? &t16 : nullptr;
+        ResolvedTexel r = resolve_texel<kPacked>(src, pose, kEmptyKey, false, 0, tap);
         int mk = 0;
         if (x < W && y < H) {
             const int p = kPacked ? y * W + x : x * H + y;
             const unsigned long long key = keys[p];
             keys[p] = kEmptyKey;
-            r = resolve_texel<kPacked>(src, pose, key, o.ct != nullptr, o.frame->first);
+            r = resolve_texel<kPacked>(src, pose, key, o.ct != nullptr, o.frame->first, tap);
             if (kPacked) { r.p1.w = o.depthF[p]; mk = o.mask[p]; s_mk[lx][ly] = (uint8_t)mk; }
         }
         if (kPacked) decay_stats_add(o, x < W && y < H, x, y, W, H, r.p1.w, mk);
@@ -498,8 +511,8 @@ __device__ __forceinline__ void index_resolve_transposing_body(Surfels src, cons
         if (x < W && y < H) {
             if (kPacked) {
                 const int tp = x * H + y;
-                o.packed[2 * tp] = s_a[lx][ly];
-                o.packed[2 * tp + 1] = s_b[lx][ly];
+                if (o.depthT) { o.packed[tp] = s_a[lx][ly]; o.depthT[tp] = s_b[lx][ly].w; }
+                else { o.packed[2 * tp] = s_a[lx][ly]; o.packed[2 * tp + 1] = s_b[lx][ly]; }
                 o.maskT[tp] = s_mk[lx][ly];
             } else {
                 const int p = y * W + x;
@@ -530,10 +543,11 @@ __device__ __forceinline__ void index_resolve_packed_body(Surfels src, const Pos
         const int tp = x * H + y;
         const unsigned long long key = keys[tp];
         keys[tp] = kEmptyKey;
-        ResolvedTexel r = resolve_texel<true>(src, pose, key, false, o.frame->first);
+        const Tap16 t16{o.tapThreshold, (float)o.frame->tick};
+        ResolvedTexel r = resolve_texel<true>(src, pose, key, false, o.frame->first, o.depthT ? &t16 : nullptr);
         r.p1.w = s_d[g][f];
-        o.packed[2 * tp] = r.p0;
-        o.packed[2 * tp + 1] = r.p1;
+        if (o.depthT) { o.packed[tp] = r.p0; o.depthT[tp] = r.p1.w; }
+        else { o.packed[2 * tp] = r.p0; o.packed[2 * tp + 1] = r.p1; }
         o.maskT[tp] = s_mk[g][f];
     }
 }
@@ -552,12 +566,13 @@ __global__ __launch_bounds__(256) void k_index_resolve_transposing(Surfels src, 
 int resolve_tiles(int W, int H) { return ((W + kResolveTile - 1) / kResolveTile) * ((H + kResolveTile - 1) / kResolveTile); }
 
 // packed != nullptr: the packed column-major map (index / vc / nr / ct unused) with the frame's filtered depth in its spare word and the mask
-// transposed into maskT; else the row-major maps.  keys_transposed: the order the scatter used.
+// transposed into maskT -- or, with depthT, the 16-byte tap with the filtered depth transposed into depthT; else the row-major maps.
+// keys_transposed: the order the scatter used.
 void launch_index_resolve(Surfels src, const FrameDev* frame, const PoseDev* pose, unsigned long long* keys, int W, int H, int* index, float4* vc,
                           float4* nr, float4* ct, float4* packed, const float* depthF, const uint8_t* mask, uint8_t* maskT, bool keys_transposed,
-                          hipStream_t s, int* decay_stats, int maskID) {
+                          hipStream_t s, int* decay_stats, int maskID, float* depthT, float tapThreshold) {
     const int P = W * H;
-    const ResolveOut o{index, vc, nr, ct, packed, depthF, mask, maskT, frame, packed ? decay_stats : nullptr, maskID};
+    const ResolveOut o{index, vc, nr, ct, packed, depthF, mask, maskT, packed ? depthT : nullptr, tapThreshold, frame, packed ? decay_stats : nullptr, maskID};
     const dim3 flat((P + 255) / 256), tiles(resolve_tiles(W, H));
     if (packed) {
         if (keys_transposed) hipLaunchKernelGGL(k_index_resolve_packed, tiles, dim3(256), 0, s, src, pose, keys, W, H, o);
@@ -582,19 +597,51 @@ struct FuseDataArgs {
     int* cand_best;                // surfel a merge candidate was associated with (read by the update pass; untouched for the others)
 };
 
+// kLanes == 1: one thread per candidate walks the nine taps.  kLanes == 4: a quad of neighbouring lanes per candidate (16 candidates per wavefront);
+// lanes 0, 1, 2 own the window columns da = -1, 0, +1 -- taps q = 3 lane .. 3 lane + 2 of the serial order -- and the three partial results are merged in
+// lane order with the same strict <: the first arg-min over the gated taps in the order q = 0..8, which is what the serial loop computes.  Every
+// lane of the quad computes the candidate's own values (same addresses, same operations); lane 0 stores.
+template <int kLanes>
 __device__ __forceinline__ void fuse_data_body(const FuseDataArgs& a) {
+    static_assert(kLanes == 1 || kLanes == 4, "one lane or a quad per candidate");
+    constexpr int kPerWave = 64 / kLanes, kTaps = kLanes == 1 ? 9 : 3;
     const int time = a.frame->tick;
     const int par = time & 1;
     const int W = a.W, H = a.H;
     const int nxc = (W - par + 1) / 2, nyc = (H - par + 1) / 2;
-    const int xi = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int ql = (int)threadIdx.x & (kLanes - 1);        // lane of the quad
+    const int xi = blockIdx.x * kPerWave + ((threadIdx.x & 63) / kLanes);
     const int yi = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (xi >= nxc || yi >= nyc) return;
+    if (xi >= nxc || yi >= nyc) return;                    // (whole quads leave together)
     const int c = xi * nyc + yi;
     const int px = 2 * xi + par, py = 2 * yi + par;
     const Intr k = a.k;
     uint8_t op = 0;
     const float x = (float)px + 0.5f, y = (float)py + 0.5f;
+    // data.vert:139-141 window: pixel-centre offsets {-1,-0.5,0,+0.5} -> texels {x-1,x,x,x+1}; a revisited texel can
+    // never replace itself (strict <), so the 3x3 distinct texels in first-visit order are equivalent.
+    // All window loads are issued unconditionally and together: guarding vertConf / normRad behind the index and
+    // z tests made every tap a chain of three dependent gathers (17.5 us for 77 k candidates).  With a quad per candidate they are issued before
+    // the candidate's validity is known as well: their addresses depend on the pixel alone (lane 3 of a quad repeats lane 2's column and drops it).
+    int cur9[kTaps]; float4 vc9[kTaps], nr9[kTaps];
+    if (kLanes == 4 && a.maskID != 0) {
+        // an OBJECT model's mask covers a small part of the image: a wavefront none of whose 16 candidates lies in it leaves before it requests anything
+        // else (one lane per candidate left after the mask test and two depth texels; the 9-object scene S2: 1 047 frames/s without this, 1 085 on one lane)
+        if (__ballot(a.mask[py * W + px] == a.maskID) == 0ull) {
+            if (ql == 0) a.cand_op[c] = 0;
+            return;
+        }
+    }
+    if (kLanes == 4) {
+#pragma unroll
+        for (int j = 0; j < kTaps; ++j) {
+            const int da = min(ql, 2) - 1, db = j - 1;
+            const int tp = clampi(py + db, 0, H - 1) * W + clampi(px + da, 0, W - 1);
+            cur9[j] = a.index[tp];
+            vc9[j] = a.vc[tp];
+            nr9[j] = a.nr[tp];
+        }
+    }
     const float3 vLocal = get_vertex(a.depthRaw, W, H, px, py, x, y, k);
     bool valid = a.mask[py * W + px] == a.maskID;
     valid = valid && !(texf(a.depthRaw, W, H, px - 1, py) == 0 || texf(a.depthRaw, W, H, px, py - 1) == 0 ||
@@ -615,41 +662,49 @@ __device__ __forceinline__ void fuse_data_body(const FuseDataArgs& a) {
         }
     }
     valid = valid && (vLocal.z > 0 && vLocal.z <= maxDepth);
+    float bestDist = 1000;
+    int best = 0;
+    bool merge = false;
+    float3 vGlobal = f3(0, 0, 0), nGlobal = vGlobal, vF = vGlobal, nLocal = vGlobal;
+    float weighting = 0.f, colour = 0.f;
+    if (kLanes == 4) {   // the frame loads of a valid candidate, requested with the window's: image texels, clamped to the image
+        vF = get_vertex(a.depthF, W, H, px, py, x, y, k);
+        nLocal = get_normal_central(a.depthF, W, H, px, py, x, y, vF, k);
+        const uint8_t* pc = a.rgb + (size_t)(py * W + px) * 3;
+        colour = (float)((pc[0] << 16) + (pc[1] << 8) + pc[2]);
+    }
     if (valid) {
         float R[9];
 #pragma unroll
         for (int q = 0; q < 9; ++q) R[q] = a.pose->R[q];
         const float3 t = f3(a.pose->t[0], a.pose->t[1], a.pose->t[2]);
-        const float3 vGlobal = mul33(R, vLocal) + t;
-        const float3 vF = get_vertex(a.depthF, W, H, px, py, x, y, k);
-        const float3 nLocal = get_normal_central(a.depthF, W, H, px, py, x, y, vF, k);
-        const float3 nGlobal = mul33(R, nLocal);
-        const uint8_t* pc = a.rgb + (size_t)(py * W + px) * 3;
-        const float weighting = a.pose->fusionWeight * a.weightMultiplier;
+        vGlobal = mul33(R, vLocal) + t;
+        if (kLanes == 1) {
+            vF = get_vertex(a.depthF, W, H, px, py, x, y, k);
+            nLocal = get_normal_central(a.depthF, W, H, px, py, x, y, vF, k);
+            const uint8_t* pc = a.rgb + (size_t)(py * W + px) * 3;
+            colour = (float)((pc[0] << 16) + (pc[1] << 8) + pc[2]);
+        }
+        nGlobal = mul33(R, nLocal);
+        weighting = a.pose->fusionWeight * a.weightMultiplier;
 
         const float xl = (x - k.cx) * (1.0f / k.fx), yl = (y - k.cy) * (1.0f / k.fy);
         const float lambda = sqrtf(xl * xl + yl * yl + 1);
         const float3 ray = f3(xl, yl, 1);
-        float bestDist = 1000;
-        int best = 0;
-        bool merge = false;
-        // data.vert:139-141 window: pixel-centre offsets {-1,-0.5,0,+0.5} -> texels {x-1,x,x,x+1}; a revisited texel can
-        // never replace itself (strict <), so the 3x3 distinct texels in first-visit order are equivalent.
-        // All 27 window loads are issued unconditionally and together: guarding vertConf / normRad behind the index and
-        // z tests made every tap a chain of three dependent gathers (17.5 us for 77 k candidates).
-        int cur9[9]; float4 vc9[9], nr9[9];
+        if (kLanes == 1) {
 #pragma unroll
-        for (int q = 0; q < 9; ++q) {
-            const int da = q / 3 - 1, db = q % 3 - 1;
-            const int tp = clampi(py + db, 0, H - 1) * W + clampi(px + da, 0, W - 1);
-            cur9[q] = a.index[tp];
-            vc9[q] = a.vc[tp];
-            nr9[q] = a.nr[tp];
+            for (int q = 0; q < kTaps; ++q) {
+                const int da = q / 3 - 1, db = q % 3 - 1;
+                const int tp = clampi(py + db, 0, H - 1) * W + clampi(px + da, 0, W - 1);
+                cur9[q] = a.index[tp];
+                vc9[q] = a.vc[tp];
+                nr9[q] = a.nr[tp];
+            }
         }
 #pragma unroll
-        for (int q = 0; q < 9; ++q) {
+        for (int q = 0; q < kTaps; ++q) {
             const int current = cur9[q];
-            if (current > 0) {
+            if (current > 0 && ql < 3) {
                 const float4 vc = vc9[q];
                 const float zdiff = vc.z - vLocal.z;
                 if (fabsf(zdiff * lambda) < 0.05f) {
@@ -663,9 +718,24 @@ __device__ __forceinline__ void fuse_data_body(const FuseDataArgs& a) {
                 }
             }
         }
+    }
+    if (kLanes == 4) {
+        // the quad's partial results, merged in lane order (every lane of the wavefront that has not left takes part in the exchange)
+        const float myDist = bestDist;
+        const int myBest = best;
+        bestDist = 1000; best = 0; merge = false;
+#pragma unroll
+        for (int l = 0; l < 3; ++l) {
+            const float d = __shfl(myDist, l, 4);
+            const int b = __shfl(myBest, l, 4);
+            if (d < bestDist) { merge = true; bestDist = d; best = b; }
+        }
+        if (ql != 0) return;
+    }
+    if (valid) {
         op = merge ? 1 : 2;
         a.cand_rec[c * 3 + 0] = make_float4(vGlobal.x, vGlobal.y, vGlobal.z, surfel_confidence(x, y, weighting, k));
-        a.cand_rec[c * 3 + 1] = make_float4((float)((pc[0] << 16) + (pc[1] << 8) + pc[2]), 0.f, (float)time, merge ? -1.f : -2.f);
+        a.cand_rec[c * 3 + 1] = make_float4(colour, 0.f, (float)time, merge ? -1.f : -2.f);
         a.cand_rec[c * 3 + 2] = make_float4(nGlobal.x, nGlobal.y, nGlobal.z, surfel_radius(vF.z, nLocal.z, k));
         if (merge) {
             atomicMin(&a.upd_first[best], c);  // first writer (lowest column-major index) wins
@@ -675,16 +745,19 @@ __device__ __forceinline__ void fuse_data_body(const FuseDataArgs& a) {
     a.cand_op[c] = op;
 }
 
-__global__ __launch_bounds__(256) void k_fuse_data(const FuseDataArgs a) { fuse_data_body(a); }
+template <int kLanes>
+__global__ __launch_bounds__(256) void k_fuse_data(const FuseDataArgs a) { fuse_data_body<kLanes>(a); }
 
 void launch_fuse_data(const uint8_t* rgb, const float* depthRaw, const float* depthF, const uint8_t* mask, int maskID,
                       const FrameDev* frame, const PoseDev* pose, float weightMultiplier, float maxDepth, int W, int H, Intr k,
                       const int* index, const float4* vc, const float4* nr, uint8_t* cand_op, float4* cand_rec, int* upd_first,
-                      int* cand_best, hipStream_t s, int bboxLimit) {
+                      int* cand_best, hipStream_t s, int bboxLimit, int lanes) {
     FuseDataArgs a{rgb, depthRaw, depthF, mask, maskID, frame, pose, weightMultiplier, maxDepth, bboxLimit, W, H, k,
                    index, vc, nr, cand_op, cand_rec, upd_first, cand_best};
-    dim3 grid(((W + 1) / 2 + 63) / 64, ((H + 1) / 2 + 3) / 4);
-    hipLaunchKernelGGL(k_fuse_data, grid, dim3(256), 0, s, a);
+    const int per_wave = lanes == 4 ? 16 : 64;
+    dim3 grid(((W + 1) / 2 + per_wave - 1) / per_wave, ((H + 1) / 2 + 3) / 4);
+    if (lanes == 4) hipLaunchKernelGGL(k_fuse_data<4>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_fuse_data<1>, grid, dim3(256), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -801,6 +874,7 @@ struct CleanArgs {
     const float4* packed;                                    // {vertConf | initTime, lastTime, index, 0} per texel
     const float* depthF; const uint8_t* mask;
     const uint8_t* maskT;                                    // the mask in the packed map's order (only with `packed`)
+    const float* depthT;                                     // the filtered depth in the same order (only with the 16-byte tap: clean_test<true>)
     const uint8_t* cand_op; const float4* cand_rec;
     uint8_t* flags; float* newconf;    // keep flag / new confidence per element: pass 1 -> pass 2 of the two-launch form
     int* block_counts;                 // [kCompactBlocks] survivors per workgroup (two-launch form)
@@ -839,6 +913,9 @@ __device__ __forceinline__ void window_slots_literal(float c, int size, int (&u)
 
 // decay: which factor the mask-disagreement rule applied to the confidence (0 none, 1: k, 2: 0.25 k) -- clean_decayed() re-applies it
 // nr_lazy != nullptr: the surfel's normal / radius record is only fetched when the window is walked (it is not needed otherwise); `nr` is then ignored
+// kTap16: a.packed holds the 16-byte tap {x, y, z', initTime} (tap16_encode: written by the resolve pass of the same enqueue, with this pass's
+// threshold and tick) instead of the 32-byte record; a tap counts under the same conditions, bit for bit.
+template <bool kTap16>
 __device__ __forceinline__ bool clean_test(const CleanArgs& a, float4 pc, float4 ct, float4 nr, float time, const float* Ri,
                                            float3 ti, float& newconf, int& decay, const float4* nr_lazy = nullptr) {
     const int W = a.W, H = a.H;
@@ -876,7 +953,14 @@ __device__ __forceinline__ bool clean_test(const CleanArgs& a, float4 pc, float4
                 if (mult <= 0) continue;   // (requesting the taps' records in groups before looking at any -- 6 + 3, all 9 -- was tried in rounds 2 and 5: slower at VGA, DESIGN.md "rejected")
                 float4 v, c;
                 int idx;
-                if (a.packed) {
+                bool upd = false;     // (16-byte tap) lastTime == tick
+                if (kTap16) {
+                    const float4 t = a.packed[tp];
+                    idx = isnan(t.z) ? 0 : 1;
+                    upd = __float_as_int(t.z) < 0;
+                    v = make_float4(t.x, t.y, fabsf(t.z), 0.f);
+                    c = make_float4(0.f, 0.f, t.w, 0.f);
+                } else if (a.packed) {
                     v = a.packed[2 * tp];
                     const float4 r1 = a.packed[2 * tp + 1];
                     c = make_float4(0.f, 0.f, r1.x, r1.y);
@@ -888,10 +972,10 @@ __device__ __forceinline__ bool clean_test(const CleanArgs& a, float4 pc, float4
                 }
                 if (idx > 0) {
                     const float dx = v.x - lp.x, dy = v.y - lp.y;
-                    if (c.z < ct.z && v.w > a.confThreshold && v.z > lp.z && v.z - lp.z < 0.01f &&
+                    if (c.z < ct.z && (kTap16 || v.w > a.confThreshold) && v.z > lp.z && v.z - lp.z < 0.01f &&
                         sqrtf(dx * dx + dy * dy) < nr.w * 1.4f)
                         count += mult;
-                    if (c.w == time && v.w > a.confThreshold && v.z > lp.z && v.z - lp.z > 0.01f && fabsf(ln.z) > 0.85f)
+                    if ((kTap16 ? upd : c.w == time) && (kTap16 || v.w > a.confThreshold) && v.z > lp.z && v.z - lp.z > 0.01f && fabsf(ln.z) > 0.85f)
                         zCount += mult;
                 }
             }
@@ -905,8 +989,9 @@ __device__ __forceinline__ bool clean_test(const CleanArgs& a, float4 pc, float4
     // mask-disagreement decay, copy_unstable.vert:139-156 (nearest fetch, clamp to edge, NaN -> texel 0)
     const int fx_ = isnan(x) ? 0 : clampi((int)fminf(fmaxf(floorf(x), -1.f), (float)W), 0, W - 1);
     const int fy_ = isnan(y) ? 0 : clampi((int)fminf(fmaxf(floorf(y), -1.f), (float)H), 0, H - 1);
-    // (with the packed map: the filtered depth rides in its spare word, the mask in the column-major plane beside it -- launch_index_resolve)
-    const float wDepth = a.packed ? a.packed[2 * (fx_ * H + fy_) + 1].w : a.depthF[fy_ * W + fx_];
+    // (with the packed map: the filtered depth rides in its spare word -- 16-byte tap: in the column-major plane depthT --, the mask in the
+    // column-major plane beside it -- launch_index_resolve)
+    const float wDepth = kTap16 ? a.depthT[fx_ * H + fy_] : a.packed ? a.packed[2 * (fx_ * H + fy_) + 1].w : a.depthF[fy_ * W + fx_];
     const int maskValue = a.packed ? a.maskT[fx_ * H + fy_] : a.mask[fy_ * W + fx_];
     newconf = pc.w;
     decay = 0;
@@ -933,6 +1018,7 @@ __device__ __forceinline__ float clean_decayed(const CleanArgs& a, float conf, i
 //     run, and their runs to its table.
 // The surviving records, their order and the count are the same bits either way (tests/test_gpu_switches.py::test_clean_forms_agree).
 // ------------------------------------------------------------------------------------------------
+template <bool kTap16>
 __device__ __forceinline__ void clean_small_flags_body(const CleanArgs& a) {
     __shared__ int s_w[4];
     // elements below `count` are the buffer's slots, the others the candidates; `first`: the first element these passes handle
@@ -953,11 +1039,11 @@ __device__ __forceinline__ void clean_small_flags_body(const CleanArgs& a) {
         float nc = 0.f;
         int dk = 0;
         if (i < count) {
-            keep = clean_test(a, a.src.pc[i], a.src.ct[i], a.src.nr[i], time, Ri, ti, nc, dk);
+            keep = clean_test<kTap16>(a, a.src.pc[i], a.src.ct[i], make_float4(0, 0, 0, 0), time, Ri, ti, nc, dk, &a.src.nr[i]);
         } else {
             const int c = i - count;
             if (a.cand_op[c] == 2)
-                keep = clean_test(a, a.cand_rec[c * 3 + 0], a.cand_rec[c * 3 + 1], a.cand_rec[c * 3 + 2], time, Ri, ti, nc, dk);
+                keep = clean_test<kTap16>(a, a.cand_rec[c * 3 + 0], a.cand_rec[c * 3 + 1], make_float4(0, 0, 0, 0), time, Ri, ti, nc, dk, &a.cand_rec[c * 3 + 2]);
         }
         a.flags[i - first] = keep ? 1 : 0;
         a.newconf[i - first] = nc;
@@ -984,7 +1070,8 @@ __device__ __forceinline__ void clean_small_flags_body(const CleanArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_clean_small_flags(const CleanArgs a) { clean_small_flags_body(a); }
+template <bool kTap16>
+__global__ __launch_bounds__(256) void k_clean_small_flags(const CleanArgs a) { clean_small_flags_body<kTap16>(a); }
 
 __device__ __forceinline__ void clean_small_compact_body(const CleanArgs& a) {
     __shared__ int s_w[4];
@@ -1188,6 +1275,7 @@ void launch_cull_clean(Surfels s, const FrameDev* frame, const PoseDev* pose, in
 
 // One run per workgroup and round (its <= kRun slots: two per thread); the runs are dealt round-robin over the grid (the listed runs come in no
 // particular order, expensive -- in view -- and cheap ones mixed).
+template <bool kTap16>
 __device__ __forceinline__ void clean_runs_body(const CleanArgs& a) {
     __shared__ int s_cnt[2][4];
     __shared__ int s_red[4][kRunRed];
@@ -1221,8 +1309,8 @@ __device__ __forceinline__ void clean_runs_body(const CleanArgs& a) {
         // nothing on the configs[4] maps, 0.43 ms either way: the pass is bound by the instructions of the test, ~2 000 per surfel in view.)
         float nc0 = 0.f, nc1 = 0.f;
         int dk = 0;
-        const bool keep0 = live0 && clean_test(a, pc0, make_float4(0.f, 0.f, tm0.x, tm0.y), make_float4(0, 0, 0, 0), time, Ri, ti, nc0, dk, &a.src.nr[start + off0]);
-        const bool keep1 = live1 && clean_test(a, pc1, make_float4(0.f, 0.f, tm1.x, tm1.y), make_float4(0, 0, 0, 0), time, Ri, ti, nc1, dk, &a.src.nr[start + off1]);
+        const bool keep0 = live0 && clean_test<kTap16>(a, pc0, make_float4(0.f, 0.f, tm0.x, tm0.y), make_float4(0, 0, 0, 0), time, Ri, ti, nc0, dk, &a.src.nr[start + off0]);
+        const bool keep1 = live1 && clean_test<kTap16>(a, pc1, make_float4(0.f, 0.f, tm1.x, tm1.y), make_float4(0, 0, 0, 0), time, Ri, ti, nc1, dk, &a.src.nr[start + off1]);
         RunAcc acc;
         acc.reset();
         // copy_unstable.vert:131: a surfel stamped -2 ("seen in this frame") leaves the pass stamped with the tick -- only an uploaded map holds one
@@ -1319,7 +1407,8 @@ __device__ __forceinline__ void clean_runs_body(const CleanArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_clean_runs(const CleanArgs a) { clean_runs_body(a); }
+template <bool kTap16>
+__global__ __launch_bounds__(256) void k_clean_runs(const CleanArgs a) { clean_runs_body<kTap16>(a); }
 
 // workgroups of a k_clean_runs launch for a buffer of ~`elements` surfels: the runs are dealt round-robin, any grid covers any table
 int clean_runs_grid(long elements) {
@@ -1557,7 +1646,7 @@ static CleanArgs clean_args(const CleanIn& in, Surfels src, Surfels dst) {
     a.literal = in.literalWindow ? 1 : 0;
     a.src = src; a.dst = dst; a.frame = in.frame; a.pose = in.pose; a.W = in.W; a.H = in.H; a.k = in.k; a.timeDelta = in.timeDelta;
     a.confThreshold = in.confThreshold; a.outlierCoeff = in.outlierCoeff; a.maskID = in.maskID; a.index = in.index; a.vc = in.vc; a.ct = in.ct;
-    a.packed = in.packed;
+    a.packed = in.packed; a.depthT = in.packed ? in.depthT : nullptr;
     a.depthF = in.depthF; a.mask = in.mask; a.maskT = in.maskT; a.cand_op = in.cand_op; a.cand_rec = in.cand_rec;
     a.flags = in.flags; a.newconf = in.newconf; a.block_counts = in.block_counts; a.host_count = in.host_count;
     a.host_append = in.host_append; a.seq = in.seq;
@@ -1571,19 +1660,22 @@ static CleanArgs clean_args(const CleanIn& in, Surfels src, Surfels dst) {
 int compact_blocks_for(long elements) { return elements >= 1500000L ? kCompactBlocks / 2 : kCompactBlocks; }
 void launch_clean_small(const CleanIn& in, Surfels src, Surfels dst, hipStream_t s, int blocks) {
     const CleanArgs a = clean_args(in, src, dst);
-    hipLaunchKernelGGL(k_clean_small_flags, dim3(blocks), dim3(256), 0, s, a);
+    if (a.depthT) hipLaunchKernelGGL(k_clean_small_flags<true>, dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_clean_small_flags<false>, dim3(blocks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_clean_small_compact, dim3(blocks), dim3(256), 0, s, a);
 }
 void launch_clean_runs(const CleanIn& in, Surfels buf, const VisList* runs, int* ctl, int blocks, hipStream_t s) {
     CleanArgs a = clean_args(in, buf, buf);
     a.run_list = runs ? runs->list : nullptr; a.run_count = runs ? runs->count : nullptr; a.ctl = ctl;
-    hipLaunchKernelGGL(k_clean_runs, dim3(blocks), dim3(256), 0, s, a);
+    if (a.depthT) hipLaunchKernelGGL(k_clean_runs<true>, dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_clean_runs<false>, dim3(blocks), dim3(256), 0, s, a);
 }
 void launch_clean_append(const CleanIn& in, Surfels buf, hipStream_t s) {
     CleanArgs a = clean_args(in, buf, buf);
     a.append = 1;
     // (the candidates are <= P / 4 elements: a grid of one 256-element slice per workgroup, at most kCompactBlocks of them)
-    hipLaunchKernelGGL(k_clean_small_flags, dim3(kCompactBlocks), dim3(256), 0, s, a);
+    if (a.depthT) hipLaunchKernelGGL(k_clean_small_flags<true>, dim3(kCompactBlocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_clean_small_flags<false>, dim3(kCompactBlocks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_clean_small_compact, dim3(kCompactBlocks), dim3(256), 0, s, a);
 }
 
@@ -1599,18 +1691,19 @@ __global__ __launch_bounds__(256) void k_obj_index_scatter(const ObjBatch b) {
 }
 __global__ __launch_bounds__(256) void k_obj_index_resolve(const ObjBatch b) {   // (the object models' keys are row-major in both passes)
     const ObjPassArgs& m = b.m[blockIdx.z];
-    index_resolve_same_body<false>(m.a, m.pose, m.keys, b.W * b.H, ResolveOut{m.index, m.ivc, m.inr, nullptr, nullptr, nullptr, nullptr, nullptr, m.frame, nullptr, 0});
+    index_resolve_same_body<false>(m.a, m.pose, m.keys, b.W * b.H, ResolveOut{m.index, m.ivc, m.inr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, m.frame, nullptr, 0});
 }
 __global__ __launch_bounds__(256) void k_obj_index_resolve_packed(const ObjBatch b) {   // the pass that feeds clean(): grid.x = 16 x 16-pixel tiles
     const ObjPassArgs& m = b.m[blockIdx.z];
     index_resolve_transposing_body<true>(b.updateCopy ? m.b : m.a, m.pose, m.keys, b.W, b.H,
-                                         ResolveOut{nullptr, nullptr, nullptr, nullptr, m.iclean, b.depthF, b.mask, b.maskT, m.frame, nullptr, 0}, (int)blockIdx.x);
+                                         ResolveOut{nullptr, nullptr, nullptr, nullptr, m.iclean, b.depthF, b.mask, b.maskT, b.depthT, m.confThreshold, m.frame, nullptr, 0}, (int)blockIdx.x);
 }
+template <int kLanes>
 __global__ __launch_bounds__(256) void k_obj_fuse_data(const ObjBatch b) {
     const ObjPassArgs& m = b.m[blockIdx.z];
     const FuseDataArgs a{b.rgb, b.depthRaw, b.depthF, b.mask, m.maskID, m.frame, m.pose, m.weightMultiplier, m.fuseMaxDepth, b.bboxLimit, b.W, b.H, b.k,
                          m.index, m.ivc, m.inr, m.cand_op, m.cand_rec, m.upd_first, m.cand_best};
-    fuse_data_body(a);
+    fuse_data_body<kLanes>(a);
 }
 __global__ __launch_bounds__(256) void k_obj_fuse_update(const ObjBatch b) {
     const ObjPassArgs& m = b.m[blockIdx.z];
@@ -1628,15 +1721,17 @@ __device__ __forceinline__ CleanArgs obj_clean_args(const ObjBatch& b, const Obj
     a.src = b.updateCopy ? m.b : m.a; a.dst = b.updateCopy ? m.a : (b.cleanSmall ? m.b : m.a);
     a.frame = m.frame; a.pose = m.pose; a.W = b.W; a.H = b.H; a.k = b.k; a.timeDelta = b.timeDelta;
     a.confThreshold = m.confThreshold; a.outlierCoeff = b.outlierCoeff; a.maskID = m.maskID; a.transposed = 1; a.literal = b.cleanLiteral;
-    a.index = m.index; a.vc = m.ivc; a.ct = nullptr; a.packed = m.iclean; a.depthF = b.depthF; a.mask = b.mask; a.maskT = b.maskT;
+    a.index = m.index; a.vc = m.ivc; a.ct = nullptr; a.packed = m.iclean; a.depthT = b.depthT; a.depthF = b.depthF; a.mask = b.mask; a.maskT = b.maskT;
     a.cand_op = m.cand_op; a.cand_rec = m.cand_rec; a.flags = m.flags; a.newconf = m.newconf;
     a.block_counts = m.block_counts; a.host_count = m.host_count;
     a.host_append = m.host_append; a.seq = m.clean_seq;
     a.append = append; a.run_list = nullptr; a.run_count = nullptr; a.ctl = m.clean_ctl;
     return a;
 }
-__global__ __launch_bounds__(256) void k_obj_clean_runs(const ObjBatch b) { clean_runs_body(obj_clean_args(b, b.m[blockIdx.z], 0)); }
-__global__ __launch_bounds__(256) void k_obj_clean_small_flags(const ObjBatch b) { clean_small_flags_body(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1)); }
+template <bool kTap16>
+__global__ __launch_bounds__(256) void k_obj_clean_runs(const ObjBatch b) { clean_runs_body<kTap16>(obj_clean_args(b, b.m[blockIdx.z], 0)); }
+template <bool kTap16>
+__global__ __launch_bounds__(256) void k_obj_clean_small_flags(const ObjBatch b) { clean_small_flags_body<kTap16>(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1)); }
 __global__ __launch_bounds__(256) void k_obj_clean_small_compact(const ObjBatch b) { clean_small_compact_body(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1)); }
 __global__ __launch_bounds__(256) void k_obj_splat_scatter(const ObjBatch b) {
     const ObjPassArgs& m = b.m[blockIdx.z];
@@ -1656,10 +1751,12 @@ __global__ void k_obj_frame_advance(const ObjBatch b) {
 void launch_obj_fuse_clean(const ObjBatch& b, int blocks, int clean_blocks, hipStream_t s, int compact_blocks) {
     const int P = b.W * b.H;
     const dim3 surfels(blocks, 1, b.n), pixels((P + 255) / 256, 1, b.n), compact(clean_blocks, 1, b.n);
-    const dim3 cands(((b.W + 1) / 2 + 63) / 64, ((b.H + 1) / 2 + 3) / 4, b.n);
+    const int per_wave = b.fuseLanes == 4 ? 16 : 64;
+    const dim3 cands(((b.W + 1) / 2 + per_wave - 1) / per_wave, ((b.H + 1) / 2 + 3) / 4, b.n);
     hipLaunchKernelGGL(k_obj_index_scatter, surfels, dim3(256), 0, s, b);
     hipLaunchKernelGGL(k_obj_index_resolve, pixels, dim3(256), 0, s, b);
-    hipLaunchKernelGGL(k_obj_fuse_data, cands, dim3(256), 0, s, b);
+    if (b.fuseLanes == 4) hipLaunchKernelGGL(k_obj_fuse_data<4>, cands, dim3(256), 0, s, b);
+    else hipLaunchKernelGGL(k_obj_fuse_data<1>, cands, dim3(256), 0, s, b);
     if (b.updateCopy) {
         hipLaunchKernelGGL(k_obj_fuse_update_copy, surfels, dim3(256), 0, s, b);
     } else {
@@ -1669,8 +1766,13 @@ void launch_obj_fuse_clean(const ObjBatch& b, int blocks, int clean_blocks, hipS
     hipLaunchKernelGGL(k_obj_index_resolve_packed, dim3(resolve_tiles(b.W, b.H), 1, b.n), dim3(256), 0, s, b);
     // two-launch form src -> dst, or (big models) the buffer's own surfels in place, run by run -- an object model's launch visits every run: its
     // bounding box is the box of ALL its drawn surfels -- and then the frame's candidates appended by the two-launch form
-    if (!b.cleanSmall) hipLaunchKernelGGL(k_obj_clean_runs, compact, dim3(256), 0, s, b);
-    hipLaunchKernelGGL(k_obj_clean_small_flags, dim3(compact_blocks, 1, b.n), dim3(256), 0, s, b);
+    if (b.depthT) {    // the 16-byte tap (the resolve pass above wrote it with each model's own threshold and tick)
+        if (!b.cleanSmall) hipLaunchKernelGGL(k_obj_clean_runs<true>, compact, dim3(256), 0, s, b);
+        hipLaunchKernelGGL(k_obj_clean_small_flags<true>, dim3(compact_blocks, 1, b.n), dim3(256), 0, s, b);
+    } else {
+        if (!b.cleanSmall) hipLaunchKernelGGL(k_obj_clean_runs<false>, compact, dim3(256), 0, s, b);
+        hipLaunchKernelGGL(k_obj_clean_small_flags<false>, dim3(compact_blocks, 1, b.n), dim3(256), 0, s, b);
+    }
     hipLaunchKernelGGL(k_obj_clean_small_compact, dim3(compact_blocks, 1, b.n), dim3(256), 0, s, b);
 }
 void launch_obj_predict_advance(const ObjBatch& b, int blocks, hipStream_t s) {
