@@ -407,6 +407,12 @@ int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
  * iteration in its prologue, as the single-model kernel does; 0: a solve launch and a pixel launch per iteration; same bytes),
  * "fusedPreprocessLaunch" (1: when only the background is tracked model by model, its model-side pyramid is built in the depth filter's launch --
  * two independent kernels of a frame side by side; 0: two launches; same bytes),
+ * "deferPredict" (a single-model context that tracks with the geometric term alone, timings off: the prediction of frame t is enqueued at the head
+ * of the next mf_process_frame[_dev] call -- or by whatever other call on the context comes first -- instead of at the end of frame t, so that it can
+ * share launches with frame t + 1's preprocessing; same bytes.  Work the caller enqueues on mf_get_stream()'s stream sees frame t's prediction only
+ * behind the next library call), "fusedBinFilter" / "fusedFramePyramids" (in that head: the prediction's binning pass in the next frame's depth
+ * filter's launch / the frame's pyramid and the model-side pyramid in one launch; 0: two launches each; same bytes); read-only: "deferredFrames" /
+ * "fusedHeadFrames" (predictions deferred / frames that took the fused head so far),
  * "hostLockstep" (1: mf_process_frame waits for frame k-2 to have run before it enqueues frame k's
  * upload), "hostWaitUpload" (1: ... and for its own upload: single-model frames), "modelApiPackedIndex" (0; 1: mf_model_predict_indices
  * also builds the packed column-major map mf_process_frame feeds Model::clean with), "tileThreads" (512) / "spriteLanes" (4) / "tileHeight" (24; 16, 20, 32: tiles of 16 pixels by that many rows): launch shape of

@@ -1,5 +1,6 @@
 // mf_bilateral_device.h -- the 13x13 bilateral depth filter's workgroup body (depth_bilateral_metric.frag:30-76), shared by k_bilateral
-// (mf_preproc.hip) and the launch that runs it beside the model-side pyramid of the same frame (mf_odometry.hip: k_bilateral_model_pyramid).
+// (mf_preproc.hip), the launch that runs it beside the model-side pyramid of the same frame (mf_odometry.hip: k_bilateral_model_pyramid) and the one
+// that runs it beside the previous frame's sprite binning (mf_splat.hip: k_bin_bilateral).
 // Every float operation of the body is rounded on its own (the pragma inside the function: the including file may allow contraction).
 #pragma once
 #include "mf_device.h"
@@ -26,18 +27,21 @@ constexpr float kBOutside = 1e15f;
 // difference to the oracle's expf path is a few ulp (tests/test_gpu_kernels.py::test_bilateral).
 // (Two pixels per thread with 2-wide packed fp32 math -- 6.5 instead of 10 VALU instructions per tap -- was tried: 31 us
 // against 19 us; half as many wavefronts left the exp / LDS latencies exposed.)
-// tile: kBLdsH * kBLdsW floats of LDS; block: the workgroup's index in a grid of xcd_padded_grid(tiles) workgroups
-__device__ __forceinline__ void bilateral_body(const float* __restrict__ depth, float* __restrict__ out, int W, int H, float* tile, int block) {
+// tile: kBLdsH * kBLdsW floats of LDS; block: the 256 threads' index in a grid of xcd_padded_grid(tiles) such groups; tid: the thread's index among
+// the 256.  live: false for a group beyond that grid.  A group without a tile is a predicate, not an early return: every thread reaches the barrier,
+// whatever else shares the workgroup (several groups in one workgroup were measured for k_bin_bilateral and lost: DESIGN.md, "Measured and rejected").
+__device__ __forceinline__ void bilateral_body(const float* __restrict__ depth, float* __restrict__ out, int W, int H, float* tile, int block, int tid,
+                                               bool live) {
 #pragma clang fp contract(off)
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int tx = tid & 63, ty = tid >> 6;
     const int tiles_x = (W + kBTileW - 1) / kBTileW, tiles = tiles_x * ((H + kBTileH - 1) / kBTileH);
     const int tile_id = xcd_contiguous_tile(block, tiles);   // each XCD's L2 fetches its own band of the image (+ halo), not all of it
-    if (tile_id >= tiles) return;
+    const bool on = live && tile_id < tiles;
     const int x0 = (tile_id % tiles_x) * kBTileW, y0 = (tile_id / tiles_x) * kBTileH;
     // stage.  The shader clips its loops at the image border; here an out-of-image tap holds kBOutside = 1e15: its range term is
     // -8e32, 2^that is exactly 0, and it adds tmp * 0 = +0 to both sums -- the same bits as skipping it, without a compare, an exec
     // mask and a branch per tap (round 3: the 169 branches also kept every ds_read on its own s_waitcnt).
-    for (int i = threadIdx.x; i < kBLdsH * kBLdsW; i += 256) {
+    for (int i = tid; on && i < kBLdsH * kBLdsW; i += 256) {
         const int ly = i / kBLdsW, lx = i - ly * kBLdsW;
         const int gx = x0 + lx - kBR, gy = y0 + ly - kBR;
         tile[i] = (gx >= 0 && gx < W && gy >= 0 && gy < H) ? depth[gy * W + gx] : kBOutside;
@@ -46,7 +50,7 @@ __device__ __forceinline__ void bilateral_body(const float* __restrict__ depth, 
     const float sigma_space2_inv_half = 0.024691358f * 1.44269504088896340736f;   // x log2(e)
     const float sigma_color2_inv_half = 555.556f * 1.44269504088896340736f;
     const int gx = x0 + tx, gy = y0 + ty;
-    if (gx >= W || gy >= H) return;
+    if (!on || gx >= W || gy >= H) return;
     const float value = tile[(ty + kBR) * kBLdsW + tx + kBR];
     float res = 0.f;
     if (!(value <= 0.03f)) {   // the shader's gate as written (`if (value <= 0.03f) 0 else filter`, :34): a NaN centre is filtered, to NaN

@@ -205,6 +205,12 @@ struct mf_ctx {
     // "fusedPreprocessLaunch": the model-side pyramids of the frame's tracking plan are built in the depth filter's launch (k_bilateral_model_pyramid):
     // the background's, or every tracked model's of a batched plan (mf_frame.inl: process_frame_impl hands the fact to the tracking loop)
     bool fused_preprocess = true;
+    // "deferPredict": the background's prediction of frame t waits as a record and is drawn in the head of frame t + 1, where its launches are shared
+    // with that frame's preprocessing ("fusedBinFilter", "fusedFramePyramids"; mf_frame.inl: defer_eligible, settle, enqueue_fused_head).  pending.m:
+    // the model whose prediction is pending (nullptr: none), pending.adv: its end-of-frame bookkeeping with the pose-log slot taken in call t
+    bool defer_predict = true, fused_bin_filter = true, fused_frame_pyramids = true;
+    struct { ModelState* m = nullptr; FrameAdvance adv{nullptr, nullptr, nullptr}; } pending;
+    long deferred_frames = 0, fused_head_frames = 0;   // "deferredFrames" / "fusedHeadFrames" (read-only): predictions deferred / heads taken so far
     bool object_stream = true;
     hipStream_t stream_obj = nullptr, obj_s = nullptr;
     hipEvent_t ev_obj_dep = nullptr, ev_obj_done = nullptr;
@@ -704,6 +710,7 @@ extern "C" const char* mf_last_error(const mf_ctx* c) { return c ? c->err.c_str(
 // MaskFusion::preallocateModels (Core/MaskFusion.cpp:144-149): object-model buffers allocated ahead of time, so that a spawn
 // inside a frame costs two tiny kernels instead of ~100 MB of hipMalloc + memset
 extern "C" int mf_preallocate_models(mf_ctx* c, uint32_t count) {
+    settle(c);
     if (!c) return MF_EINVAL;
     for (uint32_t i = 0; i < count; ++i) {
         std::unique_ptr<ModelState> m;
@@ -721,6 +728,7 @@ static __global__ void k_set_tick(FrameDev* f, int tick, FrameDev* host_mirror) 
 }
 // MaskFusion::setTick (Core/MaskFusion.h:206): the run loop uses it to start at / skip to a frame number
 extern "C" int mf_set_tick(mf_ctx* c, int32_t tick) {
+    settle(c);
     if (!c || tick < 1) return MF_EINVAL;
     if (!c->map_ready && tick != 1) { c->err = "setTick before the first frame would skip the map initialisation"; return MF_ESTATE; }
     c->host_tick = tick;
@@ -731,11 +739,13 @@ extern "C" int mf_set_tick(mf_ctx* c, int32_t tick) {
 #include "mf_model_api.inl"  // Model-level and sharded-scene entry points
 
 extern "C" int mf_get_tick(mf_ctx* c, int32_t* tick) {
+    settle(c);
     if (!c || !tick) return MF_EINVAL;
     *tick = c->host_tick;
     return MF_OK;
 }
 extern "C" int mf_num_models(mf_ctx* c, int32_t* n) {
+    settle(c);
     if (!c || !n) return MF_EINVAL;
     *n = (int32_t)c->models.size();
     return MF_OK;
@@ -746,12 +756,14 @@ static ModelState* model_at(mf_ctx* c, int32_t i) {
 }
 // the ids of the model list in list order -- host state only, no synchronisation (mf_model_info waits for the surfel count)
 extern "C" int mf_get_model_ids(mf_ctx* c, int32_t* ids, int32_t capacity, int32_t* n) {
+    settle(c);
     if (!c || !ids || !n || capacity < (int32_t)c->models.size()) return MF_EINVAL;
     for (size_t i = 0; i < c->models.size(); ++i) ids[i] = c->models[i]->id;
     *n = (int32_t)c->models.size();
     return MF_OK;
 }
 extern "C" int mf_get_pose(mf_ctx* c, int32_t model, float* out) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !out) return MF_EINVAL;
     int rc = mf_sync(c);
@@ -766,6 +778,7 @@ extern "C" int mf_get_pose(mf_ctx* c, int32_t model, float* out) {
     return MF_OK;
 }
 extern "C" int mf_get_surfel_count(mf_ctx* c, int32_t model, uint32_t* count) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !count) return MF_EINVAL;
     int rc = mf_sync(c);
@@ -774,6 +787,7 @@ extern "C" int mf_get_surfel_count(mf_ctx* c, int32_t model, uint32_t* count) {
     return MF_OK;
 }
 extern "C" int mf_model_info(mf_ctx* c, int32_t model, mf_model_info_t* out) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !out) return MF_EINVAL;
     int rc = mf_sync(c);
@@ -783,12 +797,14 @@ extern "C" int mf_model_info(mf_ctx* c, int32_t model, mf_model_info_t* out) {
     return MF_OK;
 }
 extern "C" int mf_model_state_dev(mf_ctx* c, int32_t model, float* d_out16) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !d_out16) return MF_EINVAL;
     launch_model_state(m->d_pose, m->d_frame, d_out16, c->stream);
     return check_launch(c);
 }
 extern "C" int mf_get_icp_stats(mf_ctx* c, int32_t model, float* e, float* n) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !e || !n) return MF_EINVAL;
     int rc = mf_sync(c);
@@ -812,6 +828,7 @@ static int download_pose_log(mf_ctx* c, ModelState& m, std::vector<int64_t>& ts,
     return MF_OK;
 }
 extern "C" int mf_get_pose_log(mf_ctx* c, int32_t model, int64_t* ts, float* p7, uint32_t max_entries, uint32_t* count) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !count) return MF_EINVAL;
     std::vector<int64_t> t; std::vector<float> p;
@@ -839,6 +856,7 @@ static int write_pose_file(mf_ctx* c, const std::string& dir, int id, const std:
 }
 // MaskFusion::exportPoses (Core/MaskFusion.cpp:851-879): poses-<id>.txt for live and dropped models
 extern "C" int mf_export_poses(mf_ctx* c, const char* export_dir) {
+    settle(c);
     if (!c || !export_dir) return MF_EINVAL;
     const std::string dir(export_dir);
     for (auto& m : c->models) {
@@ -862,6 +880,7 @@ extern "C" int mf_export_poses(mf_ctx* c, const char* export_dir) {
 // MaskFusion::savePly (Core/MaskFusion.cpp:733-849): cloud-<id>.ply, binary little endian, model frame, normals negated,
 // only surfels whose confidence exceeds the model's threshold
 extern "C" int mf_save_ply(mf_ctx* c, const char* export_dir) {
+    settle(c);
     if (!c || !export_dir) return MF_EINVAL;
     int rc = mf_sync(c);
     if (rc != MF_OK) return rc;
@@ -896,6 +915,7 @@ extern "C" int mf_save_ply(mf_ctx* c, const char* export_dir) {
     return MF_OK;
 }
 extern "C" int mf_get_track_stats(mf_ctx* c, int32_t model, float* out8) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !out8) return MF_EINVAL;
     int rc = mf_sync(c);
@@ -908,6 +928,7 @@ extern "C" int mf_get_track_stats(mf_ctx* c, int32_t model, float* out8) {
 // how many Gauss-Newton iterations of the model's last geometric tracking step solved a system outside the solver's stated domain (fewer
 // than 6 inliers, or a pivot below 1e-8 of the largest diagonal entry, i.e. cond(A) > 1e8): DESIGN.md finding F4
 extern "C" int mf_get_gn_condition(mf_ctx* c, int32_t model, int32_t* ill_iterations) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !ill_iterations) return MF_EINVAL;
     int rc = mf_sync(c);
@@ -916,6 +937,7 @@ extern "C" int mf_get_gn_condition(mf_ctx* c, int32_t model, int32_t* ill_iterat
     return MF_OK;
 }
 extern "C" int mf_get_last_fillin(mf_ctx* c, int32_t* used) {
+    settle(c);
     if (!c || !used) return MF_EINVAL;
     int rc = mf_sync(c);
     if (rc != MF_OK) return rc;
@@ -924,6 +946,7 @@ extern "C" int mf_get_last_fillin(mf_ctx* c, int32_t* used) {
     return MF_OK;
 }
 extern "C" int mf_download_segmentation(mf_ctx* c, uint8_t* out) {
+    settle(c);
     if (!c || !out) return MF_EINVAL;
     int rc = mf_sync(c);
     if (rc != MF_OK) return rc;
@@ -992,6 +1015,7 @@ extern "C" int mf_write_png_gray8(const char* path, const uint8_t* img, int32_t 
     return ok ? MF_OK : MF_EINVAL;
 }
 extern "C" int mf_export_segmentation_png(mf_ctx* c, const char* path) {
+    settle(c);
     if (!c || !path) return MF_EINVAL;
     std::vector<uint8_t> img((size_t)c->P);
     int rc = mf_download_segmentation(c, img.data());
@@ -1003,6 +1027,7 @@ extern "C" int mf_export_segmentation_png(mf_ctx* c, const char* path) {
 }
 
 extern "C" int mf_download_map(mf_ctx* c, int32_t model, float* out, uint32_t max_count, uint32_t* count) {
+    settle(c);
     ModelState* ms = model_at(c, model);
     if (!ms || !out || !count) return MF_EINVAL;
     require_dense(c, *ms);     // Model::downloadMap hands out the surfels in order, slot by slot: a sparse buffer is compacted first
@@ -1057,7 +1082,11 @@ static const SegRef kSegParams[] = {
 };
 
 extern "C" int mf_set_param(mf_ctx* c, const char* key, double value) {
+    settle(c);
     if (!c || !key) return MF_EINVAL;
+    if (!strcmp(key, "deferPredict")) { c->defer_predict = value != 0; return MF_OK; }   // 0: every prediction at the end of its own frame
+    if (!strcmp(key, "fusedBinFilter")) { c->fused_bin_filter = value != 0; return MF_OK; }   // 0: k_splat_bin and k_bilateral as two launches in the fused head
+    if (!strcmp(key, "fusedFramePyramids")) { c->fused_frame_pyramids = value != 0; return MF_OK; }   // 0: k_frame_pyramid and k_model_pyramid as two launches
     if (!strcmp(key, "hostProfileReset")) { for (double& v : c->host_us) v = 0; c->host_calls = 0; return MF_OK; }
     if (!strcmp(key, "timings")) { c->timings_on = value != 0; return MF_OK; }
     if (!strcmp(key, "passTimings")) {
@@ -1150,6 +1179,7 @@ extern "C" int mf_set_param(mf_ctx* c, const char* key, double value) {
     return MF_EINVAL;
 }
 extern "C" int mf_get_param(mf_ctx* c, const char* key, double* value) {
+    settle(c);
     if (!c || !key || !value) return MF_EINVAL;
     if (!strcmp(key, "confidenceThreshold")) { *value = c->models[0]->confThr; return MF_OK; }
     if (!strcmp(key, "splatTileEntries")) { *value = c->tile_entries_cap; return MF_OK; }
@@ -1157,6 +1187,11 @@ extern "C" int mf_get_param(mf_ctx* c, const char* key, double* value) {
     if (!strcmp(key, "cleanTap16")) { *value = c->clean_tap16 ? 1 : 0; return MF_OK; }
     if (!strcmp(key, "fuseLanes")) { *value = c->fuse_lanes; return MF_OK; }
     if (!strcmp(key, "indexPackedTexelBytes")) { *value = c->iclean_is_tap16 ? 16 : 32; return MF_OK; }   // the form "index_packed" holds
+    if (!strcmp(key, "deferPredict")) { *value = c->defer_predict ? 1 : 0; return MF_OK; }
+    if (!strcmp(key, "fusedBinFilter")) { *value = c->fused_bin_filter ? 1 : 0; return MF_OK; }
+    if (!strcmp(key, "fusedFramePyramids")) { *value = c->fused_frame_pyramids ? 1 : 0; return MF_OK; }
+    if (!strcmp(key, "deferredFrames")) { *value = (double)c->deferred_frames; return MF_OK; }
+    if (!strcmp(key, "fusedHeadFrames")) { *value = (double)c->fused_head_frames; return MF_OK; }
     if (!strcmp(key, "densifyCount")) { *value = (float)c->densify_count; return MF_OK; }
     if (!strcmp(key, "unstampedRuns")) {   // test tap: live runs of the background's table that carry "holds a time stamp <= 0" (k_cull_clean lists them)
         MF_HIP(c, hipStreamSynchronize(c->stream));
@@ -1204,6 +1239,7 @@ extern "C" int mf_get_param(mf_ctx* c, const char* key, double* value) {
 }
 
 extern "C" int mf_get_timings(mf_ctx* c, float* ms) {
+    settle(c);
     if (!c || !ms) return MF_EINVAL;
     int rc = mf_sync(c);
     if (rc != MF_OK) return rc;
@@ -1211,14 +1247,15 @@ extern "C" int mf_get_timings(mf_ctx* c, float* ms) {
     return MF_OK;
 }
 extern "C" int mf_get_pass_timings(mf_ctx* c, float* ms) {
+    settle(c);
     if (!c || !ms) return MF_EINVAL;
     int rc = mf_sync(c);
     if (rc != MF_OK) return rc;
     memcpy(ms, c->pass_ms, sizeof(c->pass_ms));
     return MF_OK;
 }
-extern "C" void* mf_get_stream(mf_ctx* c) { return c ? (void*)c->stream : nullptr; }
-extern "C" void* mf_get_input_stream(mf_ctx* c) { return c ? (void*)c->stream : nullptr; }
+extern "C" void* mf_get_stream(mf_ctx* c) { settle(c); return c ? (void*)c->stream : nullptr; }
+extern "C" void* mf_get_input_stream(mf_ctx* c) { settle(c); return c ? (void*)c->stream : nullptr; }
 
 static int debug_read_impl(mf_ctx* c, ModelState& mdl, const char* what, void* out, uint64_t out_bytes) {
     int rc = mf_sync(c);
@@ -1285,10 +1322,12 @@ static int debug_read_impl(mf_ctx* c, ModelState& mdl, const char* what, void* o
     return MF_OK;
 }
 extern "C" int mf_debug_read(mf_ctx* c, const char* what, void* out, uint64_t out_bytes) {
+    settle(c);
     if (!c || !what || !out) return MF_EINVAL;
     return debug_read_impl(c, *c->models[0], what, out, out_bytes);
 }
 extern "C" int mf_debug_read_model(mf_ctx* c, int32_t model, const char* what, void* out, uint64_t out_bytes) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !what || !out) return MF_EINVAL;
     return debug_read_impl(c, *m, what, out, out_bytes);

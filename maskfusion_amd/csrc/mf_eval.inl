@@ -17,6 +17,7 @@ static void eval_free(EvalScratch* e) { delete e; }
 
 extern "C" int mf_model_cloud_nn_dev(mf_ctx* c, int32_t model, float conf_threshold, const float* d_query, int32_t query_stride, int64_t n_query,
                                      const float* query_to_model16, float radius, float* d_dist, int32_t* d_idx) {
+    settle(c);
     if (!c) return MF_EINVAL;
     ModelState* m = model_at(c, model);
     if (!m) { c->err = "mf_model_cloud_nn_dev: no such model"; return MF_EINVAL; }

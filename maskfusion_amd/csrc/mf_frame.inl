@@ -442,7 +442,8 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
 // (performFillIn) is evaluated lazily by the next tracking step from the retained filtered depth.
 // advance: the end-of-frame bookkeeping of this model (processFrame's tail); the tiled prediction runs it as its epilogue, the scatter
 // form is followed by k_frame_advance.
-static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advance = nullptr) {
+// filter: the next frame's depth filter, enqueued with the binning pass (enqueue_fused_head; tiled form only)
+static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advance = nullptr, const SplatFilterJob* filter = nullptr) {
     PassTimer timer(c, m.id == 0 ? MF_PASS_BG_PREDICT : -1);
     m.pred_gray_valid = photometric_on(c);
     if (c->splat_tiles && !(c->object_scatter_splat && m.id != 0)) {
@@ -453,15 +454,35 @@ static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advanc
                                c->cfg.time_delta, c->d_tile_count, c->d_tile_entries, c->tile_entries_cap, c->d_splat_rec0, c->d_splat_rec1,
                                c->d_splat_bbox, m.d_predV, m.d_predN, m.d_predImage, m.d_predTime, c->cur_rgb,
                                gray ? m.d_predGray : nullptr, gray ? m.d_fillGray : nullptr, c->stream, advance, c->ftf_rgb ? 1 : 0,
-                               (c->splat_prof_on && m.id == 0) ? c->d_splat_prof : nullptr, c->splat_tune, vis) == 0)
+                               (c->splat_prof_on && m.id == 0) ? c->d_splat_prof : nullptr, c->splat_tune, vis, filter) == 0)
             return;
     }
+    if (filter) launch_bilateral(filter->depth, filter->out, c->W, c->H, c->stream);   // (not reached: a deferred prediction is a tiled one)
     launch_splat_scatter(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, c->cfg.max_depth_processed, m.confThr,
                          c->cfg.time_delta, c->d_keys, c->stream, surfel_blocks(c, m));
     const bool gray = photometric_on(c) ;
     launch_splat_resolve(m.surf[m.cur], m.d_pose, c->d_keys, c->W, c->H, c->K, m.d_predV, m.d_predN, m.d_predImage, m.d_predTime,
                          m.d_frame, c->cur_rgb, gray ? m.d_predGray : nullptr, gray ? m.d_fillGray : nullptr, c->stream, c->ftf_rgb ? 1 : 0);
     if (advance) launch_frame_advance(m.d_frame, c->W, c->H, advance->host_mirror, m.d_pose, advance->bg_pose, advance->log_slot, c->stream);
+}
+
+// "deferPredict": the background's prediction of frame t is not enqueued at the end of call t but kept as a record (mf_ctx::pending) and drawn at
+// the head of call t + 1, where its binning pass shares a launch with frame t + 1's depth filter (enqueue_fused_head).  Eligible: a single-model
+// context that tracks with the geometric term alone -- the tile pass then reads no caller-owned image -- through the tiled form, with no timings on
+// (the stage and pass timings bracket the prediction where it is enqueued today).  The host-side bookkeeping of the frame stays in call t.
+static bool defer_eligible(const mf_ctx* c) {
+    return c->defer_predict && c->cfg.enable_multiple_models == 0 && c->models.size() == 1 && !photometric_on(c) && c->cfg.so3 == 0 && c->splat_tiles &&
+           splat_tiled_applies(c->W, c->H, c->splat_tune) && !c->timings_on && !c->pass_timings_on && !c->splat_prof_on;
+}
+// Enqueues a pending prediction exactly as the end of its frame would have, and clears the record.  The first statement of every entry point that
+// takes a context (but the two process-frame entries, which may draw it in their fused head, and mf_destroy, which drops it): whatever reads or
+// changes the context's state afterwards finds the stream as an undeferred frame leaves it.
+static void settle(mf_ctx* c) {
+    if (!c || !c->pending.m) return;
+    ModelState* m = c->pending.m;
+    const FrameAdvance adv = c->pending.adv;
+    c->pending.m = nullptr;
+    enqueue_predict(c, *m, &adv);
 }
 
 // ObjBatch of the object models in `ms` (mf_internal.h): one entry per model, staged through a pinned slot of the ring and copied to the
@@ -603,6 +624,36 @@ static int enqueue_preprocess(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
     return MF_OK;
 }
 
+// The head of frame k when frame k - 1's prediction is pending ("deferPredict") and frame k tracks the background alone: the map chain of frame
+// k - 1 (binning -> tile pass -> model-side pyramid) and the image chain of frame k (depth filter -> frame pyramid) meet only where the model-side
+// pyramid reads the tile pass's maps, so they share launches:
+//   A  k_bin_bilateral        { binning of k - 1 | depth filter of k }     ("fusedBinFilter"; 0: k_splat_bin, k_bilateral)
+//   B  k_splat_tile           the tile pass of k - 1 with its end-of-frame epilogue, unchanged
+//   C  k_frame_model_pyramid  { frame pyramid of k | model-side pyramid }  ("fusedFramePyramids"; 0: k_frame_pyramid, k_model_pyramid)
+// -- what enqueue_predict and enqueue_preprocess enqueue for such a pair of frames, in another order: every kernel runs the same instructions on the
+// same data.  A map that needs a visibility list gets its cull launch in front of A, as enqueue_predict issues it.  The tracking loop that follows
+// is told that its model-side pyramid stands.
+static void enqueue_fused_head(mf_ctx* c, const uint8_t* d_rgb, const float* d_depth, long k, const float* fill_depth) {
+    ModelState* m = c->pending.m;
+    const FrameAdvance adv = c->pending.adv;
+    c->pending.m = nullptr;
+    const int set = (int)(k & 1);
+    float* depthF = c->d_depthF[k % 3];
+    const SplatFilterJob job{d_depth, depthF, c->fused_bin_filter ? 1 : 0};
+    enqueue_predict(c, *m, &adv, &job);                                    // A, B
+    const float* fill = m->allowFillIn ? fill_depth : nullptr;
+    if (c->fused_frame_pyramids) {
+        launch_frame_model_pyramid(depthF, c->d_vmap[set], c->d_nmap[set], c->cfg.depth_cutoff, m->d_predV, m->d_predN, fill, m->d_frame, m->d_pose,
+                                   m->d_vmap_g, m->d_nmap_g, c->W, c->H, c->K, c->stream);   // C
+    } else {
+        launch_frame_pyramid(depthF, c->d_vmap[set], c->d_nmap[set], c->W, c->H, c->K, c->cfg.depth_cutoff, c->stream);
+        launch_model_pyramid(m->d_predV, m->d_predN, fill, m->d_frame, m->d_pose, nullptr, m->d_vmap_g, m->d_nmap_g, c->W, c->H, c->K, c->stream);
+    }
+    c->cur_rgb = d_rgb;
+    c->cur_depth = d_depth;
+    c->fused_head_frames++;
+}
+
 static int download_pose_log(mf_ctx* c, ModelState& m, std::vector<int64_t>& ts, std::vector<float>& p7);
 
 // GlobalProjection::project for one model (fixed confidence threshold 12, GlobalProjection.cpp:43-107).  The background model goes
@@ -712,8 +763,9 @@ static int enqueue_fusion_loop(mf_ctx* c, size_t first, bool multi, const uint8_
 
 // predict() (Core/MaskFusion.cpp:569) + tick++ (:573) + the pose log entry (:580-596) + incrementAge (:600) over models[first..].
 // first == 1: models[0] is the stand-in of a background that lives in another context -- it is not drawn, but its frame state advances.
+// may_defer: an eligible background's prediction becomes the context's pending record instead ("deferPredict": settle / enqueue_fused_head draw it)
 static int enqueue_predict_loop(mf_ctx* c, size_t first, bool may_batch, int64_t timestamp, const uint8_t* d_rgb, const float* d_depth,
-                                const float* depthF, const uint8_t* mask, float weight_multiplier) {
+                                const float* depthF, const uint8_t* mask, float weight_multiplier, bool may_defer = false) {
     const mf_config& g = c->cfg;
     ModelState& bg = *c->models[0];
     auto log_slot = [&](ModelState& m) -> float* {   // MaskFusion.cpp:580-596
@@ -752,7 +804,13 @@ static int enqueue_predict_loop(mf_ctx* c, size_t first, bool may_batch, int64_t
     for (size_t i = first; i < c->models.size(); ++i) {
         ModelState& m = *c->models[i];
         const FrameAdvance adv{m.h_frame, i == 0 ? nullptr : bg.d_pose, log_slot(m)};
-        enqueue_predict(c, m, &adv);   // ... with tick++ / the fill-in decision / the pose log entry as its epilogue
+        if (may_defer && first == 0 && defer_eligible(c)) {   // (one model: the background)
+            c->pending.m = &m; c->pending.adv = adv;
+            m.pred_gray_valid = false;                        // what enqueue_predict would have set: no photometric term
+            c->deferred_frames++;
+        } else {
+            enqueue_predict(c, m, &adv);   // ... with tick++ / the fill-in decision / the pose log entry as its epilogue
+        }
         m.age++;  // incrementAge, :600
     }
     return MF_OK;
@@ -853,8 +911,15 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
     TrackingPlan plan;
     tracking_plan(c, 0, g.track_all_models != 0, plan);
     const bool pyr_built = c->fused_preprocess && c->map_ready && !(in_pose16 && !bootstrap);
-    int prc = enqueue_preprocess(c, d_rgb, d_depth, k, c->map_ready, pyr_built ? &plan : nullptr, depthF_prev);
-    if (prc != MF_OK) return prc;
+    // a pending prediction ("deferPredict") is drawn in this frame's head when the frame tracks the background alone; any other frame settles first
+    const bool fused_head = c->pending.m && pyr_built && !plan.batch && plan.tracked.size() == 1 && plan.tracked.front() == c->pending.m;
+    if (fused_head) {
+        enqueue_fused_head(c, d_rgb, d_depth, k, depthF_prev);
+    } else {
+        settle(c);
+        int prc = enqueue_preprocess(c, d_rgb, d_depth, k, c->map_ready, pyr_built ? &plan : nullptr, depthF_prev);
+        if (prc != MF_OK) return prc;
+    }
 
     if (!c->map_ready) {
         c->map_ready = true;
@@ -997,7 +1062,7 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
         mark(c, 7);
     }
     {
-        int rc = enqueue_predict_loop(c, 0, multi && c->map_ready && k > 0, timestamp, d_rgb, d_depth, depthF, mask, weight_multiplier);
+        int rc = enqueue_predict_loop(c, 0, multi && c->map_ready && k > 0, timestamp, d_rgb, d_depth, depthF, mask, weight_multiplier, true);
         if (rc != MF_OK) return rc;
     }
     mark(c, 8);
@@ -1022,12 +1087,14 @@ extern "C" int mf_process_frame_dev(mf_ctx* c, const uint8_t* d_rgb, const float
 
 // FrameData::classIDs (Core/FrameData.h:25-48) for frames handed over as device pointers: class_ids[v] is the class of mask value v
 extern "C" int mf_set_mask_class_ids(mf_ctx* c, const int32_t* class_ids, int32_t n) {
+    settle(c);
     if (!c || n < 0 || n > 256 || (n > 0 && !class_ids)) return MF_EINVAL;
     c->mask_classes.assign(class_ids, class_ids + n);
     return MF_OK;
 }
 
 extern "C" int mf_sync(mf_ctx* c) {
+    settle(c);
     if (!c) return MF_EINVAL;
     MF_HIP(c, hipStreamSynchronize(c->stream));
     if (c->pass_timings_on)
@@ -1127,6 +1194,7 @@ static void launch_fillin_decision(FrameDev* f, int W, int H, FrameDev* host_mir
 }
 
 extern "C" int mf_predict(mf_ctx* c) {
+    settle(c);
     if (!c) return MF_EINVAL;
     const uint8_t* keep = c->cur_rgb;
     c->cur_rgb = nullptr;  // the caller's frame buffer may be gone: the fill-in intensity keeps its last contents

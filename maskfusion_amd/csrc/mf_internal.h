@@ -148,6 +148,11 @@ void launch_vmap_nmap(const float* depth, float* vmap, float* nmap, int W, int H
 void launch_frame_pyramid(const float* depth, float* const vmap[3], float* const nmap[3], int W, int H, Intr k, float cutoff,
                           hipStream_t s);
 
+// launch_frame_pyramid's and launch_model_pyramid's work (device pose) in one launch (mf_odometry.hip: k_frame_model_pyramid)
+void launch_frame_model_pyramid(const float* depthF, float* const fvmap[3], float* const fnmap[3], float cutoff, const float4* predV, const float4* predN,
+                                const float* fillDepth, const FrameDev* frame, const PoseDev* pose, float* const vmaps[3], float* const nmaps[3], int W, int H,
+                                Intr k, hipStream_t s);
+
 // ---------------- odometry ----------------
 // Fused RGBDOdometry::initICPModel.  pose: device PoseDev (R,t used).  fill-in inputs may be null (no fill-in).
 void launch_model_pyramid(const float4* predV, const float4* predN, const float* fillDepth, const FrameDev* frame,
@@ -358,12 +363,16 @@ struct SplatTuning { int sprite_lanes = 4, tile_threads = 512, tile_h = 24; };  
 // The end-of-frame bookkeeping (k_frame_advance: pose log entry, fill-in decision for the next tracking step, tick++, host mirror) as
 // the epilogue of the tiled prediction: its last workgroup to finish runs it, one launch less per model and frame.
 struct FrameAdvance { FrameDev* host_mirror; const PoseDev* bg_pose; float* log_slot; };
+// filter (optional): the NEXT frame's depth filter (launch_bilateral(depth, out, W, H)), enqueued with the binning pass: in its launch (fused != 0,
+// k_bin_bilateral) or as a launch of its own between the binning pass and the tile pass.  The two read and write nothing in common.
+struct SplatFilterJob { const float* depth; float* out; int fused; };
 int launch_splat_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth, float confThreshold,
                        int timeDelta, int* tile_count, int* entries /*[tiles][entries_cap / tiles]*/, int entries_cap,
                        float4* rec0 /*[src.cap]*/, float4* rec1 /*[src.cap]*/, void* bbox /*[src.cap] x 8 B*/, float4* predV, float4* predN,
                        uchar4* predImage, uint16_t* predTime, const uint8_t* rgb, uint8_t* predGray, uint8_t* fillGray, hipStream_t s,
                        const FrameAdvance* advance = nullptr, int fillPassthrough = 0, unsigned long long* prof = nullptr /*[tiles][8] stamps*/,
-                       SplatTuning tune = SplatTuning(), const VisList* vis = nullptr);
+                       SplatTuning tune = SplatTuning(), const VisList* vis = nullptr, const SplatFilterJob* filter = nullptr);
+bool splat_tiled_applies(int W, int H, SplatTuning tune);   // launch_splat_tiled would not return -1 for this image
 // ---- the surfel passes of ALL object models of a frame, one launch per pass (grid.z = model) ----
 // An object model holds a few thousand surfels: each of its ~11 per-frame launches is pure launch latency (~85 us per object and frame in
 // round 2's profile).  The batched kernels are the single-model kernels' bodies called with one model's arguments, picked from a device

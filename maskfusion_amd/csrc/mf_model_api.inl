@@ -26,6 +26,7 @@ static const uint8_t* current_mask(const mf_ctx* c) { return c->cfg.enable_multi
 // upload + MaskFusion::filterDepth (:217) + Model::generateCUDATextures (Model.cpp:350-389) + intensity pyramid: everything of
 // processFrame that does not touch a model.  mask: model id per pixel = what textureMask holds for fuse / clean (NULL: left as it is)
 extern "C" int mf_stage_frame(mf_ctx* c, const uint8_t* rgb, const float* depth, const uint8_t* mask) {
+    settle(c);
     if (c) c->vis_tag.model = nullptr;   // (a visibility list belongs to one frame and one pose)
     if (!c || !rgb || !depth) return MF_EINVAL;
     hipStream_t sin = c->stream;
@@ -44,6 +45,7 @@ extern "C" int mf_stage_frame(mf_ctx* c, const uint8_t* rgb, const float* depth,
 // synchronised -- the caller orders the producers of the three buffers on the context's stream (mf_get_stream) and keeps rgb / depth alive
 // and unmodified until the frame's model-level calls have completed there.
 extern "C" int mf_stage_frame_dev(mf_ctx* c, const uint8_t* d_rgb, const float* d_depth, const uint8_t* d_mask) {
+    settle(c);
     if (c) c->vis_tag.model = nullptr;   // (a visibility list belongs to one frame and one pose)
     if (!c || !d_rgb || !d_depth) return MF_EINVAL;
     if (d_mask) MF_HIP(c, hipMemcpyAsync(c->d_mask_tex, d_mask, (size_t)c->P, hipMemcpyDeviceToDevice, c->stream));
@@ -56,6 +58,7 @@ extern "C" int mf_stage_frame_dev(mf_ctx* c, const uint8_t* d_rgb, const float* 
 
 // Model::initialise (Core/Model/Model.cpp:240-285): the map of `model` becomes the staged frame's point cloud
 extern "C" int mf_model_initialise(mf_ctx* c, int32_t model) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || c->frame_no == 0) return MF_EINVAL;
     const long k = staged_frame(c);
@@ -71,6 +74,7 @@ extern "C" int mf_model_initialise(mf_ctx* c, int32_t model) {
 
 // test / tooling tap with no upstream twin: replace the surfel buffer of `model` (count records of 12 floats, mf_download_map's layout)
 extern "C" int mf_model_upload_map(mf_ctx* c, int32_t model, const float* surfels, uint32_t count) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || (!surfels && count) || (int)count > m->cap) return MF_EINVAL;
     MF_HIP(c, hipStreamSynchronize(c->stream));
@@ -96,6 +100,7 @@ extern "C" int mf_model_upload_map(mf_ctx* c, int32_t model, const float* surfel
 
 // Model::overridePose (Core/Model/Model.h:235-238): lastPose = pose; pose = p
 extern "C" int mf_model_override_pose(mf_ctx* c, int32_t model, const float* pose16) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !pose16) return MF_EINVAL;
     launch_override_pose(m->d_pose, pose16, 0, m->h_pose, c->stream);
@@ -106,6 +111,7 @@ extern "C" int mf_model_override_pose(mf_ctx* c, int32_t model, const float* pos
 
 // Model::computeFusionWeight(weightMultiplier) (Core/Model/Model.cpp:449-464) from the model's pose and lastPose
 extern "C" int mf_model_fusion_weight(mf_ctx* c, int32_t model, float weight_multiplier, float* out) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || !out) return MF_EINVAL;
     int rc = mf_sync(c);
@@ -120,6 +126,7 @@ extern "C" int mf_model_fusion_weight(mf_ctx* c, int32_t model, float weight_mul
 extern "C" int mf_model_perform_tracking(mf_ctx* c, int32_t model, int32_t frame_to_frame_rgb, int32_t rgb_only, float icp_weight,
                                          int32_t pyramid, int32_t fast_odom, int32_t so3, float max_depth_processed, int64_t log_timestamp,
                                          int32_t try_fill_in) {
+    settle(c);
     if (c) c->vis_tag.model = nullptr;   // (a visibility list belongs to one frame and one pose)
     ModelState* m = model_at(c, model);
     (void)log_timestamp;   // only forwarded to a debug print upstream
@@ -153,6 +160,7 @@ extern "C" int mf_model_perform_tracking(mf_ctx* c, int32_t model, int32_t frame
 
 // Model::predictIndices(time, maxDepth, timeDelta) (Core/Model/Model.h:162, ModelProjection.cpp:100-152)
 extern "C" int mf_model_predict_indices(mf_ctx* c, int32_t model, int32_t time, float max_depth, int32_t time_delta) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m) return MF_EINVAL;
     hipStream_t s = c->stream;
@@ -172,6 +180,7 @@ extern "C" int mf_model_predict_indices(mf_ctx* c, int32_t model, int32_t time, 
 // Model.cpp:466-647) with the staged frame's textures: data association against the index map of the last
 // mf_model_predict_indices of THIS model, then the update pass (in place).
 extern "C" int mf_model_fuse(mf_ctx* c, int32_t model, int32_t time, float depth_cutoff, float weight_multiplier) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || c->frame_no == 0) return MF_EINVAL;
     hipStream_t s = c->stream;
@@ -191,6 +200,7 @@ extern "C" int mf_model_fuse(mf_ctx* c, int32_t model, int32_t time, float depth
 // Model::clean(time, graph, timeDelta, depthCutoff, isFern, depthFiltered, mask) (Core/Model/Model.h:146-147, Model.cpp:649-772):
 // uses the index map of the last mf_model_predict_indices and the new-surfel records of the last mf_model_fuse of THIS model
 extern "C" int mf_model_clean(mf_ctx* c, int32_t model, int32_t time, int32_t time_delta, float depth_cutoff) {
+    settle(c);
     ModelState* m = model_at(c, model);
     (void)depth_cutoff;   // the maxDepth uniform of copy_unstable.vert is never read (:53-157)
     if (!m || c->frame_no == 0) return MF_EINVAL;
@@ -210,6 +220,7 @@ extern "C" int mf_model_clean(mf_ctx* c, int32_t model, int32_t time, int32_t ti
 // Model::combinedPredict(maxDepth, time, maxTime, timeDelta, ACTIVE) (Core/Model/Model.h:158, ModelProjection.cpp:187-268);
 // the reference only ever calls it with time == maxTime (MaskFusion.cpp:616-628)
 extern "C" int mf_model_combined_predict(mf_ctx* c, int32_t model, float max_depth, int32_t time, int32_t max_time, int32_t time_delta) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || time != max_time) return MF_EINVAL;
     set_model_tick(c, *m, time);
@@ -224,6 +235,7 @@ extern "C" int mf_model_combined_predict(mf_ctx* c, int32_t model, float max_dep
 // the tail of processFrame for a frame driven through the Model-level calls: tick++ (:573), fill-in decision for the next
 // tracking step (requiresFillIn), pose log entry (:580-596), age++ (:600)
 extern "C" int mf_end_frame(mf_ctx* c, int64_t timestamp) {
+    settle(c);
     if (!c) return MF_EINVAL;
     ModelState& bg = *c->models[0];
     for (auto& m : c->models) {
@@ -249,6 +261,7 @@ extern "C" int mf_end_frame(mf_ctx* c, int64_t timestamp) {
 // ------------------------------------------------------------------------------------------------
 // the tracking loop, Core/MaskFusion.cpp:247-276 (trackable classes, static objects follow the background, the 0.2 m jump rule)
 extern "C" int mf_track_models(mf_ctx* c, int32_t first_model, int32_t track_all_models) {
+    settle(c);
     if (c) c->vis_tag.model = nullptr;   // (a visibility list belongs to one frame and one pose)
     if (!c || c->frame_no == 0 || first_model < 0 || first_model > 1 || (first_model == 0 && !c->map_ready)) return MF_EINVAL;
     const long k = staged_frame(c);
@@ -266,6 +279,7 @@ extern "C" int mf_track_models(mf_ctx* c, int32_t first_model, int32_t track_all
 // the fusion loop, Core/MaskFusion.cpp:539-565, preceded -- when spawned_model >= 1 -- by the spawn-frame pass of that model
 // (:342-353: predictIndices; fuse(maxDepthProcessed, weight 100); clean) and by the per-frame object parameters (:335-339, :369-374)
 extern "C" int mf_fuse_models(mf_ctx* c, int32_t first_model, float weight_multiplier, int32_t spawned_model) {
+    settle(c);
     if (!c || c->frame_no == 0 || first_model < 0 || first_model > 1 || (first_model == 0 && !c->map_ready) || spawned_model == 0 ||
         spawned_model >= (int32_t)c->models.size())
         return MF_EINVAL;
@@ -289,6 +303,7 @@ extern "C" int mf_fuse_models(mf_ctx* c, int32_t first_model, float weight_multi
 // predict() (:569) and the tail of the frame (tick++ :573, pose log :580-596, incrementAge :600) -- the end of a frame driven through
 // mf_stage_frame / mf_track_models / mf_fuse_models (do not call mf_end_frame as well)
 extern "C" int mf_predict_models(mf_ctx* c, int32_t first_model, int64_t timestamp) {
+    settle(c);
     if (!c || c->frame_no == 0 || first_model < 0 || first_model > 1 || (first_model == 0 && !c->map_ready)) return MF_EINVAL;
     const long k = staged_frame(c);
     int rc = enqueue_predict_loop(c, (size_t)first_model, c->cfg.enable_multiple_models != 0, timestamp, c->cur_rgb, c->cur_depth, c->d_depthF[k % 3],
@@ -299,6 +314,7 @@ extern "C" int mf_predict_models(mf_ctx* c, int32_t first_model, int64_t timesta
 }
 // mf_model_state_dev for every model of the list: d_out16[i * 16 ..] = state of models[i] (one call per frame instead of one per model)
 extern "C" int mf_models_state_dev(mf_ctx* c, float* d_out16, int32_t capacity) {
+    settle(c);
     if (!c || !d_out16 || capacity < (int32_t)c->models.size()) return MF_EINVAL;
     for (size_t i = 0; i < c->models.size(); ++i) launch_model_state(c->models[i]->d_pose, c->models[i]->d_frame, d_out16 + 16 * i, c->stream);
     return check_launch(c);
@@ -307,6 +323,7 @@ extern "C" int mf_models_state_dev(mf_ctx* c, float* d_out16, int32_t capacity) 
 // Model::makeNonStatic / makeStatic(globalPose) / isNonstatic (Core/Model/Model.h:263-268): a non-static object model is
 // tracked even when trackAllModels is off; makeStatic re-anchors it to the background's current pose
 extern "C" int mf_make_nonstatic(mf_ctx* c, int32_t model) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m) return MF_EINVAL;
     m->isStatic = false;
@@ -325,6 +342,7 @@ static __global__ void k_make_static(PoseDev* obj, const PoseDev* bg, PoseDev* h
     if (host_mirror) *host_mirror = p;
 }
 extern "C" int mf_make_static(mf_ctx* c, int32_t model) {
+    settle(c);
     if (c) c->vis_tag.model = nullptr;   // (a visibility list belongs to one frame and one pose)
     ModelState* m = model_at(c, model);
     if (!m || model == 0) return MF_EINVAL;
@@ -334,6 +352,7 @@ extern "C" int mf_make_static(mf_ctx* c, int32_t model) {
 }
 // MaskFusion::setTrackableClassIds (Core/MaskFusion.h:246, MaskFusion.cpp:261,940); n = 0 clears the set (everything trackable)
 extern "C" int mf_set_trackable_class_ids(mf_ctx* c, const int32_t* ids, int32_t n) {
+    settle(c);
     if (!c || n < 0 || (n > 0 && !ids)) return MF_EINVAL;
     c->trackable.assign(ids, ids + n);
     return MF_OK;
@@ -346,6 +365,7 @@ extern "C" int mf_set_trackable_class_ids(mf_ctx* c, const int32_t* ids, int32_t
 // ------------------------------------------------------------------------------------------------
 // GlobalProjection::project (Core/Model/GlobalProjection.cpp:43-107) of this context's models only
 extern "C" int mf_export_projection_keys_dev(mf_ctx* c, const int32_t* orders, int32_t n_orders, uint64_t* d_keys_out) {
+    settle(c);
     if (!c || !d_keys_out || n_orders != (int32_t)c->models.size() || (n_orders > 0 && !orders)) return MF_EINVAL;
     hipStream_t s = c->stream;
     bool all_objects = batch_objects_now(c) && c->frame_no > 0;
@@ -371,6 +391,7 @@ extern "C" int mf_export_projection_keys_dev(mf_ctx* c, const int32_t* orders, i
 }
 // GlobalProjection::downloadDirect (:109-114) of a key image merged over all contexts (per-pixel minimum)
 extern "C" int mf_import_projection_keys_dev(mf_ctx* c, const uint64_t* d_keys) {
+    settle(c);
     if (!c || !d_keys) return MF_EINVAL;
     MF_HIP(c, hipMemcpyAsync(c->d_keys, d_keys, (size_t)c->P * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
     launch_global_resolve(c->d_keys, c->d_proj_ids, c->P, c->stream);   // leaves the key image empty again
@@ -425,10 +446,12 @@ static int segmentation_enqueue(mf_ctx* c, const uint8_t* mask, const int32_t* c
 // stream); _end waits for the label stage alone and hands out the decision.
 extern "C" int mf_perform_segmentation_begin(mf_ctx* c, const uint8_t* mask, const int32_t* class_ids, int32_t n_masks, const int32_t* model_ids,
                                              const int32_t* model_class_ids, int32_t n_models, int32_t next_model_id, int32_t allow_new) {
+    settle(c);
     if (!c || c->labels_pending) return MF_EINVAL;
     return segmentation_enqueue(c, mask, class_ids, n_masks, model_ids, model_class_ids, n_models, next_model_id, allow_new, nullptr, nullptr);
 }
 extern "C" int mf_perform_segmentation_end(mf_ctx* c, int32_t* has_new_label, int32_t* new_class_id) {
+    settle(c);
     if (!c || !has_new_label || !new_class_id || !c->labels_pending) return MF_EINVAL;
     c->labels_pending = false;
     MF_HIP(c, hipEventSynchronize(c->ev_labels));
@@ -439,6 +462,7 @@ extern "C" int mf_perform_segmentation_end(mf_ctx* c, int32_t* has_new_label, in
 }
 // the background's share of the fusion loop (Core/MaskFusion.cpp:539-565 for models.front()), ahead of mf_fuse_models, which then skips it
 extern "C" int mf_fuse_background(mf_ctx* c, float weight_multiplier) {
+    settle(c);
     if (!c || c->frame_no == 0 || !c->map_ready) return MF_EINVAL;
     const long k = staged_frame(c);
     if (c->bg_fused_frame == k) { c->err = "mf_fuse_background: the background of this frame is already fused"; return MF_ESTATE; }
@@ -450,16 +474,19 @@ extern "C" int mf_fuse_background(mf_ctx* c, float weight_multiplier) {
 extern "C" int mf_perform_segmentation(mf_ctx* c, const uint8_t* mask, const int32_t* class_ids, int32_t n_masks, const int32_t* model_ids,
                                        const int32_t* model_class_ids, int32_t n_models, int32_t next_model_id, int32_t allow_new,
                                        int32_t* has_new_label, int32_t* new_class_id) {
+    settle(c);
     if (!has_new_label || !new_class_id || (c && c->labels_pending)) return MF_EINVAL;
     return segmentation_enqueue(c, mask, class_ids, n_masks, model_ids, model_class_ids, n_models, next_model_id, allow_new, has_new_label, new_class_id);
 }
 extern "C" int mf_export_segmentation_dev(mf_ctx* c, uint8_t* d_out) {
+    settle(c);
     if (!c || !d_out) return MF_EINVAL;
     MF_HIP(c, hipMemcpyAsync(d_out, c->d_mask_tex, (size_t)c->P, hipMemcpyDeviceToDevice, c->stream));
     return MF_OK;
 }
 // textureMask->Upload(fullSegmentation) (Core/MaskFusion.cpp:297) with a label image computed by another context
 extern "C" int mf_import_segmentation_dev(mf_ctx* c, const uint8_t* d_in) {
+    settle(c);
     if (!c || !d_in) return MF_EINVAL;
     MF_HIP(c, hipMemcpyAsync(c->d_mask_tex, d_in, (size_t)c->P, hipMemcpyDeviceToDevice, c->stream));
     return MF_OK;
@@ -467,6 +494,7 @@ extern "C" int mf_import_segmentation_dev(mf_ctx* c, const uint8_t* d_in) {
 // spawnObjectModel (Core/MaskFusion.cpp:671-684) with an id chosen by the caller (the context that runs the label stage owns
 // getNextModelID); the new model is appended to this context's list, anchored to its background pose
 extern "C" int mf_spawn_object_model(mf_ctx* c, int32_t id, int32_t class_id) {
+    settle(c);
     if (!c || id < 0 || id > 255) return MF_EINVAL;
     for (auto& m : c->models) if (m->id == id) { c->err = "model id in use"; return MF_EINVAL; }
     int rc = spawn_object(c, id, class_id);
@@ -476,12 +504,14 @@ extern "C" int mf_spawn_object_model(mf_ctx* c, int32_t id, int32_t class_id) {
 }
 // inactivateModel (Core/MaskFusion.cpp:686-713): the model leaves the list, its pose log is kept for exportPoses
 extern "C" int mf_drop_model(mf_ctx* c, int32_t model) {
+    settle(c);
     ModelState* m = model_at(c, model);
     if (!m || model == 0) return MF_EINVAL;
     return retire_model(c, (size_t)model);
 }
 // Model::updateStaticPose(globalPose) (Core/Model/Model.h:263): pose = initialC2Winv * background pose
 extern "C" int mf_model_update_static_pose(mf_ctx* c, int32_t model) {
+    settle(c);
     if (c) c->vis_tag.model = nullptr;   // (a visibility list belongs to one frame and one pose)
     ModelState* m = model_at(c, model);
     if (!m || model == 0) return MF_EINVAL;
@@ -491,6 +521,7 @@ extern "C" int mf_model_update_static_pose(mf_ctx* c, int32_t model) {
 // the per-frame object bookkeeping of processFrame for this context's object models: setMaxDepth (Core/MaskFusion.cpp:335-339)
 // and the confidence ramp min(4.5, age / 25) (:369-374)
 extern "C" int mf_update_object_params(mf_ctx* c) {
+    settle(c);
     if (!c) return MF_EINVAL;
     for (size_t i = 1; i < c->models.size(); ++i) {
         c->models[i]->maxDepth = 30.f + 30.f * 1.2f;

@@ -22,6 +22,7 @@
 #include "mf_device.h"
 #include "mf_rgbd_device.h"
 #include "mf_bilateral_device.h"
+#include "mf_frame_pyramid_device.h"
 
 namespace mf {
 
@@ -1680,7 +1681,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     int before, after;
     if (interleave) { before = (int)(((long long)b * npyr) / total); after = (int)(((long long)(b + 1) * npyr) / total); }
     else { before = b < nbil ? 0 : b - nbil; after = b < nbil ? 0 : b - nbil + 1; }
-    if (after == before) { bilateral_body(depth, out, W, H, tile, b - before); return; }
+    if (after == before) { bilateral_body(depth, out, W, H, tile, b - before, (int)threadIdx.x, true); return; }
     // (a.b.n > 0: the batched tracker's pyramids, model by model -- k_model_pyramid's grid.z unrolled)
     const int j = before;
     model_pyramid_body(a, (j % per) % gx, (j % per) / gx, j / per);
@@ -1724,6 +1725,44 @@ void launch_bilateral_model_pyramid_batch(const float* depth, float* depthF, con
     a.fillDepth = fillDepth; a.W = W; a.H = H; a.k = k; a.b = b;
     const int nbil = bilateral_grid(W, H), npyr = (((W >> 2) + 15) / 16) * (((H >> 2) + 3) / 4) * b.n;
     hipLaunchKernelGGL(k_bilateral_model_pyramid, dim3(nbil + npyr), dim3(256), 0, s, depth, depthF, W, H, nbil, (nbil + npyr > 1536) ? 1 : 0, a);
+}
+
+// The frame's pyramid and the model-side pyramid of the same tracking step in ONE launch ("fusedFramePyramids"), for a frame whose prediction was
+// deferred into its successor's head (mf_frame.inl: enqueue_fused_head): there the model-side pyramid can no longer ride beside the depth filter --
+// the prediction it reads is drawn behind the filter --, and both pyramids are streams that wait for nothing but the tile pass.  The first nfp
+// workgroups run frame_pyramid_body (mf_frame_pyramid_device.h: every operation rounded on its own), the others model_pyramid_body with their index
+// as k_model_pyramid's 2-D block: the same instructions on the same data as the two kernels, hence the same bits.  Both counts are multiples of 8
+// and a launch that is not resident at once interleaves the halves in groups of 8 workgroups, so that a frame tile's index keeps the XCD that holds
+// its neighbours (xcd_contiguous_tile) either way.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_frame_model_pyramid(const FramePyrArgs f, int nfp, int interleave, const PyrArgs a) {
+    __shared__ float lds[kFpLdsFloats];
+    const int groups = (int)gridDim.x >> 3, gpyr = groups - (nfp >> 3), g = (int)blockIdx.x >> 3, lane = (int)blockIdx.x & 7;
+    int before, after;   // pyramid groups in front of group g / of group g + 1 (a Bresenham walk, as k_bilateral_model_pyramid's)
+    if (interleave) { before = (int)(((long long)g * gpyr) / groups); after = (int)(((long long)(g + 1) * gpyr) / groups); }
+    else { before = g < (nfp >> 3) ? 0 : g - (nfp >> 3); after = g < (nfp >> 3) ? 0 : before + 1; }
+    if (after == before) { frame_pyramid_body(f, lds, ((g - before) << 3) + lane); return; }
+    const int gx = ((a.W >> 2) + 15) / 16, gy = ((a.H >> 2) + 3) / 4, j = (before << 3) + lane;
+    if (j >= gx * gy) return;   // (padding of the pyramid half to a multiple of 8)
+    model_pyramid_body(a, j % gx, j / gx, 0);
+}
+
+void launch_frame_model_pyramid(const float* depthF, float* const fvmap[3], float* const fnmap[3], float cutoff, const float4* predV, const float4* predN,
+                                const float* fillDepth, const FrameDev* frame, const PoseDev* pose, float* const vmaps[3], float* const nmaps[3], int W, int H,
+                                Intr k, hipStream_t s) {
+    FramePyrArgs f;
+    f.depth = depthF; f.W = W; f.H = H; f.k = k; f.cutoff = cutoff;
+    for (int i = 0; i < 3; ++i) { f.vmap[i] = fvmap[i]; f.nmap[i] = fnmap[i]; }
+    PyrArgs a;
+    a.predV = predV; a.predN = predN; a.fillDepth = fillDepth; a.frame = frame; a.pose = pose;
+    a.hostPose = 0;
+    for (int i = 0; i < 9; ++i) a.R[i] = 0.f;
+    for (int i = 0; i < 3; ++i) a.t[i] = 0.f;
+    for (int i = 0; i < 3; ++i) { a.vm[i] = vmaps[i]; a.nm[i] = nmaps[i]; }
+    a.W = W; a.H = H; a.k = k;
+    a.b.n = 0;
+    const int nfp = xcd_padded_grid(frame_pyramid_tiles(W, H)), npyr = xcd_padded_grid((((W >> 2) + 15) / 16) * (((H >> 2) + 3) / 4));
+    // (six 256-thread workgroups per compute unit: 1 536 are resident at once, as for k_bilateral_model_pyramid)
+    hipLaunchKernelGGL(k_frame_model_pyramid, dim3(nfp + npyr), dim3(256), 0, s, f, nfp, (nfp + npyr > 1536) ? 1 : 0, a);
 }
 
 void launch_model_pyramid_batch(const TrackBatch& b, const float* fillDepth, int W, int H, Intr k, hipStream_t s) {

@@ -56,6 +56,7 @@ extern "C" int mf_default_palette(float* out, int32_t capacity, int32_t* n) {
 }
 
 extern "C" int mf_default_render_view(mf_ctx* c, int32_t width, int32_t height, int32_t icl, mf_render_view_t* out) {
+    settle(c);
     if (!c || !out) return MF_EINVAL;
     if (width < 1 || height < 1 || width > kRenderMaxSide || height > kRenderMaxSide) return render_fail(c, "render size outside 1 .. 4096");
     float pose[16];
@@ -82,6 +83,7 @@ extern "C" int mf_default_render_view(mf_ctx* c, int32_t width, int32_t height, 
 }
 
 extern "C" int mf_sensor_render_view(mf_ctx* c, mf_render_view_t* out) {
+    settle(c);
     if (!c || !out) return MF_EINVAL;
     float pose[16];
     int rc = mf_get_pose(c, 0, pose);
@@ -234,11 +236,13 @@ static int render_enqueue(mf_ctx* c, const mf_render_view_t* v, const float* pal
 
 extern "C" int mf_render_view_dev(mf_ctx* c, const mf_render_view_t* v, const float* palette, int32_t n_palette, uint8_t* d_rgba, float* d_depth,
                                   int32_t* d_model) {
+    settle(c);
     return render_enqueue(c, v, palette, n_palette, d_rgba, d_depth, d_model);
 }
 
 extern "C" int mf_render_view(mf_ctx* c, const mf_render_view_t* v, const float* palette, int32_t n_palette, uint8_t* out_rgba, float* out_depth,
                               int32_t* out_model) {
+    settle(c);
     if (!c) return MF_EINVAL;
     if (!v || !out_rgba) return render_fail(c, "mf_render_view: null view or colour output");
     if (v->width < 1 || v->height < 1 || v->width > kRenderMaxSide || v->height > kRenderMaxSide) return render_fail(c, "render size outside 1 .. 4096");

@@ -14,6 +14,7 @@
 #include "mf_internal.h"
 #include "mf_device.h"
 #include "mf_rgbd_device.h"
+#include "mf_bilateral_device.h"
 
 namespace mf {
 
@@ -93,8 +94,10 @@ struct BinArgs {
 // its entries per tile in LDS, reserves a contiguous range per touched tile with ONE global atomicAdd (~13 k per frame
 // instead of one global atomic per covered pixel), then hands out slots inside the range with LDS atomics.  The order of
 // a tile's list is not deterministic; the z-test that consumes it is order independent.
-__global__ __launch_bounds__(kBinThreads) void k_splat_bin(const BinArgs a) {
-    extern __shared__ int s_mem[];
+// (the workgroup body: k_splat_bin below runs it on 1024 threads, k_bin_bilateral -- beside the next frame's depth filter -- on 256.  s_mem: 2 nt
+// ints of LDS; block / nblocks: this workgroup's index among the nblocks workgroups that share the rounds)
+template <int kThreads>
+__device__ __forceinline__ void splat_bin_body(const BinArgs& a, int* s_mem, const int block, const int nblocks) {
     const int nt = a.tilesX * a.tilesY;
     int* s_cnt = s_mem;           // [nt] this workgroup's entries per tile, then the start of its reserved range
     int* s_fill = s_mem + nt;     // [nt] slots handed out
@@ -108,19 +111,19 @@ __global__ __launch_bounds__(kBinThreads) void k_splat_bin(const BinArgs a) {
 #pragma unroll
     for (int q = 0; q < 9; ++q) Ri[q] = a.pose->Ri[q];
     const float3 ti = f3(a.pose->ti[0], a.pose->ti[1], a.pose->ti[2]);
-  // a round = 2048 surfel slots: 2048 consecutive surfels of the buffer, or -- with a visibility list -- the next 2048 / kRun listed runs
-  constexpr int kRunsPerRound = 2 * kBinThreads / kRun;
-  const int rounds = by_runs ? (nruns + kRunsPerRound - 1) / kRunsPerRound : (n + 2 * kBinThreads - 1) / (2 * kBinThreads);
-  for (int chunk = blockIdx.x; chunk < rounds; chunk += gridDim.x) {
-    for (int t = threadIdx.x; t < nt; t += kBinThreads) { s_cnt[t] = 0; s_fill[t] = 0; }
+  // a round = 2 kThreads surfel slots (2048 in k_splat_bin): consecutive surfels of the buffer, or -- with a visibility list -- the next 2 kThreads / kRun listed runs
+  constexpr int kRunsPerRound = 2 * kThreads / kRun;
+  const int rounds = by_runs ? (nruns + kRunsPerRound - 1) / kRunsPerRound : (n + 2 * kThreads - 1) / (2 * kThreads);
+  for (int chunk = block; chunk < rounds; chunk += nblocks) {
+    for (int t = threadIdx.x; t < nt; t += kThreads) { s_cnt[t] = 0; s_fill[t] = 0; }
     __syncthreads();
     // 2 surfels per thread; their sprite boxes stay in registers between the two phases
     int idx[2]; short4 bb[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        int i = (chunk * 2 + r) * kBinThreads + threadIdx.x;
+        int i = (chunk * 2 + r) * kThreads + threadIdx.x;
         if (by_runs) {
-            const int slot = r * kBinThreads + (int)threadIdx.x, v = chunk * kRunsPerRound + slot / kRun;
+            const int slot = r * kThreads + (int)threadIdx.x, v = chunk * kRunsPerRound + slot / kRun;
             i = n;
             if (v < nruns) {
                 const int run = a.vis_list ? a.vis_list[v] : v;
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(kBinThreads) void k_splat_bin(const BinArgs a) {
         }
     }
     __syncthreads();
-    for (int t = threadIdx.x; t < nt; t += kBinThreads)
+    for (int t = threadIdx.x; t < nt; t += kThreads)
         if (s_cnt[t]) s_cnt[t] = atomicAdd(&a.tile_count[t], s_cnt[t]);
     __syncthreads();
 #pragma unroll
@@ -163,6 +166,34 @@ __global__ __launch_bounds__(kBinThreads) void k_splat_bin(const BinArgs a) {
     }
     __syncthreads();
   }
+}
+
+__global__ __launch_bounds__(kBinThreads) void k_splat_bin(const BinArgs a) {
+    extern __shared__ int s_mem[];
+    splat_bin_body<kBinThreads>(a, s_mem, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// The binning pass of frame t's prediction and the depth filter of frame t + 1 in ONE launch ("fusedBinFilter"; mf_frame.inl: enqueue_fused_head).
+// The two are independent -- the binning pass reads the cleaned map and the pose, the filter the new depth image -- and complement each other: the
+// filter is VALU-bound, the binning pass a stream plus LDS atomics that, at 2048 surfels per workgroup, keeps half the compute units busy.  The
+// workgroups have the filter's 256 threads: nbin of them run splat_bin_body on rounds of 512 surfels, the others bilateral_body on one 64 x 4
+// tile each -- the bodies of k_splat_bin and k_bilateral.  (The order of a tile's list is no more deterministic here than there; what the tile
+// pass makes of it does not depend on the order.)  Both halves count in multiples of 8 workgroups and are dealt out in turns of 8 where the launch
+// is not resident at once (a Bresenham walk, as k_bilateral_model_pyramid's), so that a filter tile keeps the XCD k_bilateral's index gives it
+// (xcd_contiguous_tile) and both halves are in flight from the first round on.
+// (1024-thread workgroups with four filter tiles each -- the binning pass as it stands -- were measured first: 31.6 us against 14.1 + 15.9 for the
+// two launches; 300 filter workgroups of four tiles on 256 compute units leave the last ones with twice the average load.  DESIGN.md)
+constexpr int kBinFilterThreads = 256;
+__global__ __launch_bounds__(kBinFilterThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_bin_bilateral(const BinArgs a, int nbin, int interleave,
+                                                                                                               const float* __restrict__ depth,
+                                                                                                               float* __restrict__ out, int W, int H) {
+    extern __shared__ int s_mem[];
+    const int groups = (int)gridDim.x >> 3, gfil = groups - (nbin >> 3), g = (int)blockIdx.x >> 3, lane = (int)blockIdx.x & 7;
+    int before, after;   // filter groups in front of group g / of group g + 1
+    if (interleave) { before = (int)(((long long)g * gfil) / groups); after = (int)(((long long)(g + 1) * gfil) / groups); }
+    else { before = g < (nbin >> 3) ? 0 : g - (nbin >> 3); after = g < (nbin >> 3) ? 0 : before + 1; }
+    if (after == before) { splat_bin_body<kBinFilterThreads>(a, s_mem, ((g - before) << 3) + lane, nbin); return; }
+    bilateral_body(depth, out, W, H, reinterpret_cast<float*>(s_mem), (before << 3) + lane, (int)threadIdx.x, true);
 }
 
 struct TileArgs {
@@ -436,12 +467,18 @@ int launch_global_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W
     return 0;
 }
 
+bool splat_tiled_applies(int W, int H, SplatTuning tune) {
+    const int tileH = splat_tile_height(tune.tile_h);
+    return ((W + kTile - 1) / kTile) * ((H + tileH - 1) / tileH) <= kMaxTiles;
+}
+
 size_t splat_tiles_scratch_ints(int W, int H) { return (size_t)((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile); }
 
 int launch_splat_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth, float confThreshold,
                        int timeDelta, int* tile_count, int* entries, int entries_cap, float4* rec0, float4* rec1, void* bbox, float4* predV,
                        float4* predN, uchar4* predImage, uint16_t* predTime, const uint8_t* rgb, uint8_t* predGray, uint8_t* fillGray, hipStream_t s,
-                       const FrameAdvance* advance, int fillPassthrough, unsigned long long* prof, SplatTuning tune, const VisList* vis) {
+                       const FrameAdvance* advance, int fillPassthrough, unsigned long long* prof, SplatTuning tune, const VisList* vis,
+                       const SplatFilterJob* filter) {
     const int tileH = splat_tile_height(tune.tile_h);
     const int tilesX = (W + kTile - 1) / kTile, tilesY = (H + tileH - 1) / tileH, nt = tilesX * tilesY;
     if (nt > kMaxTiles) return -1;
@@ -455,7 +492,15 @@ int launch_splat_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W,
     // two 1024-thread workgroups fit on a CU (60 VGPRs): 512 workgroups are ONE round of chunks up to a million surfels (with 256 a
     // 0.6 M-surfel map was 293 chunks = two rounds, the second one on 37 CUs)
     const int nblocks = min(512, (src.cap + 2 * kBinThreads - 1) / (2 * kBinThreads));
-    hipLaunchKernelGGL(k_splat_bin, dim3(nblocks), dim3(kBinThreads), (size_t)2 * nt * sizeof(int), s, b);
+    if (filter && filter->fused) {
+        const int nbin = xcd_padded_grid(min(4 * 512, (src.cap + 2 * kBinFilterThreads - 1) / (2 * kBinFilterThreads))), nfil = bilateral_grid(W, H);
+        const size_t lds = std::max((size_t)2 * nt * sizeof(int), (size_t)(kBLdsH * kBLdsW) * sizeof(float));
+        // (eight 256-thread workgroups per compute unit: 2 048 are resident at once)
+        hipLaunchKernelGGL(k_bin_bilateral, dim3(nbin + nfil), dim3(kBinFilterThreads), lds, s, b, nbin, (nbin + nfil > 2048) ? 1 : 0, filter->depth, filter->out, W, H);
+    } else {
+        hipLaunchKernelGGL(k_splat_bin, dim3(nblocks), dim3(kBinThreads), (size_t)2 * nt * sizeof(int), s, b);
+        if (filter) launch_bilateral(filter->depth, filter->out, W, H, s);
+    }
     TileArgs t;
     t.src = src; t.frame = frame; t.pose = pose; t.W = W; t.H = H; t.k = k; t.maxDepth = maxDepth; t.confThreshold = confThreshold;
     t.timeDelta = timeDelta; t.tilesX = tilesX; t.tilesY = tilesY; t.tileH = tileH; t.tile_count = tile_count;
