@@ -413,6 +413,11 @@ int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
  * behind the next library call), "fusedBinFilter" / "fusedFramePyramids" (in that head: the prediction's binning pass in the next frame's depth
  * filter's launch / the frame's pyramid and the model-side pyramid in one launch; 0: two launches each; same bytes); read-only: "deferredFrames" /
  * "fusedHeadFrames" (predictions deferred / frames that took the fused head so far),
+ * "tilePyramid" (1: in that head every workgroup of the prediction's tile pass also writes its tile of the model-side pyramid, as the pyramid's own
+ * launch computes it without fill-in, and that launch becomes a fix-up whose workgroups leave at once unless the frame's fill-in decision is 1;
+ * 0: the model-side pyramid as a launch of its own; same bytes), "fusedTilePyramid" (needs "tilePyramid"; 1: the frame's pyramid rides in the tile
+ * pass's launch, in workgroups of its own; 0: it shares the fix-up's launch or, with "fusedFramePyramids" 0, runs alone; same bytes); read-only:
+ * "pyramidFixupFrames" (fused heads whose fix-up rebuilt the pyramid, i.e. whose tracking step fills in; synchronises the stream),
  * "hostLockstep" (1: mf_process_frame waits for frame k-2 to have run before it enqueues frame k's
  * upload), "hostWaitUpload" (1: ... and for its own upload: single-model frames), "modelApiPackedIndex" (0; 1: mf_model_predict_indices
  * also builds the packed column-major map mf_process_frame feeds Model::clean with), "tileThreads" (512) / "spriteLanes" (4) / "tileHeight" (24; 16, 20, 32: tiles of 16 pixels by that many rows): launch shape of

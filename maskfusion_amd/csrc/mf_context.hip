@@ -211,6 +211,11 @@ struct mf_ctx {
     bool defer_predict = true, fused_bin_filter = true, fused_frame_pyramids = true;
     struct { ModelState* m = nullptr; FrameAdvance adv{nullptr, nullptr, nullptr}; } pending;
     long deferred_frames = 0, fused_head_frames = 0;   // "deferredFrames" / "fusedHeadFrames" (read-only): predictions deferred / heads taken so far
+    // "tilePyramid": in the fused head the tile pass also writes the model-side pyramid (without fill-in) and the model-side pyramid's launch shrinks to
+    // a fix-up that runs only in frames whose fill-in decision is 1; "fusedTilePyramid": the frame pyramid rides in the tile pass's launch too
+    // (mf_frame.inl: enqueue_fused_head).  d_pyramid_fixups: frames whose fix-up ran, counted on the device ("pyramidFixupFrames", read-only)
+    bool tile_pyramid = true, fused_tile_pyramid = true;
+    int* d_pyramid_fixups = nullptr;
     bool object_stream = true;
     hipStream_t stream_obj = nullptr, obj_s = nullptr;
     hipEvent_t ev_obj_dep = nullptr, ev_obj_done = nullptr;
@@ -590,6 +595,7 @@ extern "C" int mf_create(const mf_config* cfg, mf_ctx** out) {
         const size_t nt = splat_tiles_scratch_ints(W, H);
         const size_t maxcap = (size_t)std::max(surfel_capacity(cfg->num_gsurfels), surfel_capacity(cfg->num_osurfels));
         A(dev_alloc(c, c->allocs, &c->d_tile_count, nt));
+        A(dev_alloc(c, c->allocs, &c->d_pyramid_fixups, 1));
         // every tile owns entries_cap / tiles list slots: 4x the surfel capacity in total (a surfel overlaps 1-4 tiles), i.e.
         // room for every surfel of a full map to land in a quarter of the image (an overflow is an error, never a drop)
         // ... and never less than 16 list slots per pixel of a tile, so that small maps can still pile up in one place
@@ -1087,6 +1093,8 @@ extern "C" int mf_set_param(mf_ctx* c, const char* key, double value) {
     if (!strcmp(key, "deferPredict")) { c->defer_predict = value != 0; return MF_OK; }   // 0: every prediction at the end of its own frame
     if (!strcmp(key, "fusedBinFilter")) { c->fused_bin_filter = value != 0; return MF_OK; }   // 0: k_splat_bin and k_bilateral as two launches in the fused head
     if (!strcmp(key, "fusedFramePyramids")) { c->fused_frame_pyramids = value != 0; return MF_OK; }   // 0: k_frame_pyramid and k_model_pyramid as two launches
+    if (!strcmp(key, "tilePyramid")) { c->tile_pyramid = value != 0; return MF_OK; }   // 0: the model-side pyramid as a launch of its own in the fused head
+    if (!strcmp(key, "fusedTilePyramid")) { c->fused_tile_pyramid = value != 0; return MF_OK; }   // 0: the frame pyramid behind the tile pass, not beside it
     if (!strcmp(key, "hostProfileReset")) { for (double& v : c->host_us) v = 0; c->host_calls = 0; return MF_OK; }
     if (!strcmp(key, "timings")) { c->timings_on = value != 0; return MF_OK; }
     if (!strcmp(key, "passTimings")) {
@@ -1190,6 +1198,15 @@ extern "C" int mf_get_param(mf_ctx* c, const char* key, double* value) {
     if (!strcmp(key, "deferPredict")) { *value = c->defer_predict ? 1 : 0; return MF_OK; }
     if (!strcmp(key, "fusedBinFilter")) { *value = c->fused_bin_filter ? 1 : 0; return MF_OK; }
     if (!strcmp(key, "fusedFramePyramids")) { *value = c->fused_frame_pyramids ? 1 : 0; return MF_OK; }
+    if (!strcmp(key, "tilePyramid")) { *value = c->tile_pyramid ? 1 : 0; return MF_OK; }
+    if (!strcmp(key, "fusedTilePyramid")) { *value = c->fused_tile_pyramid ? 1 : 0; return MF_OK; }
+    if (!strcmp(key, "pyramidFixupFrames")) {   // fused heads whose fill-in decision was 1: the fix-up launch rebuilt the model-side pyramid there
+        int v = 0;
+        MF_HIP(c, hipStreamSynchronize(c->stream));
+        MF_HIP(c, hipMemcpy(&v, c->d_pyramid_fixups, sizeof(int), hipMemcpyDeviceToHost));
+        *value = v;
+        return MF_OK;
+    }
     if (!strcmp(key, "deferredFrames")) { *value = (double)c->deferred_frames; return MF_OK; }
     if (!strcmp(key, "fusedHeadFrames")) { *value = (double)c->fused_head_frames; return MF_OK; }
     if (!strcmp(key, "densifyCount")) { *value = (float)c->densify_count; return MF_OK; }

@@ -443,7 +443,9 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
 // advance: the end-of-frame bookkeeping of this model (processFrame's tail); the tiled prediction runs it as its epilogue, the scatter
 // form is followed by k_frame_advance.
 // filter: the next frame's depth filter, enqueued with the binning pass (enqueue_fused_head; tiled form only)
-static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advance = nullptr, const SplatFilterJob* filter = nullptr) {
+// pyramid: the model-side pyramid (and the next frame's pyramid) built in the tile pass's launch (enqueue_fused_head; tiled form only)
+static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advance = nullptr, const SplatFilterJob* filter = nullptr,
+                            const SplatPyramidJob* pyramid = nullptr) {
     PassTimer timer(c, m.id == 0 ? MF_PASS_BG_PREDICT : -1);
     m.pred_gray_valid = photometric_on(c);
     if (c->splat_tiles && !(c->object_scatter_splat && m.id != 0)) {
@@ -454,7 +456,7 @@ static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advanc
                                c->cfg.time_delta, c->d_tile_count, c->d_tile_entries, c->tile_entries_cap, c->d_splat_rec0, c->d_splat_rec1,
                                c->d_splat_bbox, m.d_predV, m.d_predN, m.d_predImage, m.d_predTime, c->cur_rgb,
                                gray ? m.d_predGray : nullptr, gray ? m.d_fillGray : nullptr, c->stream, advance, c->ftf_rgb ? 1 : 0,
-                               (c->splat_prof_on && m.id == 0) ? c->d_splat_prof : nullptr, c->splat_tune, vis, filter) == 0)
+                               (c->splat_prof_on && m.id == 0) ? c->d_splat_prof : nullptr, c->splat_tune, vis, filter, pyramid) == 0)
             return;
     }
     if (filter) launch_bilateral(filter->depth, filter->out, c->W, c->H, c->stream);   // (not reached: a deferred prediction is a tiled one)
@@ -627,12 +629,19 @@ static int enqueue_preprocess(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
 // The head of frame k when frame k - 1's prediction is pending ("deferPredict") and frame k tracks the background alone: the map chain of frame
 // k - 1 (binning -> tile pass -> model-side pyramid) and the image chain of frame k (depth filter -> frame pyramid) meet only where the model-side
 // pyramid reads the tile pass's maps, so they share launches:
-//   A  k_bin_bilateral        { binning of k - 1 | depth filter of k }     ("fusedBinFilter"; 0: k_splat_bin, k_bilateral)
-//   B  k_splat_tile           the tile pass of k - 1 with its end-of-frame epilogue, unchanged
-//   C  k_frame_model_pyramid  { frame pyramid of k | model-side pyramid }  ("fusedFramePyramids"; 0: k_frame_pyramid, k_model_pyramid)
+//   A   k_bin_bilateral  { binning of k - 1 | depth filter of k }                                   ("fusedBinFilter"; 0: k_splat_bin, k_bilateral)
+//   B'  k_splat_tile     { the tile pass of k - 1 with its end-of-frame epilogue; every tile workgroup also writes its tile of the model-side
+//                          pyramid, without fill-in ("tilePyramid") | frame pyramid of k ("fusedTilePyramid") }
+//   C'  k_model_pyramid  the model-side pyramid once more, in full, if B' decided that the tracking step fills in -- every workgroup leaves at
+//                        once otherwise ("pyramidFixupFrames" counts the frames that needed it); not enqueued for a model that never fills in
 // -- what enqueue_predict and enqueue_preprocess enqueue for such a pair of frames, in another order: every kernel runs the same instructions on the
-// same data.  A map that needs a visibility list gets its cull launch in front of A, as enqueue_predict issues it.  The tracking loop that follows
-// is told that its model-side pyramid stands.
+// same data.  Only here are the tile pass and the model-side pyramid neighbours in one call with the same model pose; fill-in is a start-up state
+// (the decision is 1 while the first surfels gain confidence, and after a frame that lost half its depth).
+// "fusedTilePyramid" 0:  A, B with the pyramid epilogue, C = k_frame_model_pyramid { frame pyramid of k | fix-up as C' } ("fusedFramePyramids"; 0:
+//                        k_frame_pyramid, k_model_pyramid)
+// "tilePyramid" 0:       A, B unchanged, C = k_frame_model_pyramid { frame pyramid of k | model-side pyramid }
+// A map that needs a visibility list gets its cull launch in front of A, as enqueue_predict issues it.  The tracking loop that follows is told
+// that its model-side pyramid stands.
 static void enqueue_fused_head(mf_ctx* c, const uint8_t* d_rgb, const float* d_depth, long k, const float* fill_depth) {
     ModelState* m = c->pending.m;
     const FrameAdvance adv = c->pending.adv;
@@ -640,14 +649,22 @@ static void enqueue_fused_head(mf_ctx* c, const uint8_t* d_rgb, const float* d_d
     const int set = (int)(k & 1);
     float* depthF = c->d_depthF[k % 3];
     const SplatFilterJob job{d_depth, depthF, c->fused_bin_filter ? 1 : 0};
-    enqueue_predict(c, *m, &adv, &job);                                    // A, B
+    const bool tile_pyr = c->tile_pyramid, tile_frame = tile_pyr && c->fused_tile_pyramid;
+    SplatPyramidJob pj;
+    for (int i = 0; i < 3; ++i) { pj.vm[i] = m->d_vmap_g[i]; pj.nm[i] = m->d_nmap_g[i]; pj.frame_vmap[i] = c->d_vmap[set][i]; pj.frame_nmap[i] = c->d_nmap[set][i]; }
+    pj.frame_depth = tile_frame ? depthF : nullptr; pj.frame_cutoff = c->cfg.depth_cutoff;
+    enqueue_predict(c, *m, &adv, &job, tile_pyr ? &pj : nullptr);          // A, B / B'
     const float* fill = m->allowFillIn ? fill_depth : nullptr;
-    if (c->fused_frame_pyramids) {
+    int* fixup = tile_pyr ? c->d_pyramid_fixups : nullptr;
+    const bool model_launch = !tile_pyr || fill != nullptr;                // (without fill-in the epilogue's pyramid is final)
+    if (tile_frame) {
+        if (model_launch) launch_model_pyramid(m->d_predV, m->d_predN, fill, m->d_frame, m->d_pose, nullptr, m->d_vmap_g, m->d_nmap_g, c->W, c->H, c->K, c->stream, fixup);   // C'
+    } else if (c->fused_frame_pyramids && model_launch) {
         launch_frame_model_pyramid(depthF, c->d_vmap[set], c->d_nmap[set], c->cfg.depth_cutoff, m->d_predV, m->d_predN, fill, m->d_frame, m->d_pose,
-                                   m->d_vmap_g, m->d_nmap_g, c->W, c->H, c->K, c->stream);   // C
+                                   m->d_vmap_g, m->d_nmap_g, c->W, c->H, c->K, c->stream, fixup);   // C
     } else {
         launch_frame_pyramid(depthF, c->d_vmap[set], c->d_nmap[set], c->W, c->H, c->K, c->cfg.depth_cutoff, c->stream);
-        launch_model_pyramid(m->d_predV, m->d_predN, fill, m->d_frame, m->d_pose, nullptr, m->d_vmap_g, m->d_nmap_g, c->W, c->H, c->K, c->stream);
+        if (model_launch) launch_model_pyramid(m->d_predV, m->d_predN, fill, m->d_frame, m->d_pose, nullptr, m->d_vmap_g, m->d_nmap_g, c->W, c->H, c->K, c->stream, fixup);
     }
     c->cur_rgb = d_rgb;
     c->cur_depth = d_depth;

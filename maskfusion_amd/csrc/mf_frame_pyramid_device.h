@@ -104,9 +104,14 @@ constexpr int kFpLdsFloats = kFpL0 * kFpL0 + kFpL1 * kFpL1 + kFpL2 * kFpL2;     
 
 inline int frame_pyramid_tiles(int W, int H) { return (((W >> 2) + kFpT2 - 1) / kFpT2) * (((H >> 2) + kFpT2 - 1) / kFpT2); }
 
-// lds: kFpLdsFloats floats; block: the workgroup's index in a grid of xcd_padded_grid(frame_pyramid_tiles(W, H)) workgroups of 256 threads.
-// (a workgroup without a tile leaves as a whole, before the first barrier)
-__device__ __forceinline__ void frame_pyramid_body(const FramePyrArgs& a, float* lds, const int block) {
+// lds: kFpLdsFloats floats; block: the workgroup's index in a grid of at least xcd_padded_grid(frame_pyramid_tiles(W, H)) workgroups of 256 threads;
+// tid: the thread's index among the 256 that share the tile.
+// kLeave: a workgroup without a tile leaves as a whole, before the first barrier (k_frame_pyramid, k_frame_model_pyramid).  false: it stays and takes
+// part in the barriers only -- for a caller whose workgroup holds several tiles' worth of threads, each 256 with an LDS slice of their own
+// (mf_splat.hip: k_splat_tile beside the tile pass), or threads that belong to no tile at all (enabled == false).  Every float operation is the same.
+template <bool kLeave = true>
+__device__ __forceinline__ void frame_pyramid_body(const FramePyrArgs& a, float* lds, const int block, const int tid = (int)threadIdx.x,
+                                                   const bool enabled = true) {
 #pragma clang fp contract(off)
     float* const s0 = lds;
     float* const s1 = s0 + kFpL0 * kFpL0;
@@ -114,12 +119,13 @@ __device__ __forceinline__ void frame_pyramid_body(const FramePyrArgs& a, float*
     const int W0 = a.W, H0 = a.H, W1 = W0 >> 1, H1 = H0 >> 1, W2 = W0 >> 2, H2 = H0 >> 2;
     const int tiles_x = (W2 + kFpT2 - 1) / kFpT2, tiles = tiles_x * ((H2 + kFpT2 - 1) / kFpT2);
     const int tile = xcd_contiguous_tile(block, tiles);     // XCD k works on the k-th band of tile rows (mf_device.h)
-    if (tile >= tiles) return;
+    // (a block index beyond the padded grid would wrap into the next XCD's band: a caller that pads further has no tile there)
+    const bool on = enabled && block < xcd_padded_grid(tiles) && tile < tiles;
+    if (kLeave && !on) return;
     const int X2 = (tile % tiles_x) * kFpT2, Y2 = (tile / tiles_x) * kFpT2;  // tile origin at level 2
     const int ox1 = 2 * X2 - 2, oy1 = 2 * Y2 - 2;                // LDS origins (may be negative)
     const int ox0 = 2 * ox1 - 2, oy0 = 2 * oy1 - 2;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < kFpL0 * kFpL0; i += 256) {
+    if (on) for (int i = tid; i < kFpL0 * kFpL0; i += 256) {
         const int ly = i / kFpL0, lx = i - ly * kFpL0;
         const int gx = ox0 + lx, gy = oy0 + ly;
         s0[i] = (gx >= 0 && gx < W0 && gy >= 0 && gy < H0) ? a.depth[gy * W0 + gx] : qnan();
@@ -129,27 +135,27 @@ __device__ __forceinline__ void frame_pyramid_body(const FramePyrArgs& a, float*
     const Intr k0 = a.k;
     const Intr k1 = Intr{a.k.fx / 2.f, a.k.fy / 2.f, a.k.cx / 2.f, a.k.cy / 2.f};
     const Intr k2 = Intr{a.k.fx / 4.f, a.k.fy / 4.f, a.k.cx / 4.f, a.k.cy / 4.f};
-    for (int l = tid; l < 16 * kFpT2 * kFpT2; l += 256) {
+    if (on) for (int l = tid; l < 16 * kFpT2 * kFpT2; l += 256) {
         const int u = 4 * X2 + l % (4 * kFpT2), v = 4 * Y2 + l / (4 * kFpT2);
         if (u < W0 && v < H0) vmap_nmap_px(s0, kFpL0, ox0, oy0, u, v, W0, H0, k0, a.cutoff, a.vmap[0], a.nmap[0]);
     }
-    for (int i = tid; i < kFpL1 * kFpL1; i += 256) {
+    if (on) for (int i = tid; i < kFpL1 * kFpL1; i += 256) {
         const int ly = i / kFpL1, lx = i - ly * kFpL1;
         const int gx = ox1 + lx, gy = oy1 + ly;
         s1[i] = (gx >= 0 && gx < W1 && gy >= 0 && gy < H1) ? pyrdown_px(s0, kFpL0, ox0, oy0, gx, gy, W0, H0) : qnan();
     }
     __syncthreads();
-    for (int l = tid; l < 4 * kFpT2 * kFpT2; l += 256) {
+    if (on) for (int l = tid; l < 4 * kFpT2 * kFpT2; l += 256) {
         const int u = 2 * X2 + l % (2 * kFpT2), v = 2 * Y2 + l / (2 * kFpT2);
         if (u < W1 && v < H1) vmap_nmap_px(s1, kFpL1, ox1, oy1, u, v, W1, H1, k1, a.cutoff, a.vmap[1], a.nmap[1]);
     }
-    for (int i = tid; i < kFpL2 * kFpL2; i += 256) {
+    if (on) for (int i = tid; i < kFpL2 * kFpL2; i += 256) {
         const int ly = i / kFpL2, lx = i - ly * kFpL2;
         const int gx = X2 + lx, gy = Y2 + ly;
         s2[i] = (gx < W2 && gy < H2) ? pyrdown_px(s1, kFpL1, ox1, oy1, gx, gy, W1, H1) : qnan();
     }
     __syncthreads();
-    for (int l = tid; l < kFpT2 * kFpT2; l += 256) {
+    if (on) for (int l = tid; l < kFpT2 * kFpT2; l += 256) {
         const int u = X2 + l % kFpT2, v = Y2 + l / kFpT2;
         if (u < W2 && v < H2) vmap_nmap_px(s2, kFpL2, X2, Y2, u, v, W2, H2, k2, a.cutoff, a.vmap[2], a.nmap[2]);
     }

@@ -151,13 +151,15 @@ void launch_frame_pyramid(const float* depth, float* const vmap[3], float* const
 // launch_frame_pyramid's and launch_model_pyramid's work (device pose) in one launch (mf_odometry.hip: k_frame_model_pyramid)
 void launch_frame_model_pyramid(const float* depthF, float* const fvmap[3], float* const fnmap[3], float cutoff, const float4* predV, const float4* predN,
                                 const float* fillDepth, const FrameDev* frame, const PoseDev* pose, float* const vmaps[3], float* const nmaps[3], int W, int H,
-                                Intr k, hipStream_t s);
+                                Intr k, hipStream_t s, int* fixup = nullptr);   // fixup: as launch_model_pyramid's
 
 // ---------------- odometry ----------------
 // Fused RGBDOdometry::initICPModel.  pose: device PoseDev (R,t used).  fill-in inputs may be null (no fill-in).
 void launch_model_pyramid(const float4* predV, const float4* predN, const float* fillDepth, const FrameDev* frame,
                           const PoseDev* pose, const float* R9t3_host_or_null, float* const vmaps[3],
-                          float* const nmaps[3], int W, int H, Intr k, hipStream_t s);
+                          float* const nmaps[3], int W, int H, Intr k, hipStream_t s, int* fixup = nullptr);
+// fixup ("tilePyramid"): the tile pass has already written the pyramid without fill-in -- the launch runs only if frame->useFillIn is set, and then
+// counts the frame in *fixup
 // One Gauss-Newton iteration: [reduce+solve of the previous launch] -> normal equations of this level.
 struct IcpLaunch {
     const float* vmap_curr; const float* nmap_curr; const float* vmap_prev; const float* nmap_prev;
@@ -366,12 +368,18 @@ struct FrameAdvance { FrameDev* host_mirror; const PoseDev* bg_pose; float* log_
 // filter (optional): the NEXT frame's depth filter (launch_bilateral(depth, out, W, H)), enqueued with the binning pass: in its launch (fused != 0,
 // k_bin_bilateral) or as a launch of its own between the binning pass and the tile pass.  The two read and write nothing in common.
 struct SplatFilterJob { const float* depth; float* out; int fused; };
+// pyramid (optional, "tilePyramid"): every tile workgroup also writes the three levels of the model-side pyramid of its tile (vm / nm: launch_model_pyramid's
+// planes; the model pose is `pose`), as launch_model_pyramid computes them WITHOUT fill-in -- a frame whose fill-in decision comes out 1 needs that launch
+// behind.  frame_depth != nullptr ("fusedTilePyramid"): launch_frame_pyramid(frame_depth, frame_vmap, frame_nmap, W, H, k, frame_cutoff)'s work rides in
+// the same launch, in workgroups of its own behind the tile workgroups.  The tile pass and that pyramid read and write nothing in common.
+struct SplatPyramidJob { float* vm[3]; float* nm[3]; const float* frame_depth; float* frame_vmap[3]; float* frame_nmap[3]; float frame_cutoff; };
 int launch_splat_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth, float confThreshold,
                        int timeDelta, int* tile_count, int* entries /*[tiles][entries_cap / tiles]*/, int entries_cap,
                        float4* rec0 /*[src.cap]*/, float4* rec1 /*[src.cap]*/, void* bbox /*[src.cap] x 8 B*/, float4* predV, float4* predN,
                        uchar4* predImage, uint16_t* predTime, const uint8_t* rgb, uint8_t* predGray, uint8_t* fillGray, hipStream_t s,
                        const FrameAdvance* advance = nullptr, int fillPassthrough = 0, unsigned long long* prof = nullptr /*[tiles][8] stamps*/,
-                       SplatTuning tune = SplatTuning(), const VisList* vis = nullptr, const SplatFilterJob* filter = nullptr);
+                       SplatTuning tune = SplatTuning(), const VisList* vis = nullptr, const SplatFilterJob* filter = nullptr,
+                       const SplatPyramidJob* pyramid = nullptr);
 bool splat_tiled_applies(int W, int H, SplatTuning tune);   // launch_splat_tiled would not return -1 for this image
 // ---- the surfel passes of ALL object models of a frame, one launch per pass (grid.z = model) ----
 // An object model holds a few thousand surfels: each of its ~11 per-frame launches is pure launch latency (~85 us per object and frame in

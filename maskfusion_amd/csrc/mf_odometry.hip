@@ -23,6 +23,7 @@
 #include "mf_rgbd_device.h"
 #include "mf_bilateral_device.h"
 #include "mf_frame_pyramid_device.h"
+#include "mf_model_pyramid_device.h"
 
 namespace mf {
 
@@ -1496,8 +1497,6 @@ void launch_rgbd_finalize(const float* icp_partials, const float* rgb_partials, 
 // level-0 pixels = 2x2 of level 1 = 1 pixel of level 2, so the averages follow the reference's operation order
 // ((x00 + x01 + x10 + x11) / 4, level 2 from level-1 values) and nothing is re-read from HBM.
 // ------------------------------------------------------------------------------------------------
-struct MapPx { float3 v, n; bool vok, nok; };
-
 __device__ __forceinline__ MapPx load_model_px(const float4* __restrict__ predV, const float4* __restrict__ predN,
                                                const float* __restrict__ fillDepth, bool useFill, int x, int y, int W,
                                                int H, Intr k) {
@@ -1514,52 +1513,18 @@ __device__ __forceinline__ MapPx load_model_px(const float4* __restrict__ predV,
             n4 = make_float4(n.x, n.y, n.z, 1.f);
         }
     }
-    MapPx r;
-    if (!(v4.z == 0)) {  // copyMapsKernel, cudafuncs.cu:286-305
-        r.v = f3(v4.x, v4.y, v4.z); r.n = f3(n4.x, n4.y, n4.z);
-        r.vok = !isnan(r.v.x); r.nok = !isnan(r.n.x);
-    } else {
-        r.v = r.n = f3(qnan(), qnan(), qnan());
-        r.vok = r.nok = false;
-    }
-    return r;
+    return copy_maps_px(v4, n4);   // copyMapsKernel, cudafuncs.cu:286-305
 }
 
-// R a with the fused multiply-adds written out.  This file allows contraction, and under "fast" the back end decides per use WHICH product of
-// (R0 ax + R1 ay) + R2 az keeps its own rounding -- by operand order after scheduling: moving this kernel's body into a function (round 6) turned
-// the level-2 normals' R1 ay into R0 ax and every fifth normal moved by an ulp, enough to shift a tracked pose by 1e-7 and flip a surfel of a
-// count-exact test.  The form below is the one every use of the kernel compiled to through rounds 1-5; written out it no longer depends on context.
-__device__ __forceinline__ float3 mul33_fixed(const float* R, float3 a) {
-#pragma clang fp contract(off)
-    return f3(fmaf(R[2], a.z, fmaf(R[0], a.x, R[1] * a.y)), fmaf(R[5], a.z, fmaf(R[3], a.x, R[4] * a.y)),
-              fmaf(R[8], a.z, fmaf(R[6], a.x, R[7] * a.y)));
-}
-
-__device__ __forceinline__ void store_tx(float* __restrict__ vm, float* __restrict__ nm, int P, int i, float3 v, bool vok,
-                                         float3 n, bool nok, const float* R, float3 t) {
-    // tranformMapsKernel, cudafuncs.cu:207-249
-    float3 vd = f3(qnan(), qnan(), qnan()), nd = vd;
-    if (vok) vd = mul33_fixed(R, v) + t;
-    if (nok) nd = mul33_fixed(R, n);
-    vm[i] = vd.x; vm[P + i] = vd.y; vm[2 * P + i] = vd.z;
-    nm[i] = nd.x; nm[P + i] = nd.y; nm[2 * P + i] = nd.z;
-}
-
+// (mul33_fixed, store_tx, the quad broadcasts and the two smaller levels' arithmetic: mf_model_pyramid_device.h, shared with the tile pass's epilogue)
 struct PyrArgs {
     const float4* predV; const float4* predN; const float* fillDepth; const FrameDev* frame; const PoseDev* pose;
     float R[9]; float t[3]; int hostPose;
     float* vm[3]; float* nm[3];
     int W, H; Intr k;
     TrackBatch b;   // b.n > 0: grid.z = model, everything but fillDepth / W / H / k comes from the model's block
+    int* fixup;     // non-null ("tilePyramid"): the tile pass has written the no-fill pyramid -- run only if frame->useFillIn, and count such frames here
 };
-
-// value of lane (quad base + kB) for every lane of a quad: one DPP quad_perm broadcast, no LDS traffic
-template <int kB>
-__device__ __forceinline__ float quad_bcast(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kB | (kB << 2) | (kB << 4) | (kB << 6), 0xf, 0xf, false));
-}
-template <int kB>
-__device__ __forceinline__ float3 quad_bcast3(float3 v) { return f3(quad_bcast<kB>(v.x), quad_bcast<kB>(v.y), quad_bcast<kB>(v.z)); }
 
 // One thread per LEVEL-1 pixel (2x2 level-0 pixels); the four lanes of a DPP quad hold the 2x2 level-1 block of one level-2
 // pixel and exchange their values with quad broadcasts, so the averages keep the reference's operation order
@@ -1594,12 +1559,10 @@ __device__ __forceinline__ void model_pyramid_body(const PyrArgs& a0, const int 
     const int W = a.W, H = a.H, W1 = W >> 1, H1 = H >> 1;
     const int P0 = W * H, P1 = W1 * H1, P2 = W2 * H2;
 
-    float3 v1 = f3(qnan(), qnan(), qnan()), n1 = v1;
-    bool v1ok = false, n1ok = false;
     bool n0any = false;                       // (batched tracker) this thread's level-0 pixels that hold a normal: their box
     int n0x0 = 0, n0y0 = 0, n0x1 = 0, n0y1 = 0;
+    MapPx px[4];
     if (inside) {
-        MapPx px[4];
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
@@ -1613,37 +1576,9 @@ __device__ __forceinline__ void model_pyramid_body(const PyrArgs& a0, const int 
                     n0any = true;
                 }
             }
-        // resizeMapKernel<false/true>, cudafuncs.cu:366-417: order x00 + x01 + x10 + x11
-        v1ok = px[0].vok && px[1].vok && px[2].vok && px[3].vok;
-        n1ok = px[0].nok && px[1].nok && px[2].nok && px[3].nok;
-        v1 = f3((px[0].v.x + px[1].v.x + px[2].v.x + px[3].v.x) / 4, (px[0].v.y + px[1].v.y + px[2].v.y + px[3].v.y) / 4,
-                (px[0].v.z + px[1].v.z + px[2].v.z + px[3].v.z) / 4);
-        n1 = normalized_rsqrt(f3((px[0].n.x + px[1].n.x + px[2].n.x + px[3].n.x) / 4,
-                                 (px[0].n.y + px[1].n.y + px[2].n.y + px[3].n.y) / 4,
-                                 (px[0].n.z + px[1].n.z + px[2].n.z + px[3].n.z) / 4));
-        if (!v1ok) v1 = f3(qnan(), qnan(), qnan());
-        if (!n1ok) n1 = f3(qnan(), qnan(), qnan());
-        n1ok = n1ok && !isnan(n1.x);
-        const int x1 = 2 * x2 + bx, y1 = 2 * y2 + by;
-        store_tx(a.vm[1], a.nm[1], P1, y1 * W1 + x1, v1, v1ok, n1, n1ok, R, t);
     }
-    // level 2: the quad's four level-1 values in block order b = by * 2 + bx (executed by every lane: DPP needs them active)
-    const float okv = v1ok ? 1.f : 0.f, okn = n1ok ? 1.f : 0.f;
-    const float3 va = quad_bcast3<0>(v1), vb = quad_bcast3<1>(v1), vc = quad_bcast3<2>(v1), vd = quad_bcast3<3>(v1);
-    const float3 na = quad_bcast3<0>(n1), nb = quad_bcast3<1>(n1), nc = quad_bcast3<2>(n1), nd = quad_bcast3<3>(n1);
-    // (every broadcast is executed by every lane -- no short-circuit: the wavefront reductions below need the lanes in step)
-    const float ov0 = quad_bcast<0>(okv), ov1 = quad_bcast<1>(okv), ov2 = quad_bcast<2>(okv), ov3 = quad_bcast<3>(okv);
-    const float on0 = quad_bcast<0>(okn), on1 = quad_bcast<1>(okn), on2 = quad_bcast<2>(okn), on3 = quad_bcast<3>(okn);
-    const bool v2ok = (ov0 != 0.f) & (ov1 != 0.f) & (ov2 != 0.f) & (ov3 != 0.f);
-    bool n2ok = (on0 != 0.f) & (on1 != 0.f) & (on2 != 0.f) & (on3 != 0.f);
-    if (inside && b == 0) {
-        float3 v2 = f3((va.x + vb.x + vc.x + vd.x) / 4, (va.y + vb.y + vc.y + vd.y) / 4, (va.z + vb.z + vc.z + vd.z) / 4);
-        float3 n2 = normalized_rsqrt(f3((na.x + nb.x + nc.x + nd.x) / 4, (na.y + nb.y + nc.y + nd.y) / 4, (na.z + nb.z + nc.z + nd.z) / 4));
-        if (!v2ok) v2 = f3(qnan(), qnan(), qnan());
-        if (!n2ok) n2 = f3(qnan(), qnan(), qnan());
-        n2ok = n2ok && !isnan(n2.x);
-        store_tx(a.vm[2], a.nm[2], P2, y2 * W2 + x2, v2, v2ok, n2, n2ok, R, t);
-    }
+    // levels 1 and 2 (mf_model_pyramid_device.h; executed by every lane: its quad broadcasts need them active)
+    model_pyramid_down(px, inside, b, R, t, a.vm[1], a.nm[1], P1, (2 * y2 + by) * W1 + 2 * x2 + bx, a.vm[2], a.nm[2], P2, y2 * W2 + x2);
     if (a0.b.n > 0 && !a0.b.m[blk_z]->allow_fill) {
         // batched tracker, object models: the rectangle of level-0 pixels that hold a normal (TrackModelDev::rect) -- a superset of the pixels store_tx
         // wrote a normal to (it writes NaN wherever the flag is off), which is all the pixel pass of the Gauss-Newton loop can pair a frame pixel
@@ -1659,7 +1594,21 @@ __device__ __forceinline__ void model_pyramid_body(const PyrArgs& a0, const int 
     }
 }
 
-__global__ __launch_bounds__(256) void k_model_pyramid(const PyrArgs a) { model_pyramid_body(a, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z); }
+// "tilePyramid": the tile pass of the fused head has already written the three levels without fill-in (mf_splat.hip: k_splat_tile's epilogue), and its
+// last workgroup has decided frame->useFillIn behind them -- the kernel boundary orders that write.  A launch with a.fixup set only repairs the
+// frames whose decision came out "fill": every workgroup leaves at once otherwise; else the launch runs as ever and overwrites all three levels, and
+// its first workgroup counts the frame ("pyramidFixupFrames").  true: this workgroup has nothing to do.
+__device__ __forceinline__ bool pyramid_fixup_skips(const PyrArgs& a, const bool first) {
+    if (a.fixup == nullptr) return false;
+    if (a.frame->useFillIn == 0) return true;
+    if (first && threadIdx.x == 0) *a.fixup += 1;
+    return false;
+}
+
+__global__ __launch_bounds__(256) void k_model_pyramid(const PyrArgs a) {
+    if (pyramid_fixup_skips(a, blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)) return;
+    model_pyramid_body(a, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
+}
 
 // The depth filter of the frame and the model-side pyramid of the same frame's tracking step in ONE launch ("fusedPreprocessLaunch"): the two are
 // independent -- the filter reads the new depth image, the pyramid the previous frame's prediction -- and complement each other (the filter is
@@ -1689,9 +1638,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 
 void launch_model_pyramid(const float4* predV, const float4* predN, const float* fillDepth, const FrameDev* frame,
                           const PoseDev* pose, const float* R9t3_host_or_null, float* const vmaps[3], float* const nmaps[3],
-                          int W, int H, Intr k, hipStream_t s) {
+                          int W, int H, Intr k, hipStream_t s, int* fixup) {
     PyrArgs a;
     a.predV = predV; a.predN = predN; a.fillDepth = fillDepth; a.frame = frame; a.pose = pose;
+    a.fixup = fixup;
     a.hostPose = R9t3_host_or_null != nullptr;
     for (int i = 0; i < 9; ++i) a.R[i] = a.hostPose ? R9t3_host_or_null[i] : 0.f;
     for (int i = 0; i < 3; ++i) a.t[i] = a.hostPose ? R9t3_host_or_null[9 + i] : 0.f;
@@ -1707,6 +1657,7 @@ void launch_bilateral_model_pyramid(const float* depth, float* depthF, const flo
                                     hipStream_t s) {
     PyrArgs a;
     a.predV = predV; a.predN = predN; a.fillDepth = fillDepth; a.frame = frame; a.pose = pose;
+    a.fixup = nullptr;
     a.hostPose = 0;
     for (int i = 0; i < 9; ++i) a.R[i] = 0.f;
     for (int i = 0; i < 3; ++i) a.t[i] = 0.f;
@@ -1743,17 +1694,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     if (after == before) { frame_pyramid_body(f, lds, ((g - before) << 3) + lane); return; }
     const int gx = ((a.W >> 2) + 15) / 16, gy = ((a.H >> 2) + 3) / 4, j = (before << 3) + lane;
     if (j >= gx * gy) return;   // (padding of the pyramid half to a multiple of 8)
+    if (pyramid_fixup_skips(a, j == 0)) return;
     model_pyramid_body(a, j % gx, j / gx, 0);
 }
 
 void launch_frame_model_pyramid(const float* depthF, float* const fvmap[3], float* const fnmap[3], float cutoff, const float4* predV, const float4* predN,
                                 const float* fillDepth, const FrameDev* frame, const PoseDev* pose, float* const vmaps[3], float* const nmaps[3], int W, int H,
-                                Intr k, hipStream_t s) {
+                                Intr k, hipStream_t s, int* fixup) {
     FramePyrArgs f;
     f.depth = depthF; f.W = W; f.H = H; f.k = k; f.cutoff = cutoff;
     for (int i = 0; i < 3; ++i) { f.vmap[i] = fvmap[i]; f.nmap[i] = fnmap[i]; }
     PyrArgs a;
     a.predV = predV; a.predN = predN; a.fillDepth = fillDepth; a.frame = frame; a.pose = pose;
+    a.fixup = fixup;
     a.hostPose = 0;
     for (int i = 0; i < 9; ++i) a.R[i] = 0.f;
     for (int i = 0; i < 3; ++i) a.t[i] = 0.f;

@@ -15,6 +15,8 @@
 #include "mf_device.h"
 #include "mf_rgbd_device.h"
 #include "mf_bilateral_device.h"
+#include "mf_frame_pyramid_device.h"
+#include "mf_model_pyramid_device.h"
 
 namespace mf {
 
@@ -207,6 +209,8 @@ struct TileArgs {
     const int* vis_list; const int* vis_count;   // as BinArgs
     int advance; FrameAdvance adv;   // advance != 0: the last workgroup also runs the end-of-frame bookkeeping (k_frame_advance)
     unsigned long long* prof;        // optional ("splatProfile"): [tiles][8] shader-clock stamps of thread 0 + the tile's list length
+    float* vm[3]; float* nm[3];      // optional ("tilePyramid"; vm[0] == nullptr: off): the model-side pyramid's planes -- every tile workgroup also writes their texels
+    int tile_wgs;                    // workgroups of the launch that run the tile pass (the padded tile count); any behind them build the frame pyramid
 };
 
 // The z-test of one 16x16 tile in LDS, shared by the prediction (payload = surfel index) and the global projection (payload =
@@ -308,12 +312,40 @@ __device__ __forceinline__ void tile_ztest(int tile, int tilesX, int tileH, Intr
 
 // Pass 3: one workgroup (512 threads by default, the first 256 own the pixels) per 16x16 tile: LDS z-test over the tile's surfel list, then the fragment outputs
 // (combo_splat.frag) of every pixel of the tile.
+//
+// "tilePyramid" (a.vm set): the workgroup then also writes the three levels of the model-side pyramid for its tile -- what model_pyramid_body
+// (mf_odometry.hip) computes WITHOUT fill-in from the prediction maps this workgroup has just written.  Every output of that pyramid depends on one
+// aligned 4 x 4 block of level-0 texels, and a tile is a whole number of such blocks: level 0 goes out from the registers that hold the pixel, the
+// pixel's copyMaps value is staged in the z-test's LDS (free by now: rays in s_ray, keys in s_key -- a thread overwrites only the slot it has read),
+// and behind the barrier the workgroup takes anyway one thread per level-1 texel, a DPP quad per level-2 texel, runs model_pyramid_down
+// (mf_model_pyramid_device.h) -- the function model_pyramid_body calls.  Whether the tracking step fills in is decided by THIS launch's last
+// workgroup from the coverage of the whole image, so no tile knows it: a frame whose decision comes out "fill" gets its pyramid rebuilt by the
+// fix-up launch behind (k_model_pyramid with PyrArgs::fixup; mf_frame.inl: enqueue_fused_head).
+//
+// "fusedTilePyramid": workgroups behind the a.tile_wgs tile workgroups build the NEXT frame's pyramid from its filtered depth (frame_pyramid_body,
+// mf_frame_pyramid_device.h) -- independent of the tile pass, LDS-tiled and light on VALU, where the tile pass waits for gathers and its workgroups
+// live 10 us of a 25 us launch.  The body is written for 256 threads: a workgroup of 512 (1024) takes two (four) pyramid tiles, each 256 threads with
+// an LDS slice of their own; they meet only in the body's barriers.  A pyramid workgroup takes no ticket.
+constexpr int kTilePoolFloat4 = (4 * kFpLdsFloats + 3) / 4;   // LDS of a workgroup: rays + keys of a tile (768 float4), or four pyramid tiles' depths
+static_assert(kTilePoolFloat4 >= kTile * kTileHMax + kTile * kTileHMax / 2, "the pool holds a tile's rays and keys");
 template <int kSpriteLanes>
-__global__ __launch_bounds__(1024) void k_splat_tile(const TileArgs a) {
-    __shared__ unsigned long long s_key[kTile * kTileHMax];
-    __shared__ float4 s_ray[kTile * kTileHMax];
+// (eight wavefronts per SIMD, as before the epilogue: left alone the compiler takes 75 registers for it and a compute unit holds three 512-thread
+// workgroups instead of four)
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_splat_tile(const TileArgs a, const FramePyrArgs fp) {
+    __shared__ float4 s_pool[kTilePoolFloat4];
     __shared__ int s_range[1];
     __shared__ int s_cover;
+    if ((int)blockIdx.x >= a.tile_wgs) {
+        // pyramid tiles of this workgroup: sub-tile `sub` of workgroup j is block (j / 8 * nsub + sub) * 8 + j % 8 of the body's grid -- the index keeps
+        // its XCD (a.tile_wgs is a multiple of 8) and the XCD its band of tile rows (xcd_contiguous_tile)
+        const int nsub = (int)blockDim.x >> 8, sub = (int)threadIdx.x >> 8, j = (int)blockIdx.x - a.tile_wgs;
+        const bool has = sub < nsub;   // (a workgroup of 320 / 384 threads: the threads behind the first 256 belong to no tile)
+        frame_pyramid_body<false>(fp, reinterpret_cast<float*>(s_pool) + (has ? sub : 0) * kFpLdsFloats, ((((j >> 3) * nsub + sub) << 3) + (j & 7)),
+                                  (int)threadIdx.x & 255, has);
+        return;
+    }
+    float4* const s_ray = s_pool;
+    unsigned long long* const s_key = reinterpret_cast<unsigned long long*>(s_pool + kTile * kTileHMax);
     // XCD k draws the k-th contiguous eighth of the tile list (mf_device.h): a sprite overlaps 1.8 tiles on average, and neighbouring
     // tiles now find its records in the same L2.  The grid is padded to a multiple of 8; a padding workgroup draws nothing but still
     // takes its ticket below.
@@ -333,12 +365,14 @@ __global__ __launch_bounds__(1024) void k_splat_tile(const TileArgs a) {
                                             prof, stamp, a.vis_list, a.vis_count, a.src.box);
     const int px = tx0 + (threadIdx.x & (kTile - 1)), py = ty0 + (threadIdx.x >> 4);
     int covered = 0;   // this pixel is one of the 20x down-sampled samples of MaskFusion::requiresFillIn and carries a colour
+    const bool pyr = a.vm[0] != nullptr;
     // (gathering the winners' records along the tile's COLUMNS and transposing the outputs through the LDS -- what made the index map's resolve
     // twice as fast -- changes nothing here: 61.3 against 60.0 us for the stage, profiles/r05r_ab.txt; a sprite covers ~4 x 4 pixels, neighbouring
     // pixels share their winner either way)
     if (live && (int)threadIdx.x < kTile * a.tileH && px < a.W && py < a.H) {   // (threads beyond the tile's 256 pixels only helped with the list)
       const int p = py * a.W + px;
       const unsigned long long key = s_key[threadIdx.x];
+      float4 v4 = make_float4(0, 0, 0, 0), n4 = v4;
       if (key == kEmptyKey) {
         a.predV[p] = a.predN[p] = make_float4(0, 0, 0, 0);
         a.predImage[p] = make_uchar4(0, 0, 0, 0);
@@ -348,11 +382,13 @@ __global__ __launch_bounds__(1024) void k_splat_tile(const TileArgs a) {
       } else {
         const int i = (int)(unsigned)(key & 0xFFFFFFFFull);
         const float z = __uint_as_float((unsigned)(key >> 32));
-        const float4 pc = a.src.pc[i], c4 = a.src.ct[i], n4 = a.src.nr[i];
-        const float3 n = normalize_gl(mul33(a.pose->Ri, f3(n4.x, n4.y, n4.z)));
+        const float4 pc = a.src.pc[i], c4 = a.src.ct[i], s4 = a.src.nr[i];
+        const float3 n = normalize_gl(mul33(a.pose->Ri, f3(s4.x, s4.y, s4.z)));
         const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;
-        a.predV[p] = make_float4((fcx - k.cx) * z * (1.f / k.fx), (fcy - k.cy) * z * (1.f / k.fy), z, pc.w);  // combo_splat.frag:56
-        a.predN[p] = make_float4(n.x, n.y, n.z, n4.w);
+        v4 = make_float4((fcx - k.cx) * z * (1.f / k.fx), (fcy - k.cy) * z * (1.f / k.fy), z, pc.w);  // combo_splat.frag:56
+        n4 = make_float4(n.x, n.y, n.z, s4.w);
+        a.predV[p] = v4;
+        a.predN[p] = n4;
         const int ci = (int)c4.x;
         const uchar4 col = make_uchar4((ci >> 16) & 0xFF, (ci >> 8) & 0xFF, ci & 0xFF, 255);
         a.predImage[p] = col;
@@ -367,6 +403,18 @@ __global__ __launch_bounds__(1024) void k_splat_tile(const TileArgs a) {
         }
         // MaskFusion::requiresFillIn (MaskFusion.cpp:630-648): nearest sample of the 20x down-sampled colour prediction
         covered = ((px % 20) == 10 && (py % 20) == 10 && px / 20 < a.W / 20 && py / 20 < a.H / 20 && col.x > 0 && col.y > 0 && col.z > 0) ? 1 : 0;
+      }
+      if (pyr) {
+        // copyMapsKernel of the texel; its flags are the values' own NaNs (vok = !isnan(v.x), nok = !isnan(n.x)), so six floats carry it.  Level 0
+        // covers the whole 4 x 4 blocks of the image, as model_pyramid_body's threads do
+        const MapPx m = copy_maps_px(v4, n4);
+        float Rm[9];   // the model pose, as model_pyramid_body reads it (scalar loads; read again behind the barrier rather than kept across it)
+#pragma unroll
+        for (int q = 0; q < 9; ++q) Rm[q] = a.pose->R[q];
+        const float3 tm = f3(a.pose->t[0], a.pose->t[1], a.pose->t[2]);
+        s_ray[threadIdx.x] = make_float4(m.v.x, m.v.y, m.v.z, m.n.x);
+        s_key[threadIdx.x] = ((unsigned long long)__float_as_uint(m.n.z) << 32) | (unsigned long long)__float_as_uint(m.n.y);
+        if (px < 4 * (a.W >> 2) && py < 4 * (a.H >> 2)) store_tx(a.vm[0], a.nm[0], a.W * a.H, p, m.v, m.vok, m.n, m.nok, Rm, tm);
       }
     }
     // One 64-bit atomic per workgroup carries both its coverage count and its "finished" ticket (the count travels IN the atomic, so
@@ -385,7 +433,7 @@ __global__ __launch_bounds__(1024) void k_splat_tile(const TileArgs a) {
     if (threadIdx.x == 0) {
         const int wg_cover = s_cover;
         const unsigned long long old = atomicAdd(&a.frame->done_cover, (1ull << 32) | (unsigned long long)(unsigned)wg_cover);
-        if ((unsigned)(old >> 32) == gridDim.x - 1u) {
+        if ((unsigned)(old >> 32) == (unsigned)a.tile_wgs - 1u) {   // (the tile workgroups' tickets: others may share the launch)
             const int cover = (int)(unsigned)(old & 0xFFFFFFFFull) + wg_cover;
             FrameDev* f = a.frame;
             f->done_cover = 0ull;
@@ -402,6 +450,33 @@ __global__ __launch_bounds__(1024) void k_splat_tile(const TileArgs a) {
                 f->cover += cover;
             }
         }
+    }
+    if (pyr) {
+        // levels 1 and 2 of the tile: thread t takes level-1 texel b = t % 4 of the tile's level-2 texel t / 4 (4 per row).  Every thread of the
+        // workgroup makes the call -- the quad broadcasts need whole wavefronts -- and only those with a texel inside the image read and write
+        const int W1 = a.W >> 1, H1 = a.H >> 1, W2 = a.W >> 2, H2 = a.H >> 2;
+        const int q = (int)threadIdx.x >> 2, b = (int)threadIdx.x & 3, bx = b & 1, by = b >> 1, lx2 = q & 3, ly2 = q >> 2;
+        const int x2 = (tx0 >> 2) + lx2, y2 = (ty0 >> 2) + ly2;
+        const bool inside = live && ly2 < (a.tileH >> 2) && x2 < W2 && y2 < H2;
+        float Rm[9];
+#pragma unroll
+        for (int q = 0; q < 9; ++q) Rm[q] = a.pose->R[q];
+        const float3 tm = f3(a.pose->t[0], a.pose->t[1], a.pose->t[2]);
+        MapPx m4[4];
+        if (inside) {
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) {
+                    const int l = (4 * ly2 + 2 * by + dy) * kTile + 4 * lx2 + 2 * bx + dx;
+                    const float4 r = s_ray[l];
+                    const unsigned long long w = s_key[l];
+                    MapPx& m = m4[dy * 2 + dx];
+                    m.v = f3(r.x, r.y, r.z); m.n = f3(r.w, __uint_as_float((unsigned)(w & 0xFFFFFFFFull)), __uint_as_float((unsigned)(w >> 32)));
+                    m.vok = !isnan(m.v.x); m.nok = !isnan(m.n.x);
+                }
+        }
+        model_pyramid_down(m4, inside, b, Rm, tm, a.vm[1], a.nm[1], W1 * H1, (2 * y2 + by) * W1 + 2 * x2 + bx, a.vm[2], a.nm[2], W2 * H2, y2 * W2 + x2);
     }
 }
 
@@ -478,7 +553,7 @@ int launch_splat_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W,
                        int timeDelta, int* tile_count, int* entries, int entries_cap, float4* rec0, float4* rec1, void* bbox, float4* predV,
                        float4* predN, uchar4* predImage, uint16_t* predTime, const uint8_t* rgb, uint8_t* predGray, uint8_t* fillGray, hipStream_t s,
                        const FrameAdvance* advance, int fillPassthrough, unsigned long long* prof, SplatTuning tune, const VisList* vis,
-                       const SplatFilterJob* filter) {
+                       const SplatFilterJob* filter, const SplatPyramidJob* pyramid) {
     const int tileH = splat_tile_height(tune.tile_h);
     const int tilesX = (W + kTile - 1) / kTile, tilesY = (H + tileH - 1) / tileH, nt = tilesX * tilesY;
     if (nt > kMaxTiles) return -1;
@@ -512,12 +587,22 @@ int launch_splat_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W,
     t.vis_list = b.vis_list; t.vis_count = b.vis_count;
     t.advance = advance ? 1 : 0;
     t.adv = advance ? *advance : FrameAdvance{nullptr, nullptr, nullptr};
+    t.tile_wgs = xcd_padded_grid(nt);
+    for (int i = 0; i < 3; ++i) { t.vm[i] = pyramid ? pyramid->vm[i] : nullptr; t.nm[i] = pyramid ? pyramid->nm[i] : nullptr; }
+    FramePyrArgs fp{};
+    int grid = t.tile_wgs;
+    if (pyramid && pyramid->frame_depth) {   // the next frame's pyramid behind the tile workgroups: g_tile_threads / 256 of its tiles per workgroup
+        fp.depth = pyramid->frame_depth; fp.W = W; fp.H = H; fp.k = k; fp.cutoff = pyramid->frame_cutoff;
+        for (int i = 0; i < 3; ++i) { fp.vmap[i] = pyramid->frame_vmap[i]; fp.nmap[i] = pyramid->frame_nmap[i]; }
+        const int nsub = g_tile_threads >> 8, groups = xcd_padded_grid(frame_pyramid_tiles(W, H)) >> 3;
+        grid += ((groups + nsub - 1) / nsub) << 3;
+    }
     switch (g_sprite_lanes) {
-        case 1: hipLaunchKernelGGL(k_splat_tile<1>, dim3(xcd_padded_grid(nt)), dim3(g_tile_threads), 0, s, t); break;
-        case 2: hipLaunchKernelGGL(k_splat_tile<2>, dim3(xcd_padded_grid(nt)), dim3(g_tile_threads), 0, s, t); break;
-        case 8: hipLaunchKernelGGL(k_splat_tile<8>, dim3(xcd_padded_grid(nt)), dim3(g_tile_threads), 0, s, t); break;
-        case 16: hipLaunchKernelGGL(k_splat_tile<16>, dim3(xcd_padded_grid(nt)), dim3(g_tile_threads), 0, s, t); break;
-        default: hipLaunchKernelGGL(k_splat_tile<4>, dim3(xcd_padded_grid(nt)), dim3(g_tile_threads), 0, s, t); break;
+        case 1: hipLaunchKernelGGL(k_splat_tile<1>, dim3(grid), dim3(g_tile_threads), 0, s, t, fp); break;
+        case 2: hipLaunchKernelGGL(k_splat_tile<2>, dim3(grid), dim3(g_tile_threads), 0, s, t, fp); break;
+        case 8: hipLaunchKernelGGL(k_splat_tile<8>, dim3(grid), dim3(g_tile_threads), 0, s, t, fp); break;
+        case 16: hipLaunchKernelGGL(k_splat_tile<16>, dim3(grid), dim3(g_tile_threads), 0, s, t, fp); break;
+        default: hipLaunchKernelGGL(k_splat_tile<4>, dim3(grid), dim3(g_tile_threads), 0, s, t, fp); break;
     }
     return 0;
 }
