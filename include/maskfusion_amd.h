@@ -277,6 +277,52 @@ int mf_cloud_fpfh_dev(const float* d_points, int32_t stride, int32_t normal_offs
  * rows or a null pointer.  Enqueued on `stream`, which the call synchronises before it returns. */
 int mf_feature_match_dev(const float* d_target, int64_t n_target, const float* d_query, int64_t n_query, int32_t dim, int32_t* d_idx,
                          float* d_d2, void* stream);
+/* A triangle mesh of a cloud of oriented points (surfels), on the GPU (kernels: mf_mesh.hip; DESIGN.md "Surfel meshing"; the Python side:
+ * maskfusion_amd.mesh): naive surface nets over a moving-least-squares signed distance to the points' tangent planes.  No table of cases.
+ * INPUT.  n records of `stride` floats at d_points: x y z at offset 0, a normal at normal_offset (>= 3) and, with color_offset >= 3, three
+ * colour floats there, in any linear scale (color_offset < 0: no colour).  A point is ELIGIBLE when its position and its normal are finite and
+ * the normal is not zero -- mf_cloud_fpfh_dev's rule --; normals are normalised in fp64.  The others take no part.
+ * LATTICE (HOST parameters).  origin3, voxel > 0, dims3 = corners per axis (each >= 2), support with voxel <= support <= 8 voxel,
+ * min_neighbours >= 1.  Corner (i, j, k) stands, per axis, at xf = (float)((double)origin + (double)i * (double)voxel).
+ * CORNER.  Its neighbours are the eligible points that pass mf_cloud_nn_dev's fp32 radius test against xf with radius = support (d2 = dx*dx +
+ * dy*dy + dz*dz without contraction, d2 <= fl(support * support)), found over mf_cloud_nn_dev's grid.  In fp64 from the fp32 values, with
+ * d = xf - p, q = (d . d) * (1 / support^2) and w = max(1 - q, 0)^2:  W = sum w,  f = sum w (n . d) / W,  a = sum w n / W,  c = sum w colour / W
+ * (n the unit normal).  The corner is VALID when it has >= min_neighbours neighbours and W > 0.  A valid corner is INSIDE when f < 0; f == 0
+ * counts as outside.
+ * CELL (i, j, k) has the corners (i + {0,1}, j + {0,1}, k + {0,1}).  It is ACTIVE when all eight are valid and they are not all on one side.
+ * QUADS.  The lattice edge from corner c to c + e_a (a = 0, 1, 2; u = (a + 1) mod 3, w = (a + 2) mod 3) whose two ends are valid and on
+ * different sides gives one quad when the four cells around it -- c, c - e_u, c - e_u - e_w, c - e_w -- are all active: the vertices of
+ * those cells in that order when f(c) < 0, in the reverse order otherwise.  Seen from the outside (f > 0) every face is counter-clockwise.
+ * VERTICES.  A cell carries a vertex iff it is active and a quad names it: there is no unreferenced vertex.  Its position is the mean, over
+ * the cell's sign-changing edges -- the x-edges first, then y, then z; within axis a the edges at offsets (0,0), (1,0), (0,1), (1,1) along
+ * (u, w) --, of xa + t (xb - xa) with t = fa / (fa - fb), in fp64 from the fp32 corner positions.  Its normal is the normalised mean of
+ * a_a + t (a_b - a_a) over the same edges, or zero when that mean is zero; its colour the plain mean of c_a + t (c_b - c_a).  All are stored
+ * as fp32.
+ * REPRODUCIBILITY.  The order of the vertices and of the quads is a function of the inputs alone (integer scans; no atomic's rank enters).
+ * The fp64 sums of a corner follow the grid's bucket order, i.e. the order of the build's atomics, so positions, normals and colours are
+ * reproducible to rounding only, as mf_cloud_normals_dev's normals are.
+ * CALLS.  mf_cloud_mesh_build_dev does all the work but the output: *out receives a handle that owns its device memory (as a context does;
+ * it keeps no pointer to d_points), *n_vertices and *n_quads the counts.  Memory and work follow the occupied part of the lattice, not its
+ * volume, except for a directory of 4 bytes per block of 8 x 8 x 8 corners.  stage_ms (HOST, MF_MESH_STAGES floats, or NULL): the device
+ * time of the stages in milliseconds -- 0 eligible points, normals and block marks, directory scan; 1 grid build; 2 the host's wait, read-back
+ * and allocation; 3 block list and the field; 4 cells and quads; 5 the two scans.  Enqueued on `stream`, which the call synchronises before
+ * it returns the counts.  n == 0 gives an empty mesh and MF_OK.  mf_cloud_mesh_emit_dev fills the caller's DEVICE arrays: d_vertices
+ * [n_vertices][3], d_normals [n_vertices][3] or NULL, d_colors [n_vertices][3] or NULL (only for a mesh built with colour), d_cells
+ * (int32 [n_vertices][3]: each vertex's lattice cell) or NULL, d_quads (int32 [n_quads][4]: vertex indices); it synchronises `stream` too.
+ * mf_cloud_mesh_free releases the handle (NULL: nothing).
+ * MF_EINVAL, with nothing enqueued and the reason in mf_last_error(NULL) (per thread), for a null pointer, n < 0 or n > 2^30, stride < 6, a
+ * normal or colour offset below 3 or ending beyond the stride, an origin, voxel or support that is not finite, voxel <= 0, support outside
+ * voxel .. 8 voxel, min_neighbours < 1, a dims entry < 2, a lattice corner with |x / support| >= 2^30 - 2 and a lattice of more than 2^27
+ * blocks (the directory's limit); after the grid build, for an eligible point with |x / support| >= 2^30.  MF_ENOMEM when an allocation
+ * fails or more than 2^20 blocks are occupied. */
+typedef struct mf_mesh mf_mesh;
+#define MF_MESH_STAGES 6
+int mf_cloud_mesh_build_dev(const float* d_points, int32_t stride, int32_t normal_offset, int32_t color_offset, int64_t n, const float* origin3,
+                            float voxel, const int32_t* dims3, float support, int32_t min_neighbours, mf_mesh** out, uint32_t* n_vertices,
+                            uint32_t* n_quads, float* stage_ms, void* stream);
+int mf_cloud_mesh_emit_dev(const mf_mesh* mesh, float* d_vertices, float* d_normals, float* d_colors, int32_t* d_cells, int32_t* d_quads,
+                           void* stream);
+void mf_cloud_mesh_free(mf_mesh* mesh);
 /* Segmentation scores on the GPU (kernels: mf_eval_image.hip; DESIGN.md "Segmentation evaluation"; the metrics built on them:
  * maskfusion_amd.eval.seg_metrics).  Both calls compare two label streams d_est, d_gt (DEVICE, uint8 [n_frames][height][width], any byte
  * alignment).  lut_est and lut_gt (HOST, 256 entries each) map a raw label value to a compact class index < n_est (< n_gt), or to 255: void.

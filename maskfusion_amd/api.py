@@ -250,6 +250,23 @@ class MaskFusion:
     def savePly(self, exportDir: str):
         self._chk(self._L.mf_save_ply(self._h, exportDir.encode()))
 
+    def saveMesh(self, exportDir: str, voxel: float, support: float | None = None, min_neighbours: int = 3):
+        """mesh-<id>.ply per model, beside savePly's cloud-<id>.ply: the surfels savePly writes (confidence above the model's threshold, from
+        mf_download_map), their normal (offset 8, negated as savePly negates it: it then faces the camera that saw the surfel) and their
+        colour decoded on the host, meshed on the GPU (maskfusion_amd.mesh.mesh_cloud, DESIGN.md "Surfel meshing"; model frame).  A model
+        without such surfels gets a file with no vertices.  Returns the paths."""
+        from . import mesh as _mesh
+        paths = []
+        for m in self.getModels():
+            rec = m.downloadMap()
+            rec = rec[rec[:, 3] > m.getConfidenceThreshold()]
+            col = rec[:, 4].astype(np.int64)
+            rgb = np.stack([col >> 16 & 0xFF, col >> 8 & 0xFF, col & 0xFF], 1).astype(np.float32)
+            v, n, c, t = _mesh.mesh_cloud(rec[:, :3], -rec[:, 8:11], rgb, voxel=voxel, support=support, min_neighbours=min_neighbours)
+            paths.append(f"{exportDir}mesh-{m.getID()}.ply")
+            _mesh.write_mesh_ply(paths[-1], v, n, c, t)
+        return paths
+
     def exportPoses(self, exportDir: str):
         self._chk(self._L.mf_export_poses(self._h, exportDir.encode()))
 

@@ -18,6 +18,8 @@ in the working directory (upstream refuses to start without it; here: every clas
 An addition to the reference's flags: -evalviews scores the maps against the input after every processed frame -- the render from the
 sensor's own view (MaskFusion.sensorRenderView) compared with the frame on the GPU (maskfusion_amd.eval.ViewScorer: coverage, depth L1,
 PSNR, SSIM, per model and for the whole image) -- and writes the result to <exportdir>views.json at the end.
+Another: -emesh <voxel> writes, beside -em's cloud-<id>.ply, a triangle mesh mesh-<id>.ply of every model's map (MaskFusion.saveMesh: GPU
+surface nets at that voxel size in metres, maskfusion_amd.mesh).
 """
 from __future__ import annotations
 
@@ -30,7 +32,7 @@ import numpy as np
 _VALUE_FLAGS = {"-l", "-dir", "-depthdir", "-maskdir", "-colorprefix", "-depthprefix", "-maskprefix", "-indexW", "-cal", "-basedir",
                 "-exportdir", "-d", "-i", "-or", "-confG", "-confO", "-s", "-e", "-nm", "-offset", "-t", "-ie", "-cv", "-pt", "-ft",
                 "-ic", "-a", "-frameQ", "-method", "-p", "-segMinNew", "-segMaxNew", "-thNew", "-gpu", "-name", "-k", "-crfRGB", "-crfDepth",
-                "-crfPos", "-crfAppearance", "-crfSmooth"}
+                "-crfPos", "-crfAppearance", "-crfSmooth", "-emesh"}
 _BOOL_FLAGS = {"-static", "-run", "-q", "-ep", "-em", "-es", "-ev", "-el", "-en", "-fo", "-nso", "-f", "-tum3", "-v2", "-icl", "-rl",
                "-fs", "-r", "-ftf", "-sc", "-keep", "-o", "-v1", "-rgbonly", "-evalviews"}
 
@@ -194,6 +196,8 @@ def main(argv=None):
         mf.exportPoses(export_dir)
     if "-em" in flags:
         mf.savePly(export_dir)
+    if "-emesh" in flags:
+        mf.saveMesh(export_dir, float(flags["-emesh"]))
     if views is not None and views.frames:
         import json
         from .eval import _clean

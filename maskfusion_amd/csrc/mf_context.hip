@@ -709,7 +709,11 @@ extern "C" void mf_destroy(mf_ctx* c) {
     delete c;
 }
 
-extern "C" const char* mf_last_error(const mf_ctx* c) { return c ? c->err.c_str() : "null context"; }
+extern "C" const char* mf_last_error(const mf_ctx* c) {
+    if (c) return c->err.c_str();
+    const char* e = cloud_last_error();     // a call without a context (mf_cloud_mesh_*) failed on this thread
+    return e ? e : "null context";
+}
 
 #include "mf_frame.inl"      // processFrame: stages, batches, spawn / retire, mf_process_frame[_dev], mf_sync, mf_predict
 

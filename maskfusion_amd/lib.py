@@ -16,6 +16,7 @@ TIMING_LABELS = ["Preprocess", "odomInit", "odom", "indexMap", "Fuse::Data", "Fu
                  "mmGlobalProjection", "mmEdgeLabels", "mmBackgroundFuseClean", "mmHostStall", "mmObjectFuseClean", "mmHostWaitMs"]
 
 
+MF_MESH_STAGES = 6
 MF_N_PASSES = 12
 PASS_LABELS = ["bgGlobalProjection", "bgIndexMap", "bgFuseData", "bgFuseUpdate", "bgIndexMap2", "bgClean", "bgAppend", "bgPredict",
                "objGlobalProjection", "objFuseClean", "objPredict", "compaction"]
@@ -176,6 +177,10 @@ SYMBOLS = {
     "mf_cloud_fpfh_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                     C.c_void_p]),
     "mf_feature_match_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mf_cloud_mesh_build_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_float,
+                                          C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]),
+    "mf_cloud_mesh_emit_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mf_cloud_mesh_free": (None, [C.c_void_p]),
     "mf_label_confusion_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_void_p]),
     "mf_label_boundary_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
