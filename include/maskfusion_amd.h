@@ -323,6 +323,62 @@ int mf_cloud_mesh_build_dev(const float* d_points, int32_t stride, int32_t norma
 int mf_cloud_mesh_emit_dev(const mf_mesh* mesh, float* d_vertices, float* d_normals, float* d_colors, int32_t* d_cells, int32_t* d_quads,
                            void* stream);
 void mf_cloud_mesh_free(mf_mesh* mesh);
+/* Scoring against a triangle mesh, on the GPU (kernels: mf_eval_trimesh.hip; DESIGN.md "Mesh evaluation"; the Python side:
+ * maskfusion_amd.eval.TriMesh, compare_cloud_mesh): the exact distance from every query point to the nearest triangle within a radius, and a
+ * deterministic area-uniform sampler of the mesh whose samples serve wherever a reference cloud is consumed.
+ * INPUT.  n_vertices vertices, x y z at d_vertices + i * vertex_stride floats; n_triangles index triples at d_triangles (DEVICE, int32
+ * [n_triangles][3]).  A triangle (a, b, c) is ELIGIBLE when its three indices are in [0, n_vertices), its nine coordinates are finite with
+ * |x / cell| < 2^30, and the fp64 squared norm of n = (b - a) x (c - a) is > 0:  ab = b - a, ac = c - a per component in fp64 from the fp32
+ * values, n = (ab.y ac.z - ab.z ac.y, ab.z ac.x - ab.x ac.z, ab.x ac.y - ab.y ac.x), |n|^2 = (n.x n.x + n.y n.y) + n.z n.z.  The other
+ * triangles are skipped: never returned, never sampled.  They keep their index: returned indices are indices into the caller's array.
+ * *n_eligible receives the number of eligible triangles.  cell is the edge of the search structure's cells; it decides speed only.
+ * DISTANCE.  The query is mapped first by query_to_mesh16 (HOST, column-major 4 x 4, or NULL) with mf_cloud_nn_dev's fp32 transform, x' =
+ * ((T00 x + T01 y) + T02 z) + T03.  Then everything is fp64 from the fp32 values, every operation rounded on its own (no contraction); a dot
+ * product is u . v = (u.x v.x + u.y v.y) + u.z v.z.  The closest point of an eligible triangle to p follows Ericson, Real-Time Collision
+ * Detection 5.1.5, with the tests in the book's order and the first that holds deciding:
+ *   ab = b - a, ac = c - a, ap = p - a;  d1 = ab . ap, d2 = ac . ap
+ *   1. d1 <= 0 and d2 <= 0:                                   closest = a                  (vertex region A)
+ *   bp = p - b;  d3 = ab . bp, d4 = ac . bp
+ *   2. d3 >= 0 and d4 <= d3:                                  closest = b                  (vertex region B)
+ *   vc = d1 d4 - d3 d2
+ *   3. vc <= 0 and d1 >= 0 and d3 <= 0:  v = d1 / (d1 - d3),  closest = a + v ab           (edge AB)
+ *   cp = p - c;  d5 = ab . cp, d6 = ac . cp
+ *   4. d6 >= 0 and d5 <= d6:                                  closest = c                  (vertex region C)
+ *   vb = d5 d2 - d1 d6
+ *   5. vb <= 0 and d2 >= 0 and d6 <= 0:  w = d2 / (d2 - d6),  closest = a + w ac           (edge AC)
+ *   va = d3 d6 - d5 d4
+ *   6. va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0:  w = (d4 - d3) / ((d4 - d3) + (d5 - d6)),  closest = b + w (c - b)   (edge BC)
+ *   7. otherwise:  den = 1 / ((va + vb) + vc), v = vb den, w = vc den,  closest = (a + ab v) + ac w   (face)
+ * and D2 = (e.x e.x + e.y e.y) + e.z e.z with e = p - closest.  A triangle COUNTS when D2 <= (double)radius * (double)radius.  The result is
+ * the minimum over (D2, t) lexicographically among the counting triangles -- ties go to the smallest triangle index t --: d_dist[i] =
+ * (float)sqrt(D2), d_tri[i] = t, d_closest[i] (float [n_query][3], or NULL) the fp32 rounding of the fp64 closest point.  When no triangle
+ * counts or the query is not finite: +inf, -1 and NaN.  The result depends on the mesh, the query and the radius alone: not on cell, and it
+ * is the same for every call.  Queries are read as x, y, z at d_query + i * query_stride floats.
+ * SAMPLING.  Systematic along the cumulative area; what decides is integer.  Triangle t has u_t = llrint(0.5 * sqrt(|n|^2) * (double)density
+ * * 256) units (a unit is 1 / 256 sample; density in samples per unit area; 0 units when not eligible), S is the exclusive scan of u in
+ * triangle order and S_total its sum.  n_samples = S_total / 256 (integer division).  Sample k sits at unit 256 k + 128: its triangle is the t
+ * with S[t] <= unit < S[t + 1].  Its barycentrics come from the R2 sequence in fp64: r1 = frac((k + 1) * 0.7548776662466927), r2 =
+ * frac((k + 1) * 0.5698402909980532), frac(x) = x - floor(x); when r1 + r2 > 1 both are replaced by 1 - r.  The point is
+ * (a + r1 (b - a)) + r2 (c - a) per component in fp64, stored as fp32; the normal is n / sqrt(|n|^2), stored as fp32.  Samples come in the order
+ * of k, so their triangle indices never decrease.
+ * CALLS.  mf_trimesh_build_dev builds the search structure: *out receives a handle that owns its device memory and keeps no pointer to the
+ * caller's arrays.  mf_trimesh_sample_plan_dev computes u and S for a density and returns n_samples; mf_trimesh_sample_emit_dev writes the
+ * samples of the handle's latest plan: d_points [n_samples][3], d_normals [n_samples][3] or NULL, d_tri (int32 [n_samples]) or NULL.  Every
+ * call is enqueued on `stream` and synchronises it before it returns.  Zero triangles is valid: every query gets +inf and -1, and there are 0
+ * samples.  mf_trimesh_free releases the handle (NULL: nothing).
+ * MF_EINVAL, with nothing enqueued and the reason in mf_last_error(NULL) (per thread), for a null pointer where the count is not zero (or a
+ * null handle or result pointer), a count above 2^30 or below 0, vertex_stride or query_stride < 3, a cell, radius or density that is not
+ * finite or <= 0, radius > 16 cell, a transform that is not finite, mf_trimesh_sample_emit_dev before a plan, and S_total >= 2^32; after the
+ * query kernel, for a finite query with |x / cell| >= 2^30 after the transform.  MF_ENOMEM when an allocation fails or the structure would
+ * hold 2^32 (triangle, cell) pairs. */
+typedef struct mf_trimesh mf_trimesh;
+int mf_trimesh_build_dev(const float* d_vertices, int32_t vertex_stride, int64_t n_vertices, const int32_t* d_triangles, int64_t n_triangles,
+                         float cell, mf_trimesh** out, uint32_t* n_eligible, void* stream);
+int mf_trimesh_distance_dev(const mf_trimesh* mesh, const float* d_query, int32_t query_stride, int64_t n_query, const float* query_to_mesh16,
+                            float radius, float* d_dist, int32_t* d_tri, float* d_closest, void* stream);
+int mf_trimesh_sample_plan_dev(mf_trimesh* mesh, float density, uint64_t* n_samples, void* stream);
+int mf_trimesh_sample_emit_dev(const mf_trimesh* mesh, float* d_points, float* d_normals, int32_t* d_tri, void* stream);
+void mf_trimesh_free(mf_trimesh* mesh);
 /* Segmentation scores on the GPU (kernels: mf_eval_image.hip; DESIGN.md "Segmentation evaluation"; the metrics built on them:
  * maskfusion_amd.eval.seg_metrics).  Both calls compare two label streams d_est, d_gt (DEVICE, uint8 [n_frames][height][width], any byte
  * alignment).  lut_est and lut_gt (HOST, 256 entries each) map a raw label value to a compact class index < n_est (< n_gt), or to 255: void.

@@ -465,6 +465,8 @@ void launch_render(RenderArgs a, const RenderView& v, const PoseDev* bg_pose, in
 uint64_t nn_workspace_bytes(int64_t n_target);
 // the reason of the calling thread's last failed call that takes no context (mf_mesh.hip), or null: what mf_last_error(NULL) returns
 const char* cloud_last_error();
+// records who + text as that reason and returns rc (mf_mesh.hip's and mf_eval_trimesh.hip's failures)
+int cloud_fail(const char* who, const char* text, int rc);
 // the whole of mf_cloud_nn_dev (include/maskfusion_amd.h): grid build + query on stream s, then a synchronisation of s; *why (why may be null): the reason of an error, untouched when there is none
 int nn_run(const float* d_target, int target_stride, int64_t n_target, const float* d_query, int query_stride, int64_t n_query,
            const float* T16 /*host, column-major, or null*/, float radius, float* d_dist, int32_t* d_idx, void* d_ws, uint64_t ws_bytes, hipStream_t s,

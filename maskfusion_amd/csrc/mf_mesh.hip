@@ -330,10 +330,11 @@ __global__ __launch_bounds__(kNnThreads) void k_mesh_emit_quads(MeshDev m, MeshO
 // ---------------- host side ----------------
 static thread_local std::string t_cloud_error;     // the reason of the last failure of a call that has no context (mf_last_error(NULL))
 const char* cloud_last_error() { return t_cloud_error.empty() ? nullptr : t_cloud_error.c_str(); }
-static int mesh_fail(const char* text, int rc) {
-    t_cloud_error = std::string("mf_cloud_mesh: ") + text;
+int cloud_fail(const char* who, const char* text, int rc) {
+    t_cloud_error = std::string(who) + text;
     return rc;
 }
+static int mesh_fail(const char* text, int rc) { return cloud_fail("mf_cloud_mesh: ", text, rc); }
 
 }  // namespace mf
 

@@ -12,6 +12,7 @@ seeded RANSAC over the matches in numpy, then register().
     python -m maskfusion_amd.eval --est DIR [--ref DIR] [--gt FILE] [--radius R] [--tau a,b,c] [--pair est_id:ref_id ...]
                                   [--register [--register-radius R0,R1,...] [--register-iterations N] [--point-to-point]]
                                   [--register-global[=VOXEL]] [--ref-cloud FILE [--init FILE]] [--estimate-normals[=R]] [--normals]
+                                  [--ref-mesh FILE [--mesh-density D] [--mesh-cell C]]
                                   [--seg-gt DIR [--seg-gt-prefix Mask] [--seg-index-width 4] [--seg-radius R] [--seg-void V]]
                                   [--observed-from SEQ [--observed-poses FILE] [--observed-cal FILE] [--observed-tol A[,R]]
                                    [--observed-rule seen|surface] [--observed-min-frames K] [--observed-stride S] [--observed-max-depth D]
@@ -23,6 +24,8 @@ mf_label_confusion_dev / mf_label_boundary_dev).  ViewScorer scores what needs n
 sensor's own view against the frame it just saw (mf_view_score_dev; the driver's -evalviews flag writes its result as views.json).
 With --observed-from, completeness and F-score are also reported over the part of the reference the sequence observed: every reference point
 is classified against every depth frame on the GPU (mf_cloud_visibility_dev; Visibility, observed, observe_sequence).
+With --ref-mesh the reference is a triangle mesh (.ply or .obj): accuracy is the exact distance to its triangles and its area-uniform samples
+stand in for the reference cloud everywhere else (TriMesh, compare_cloud_mesh; mf_trimesh_*, kernels: csrc/mf_eval_trimesh.hip).
 """
 from __future__ import annotations
 
@@ -344,6 +347,113 @@ def compare_clouds(est, ref, radius: float = 0.05, taus=(0.01, 0.02, 0.05), T=No
         p, r = acc["fraction"][k], comp["fraction"][k]
         f[k] = 2 * p * r / (p + r) if p + r > 0 else 0.0
     return {"radius": radius, "accuracy": acc, "completeness": comp, "fscore": f}
+
+
+class TriMesh:
+    """The library's handle of a triangle mesh to score against (mf_trimesh; include/maskfusion_amd.h has the definitions): distance() is the
+    exact distance to the nearest triangle, sample() the deterministic area-uniform sampler.  vertices (n, >= 3) float32, triangles (m, 3)
+    int32 -- numpy arrays or device tensors; cell: the edge of the search structure's cells (speed only; radius <= 16 cell).  A context
+    manager, like mesh.Mesh."""
+
+    def __init__(self, vertices, triangles, cell: float):
+        import torch
+        from .lib import MFError, load
+        self._L = load()
+        self._h = C.c_void_p()
+        v = _device_points(vertices, 3, "vertices must be (n, >= 3) float32")
+        t = triangles if isinstance(triangles, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(triangles, np.int32)).reshape(-1, 3))
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("triangles must be (m, 3) int32")
+        t = t.to(v.device).contiguous()
+        self.device = v.device
+        self._stream = _stream_of(v.device)
+        nv, nt = int(v.shape[0]), int(t.shape[0])
+        ne = C.c_uint32(0)
+        rc = self._L.mf_trimesh_build_dev(v.data_ptr() if nv else None, int(v.shape[1]), nv, t.data_ptr() if nt else None, nt, float(cell),
+                                          C.byref(self._h), C.byref(ne), self._stream)
+        if rc != 0:
+            raise MFError(f"mf_trimesh_build_dev failed with code {rc}: {self._L.mf_last_error(None).decode()}")
+        self.n_triangles, self.n_eligible, self.cell, self.density = nt, int(ne.value), float(cell), None
+
+    def _fail(self, name, rc):
+        from .lib import MFError
+        raise MFError(f"{name} failed with code {rc}: {self._L.mf_last_error(None).decode()}")
+
+    def distance(self, query, radius: float, T=None, closest: bool = False):
+        """numpy (dist float32, +inf: no triangle within radius; tri int32, -1: none[; closest (n, 3) float32, NaN: none]) for every query
+        point; T: 4 x 4 applied to the queries first, as nearest()'s"""
+        import torch
+        q = _device_points(query)
+        nq = int(q.shape[0])
+        dist = torch.empty(max(nq, 1), dtype=torch.float32, device=q.device)
+        tri = torch.empty(max(nq, 1), dtype=torch.int32, device=q.device)
+        cl = torch.empty((max(nq, 1), 3), dtype=torch.float32, device=q.device) if closest else None
+        T16 = _pack_T(T)
+        rc = self._L.mf_trimesh_distance_dev(self._h, q.data_ptr() if nq else None, int(q.shape[1]), nq, T16.ctypes.data if T16 is not None else None,
+                                             float(radius), dist.data_ptr(), tri.data_ptr(), cl.data_ptr() if closest else None, self._stream)
+        if rc != 0:
+            self._fail("mf_trimesh_distance_dev", rc)
+        out = (dist[:nq].cpu().numpy(), tri[:nq].cpu().numpy())
+        return out + (cl[:nq].cpu().numpy(),) if closest else out
+
+    def sample(self, density: float):
+        """numpy (points (n, 3) float32, unit face normals (n, 3) float32, triangle index int32 (n,)) of the sampler at `density` samples
+        per unit area"""
+        import torch
+        n = C.c_uint64(0)
+        rc = self._L.mf_trimesh_sample_plan_dev(self._h, float(density), C.byref(n), self._stream)
+        if rc != 0:
+            self._fail("mf_trimesh_sample_plan_dev", rc)
+        n = int(n.value)
+        p = torch.empty((max(n, 1), 3), dtype=torch.float32, device=self.device)
+        nr = torch.empty((max(n, 1), 3), dtype=torch.float32, device=self.device)
+        tri = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        rc = self._L.mf_trimesh_sample_emit_dev(self._h, p.data_ptr(), nr.data_ptr(), tri.data_ptr(), self._stream)
+        if rc != 0:
+            self._fail("mf_trimesh_sample_emit_dev", rc)
+        self.density = float(density)
+        return p[:n].cpu().numpy(), nr[:n].cpu().numpy(), tri[:n].cpu().numpy()
+
+    def close(self):
+        if self._h:
+            self._L.mf_trimesh_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def compare_cloud_mesh(est, trimesh, samples, radius: float = 0.05, taus=(0.01, 0.02, 0.05), T=None, ref_keep=None) -> dict:
+    """compare_clouds against a triangle mesh: accuracy = est -> triangles (TriMesh.distance: exact, free of the sampling's bias),
+    completeness = samples -> est (nearest; samples: TriMesh.sample()'s points), the same F-score, plus "reference".  T and ref_keep (one
+    bool per sample) as in compare_clouds."""
+    if T is not None:
+        est = transform_f32(T, est.cpu().numpy() if hasattr(est, "cpu") else est)
+    acc = cloud_stats(trimesh.distance(est, radius)[0], radius, taus)
+    ref = samples.cpu().numpy() if hasattr(samples, "cpu") else np.asarray(samples, np.float32)
+    n_samples = len(ref)
+    if ref_keep is not None:
+        keep = np.asarray(ref_keep)
+        if keep.dtype != np.bool_ or keep.shape != (len(ref),):
+            raise ValueError("ref_keep must be one bool per sample")
+        ref = ref[keep]
+    comp = cloud_stats(nearest(est, ref, radius)[0], radius, taus)
+    f = {}
+    for t in taus:
+        k = f"{t:g}"
+        p, r = acc["fraction"][k], comp["fraction"][k]
+        f[k] = 2 * p * r / (p + r) if p + r > 0 else 0.0
+    return {"radius": radius, "accuracy": acc, "completeness": comp, "fscore": f,
+            "reference": {"triangles": trimesh.n_triangles, "eligible": trimesh.n_eligible, "samples": n_samples, "density": trimesh.density}}
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -1515,6 +1625,10 @@ def main(argv=None) -> int:
     ap.add_argument("--register-seed", type=int, default=0, help="seed of --register-global's RANSAC (default 0)")
     ap.add_argument("--ref-cloud", metavar="FILE", help="a single reference PLY (a ground-truth model) for the background cloud of --est")
     ap.add_argument("--init", metavar="FILE", help="with --ref-cloud: text file with the 4 x 4 est -> ref start")
+    ap.add_argument("--ref-mesh", metavar="FILE", help="a reference triangle mesh (.ply or .obj) in place of --ref-cloud: accuracy is the exact "
+                    "distance to its triangles; its area-uniform samples and face normals serve as the reference cloud everywhere else")
+    ap.add_argument("--mesh-density", type=float, metavar="D", help="samples per square metre of --ref-mesh (default 10000)")
+    ap.add_argument("--mesh-cell", type=float, metavar="C", help="cell edge of the triangle search structure (default --radius / 2)")
     ap.add_argument("--estimate-normals", nargs="?", const=True, type=float, metavar="R", help="estimate the normals of a reference cloud whose PLY "
                     "has none, on the GPU from neighbourhoods of radius R (default 2 x --radius): --register then runs point-to-plane against it")
     ap.add_argument("--normals", action="store_true", help="add normal_consistency to every cloud comparison in which both clouds have normals "
@@ -1545,7 +1659,7 @@ def main(argv=None) -> int:
     obs = None
     given = [k for k in ("poses", "cal", "tol", "rule", "min_frames", "stride", "max_depth", "time_scale") if getattr(a, "observed_" + k) is not None]
     if a.observed_from:
-        if not (a.ref or a.ref_cloud):
+        if not (a.ref or a.ref_cloud or a.ref_mesh):
             ap.error("--observed-from needs --ref or --ref-cloud")
         try:
             tol = [float(x) for x in (a.observed_tol or str(a.radius)).split(",")]
@@ -1570,10 +1684,18 @@ def main(argv=None) -> int:
         ap.error("--seg-radius and --seg-void need --seg-gt")
     if a.seg_radius is not None and not 0 <= a.seg_radius <= MAX_RADIUS:
         ap.error(f"--seg-radius takes 0..{MAX_RADIUS}")
-    if a.init and not a.ref_cloud:
+    if a.init and not (a.ref_cloud or a.ref_mesh):
         ap.error("--init needs --ref-cloud")
     if a.ref_cloud and a.ref:
         ap.error("give --ref or --ref-cloud, not both")
+    if a.ref_mesh and (a.ref or a.ref_cloud):
+        ap.error("--ref-mesh takes the place of --ref and --ref-cloud: give one of the three")
+    if not a.ref_mesh and (a.mesh_density is not None or a.mesh_cell is not None):
+        ap.error("--mesh-density and --mesh-cell need --ref-mesh")
+    mesh_density = 10000.0 if a.mesh_density is None else a.mesh_density
+    mesh_cell = a.radius / 2 if a.mesh_cell is None else a.mesh_cell
+    if a.ref_mesh and not (math.isfinite(mesh_density) and mesh_density > 0 and math.isfinite(mesh_cell) and mesh_cell > 0):
+        ap.error("--mesh-density and --mesh-cell take positive numbers")
     global_voxel = None
     if a.register_global is not None:
         global_voxel = a.radius if a.register_global is True else a.register_global
@@ -1584,9 +1706,9 @@ def main(argv=None) -> int:
         a.register = True
     if not a.register and (a.register_radius or a.point_to_point):
         ap.error("--register-radius and --point-to-point need --register")
-    if a.register and not (a.ref or a.ref_cloud):
+    if a.register and not (a.ref or a.ref_cloud or a.ref_mesh):
         ap.error("--register and --register-global need --ref or --ref-cloud")
-    if (a.estimate_normals is not None or a.normals) and not (a.ref or a.ref_cloud):
+    if (a.estimate_normals is not None or a.normals) and not (a.ref or a.ref_cloud or a.ref_mesh):
         ap.error("--estimate-normals and --normals need --ref or --ref-cloud")
     normals_radius = None
     if a.estimate_normals is not None:
@@ -1601,6 +1723,13 @@ def main(argv=None) -> int:
             ap.error("--register-radius takes comma-separated numbers")
         if not radii or not all(math.isfinite(r) and r > 0 for r in radii) or a.register_iterations < 1:
             ap.error("--register-radius needs positive radii, --register-iterations at least 1")
+
+    tm = [None]      # --ref-mesh: the TriMesh every cloud* block is scored against
+
+    def compare(ce, cr, T=None, ref_keep=None):
+        if tm[0] is not None:
+            return compare_cloud_mesh(ce, tm[0], cr, a.radius, taus, T=T, ref_keep=ref_keep)
+        return compare_clouds(ce, cr, a.radius, taus, T=T, ref_keep=ref_keep)
 
     def ref_normals(o, cr, nr):
         """the reference's normals: the file's, or with --estimate-normals and none in the file the estimated ones (recorded in o)"""
@@ -1625,7 +1754,7 @@ def main(argv=None) -> int:
         else:
             res = register(ce, cr, radii[-1], T0=T0, ref_normals=None if a.point_to_point else nr, max_iterations=a.register_iterations,
                            schedule=radii, method="point" if a.point_to_point else "plane")
-        o["cloud_registered"] = compare_clouds(ce, cr, a.radius, taus, T=res["T"])
+        o["cloud_registered"] = compare(ce, cr, T=res["T"])
         o["registration"] = registration_summary(res)
         if global_voxel is not None:
             o["registration"]["coarse"] = coarse_summary(res["coarse"])
@@ -1651,7 +1780,7 @@ def main(argv=None) -> int:
                            min_frames=obs["min_frames"], tol_abs=obs["tol_abs"], tol_rel=obs["tol_rel"], max_depth=obs["max_depth"],
                            poses=a.observed_poses or "estimate")
             o["observed" + suffix] = summary
-        o["cloud" + suffix + "_observed"] = compare_clouds(ce, cr, a.radius, taus, T=T, ref_keep=obs["keep"])
+        o["cloud" + suffix + "_observed"] = compare(ce, cr, T=T, ref_keep=obs["keep"])
         return True
 
     est = _run_files(a.est)
@@ -1718,7 +1847,7 @@ def main(argv=None) -> int:
             if ei == 0 and a.gt:
                 o["trajectory_vs_gt"] = gt_res
             results.append(o)
-    elif a.ref_cloud:
+    elif a.ref_cloud or a.ref_mesh:
         if 0 not in est or "cloud" not in est[0]:
             sys.stderr.write(f"eval: {a.est} holds no cloud-0.ply (background map)\n")
             return 2
@@ -1727,8 +1856,21 @@ def main(argv=None) -> int:
         except (OSError, ValueError) as e:
             sys.stderr.write(f"eval: --init: {e}\n")
             return 2
-        (ce, ne), (cr, nr) = read_ply(est[0]["cloud"], normals=True), read_ply(a.ref_cloud, normals=True)
-        o = {"model": 0, "ref_cloud": a.ref_cloud, "cloud": compare_clouds(ce, cr, a.radius, taus, T=T0)}
+        ce, ne = read_ply(est[0]["cloud"], normals=True)
+        if a.ref_mesh:
+            from .mesh import read_triangle_mesh
+            try:
+                rm = read_triangle_mesh(a.ref_mesh)
+            except (OSError, ValueError) as e:
+                sys.stderr.write(f"eval: --ref-mesh: {e}\n")
+                return 2
+            tm[0] = TriMesh(rm["vertices"], rm["triangles"], mesh_cell)
+            cr, nr, _ = tm[0].sample(mesh_density)
+            o = {"model": 0, "ref_mesh": a.ref_mesh}
+        else:
+            cr, nr = read_ply(a.ref_cloud, normals=True)
+            o = {"model": 0, "ref_cloud": a.ref_cloud}
+        o["cloud"] = compare(ce, cr, T=T0)
         if not observed_part(o, ce, cr, T0):
             return 2
         nr = ref_normals(o, cr, nr)
@@ -1743,7 +1885,7 @@ def main(argv=None) -> int:
     elif a.gt:
         results.append({"model": 0, "trajectory_vs_gt": gt_res})
     elif not a.seg_gt:
-        ap.error("give --ref, --ref-cloud, --gt, --seg-gt or a combination")
+        ap.error("give --ref, --ref-cloud, --ref-mesh, --gt, --seg-gt or a combination")
     if a.seg_gt:
         try:
             results += score_segmentation(a.est, a.seg_gt, a.seg_gt_prefix, a.seg_index_width, a.seg_radius, a.seg_void)

@@ -6,7 +6,8 @@ meshing").
 
 mesh_cloud() meshes oriented points, write_mesh_ply() writes the result as a binary PLY whose vertex element has mf_save_ply's property
 names (so maskfusion_amd.eval.read_ply and every mesh viewer read it) followed by a `face` element.  MaskFusion.saveMesh (api.py) and the
-command line's -emesh write one mesh-<id>.ply per model.
+command line's -emesh write one mesh-<id>.ply per model.  read_triangle_mesh() reads a mesh back from .ply or .obj (read_obj) for
+maskfusion_amd.eval --ref-mesh; --fidelity adds the exact distances from the input points to the mesh just written (eval.TriMesh).
 """
 from __future__ import annotations
 
@@ -189,6 +190,51 @@ def read_mesh_ply(path: str):
             "triangles": np.array(fa["i"], np.int32).reshape(-1, 3)}
 
 
+def read_obj(path: str):
+    """A Wavefront OBJ's `v` and `f` records as a dict like read_mesh_ply's (normals and colours None): face corners of the forms i, i/j,
+    i/j/k and i//k, negative indices counting back from the vertices read so far, polygons cut into a fan; every other record is ignored"""
+    v, t = [], []
+    with open(path, "r", errors="replace") as f:
+        for no, line in enumerate(f, 1):
+            w = line.split()
+            if not w:
+                continue
+            try:
+                if w[0] == "v":
+                    v.append((float(w[1]), float(w[2]), float(w[3])))
+                elif w[0] == "f":
+                    idx = []
+                    for corner in w[1:]:
+                        i = int(corner.split("/")[0])
+                        idx.append(i - 1 if i > 0 else len(v) + i)
+                        if i == 0:
+                            raise ValueError("index 0")
+                    for k in range(1, len(idx) - 1):
+                        t.append((idx[0], idx[k], idx[k + 1]))
+            except (ValueError, IndexError):
+                raise ValueError(f"{path}:{no}: cannot read `{line.strip()}`")
+    return {"vertices": np.array(v, np.float32).reshape(-1, 3), "normals": None, "colors": None, "triangles": np.array(t, np.int32).reshape(-1, 3)}
+
+
+def write_obj(path: str, vertices, triangles):
+    """`v` and `f` records, the coordinates with the nine digits that give a float32 back"""
+    with open(path, "w") as f:
+        for x, y, z in np.asarray(vertices, np.float32).reshape(-1, 3).tolist():
+            f.write("v %.9g %.9g %.9g\n" % (x, y, z))
+        for a, b, c in np.asarray(triangles, np.int64).reshape(-1, 3).tolist():
+            f.write("f %d %d %d\n" % (a + 1, b + 1, c + 1))
+
+
+def read_triangle_mesh(path: str):
+    """read_mesh_ply for .ply, read_obj for .obj (by the extension, in any case)"""
+    ext = path.rsplit(".", 1)[-1].lower() if "." in path else ""
+    if ext == "ply":
+        return read_mesh_ply(path)
+    if ext == "obj":
+        return read_obj(path)
+    raise ValueError(f"{path}: a triangle mesh is read from .ply or .obj")
+
+
 def read_cloud_ply(path: str):
     """(points, normals, colours or None) of a cloud as mf_save_ply writes it; the normals are required"""
     from .eval import read_ply
@@ -238,6 +284,8 @@ def main(argv=None) -> int:
     ap.add_argument("--support", type=float, default=None, help="radius of the distance field's weights (default 2.5 voxel; voxel .. 8 voxel)")
     ap.add_argument("--min-neighbours", type=int, default=3, help="points a lattice corner needs within the support (default 3)")
     ap.add_argument("-o", "--output", required=True, help="the mesh, a binary PLY")
+    ap.add_argument("--fidelity", action="store_true", help="add cloud_to_mesh to the JSON line: the exact distances from the input points to "
+                    "the mesh just written (radius: the support)")
     a = ap.parse_args(argv)
     try:
         pts, nrm, col = read_cloud_ply(a.cloud)
@@ -246,8 +294,13 @@ def main(argv=None) -> int:
         return 2
     v, n, c, t = mesh_cloud(pts, nrm, col, voxel=a.voxel, support=a.support, min_neighbours=a.min_neighbours)
     write_mesh_ply(a.output, v, n, c, t)
-    print(json.dumps({"points": int(len(pts)), "vertices": int(len(v)), "triangles": int(len(t)), "voxel": a.voxel,
-                      "support": a.support if a.support is not None else 2.5 * a.voxel, "output": a.output}))
+    support = a.support if a.support is not None else 2.5 * a.voxel
+    info = {"points": int(len(pts)), "vertices": int(len(v)), "triangles": int(len(t)), "voxel": a.voxel, "support": support, "output": a.output}
+    if a.fidelity:
+        from .eval import TriMesh, cloud_stats
+        with TriMesh(v, t, support / 2) as tm:
+            info["cloud_to_mesh"] = cloud_stats(tm.distance(pts, support)[0], support, (a.voxel / 4, a.voxel / 2, a.voxel))
+    print(json.dumps(info))
     return 0
 
 
