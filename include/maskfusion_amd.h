@@ -379,6 +379,48 @@ int mf_trimesh_distance_dev(const mf_trimesh* mesh, const float* d_query, int32_
 int mf_trimesh_sample_plan_dev(mf_trimesh* mesh, float density, uint64_t* n_samples, void* stream);
 int mf_trimesh_sample_emit_dev(const mf_trimesh* mesh, float* d_points, float* d_normals, int32_t* d_tri, void* stream);
 void mf_trimesh_free(mf_trimesh* mesh);
+/* Ray casting against a triangle mesh, on the GPU (kernels: mf_trimesh_ray.hip; DESIGN.md "Mesh rendering"; the Python side:
+ * maskfusion_amd.eval.TriMesh.raycast / render, maskfusion_amd.meshseq, the mesh command's --views): for every ray the first triangle of an
+ * mf_trimesh handle it hits.  The reference never renders a mesh: the definition is this project's own.
+ * RAYS.  mf_trimesh_raycast_dev reads ray i as x y z at d_origin + i * ray_stride and at d_dir + i * ray_stride floats (ray_stride >= 3).
+ * ray_to_mesh16 (HOST, column-major 4 x 4, or NULL) maps the origin with mf_cloud_nn_dev's fp32 transform, o' = ((T00 x + T01 y) + T02 z) +
+ * T03, and the direction with its linear part alone in the same operation order, d' = (T00 x + T01 y) + T02 z: no translation.  A ray is
+ * VALID when its six mapped values are finite and the direction is not zero.  The direction need not be of unit length: t counts in
+ * lengths of d'.  Which triangles are ELIGIBLE is what mf_trimesh_build_dev decided.
+ * INTERSECTION.  Everything after the transform is fp64 from the fp32 values, every operation rounded on its own (no contraction): the
+ * watertight test of Woop, Benthin and Wald (Journal of Computer Graphics Techniques 2 (1), 2013), written out.  With o, d the mapped ray:
+ *   kz = the first axis in the order x, y, z with the largest |d|;  kx = (kz + 1) % 3, ky = (kx + 1) % 3;  when d[kz] < 0, kx and ky swap
+ *   Sx = d[kx] / d[kz],  Sy = d[ky] / d[kz],  Sz = 1 / d[kz]
+ *   for each vertex P of (a, b, c):  P' = P - o per component;  Px = P'[kx] - Sx P'[kz],  Py = P'[ky] - Sy P'[kz],  Pz = Sz P'[kz]
+ *   U = Cx By - Cy Bx,  V = Ax Cy - Ay Cx,  W = Bx Ay - By Ax
+ *   the triangle is missed when (U < 0 or V < 0 or W < 0) and (U > 0 or V > 0 or W > 0)
+ *   det = (U + V) + W;  det == 0 is a miss
+ *   T = (U Az + V Bz) + W Cz,  t = T / det
+ * A triangle COUNTS when tmin <= t <= tmax, compared after (double) of the fp32 arguments; tmax may be +inf.  An edge's function is computed
+ * from its two end points and the ray alone, so two triangles that share an edge see the same value: no ray slips between them.
+ * RESULT.  The minimum over (t, index) lexicographically among the counting triangles -- ties go to the smallest triangle index --:
+ * d_t[i] = (float)t, d_tri[i] = index, d_uv[i] (float [n_rays][2], or NULL) = ((float)(V / det), (float)(W / det)), the weights of b and c
+ * (a's is 1 - u - v), d_front[i] (uint8 [n_rays], or NULL) = det > 0: the ray meets the side from which (a, b, c) is counter-clockwise.
+ * When nothing counts or the ray is not valid: +inf, -1, NaN NaN and 0.  The result depends on the mesh, the ray, tmin and tmax alone: not
+ * on cell, and it is the same for every call.
+ * PINHOLE.  mf_trimesh_render_dev casts, for pixel (x, y) of a width x height image, the ray of camera-frame origin (0, 0, 0) and direction
+ *   (((float)x - cx) * (1.f / fx),  ((float)y - cy) * (1.f / fy),  1)       in fp32, each operation rounded on its own
+ * -- the expressions by which the pipeline's vertex map (k_vmap_nmap) back-projects a pixel of depth 1, so a rendered depth back-projects
+ * onto the mesh --, mapped by mesh_from_cam16 (HOST, required) as above, through the same device function as the generic call.  The
+ * camera-frame z of the direction being 1, t IS the depth: d_depth[y * width + x] = (float)t, and 0, the pipeline's "no measurement",
+ * where nothing counts; d_tri, d_uv, d_front as above, in pixel order.
+ * CALLS.  Both are enqueued on `stream` and synchronise it before they return.  A mesh of zero triangles is valid: every ray misses.
+ * MF_EINVAL, with nothing enqueued and the reason in mf_last_error(NULL) (per thread), for a null handle, a null pointer where the count is
+ * not zero (d_uv and d_front may be NULL), a count above 2^30 or below 0, ray_stride < 3, a transform that is not finite (or, for the
+ * pinhole form, NULL), tmin not finite, tmax NaN or tmax < tmin, fx or fy not finite or 0, cx or cy not finite, a width or height below 1
+ * or above 16 384, and a mesh whose triangles in the cell grid (those mf_trimesh_build_dev did not put on its list of wide ones) span more
+ * than 2^15 cells on an axis, which bounds every ray's walk: build the mesh with a larger cell. */
+int mf_trimesh_raycast_dev(const mf_trimesh* mesh, const float* d_origin, const float* d_dir, int32_t ray_stride, int64_t n_rays,
+                           const float* ray_to_mesh16, float tmin, float tmax, float* d_t, int32_t* d_tri, float* d_uv, uint8_t* d_front,
+                           void* stream);
+int mf_trimesh_render_dev(const mf_trimesh* mesh, int32_t width, int32_t height, float fx, float fy, float cx, float cy,
+                          const float* mesh_from_cam16, float tmin, float tmax, float* d_depth, int32_t* d_tri, float* d_uv, uint8_t* d_front,
+                          void* stream);
 /* Segmentation scores on the GPU (kernels: mf_eval_image.hip; DESIGN.md "Segmentation evaluation"; the metrics built on them:
  * maskfusion_amd.eval.seg_metrics).  Both calls compare two label streams d_est, d_gt (DEVICE, uint8 [n_frames][height][width], any byte
  * alignment).  lut_est and lut_gt (HOST, 256 entries each) map a raw label value to a compact class index < n_est (< n_gt), or to 255: void.

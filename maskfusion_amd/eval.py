@@ -414,6 +414,45 @@ class TriMesh:
         self.density = float(density)
         return p[:n].cpu().numpy(), nr[:n].cpu().numpy(), tri[:n].cpu().numpy()
 
+    def raycast(self, origins, dirs, T=None, tmin: float = 0.0, tmax: float = float("inf")):
+        """numpy (t float32, +inf: no hit; tri int32, -1: none; uv (n, 2) float32, the weights of the triangle's b and c, NaN: none; front
+        bool: the ray met the counter-clockwise side) of the first triangle each ray origins[i] + t dirs[i] hits with tmin <= t <= tmax
+        (mf_trimesh_raycast_dev); T: 4 x 4 applied to the rays first, the directions by its linear part"""
+        import torch
+        o, d = _device_points(origins), _device_points(dirs)
+        if o.shape != d.shape:
+            raise ValueError("origins and dirs must have one shape")
+        n = int(o.shape[0])
+        t = torch.empty(max(n, 1), dtype=torch.float32, device=o.device)
+        tri = torch.empty(max(n, 1), dtype=torch.int32, device=o.device)
+        uv = torch.empty((max(n, 1), 2), dtype=torch.float32, device=o.device)
+        front = torch.empty(max(n, 1), dtype=torch.uint8, device=o.device)
+        T16 = _pack_T(T)
+        rc = self._L.mf_trimesh_raycast_dev(self._h, o.data_ptr() if n else None, d.data_ptr() if n else None, int(o.shape[1]), n,
+                                            T16.ctypes.data if T16 is not None else None, float(tmin), float(tmax), t.data_ptr(), tri.data_ptr(),
+                                            uv.data_ptr(), front.data_ptr(), self._stream)
+        if rc != 0:
+            self._fail("mf_trimesh_raycast_dev", rc)
+        return t[:n].cpu().numpy(), tri[:n].cpu().numpy(), uv[:n].cpu().numpy(), front[:n].cpu().numpy().astype(bool)
+
+    def render(self, W: int, H: int, fx: float, fy: float, cx: float, cy: float, mesh_from_cam, tmin: float = 0.0, tmax: float = float("inf")):
+        """numpy (depth (H, W) float32, 0: nothing hit; tri (H, W) int32; uv (H, W, 2) float32; front (H, W) bool) of the mesh seen by the
+        pinhole camera whose pose in the mesh's frame is mesh_from_cam (4 x 4): mf_trimesh_render_dev"""
+        import torch
+        W, H = int(W), int(H)
+        n = max(W, 1) * max(H, 1)
+        depth = torch.empty(n, dtype=torch.float32, device=self.device)
+        tri = torch.empty(n, dtype=torch.int32, device=self.device)
+        uv = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        front = torch.empty(n, dtype=torch.uint8, device=self.device)
+        T16 = _pack_T(mesh_from_cam)
+        rc = self._L.mf_trimesh_render_dev(self._h, W, H, float(fx), float(fy), float(cx), float(cy), T16.ctypes.data if T16 is not None else None,
+                                           float(tmin), float(tmax), depth.data_ptr(), tri.data_ptr(), uv.data_ptr(), front.data_ptr(), self._stream)
+        if rc != 0:
+            self._fail("mf_trimesh_render_dev", rc)
+        return (depth.cpu().numpy().reshape(H, W), tri.cpu().numpy().reshape(H, W), uv.cpu().numpy().reshape(H, W, 2),
+                front.cpu().numpy().reshape(H, W).astype(bool))
+
     def close(self):
         if self._h:
             self._L.mf_trimesh_free(self._h)

@@ -24,15 +24,22 @@ def write_klg(path, frames, compress_depth=True):
             f.write(img)
 
 
-def write_image_dir(path, frames, masks=None, class_ids=None, calibration=None, index_width=4, start_index=0):
-    """Color####.png / Depth####.png (16-bit millimetres) / Mask####.png + Mask####.txt, as ImageLogReader expects."""
+def write_image_dir(path, frames, masks=None, class_ids=None, calibration=None, index_width=4, start_index=0, depth_format="png"):
+    """Color####.png / Depth####.png (16-bit millimetres) / Mask####.png + Mask####.txt, as ImageLogReader expects.  depth_format "exr":
+    Depth####.exr, one float32 channel in metres -- nothing is rounded (the reader takes .exr before .png)."""
+    if depth_format not in ("png", "exr"):
+        raise ValueError("depth_format is png or exr")
     from PIL import Image
     os.makedirs(path, exist_ok=True)
     for i, (rgb, depth) in enumerate(frames):
         s = f"{i + start_index:0{index_width}d}"
         Image.fromarray(np.ascontiguousarray(rgb, np.uint8), "RGB").save(os.path.join(path, f"Color{s}.png"))
-        d16 = np.clip(np.rint(np.asarray(depth, np.float64) * 1000.0), 0, 65535).astype(np.uint16)
-        Image.fromarray(d16).save(os.path.join(path, f"Depth{s}.png"))
+        if depth_format == "exr":
+            from .exr import write_exr
+            write_exr(os.path.join(path, f"Depth{s}.exr"), {"Z": np.asarray(depth, np.float32)})
+        else:
+            d16 = np.clip(np.rint(np.asarray(depth, np.float64) * 1000.0), 0, 65535).astype(np.uint16)
+            Image.fromarray(d16).save(os.path.join(path, f"Depth{s}.png"))
         if masks is not None:
             Image.fromarray(np.ascontiguousarray(masks[i], np.uint8), "L").save(os.path.join(path, f"Mask{s}.png"))
             if class_ids is not None:

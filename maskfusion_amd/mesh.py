@@ -8,6 +8,12 @@ mesh_cloud() meshes oriented points, write_mesh_ply() writes the result as a bin
 names (so maskfusion_amd.eval.read_ply and every mesh viewer read it) followed by a `face` element.  MaskFusion.saveMesh (api.py) and the
 command line's -emesh write one mesh-<id>.ply per model.  read_triangle_mesh() reads a mesh back from .ply or .obj (read_obj) for
 maskfusion_amd.eval --ref-mesh; --fidelity adds the exact distances from the input points to the mesh just written (eval.TriMesh).
+
+    python -m maskfusion_amd.mesh --mesh scene.obj --views seq/ --poses seq/groundtruth.txt
+
+--views renders the mesh -- the one just written, or with --mesh an existing one -- from every frame's pose (eval.TriMesh.render: GPU ray
+casting, mf_trimesh_render_dev; DESIGN.md "Mesh rendering") and scores depth and colour against the sensor's frames (eval.ViewScorer);
+shade() turns a render's triangle indices and weights into colours on the host.
 """
 from __future__ import annotations
 
@@ -225,6 +231,78 @@ def write_obj(path: str, vertices, triangles):
             f.write("f %d %d %d\n" % (a + 1, b + 1, c + 1))
 
 
+def shade(mesh_colors, triangles, tri, uv, front, base=(180.0, 180.0, 180.0), vertices=None, dirs=None):
+    """Colours for a render of eval.TriMesh.render / raycast, on the host (off the hot path): uint8 of tri's shape + (3,).  tri, uv, front:
+    the render's.  With mesh_colors ((n_vertices, 3), 0..255) the colour of a hit is (1 - u - v) Ca + u Cb + v Cc.  Without them it is `base`
+    times a headlight term, |n . d| / (|n| |d|) of the face normal n = (b - a) x (c - a) and the ray's direction d -- vertices ((n_vertices,
+    3)) and dirs (tri's shape + (3,), in the mesh's frame) are needed for that; without them the term is 1.  A face seen from behind (front
+    False) is drawn at half the brightness.  Misses are black."""
+    tri = np.asarray(tri)
+    shape = tri.shape
+    t = tri.reshape(-1)
+    hit = t >= 0
+    F = np.asarray(triangles, np.int64).reshape(-1, 3)[t[hit]]
+    out = np.zeros((t.size, 3), np.float64)
+    if mesh_colors is not None:
+        w = np.asarray(uv, np.float64).reshape(-1, 2)[hit]
+        c = np.asarray(mesh_colors, np.float64).reshape(-1, 3)
+        col = (1.0 - w[:, :1] - w[:, 1:]) * c[F[:, 0]] + w[:, :1] * c[F[:, 1]] + w[:, 1:] * c[F[:, 2]]
+    else:
+        col = np.broadcast_to(np.asarray(base, np.float64), (len(F), 3)).copy()
+        if vertices is not None and dirs is not None:
+            v = np.asarray(vertices, np.float64).reshape(-1, 3)
+            n = np.cross(v[F[:, 1]] - v[F[:, 0]], v[F[:, 2]] - v[F[:, 0]])
+            d = np.asarray(dirs, np.float64).reshape(-1, 3)[hit]
+            with np.errstate(all="ignore"):
+                k = np.abs((n * d).sum(1)) / (np.linalg.norm(n, axis=1) * np.linalg.norm(d, axis=1))
+            col *= np.nan_to_num(k)[:, None]
+    col = np.where(np.asarray(front, bool).reshape(-1)[hit][:, None], col, 0.5 * col)
+    out[hit] = col
+    return np.clip(np.rint(out), 0, 255).astype(np.uint8).reshape(shape + (3,))
+
+
+def camera_dirs(W: int, H: int, fx: float, fy: float, cx: float, cy: float, mesh_from_cam=None) -> np.ndarray:
+    """(H, W, 3) float64: the directions of mf_trimesh_render_dev's pixel rays, turned into the mesh's frame by mesh_from_cam -- for shade()"""
+    y, x = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    d = np.stack([(x - cx) / fx, (y - cy) / fy, np.ones_like(x)], -1)
+    return d if mesh_from_cam is None else d @ np.asarray(mesh_from_cam, np.float64)[:3, :3].T
+
+
+def score_views(trimesh, vertices, triangles, colors, seq: str, poses: str, cal=None, stride: int = 1, max_dt: float = 0.02, time_scale: float = 1e-6):
+    """The mesh of `trimesh` (eval.TriMesh; vertices, triangles, colors: what it was built from) rendered from the pose of every stride-th
+    frame of the sequence `seq` (a directory or a .klg) and scored against that frame with eval.ViewScorer.add: coverage, depth L1, PSNR and
+    SSIM.  poses: a TUM file, camera -> the mesh's frame, its stamps the frames' times time_scale (mf_export_poses' and meshseq's scale).
+    cal: (fx, fy, cx, cy); default: calibration.txt of the sequence.  Where the sequence has masks, a pixel is counted in the group of its
+    mask value (0: the static scene; values above 63 nowhere), so a scene's mesh is scored on the scene's pixels (group 0) apart from
+    those a masked object covers.  Returns {"summary", "groups", "frames", "frames_skipped"}: ViewScorer.result()'s, without the counters."""
+    from .eval import ViewScorer, _clean, associate, read_tum
+    from .io.readers import load_calibration, open_log
+    reader = open_log(seq)
+    if cal is None:
+        if getattr(reader, "calibrationFile", None) is None:
+            raise ValueError(f"{seq} holds no calibration.txt: give --cal")
+        cal = load_calibration(reader.calibrationFile)
+    fx, fy, cx, cy = (float(v) for v in cal[:4])
+    stamps, T = read_tum(poses)
+    times = np.asarray(reader.timestamps(), np.float64)
+    chosen = np.arange(0, len(times), max(1, int(stride)))
+    pairs = associate(times[chosen] * time_scale, stamps, max_dt)
+    if len(pairs) == 0:
+        raise ValueError(f"none of the frames of {seq} has a pose in {poses}")
+    pose_of = {int(chosen[i]): int(j) for i, j in pairs}
+    scorer = ViewScorer()
+    frames = (reader.load(k) for k in sorted(pose_of)) if hasattr(reader, "load") else (f for f in reader if f.index in pose_of)
+    for f in frames:
+        H, W = f.depth.shape
+        M = T[pose_of[f.index]]
+        depth, tri, uv, front = trimesh.render(W, H, fx, fy, cx, cy, M)
+        rgb = shade(colors, triangles, tri, uv, front, vertices=vertices, dirs=camera_dirs(W, H, fx, fy, cx, cy, M))
+        rgba = np.concatenate([rgb, np.where(tri >= 0, 255, 0).astype(np.uint8)[..., None]], -1)
+        scorer.add(rgba, depth, f.rgb, f.depth, group=f.mask)
+    res = scorer.result()
+    return _clean({"summary": res["summary"], "groups": res["groups"], "frames": res["frames"], "frames_skipped": int(len(chosen) - len(pairs))})
+
+
 def read_triangle_mesh(path: str):
     """read_mesh_ply for .ply, read_obj for .obj (by the extension, in any case)"""
     ext = path.rsplit(".", 1)[-1].lower() if "." in path else ""
@@ -278,28 +356,69 @@ def read_ply_colors(path: str, n: int):
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser(prog="python -m maskfusion_amd.mesh", description="Mesh an exported surfel cloud (cloud-<id>.ply) on the GPU.")
-    ap.add_argument("--cloud", required=True, help="a PLY cloud with normals, as -em / mf_save_ply writes it")
-    ap.add_argument("--voxel", type=float, required=True, help="edge of a lattice cell in the cloud's unit (metres)")
+    ap = argparse.ArgumentParser(prog="python -m maskfusion_amd.mesh", description="Mesh an exported surfel cloud (cloud-<id>.ply) on the GPU; "
+                                 "score a mesh's renders against a sequence.")
+    ap.add_argument("--cloud", help="a PLY cloud with normals, as -em / mf_save_ply writes it")
+    ap.add_argument("--mesh", metavar="FILE", help="with --views, in place of --cloud: an existing triangle mesh (.ply or .obj) to render")
+    ap.add_argument("--voxel", type=float, help="edge of a lattice cell in the cloud's unit (metres)")
     ap.add_argument("--support", type=float, default=None, help="radius of the distance field's weights (default 2.5 voxel; voxel .. 8 voxel)")
     ap.add_argument("--min-neighbours", type=int, default=3, help="points a lattice corner needs within the support (default 3)")
-    ap.add_argument("-o", "--output", required=True, help="the mesh, a binary PLY")
+    ap.add_argument("-o", "--output", help="the mesh, a binary PLY")
     ap.add_argument("--fidelity", action="store_true", help="add cloud_to_mesh to the JSON line: the exact distances from the input points to "
                     "the mesh just written (radius: the support)")
+    ap.add_argument("--views", metavar="SEQ", help="a sequence (a directory or a .klg): adds mesh_views to the JSON line -- the mesh rendered by "
+                    "GPU ray casting from every frame's pose against the sensor's frame: coverage, depth L1, PSNR, SSIM")
+    ap.add_argument("--poses", metavar="FILE", help="with --views: TUM file, camera -> the mesh's frame, stamped with the frames' times (x 1e-6, as "
+                    "poses-<id>.txt and meshseq's groundtruth.txt are)")
+    ap.add_argument("--cal", metavar="FILE", help="with --views: fx fy cx cy (default: the sequence's calibration.txt)")
+    ap.add_argument("--stride", type=int, default=1, help="with --views: every S-th frame (default 1)")
+    ap.add_argument("--view-cell", type=float, default=None, help="with --views: the ray caster's cell (default: the voxel, or for --mesh the "
+                    "mesh's largest extent / 256)")
     a = ap.parse_args(argv)
+    if (a.cloud is None) == (a.mesh is None):
+        ap.error("give --cloud, or --mesh with --views")
+    if a.mesh is not None and (a.views is None or a.fidelity or a.output or a.voxel is not None):
+        ap.error("--mesh goes with --views and takes no --voxel, -o or --fidelity")
+    if a.cloud is not None and (a.voxel is None or a.output is None):
+        ap.error("--cloud needs --voxel and -o")
+    if (a.views is None) != (a.poses is None):
+        ap.error("--views and --poses go together")
+    if a.views is None and (a.cal is not None or a.stride != 1 or a.view_cell is not None):
+        ap.error("--cal, --stride and --view-cell need --views")
+    if a.stride < 1 or (a.view_cell is not None and not (math.isfinite(a.view_cell) and a.view_cell > 0)):
+        ap.error("--stride takes at least 1, --view-cell a positive length")
     try:
-        pts, nrm, col = read_cloud_ply(a.cloud)
+        if a.mesh is not None:
+            m = read_triangle_mesh(a.mesh)
+            v, n, c, t = m["vertices"], m["normals"], m["colors"], m["triangles"]
+            info = {"mesh": a.mesh, "vertices": int(len(v)), "triangles": int(len(t))}
+        else:
+            pts, nrm, col = read_cloud_ply(a.cloud)
     except (OSError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 2
-    v, n, c, t = mesh_cloud(pts, nrm, col, voxel=a.voxel, support=a.support, min_neighbours=a.min_neighbours)
-    write_mesh_ply(a.output, v, n, c, t)
-    support = a.support if a.support is not None else 2.5 * a.voxel
-    info = {"points": int(len(pts)), "vertices": int(len(v)), "triangles": int(len(t)), "voxel": a.voxel, "support": support, "output": a.output}
-    if a.fidelity:
-        from .eval import TriMesh, cloud_stats
-        with TriMesh(v, t, support / 2) as tm:
-            info["cloud_to_mesh"] = cloud_stats(tm.distance(pts, support)[0], support, (a.voxel / 4, a.voxel / 2, a.voxel))
+    if a.mesh is None:
+        v, n, c, t = mesh_cloud(pts, nrm, col, voxel=a.voxel, support=a.support, min_neighbours=a.min_neighbours)
+        write_mesh_ply(a.output, v, n, c, t)
+        support = a.support if a.support is not None else 2.5 * a.voxel
+        info = {"points": int(len(pts)), "vertices": int(len(v)), "triangles": int(len(t)), "voxel": a.voxel, "support": support, "output": a.output}
+        if a.fidelity:
+            from .eval import TriMesh, cloud_stats
+            with TriMesh(v, t, support / 2) as tm:
+                info["cloud_to_mesh"] = cloud_stats(tm.distance(pts, support)[0], support, (a.voxel / 4, a.voxel / 2, a.voxel))
+    if a.views:
+        from .eval import TriMesh
+        from .io.readers import load_calibration
+        cell = a.view_cell if a.view_cell is not None else a.voxel
+        if cell is None:
+            fin = v[np.isfinite(v).all(1)] if len(v) else v
+            cell = max(float((fin.max(0) - fin.min(0)).max()) / 256.0, 1e-6) if len(fin) else 1.0
+        try:
+            with TriMesh(v, t, cell) as tm:
+                info["mesh_views"] = score_views(tm, v, t, c, a.views, a.poses, load_calibration(a.cal) if a.cal else None, a.stride)
+        except (OSError, ValueError, EOFError) as e:
+            print(f"error: --views: {e}", file=sys.stderr)
+            return 2
     print(json.dumps(info))
     return 0
 
