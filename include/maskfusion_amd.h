@@ -519,6 +519,10 @@ int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
  * mf_model_predict_indices -> mf_model_clean always use), "fuseLanes" (4: the data association handles a candidate on a quad of lanes, one window
  * column per lane, merged in the serial order; 1: one lane per candidate -- same results), read-only "indexPackedTexelBytes" (16 or 32: the form the
  * debug tap "index_packed" holds),
+ * "cleanTapGroup" (3: with 16-byte taps Model::clean requests the three taps of a window column together before it looks at the first; 1: one tap
+ * after the other; 9: the whole window at once -- the counts are integer sums, the results the same), "maskFreeClean" (1: in a context that takes
+ * no masks the background's clean pass and the index pass that feeds it carry no mask / depth plane -- no texel can disagree with model 0 --; 0:
+ * the planes travel in every context; a context with masks and the model-level calls always carry them),
  * "cleanLiteralWindow" (1: Model::clean walks its window with copy_unstable.vert's own fp32 trip count, 4 or 5 taps per axis;
  * 0: 4 x 4), "timings", "passTimings" (mf_get_pass_timings), "icpProfile", "objectSmallGrids" (1; 1: the grid-stride
  * surfel kernels of an object model run on a grid sized from its last known surfel count instead of 2048 workgroups), "objectScatterSplat" (1;

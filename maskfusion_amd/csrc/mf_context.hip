@@ -169,6 +169,8 @@ struct mf_ctx {
     Intr K;
     hipStream_t stream = nullptr;      // the frame's chain: preprocessing, tracking, fusion, prediction
     bool clean_tap16 = true;                           // the pass that feeds clean() inside a frame writes 16-byte window taps ("cleanTap16"; 0: the 32-byte record)
+    int clean_tap_group = 3;                           // 16-byte taps a clean pass requests before it looks at one: 1, 3 (a window column), 9 ("cleanTapGroup")
+    bool mask_free_clean = true;                       // a frame without a mask carries no mask / depth plane into the background's clean pass ("maskFreeClean")
     bool iclean_is_tap16 = false;                      // the form d_iclean holds (debug tap "index_packed")
     int fuse_lanes = 4;                                // lanes per candidate of the data association ("fuseLanes": 1 or 4)
     bool clean_literal = true;                         // Model::clean walks its window with the shader text's fp32 trip count ("cleanLiteralWindow")
@@ -1160,6 +1162,11 @@ extern "C" int mf_set_param(mf_ctx* c, const char* key, double value) {
         c->vis_tag.model = nullptr;
         return check_launch(c);
     }
+    if (!strcmp(key, "cleanTapGroup")) {   // 1: the serial walk
+        if (value != 1 && value != 3 && value != 9) { c->err = "cleanTapGroup is 1, 3 or 9"; return MF_EINVAL; }
+        c->clean_tap_group = (int)value; return MF_OK;
+    }
+    if (!strcmp(key, "maskFreeClean")) { c->mask_free_clean = value != 0; return MF_OK; }   // 0: the planes travel in every context
     if (!strcmp(key, "cleanTap16")) { c->clean_tap16 = value != 0; return MF_OK; }   // 0: the 32-byte record in every clean pass
     if (!strcmp(key, "fuseLanes")) {
         if ((int)value != 1 && (int)value != 4) { c->err = "fuseLanes: 1 or 4"; return MF_EINVAL; }
@@ -1197,6 +1204,8 @@ extern "C" int mf_get_param(mf_ctx* c, const char* key, double* value) {
     if (!strcmp(key, "splatTileEntries")) { *value = c->tile_entries_cap; return MF_OK; }
     if (!strcmp(key, "cullRuns")) { *value = c->cull_runs ? 1 : 0; return MF_OK; }
     if (!strcmp(key, "cleanTap16")) { *value = c->clean_tap16 ? 1 : 0; return MF_OK; }
+    if (!strcmp(key, "cleanTapGroup")) { *value = c->clean_tap_group; return MF_OK; }
+    if (!strcmp(key, "maskFreeClean")) { *value = c->mask_free_clean ? 1 : 0; return MF_OK; }
     if (!strcmp(key, "fuseLanes")) { *value = c->fuse_lanes; return MF_OK; }
     if (!strcmp(key, "indexPackedTexelBytes")) { *value = c->iclean_is_tap16 ? 16 : 32; return MF_OK; }   // the form "index_packed" holds
     if (!strcmp(key, "deferPredict")) { *value = c->defer_predict ? 1 : 0; return MF_OK; }

@@ -328,12 +328,18 @@ static void after_clean(mf_ctx* c, ModelState& m, bool in_place, int live) {
 }
 // the arguments every clean form of model m shares (shared scratch of the single-model path)
 // tap16: the packed map holds the 16-byte taps a resolve pass of the SAME enqueue wrote with this model's threshold and tick
+// A frame without a mask (mf_process_frame of a single-model context: every byte of c->d_zero_mask is 0) cannot disagree with the background, id 0:
+// with 16-byte taps the resolve pass then leaves the planes depthT / maskT alone and the clean pass reads neither ("maskFreeClean")
+static bool mask_free(const mf_ctx* c, const ModelState& m, const uint8_t* mask, bool tap16) {
+    return c->mask_free_clean && tap16 && mask == c->d_zero_mask && m.id == 0;
+}
 static CleanIn clean_in(mf_ctx* c, ModelState& m, int time_delta, bool packed, const float* depthF, const uint8_t* mask, bool tap16 = false) {
     CleanIn in;
     in.frame = m.d_frame; in.pose = m.d_pose; in.W = c->W; in.H = c->H; in.k = c->K; in.timeDelta = time_delta; in.confThreshold = m.confThr;
     in.outlierCoeff = c->cfg.outlier_coefficient; in.maskID = m.id;
     in.index = c->d_index; in.vc = c->d_ivc; in.ct = c->d_ict; in.packed = packed ? c->d_iclean : nullptr; in.maskT = c->d_maskT;
-    in.depthT = packed && tap16 ? c->d_depthT : nullptr;
+    in.tap16 = packed && tap16; in.tapGroup = c->clean_tap_group; in.maskFree = mask_free(c, m, mask, in.tap16);
+    in.depthT = in.tap16 && !in.maskFree ? c->d_depthT : nullptr;
     in.depthF = depthF; in.mask = mask; in.cand_op = c->d_cand_op; in.cand_rec = c->d_cand_rec;
     in.flags = c->d_flags; in.newconf = c->d_newconf; in.block_counts = c->d_block_counts; in.host_count = m.h_count;
     in.host_append = append_mirror_fits(c, m) ? m.h_append : nullptr; in.seq = m.clean_seq + 1;     // (after_clean counts the pass)
@@ -409,7 +415,7 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
         if (secondIndexPass) {
             PassTimer t(c, timed ? MF_PASS_BG_INDEX2 : -1);
             launch_index_resolve(m.surf[live], m.d_frame, m.d_pose, c->d_keys, W, H, nullptr, nullptr, nullptr, nullptr, c->d_iclean, depthF, mask, c->d_maskT, true, s,
-                                 nullptr, 0, depthT, m.confThr);
+                                 nullptr, 0, depthT, m.confThr, mask_free(c, m, mask, tap16));
         }
     } else {
         // update.vert in place -- only the surfels a candidate merged into are touched (the reference copies the whole buffer,
@@ -423,7 +429,7 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
             PassTimer t(c, timed ? MF_PASS_BG_INDEX2 : -1);
             launch_index_scatter(m.surf[src], m.d_frame, m.d_pose, W, H, c->K, g.max_depth_processed, g.time_delta, c->d_keys, true, s, blocks, vis);
             launch_index_resolve(m.surf[src], m.d_frame, m.d_pose, c->d_keys, W, H, nullptr, nullptr, nullptr, nullptr, c->d_iclean, depthF, mask, c->d_maskT, true, s,
-                                 cull_clean ? c->d_decay_stats : nullptr, m.id, depthT, m.confThr);
+                                 cull_clean ? c->d_decay_stats : nullptr, m.id, depthT, m.confThr, mask_free(c, m, mask, tap16));
         }
     }
     // clean: two launches live -> the other buffer (a dense copy) below big_map_elements; from there on in place, run by run
@@ -525,7 +531,7 @@ static int make_obj_batch(mf_ctx* c, const std::vector<ModelState*>& ms, const s
     b.denseSprites = 0;
     for (ModelState* m : ms) if ((long)*m->h_count >= (long)c->in_place_elements) b.denseSprites = 1;
     b.rgb = d_rgb; b.depthRaw = d_depth; b.depthF = depthF; b.mask = mask; b.maskT = s == c->stream ? c->d_maskT : c->d_maskT_obj;
-    b.depthT = !c->clean_tap16 ? nullptr : s == c->stream ? c->d_depthT : c->d_depthT_obj; b.fuseLanes = c->fuse_lanes; b.bg_pose = c->models[0]->d_pose; b.global_keys = c->d_keys;
+    b.depthT = !c->clean_tap16 ? nullptr : s == c->stream ? c->d_depthT : c->d_depthT_obj; b.fuseLanes = c->fuse_lanes; b.cleanTapGroup = c->clean_tap_group; b.bg_pose = c->models[0]->d_pose; b.global_keys = c->d_keys;
     return MF_OK;
 }
 // every object model of the list, with its position in the list (the GlobalProjection payload)

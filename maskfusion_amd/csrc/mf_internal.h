@@ -288,7 +288,9 @@ void launch_index_resolve(Surfels src, const FrameDev* frame, const PoseDev* pos
                           bool keys_transposed /* the order the scatter used */, hipStream_t s, int* decay_stats = nullptr, int maskID = 0,
                           float* depthT = nullptr /* with packed: the 16-byte tap {x, y, z', initTime} per texel instead (z' = NaN unless index > 0, confidence >
                           tapThreshold and z > 0, sign bit = lastTime == tick), the filtered depth in this column-major plane -- only for a clean pass enqueued
-                          with it, with the same tick and threshold */, float tapThreshold = 0.f);
+                          with it, with the same tick and threshold */, float tapThreshold = 0.f,
+                          bool maskFree = false /* with depthT: every byte of `mask` is maskID (a frame without a mask, for the background) -- the taps are
+                          written, the planes depthT / maskT and the statistics are not touched: clean_test's mask rule cannot apply ("maskFreeClean") */);
 void launch_fuse_data(const uint8_t* rgb, const float* depthRaw, const float* depthF, const uint8_t* mask,
                       int maskID, const FrameDev* frame, const PoseDev* pose, float weightMultiplier, float maxDepth,
                       int W, int H, Intr k, const int* index, const float4* vc, const float4* nr, uint8_t* cand_op,
@@ -308,7 +310,10 @@ struct CleanIn {
     FrameDev* frame; const PoseDev* pose; int W, H; Intr k; int timeDelta; float confThreshold, outlierCoeff; int maskID;
     const int* index; const float4* vc; const float4* ct;    // the index map as separate images, or
     const float4* packed; const uint8_t* maskT;              // ... the packed column-major map with the mask beside it
-    const float* depthT = nullptr;                           // != nullptr: `packed` holds 16-byte taps and this plane the filtered depth (launch_index_resolve)
+    const float* depthT = nullptr;                           // with tap16: the plane of the filtered depth (launch_index_resolve), unless maskFree
+    bool tap16 = false;                                      // `packed` holds 16-byte taps
+    int tapGroup = 1;                                        // 16-byte taps requested together: 1, 3 (a window column) or 9 ("cleanTapGroup")
+    bool maskFree = false;                                   // with tap16: launch_index_resolve's maskFree -- depthT and maskT were not written
     const float* depthF; const uint8_t* mask;
     const uint8_t* cand_op; const float4* cand_rec;
     uint8_t* flags; float* newconf; int* block_counts;       // [elements], [elements], [kCompactBlocks]
@@ -409,6 +414,7 @@ struct ObjBatch {
     uint8_t* maskT;                    // the mask in column-major order, beside the packed maps (every model's resolve writes the same bytes)
     float* depthT;                     // != nullptr: the packed maps hold 16-byte taps, and this plane the filtered depth in column-major order (as maskT)
     int fuseLanes;                     // lanes per candidate of the association pass: 1 or 4
+    int cleanTapGroup;                 // 16-byte taps requested together: 1, 3 or 9 (CleanIn::tapGroup)
     unsigned long long* global_keys;
 };
 void launch_obj_global_scatter(const ObjBatch& b, int blocks, hipStream_t s);          // GlobalProjection of every object model (mf_segment.hip)

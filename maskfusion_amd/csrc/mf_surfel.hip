@@ -438,13 +438,16 @@ __device__ __forceinline__ ResolvedTexel resolve_texel(const Surfels& src, const
 // depthF -> the packed record's spare word (32-byte record) or depthT (16-byte tap: column-major floats), mask -> maskT (column-major bytes)
 struct ResolveOut {
     int* index; float4* vc; float4* nr; float4* ct; float4* packed; const float* depthF; const uint8_t* mask; uint8_t* maskT;
-    float* depthT; float tapThreshold;    // depthT != nullptr: the 16-byte tap (one float4 per texel), live against this confidence threshold
+    float* depthT; float tapThreshold;    // tap16: the 16-byte tap (one float4 per texel), live against this confidence threshold; depthT: its depth plane
     const FrameDev* frame;    // the buffer's frame state (`first`)
     // with `packed`, optional: what Model::clean's mask-disagreement rule (copy_unstable.vert:139-156) can meet in this frame, for the run culling of
     // the in-place clean (k_cull_clean): order-preserving ints -- {min, max} filtered depth over the texels of the LEFT column, the RIGHT column, the
     // TOP row, the BOTTOM row whose mask is foreign to the model (neither its id nor >= 255), then the min over ALL foreign texels (kDecayStats
     // ints); armed (empty) between frames
     int* decay_stats; int maskID;
+    // packed: one float4 per texel (tap16_encode) instead of the 32-byte record.  The frame planes travel in depthT / maskT -- unless both are
+    // nullptr: a frame without a mask, for the background ("maskFreeClean": clean_test<.., kMaskFree = true> reads neither)
+    int tap16;
 };
 // a workgroup's texels -> the decay statistics (one atomic per statistic and wavefront that saw such a texel)
 __device__ __forceinline__ void decay_stats_add(const ResolveOut& o, bool in_image, int x, int y, int W, int H, float depth, int maskValue) {
@@ -490,7 +493,7 @@ __device__ __forceinline__ void index_resolve_transposing_body(Surfels src, cons
         const int lx = kPacked ? f : g, ly = kPacked ? g : f;
         const int x = x0 + lx, y = y0 + ly;
         const Tap16 t16{o.tapThreshold, (float)o.frame->tick};
-        const Tap16* tap = (kPacked && o.depthT) ? &t16 : nullptr;
+        const Tap16* tap = (kPacked && o.tap16) ? &t16 : nullptr;
         ResolvedTexel r = resolve_texel<kPacked>(src, pose, kEmptyKey, false, 0, tap);
         int mk = 0;
         if (x < W && y < H) {
@@ -498,9 +501,9 @@ __device__ __forceinline__ void index_resolve_transposing_body(Surfels src, cons
             const unsigned long long key = keys[p];
             keys[p] = kEmptyKey;
             r = resolve_texel<kPacked>(src, pose, key, o.ct != nullptr, o.frame->first, tap);
-            if (kPacked) { r.p1.w = o.depthF[p]; mk = o.mask[p]; s_mk[lx][ly] = (uint8_t)mk; }
+            if (kPacked && o.maskT) { r.p1.w = o.depthF[p]; mk = o.mask[p]; s_mk[lx][ly] = (uint8_t)mk; }
         }
-        if (kPacked) decay_stats_add(o, x < W && y < H, x, y, W, H, r.p1.w, mk);
+        if (kPacked && o.maskT) decay_stats_add(o, x < W && y < H, x, y, W, H, r.p1.w, mk);
         if (kPacked) { s_a[lx][ly] = r.p0; s_b[lx][ly] = r.p1; }
         else { s_i[lx][ly] = r.index; s_a[lx][ly] = r.vc; s_b[lx][ly] = r.nr; if (o.ct) s_c[lx][ly] = r.ct; }
     }
@@ -511,9 +514,9 @@ __device__ __forceinline__ void index_resolve_transposing_body(Surfels src, cons
         if (x < W && y < H) {
             if (kPacked) {
                 const int tp = x * H + y;
-                if (o.depthT) { o.packed[tp] = s_a[lx][ly]; o.depthT[tp] = s_b[lx][ly].w; }
+                if (o.tap16) { o.packed[tp] = s_a[lx][ly]; if (o.depthT) o.depthT[tp] = s_b[lx][ly].w; }
                 else { o.packed[2 * tp] = s_a[lx][ly]; o.packed[2 * tp + 1] = s_b[lx][ly]; }
-                o.maskT[tp] = s_mk[lx][ly];
+                if (o.maskT) o.maskT[tp] = s_mk[lx][ly];
             } else {
                 const int p = y * W + x;
                 o.index[p] = s_i[lx][ly]; o.vc[p] = s_a[lx][ly]; o.nr[p] = s_b[lx][ly];
@@ -530,25 +533,26 @@ __device__ __forceinline__ void index_resolve_packed_body(Surfels src, const Pos
     const int tilesX = (W + kResolveTile - 1) / kResolveTile;
     const int x0 = (tile % tilesX) * kResolveTile, y0 = (tile / tilesX) * kResolveTile;
     const int f = threadIdx.x & (kResolveTile - 1), g = threadIdx.x / kResolveTile;
-    {
+    const bool planes = o.maskT != nullptr;    // (the same in every workgroup of the launch)
+    if (planes) {
         const int x = x0 + f, y = y0 + g;
         float d = 0.f;
         int mk = 0;
         if (x < W && y < H) { d = o.depthF[y * W + x]; mk = o.mask[y * W + x]; s_d[f][g] = d; s_mk[f][g] = (uint8_t)mk; }
         decay_stats_add(o, x < W && y < H, x, y, W, H, d, mk);
+        __syncthreads();
     }
-    __syncthreads();
     const int x = x0 + g, y = y0 + f;
     if (x < W && y < H) {
         const int tp = x * H + y;
         const unsigned long long key = keys[tp];
         keys[tp] = kEmptyKey;
         const Tap16 t16{o.tapThreshold, (float)o.frame->tick};
-        ResolvedTexel r = resolve_texel<true>(src, pose, key, false, o.frame->first, o.depthT ? &t16 : nullptr);
-        r.p1.w = s_d[g][f];
-        if (o.depthT) { o.packed[tp] = r.p0; o.depthT[tp] = r.p1.w; }
+        ResolvedTexel r = resolve_texel<true>(src, pose, key, false, o.frame->first, o.tap16 ? &t16 : nullptr);
+        if (planes) r.p1.w = s_d[g][f];
+        if (o.tap16) { o.packed[tp] = r.p0; if (planes) o.depthT[tp] = r.p1.w; }
         else { o.packed[2 * tp] = r.p0; o.packed[2 * tp + 1] = r.p1; }
-        o.maskT[tp] = s_mk[g][f];
+        if (planes) o.maskT[tp] = s_mk[g][f];
     }
 }
 __global__ __launch_bounds__(256) void k_index_resolve(Surfels src, const PoseDev* __restrict__ pose, unsigned long long* __restrict__ keys, int P, ResolveOut o) {
@@ -570,9 +574,13 @@ int resolve_tiles(int W, int H) { return ((W + kResolveTile - 1) / kResolveTile)
 // keys_transposed: the order the scatter used.
 void launch_index_resolve(Surfels src, const FrameDev* frame, const PoseDev* pose, unsigned long long* keys, int W, int H, int* index, float4* vc,
                           float4* nr, float4* ct, float4* packed, const float* depthF, const uint8_t* mask, uint8_t* maskT, bool keys_transposed,
-                          hipStream_t s, int* decay_stats, int maskID, float* depthT, float tapThreshold) {
+                          hipStream_t s, int* decay_stats, int maskID, float* depthT, float tapThreshold, bool maskFree) {
     const int P = W * H;
-    const ResolveOut o{index, vc, nr, ct, packed, depthF, mask, maskT, packed ? depthT : nullptr, tapThreshold, frame, packed ? decay_stats : nullptr, maskID};
+    const bool tap16 = packed && depthT;
+    // maskFree (16-byte taps only): every mask byte is the model's id -- no plane is carried, and no texel is foreign: the statistics stay armed
+    const bool planes = !(tap16 && maskFree);
+    const ResolveOut o{index, vc, nr, ct, packed, depthF, mask, planes ? maskT : nullptr, tap16 && planes ? depthT : nullptr, tapThreshold, frame,
+                       packed && planes ? decay_stats : nullptr, maskID, tap16 ? 1 : 0};
     const dim3 flat((P + 255) / 256), tiles(resolve_tiles(W, H));
     if (packed) {
         if (keys_transposed) hipLaunchKernelGGL(k_index_resolve_packed, tiles, dim3(256), 0, s, src, pose, keys, W, H, o);
@@ -874,7 +882,7 @@ struct CleanArgs {
     const float4* packed;                                    // {vertConf | initTime, lastTime, index, 0} per texel
     const float* depthF; const uint8_t* mask;
     const uint8_t* maskT;                                    // the mask in the packed map's order (only with `packed`)
-    const float* depthT;                                     // the filtered depth in the same order (only with the 16-byte tap: clean_test<true>)
+    const float* depthT;                                     // the filtered depth in the same order (only with the 16-byte tap, unless maskFree)
     const uint8_t* cand_op; const float4* cand_rec;
     uint8_t* flags; float* newconf;    // keep flag / new confidence per element: pass 1 -> pass 2 of the two-launch form
     int* block_counts;                 // [kCompactBlocks] survivors per workgroup (two-launch form)
@@ -884,6 +892,9 @@ struct CleanArgs {
                                        // handle the frame's candidates only and append the survivors at frame->phys (dst = src)
     const int* run_list; const int* run_count;   // k_clean_runs: the runs to visit (k_cull_clean); nullptr: every run of the table
     int* ctl;                          // k_clean_runs: kCleanCtlInts ints, zero between launches
+    int tap16;                         // `packed` holds 16-byte taps (clean_test<true>)
+    int tapGroup;                      // 16-byte taps requested together: 1 (one by one), 3 (a window column) or 9 (the window) -- "cleanTapGroup"
+    int maskFree;                      // 1: the frame has no mask and the model is id 0: no mask / depth planes travel with the taps -- "maskFreeClean"
 };
 
 // The window of copy_unstable.vert:85-86 along one axis, exactly as the shader text walks it: `for (i = c - 2s; i < c + 2s; i += s)` on an
@@ -911,13 +922,52 @@ __device__ __forceinline__ void window_slots_literal(float c, int size, int (&u)
     }
 }
 
+// one 16-byte tap into the two counting rules of copy_unstable.vert:92-106
+__device__ __forceinline__ void clean_count_tap16(float4 t, int mult, float3 lp, float initTime, float radius, float lnz, int& count, int& zCount) {
+    const float vz = fabsf(t.z);
+    if (!isnan(t.z) && mult > 0) {
+        const float dx = t.x - lp.x, dy = t.y - lp.y;
+        if (t.w < initTime && vz > lp.z && vz - lp.z < 0.01f && sqrtf(dx * dx + dy * dy) < radius * 1.4f) count += mult;
+        if (__float_as_int(t.z) < 0 && vz > lp.z && vz - lp.z > 0.01f && fabsf(lnz) > 0.85f) zCount += mult;
+    }
+}
+// the window of 16-byte taps, kGroup (3: a column, 9: all) of them requested before the first is looked at
+template <int kGroup>
+__device__ __forceinline__ void clean_window_grouped(const CleanArgs& a, const int (&ux)[3], const int (&mx)[3], const int (&uy)[3], const int (&my)[3],
+                                                     float3 lp, float initTime, float radius, float lnz, int& count, int& zCount) {
+    const int W = a.W, H = a.H;
+    // slot -> texel: an unused slot reads slot 0's texel again
+    const int gx[3] = {ux[0], mx[1] > 0 ? ux[1] : ux[0], mx[2] > 0 ? ux[2] : ux[0]};
+    const int gy[3] = {uy[0], my[1] > 0 ? uy[1] : uy[0], my[2] > 0 ? uy[2] : uy[0]};
+    float4 t[3][3];
+    if (kGroup == 9) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) t[q / 3][q % 3] = a.packed[a.transposed ? gx[q / 3] * H + gy[q % 3] : gy[q % 3] * W + gx[q / 3]];
+    }
+#pragma unroll
+    for (int ia = 0; ia < 3; ++ia) {
+        if (kGroup == 3) {
+#pragma unroll
+            for (int ib = 0; ib < 3; ++ib) t[ia][ib] = a.packed[a.transposed ? gx[ia] * H + gy[ib] : gy[ib] * W + gx[ia]];
+        }
+#pragma unroll
+        for (int ib = 0; ib < 3; ++ib) clean_count_tap16(t[ia][ib], mx[ia] * my[ib], lp, initTime, radius, lnz, count, zCount);
+    }
+}
 // decay: which factor the mask-disagreement rule applied to the confidence (0 none, 1: k, 2: 0.25 k) -- clean_decayed() re-applies it
 // nr_lazy != nullptr: the surfel's normal / radius record is only fetched when the window is walked (it is not needed otherwise); `nr` is then ignored
 // kTap16: a.packed holds the 16-byte tap {x, y, z', initTime} (tap16_encode: written by the resolve pass of the same enqueue, with this pass's
 // threshold and tick) instead of the 32-byte record; a tap counts under the same conditions, bit for bit.
-template <bool kTap16>
+// kGroup (16-byte taps only): how many taps are requested before the first of them is looked at -- 1: each tap is loaded, tested, and only then
+// the next one requested (nine dependent gathers); 3: the three taps of a window column ux[ia] together -- in the column-major packed map they
+// are at most three neighbouring texels, mostly one cache line --; 9: the whole window.  count / zCount are integer sums of multiplicities: the
+// same whatever the order.  An unused slot (multiplicity 0) is requested at the address of slot 0 and ignored: no branch stands between the loads.
+// kMaskFree: the frame has no mask and the model is id 0 -- `maskValue != a.maskID` below is false for every surfel --: neither plane is read.
+template <bool kTap16, int kGroup = 1, bool kMaskFree = false>
 __device__ __forceinline__ bool clean_test(const CleanArgs& a, float4 pc, float4 ct, float4 nr, float time, const float* Ri,
                                            float3 ti, float& newconf, int& decay, const float4* nr_lazy = nullptr) {
+    static_assert(kTap16 || (kGroup == 1 && !kMaskFree), "grouped taps and the mask-free form are forms of the 16-byte tap");
+    static_assert(kGroup == 1 || kGroup == 3 || kGroup == 9, "a tap, a window column or the window");
     const int W = a.W, H = a.H;
     bool test = true;
     const float3 lp = mul33(Ri, f3(pc.x, pc.y, pc.z)) + ti;
@@ -944,13 +994,15 @@ __device__ __forceinline__ bool clean_test(const CleanArgs& a, float4 pc, float4
             window_slots_literal(x / (float)W, W, ux, mx);
             window_slots_literal(y / (float)H, H, uy, my);
         }
+        constexpr bool kGrouped = kTap16 && kGroup > 1;
+        if (kGrouped) clean_window_grouped<kGroup>(a, ux, mx, uy, my, lp, ct.z, nr.w, ln.z, count, zCount);
 #pragma unroll
-        for (int ia = 0; ia < 3; ++ia) {
+        for (int ia = 0; ia < (kGrouped ? 0 : 3); ++ia) {
 #pragma unroll
             for (int ib = 0; ib < 3; ++ib) {
                 const int tp = a.transposed ? ux[ia] * H + uy[ib] : uy[ib] * W + ux[ia];
                 const int mult = mx[ia] * my[ib];
-                if (mult <= 0) continue;   // (requesting the taps' records in groups before looking at any -- 6 + 3, all 9 -- was tried in rounds 2 and 5: slower at VGA, DESIGN.md "rejected")
+                if (mult <= 0) continue;   // (requesting these 32-byte records in groups before looking at any -- 6 + 3, all 9 -- was tried in rounds 2 and 5: slower at VGA, DESIGN.md "rejected")
                 float4 v, c;
                 int idx;
                 bool upd = false;     // (16-byte tap) lastTime == tick
@@ -986,6 +1038,9 @@ __device__ __forceinline__ bool clean_test(const CleanArgs& a, float4 pc, float4
     if (w == -2.f) w = time;
     if (w == -1.f || ((time - w) > 20 && pc.w < a.confThreshold)) test = false;
     if (w > 0 && time - w > (float)a.timeDelta) test = true;
+    newconf = pc.w;
+    decay = 0;
+    if (kMaskFree) return test;
     // mask-disagreement decay, copy_unstable.vert:139-156 (nearest fetch, clamp to edge, NaN -> texel 0)
     const int fx_ = isnan(x) ? 0 : clampi((int)fminf(fmaxf(floorf(x), -1.f), (float)W), 0, W - 1);
     const int fy_ = isnan(y) ? 0 : clampi((int)fminf(fmaxf(floorf(y), -1.f), (float)H), 0, H - 1);
@@ -993,8 +1048,6 @@ __device__ __forceinline__ bool clean_test(const CleanArgs& a, float4 pc, float4
     // column-major plane beside it -- launch_index_resolve)
     const float wDepth = kTap16 ? a.depthT[fx_ * H + fy_] : a.packed ? a.packed[2 * (fx_ * H + fy_) + 1].w : a.depthF[fy_ * W + fx_];
     const int maskValue = a.packed ? a.maskT[fx_ * H + fy_] : a.mask[fy_ * W + fx_];
-    newconf = pc.w;
-    decay = 0;
     if (maskValue != a.maskID && maskValue < 255 && (wDepth > lp.z - 0.05f && wDepth < lp.z + 0.05f)) {
         const float kk = 0.5f + 0.5f * (1 - a.outlierCoeff / 10.0f);
         if (maskValue == 0) { newconf *= kk; decay = 1; }
@@ -1018,7 +1071,7 @@ __device__ __forceinline__ float clean_decayed(const CleanArgs& a, float conf, i
 //     run, and their runs to its table.
 // The surviving records, their order and the count are the same bits either way (tests/test_gpu_switches.py::test_clean_forms_agree).
 // ------------------------------------------------------------------------------------------------
-template <bool kTap16>
+template <bool kTap16, int kGroup, bool kMaskFree>
 __device__ __forceinline__ void clean_small_flags_body(const CleanArgs& a) {
     __shared__ int s_w[4];
     // elements below `count` are the buffer's slots, the others the candidates; `first`: the first element these passes handle
@@ -1039,11 +1092,11 @@ __device__ __forceinline__ void clean_small_flags_body(const CleanArgs& a) {
         float nc = 0.f;
         int dk = 0;
         if (i < count) {
-            keep = clean_test<kTap16>(a, a.src.pc[i], a.src.ct[i], make_float4(0, 0, 0, 0), time, Ri, ti, nc, dk, &a.src.nr[i]);
+            keep = clean_test<kTap16, kGroup, kMaskFree>(a, a.src.pc[i], a.src.ct[i], make_float4(0, 0, 0, 0), time, Ri, ti, nc, dk, &a.src.nr[i]);
         } else {
             const int c = i - count;
             if (a.cand_op[c] == 2)
-                keep = clean_test<kTap16>(a, a.cand_rec[c * 3 + 0], a.cand_rec[c * 3 + 1], make_float4(0, 0, 0, 0), time, Ri, ti, nc, dk, &a.cand_rec[c * 3 + 2]);
+                keep = clean_test<kTap16, kGroup, kMaskFree>(a, a.cand_rec[c * 3 + 0], a.cand_rec[c * 3 + 1], make_float4(0, 0, 0, 0), time, Ri, ti, nc, dk, &a.cand_rec[c * 3 + 2]);
         }
         a.flags[i - first] = keep ? 1 : 0;
         a.newconf[i - first] = nc;
@@ -1070,8 +1123,8 @@ __device__ __forceinline__ void clean_small_flags_body(const CleanArgs& a) {
     }
 }
 
-template <bool kTap16>
-__global__ __launch_bounds__(256) void k_clean_small_flags(const CleanArgs a) { clean_small_flags_body<kTap16>(a); }
+template <bool kTap16, int kGroup, bool kMaskFree>
+__global__ __launch_bounds__(256) void k_clean_small_flags(const CleanArgs a) { clean_small_flags_body<kTap16, kGroup, kMaskFree>(a); }
 
 __device__ __forceinline__ void clean_small_compact_body(const CleanArgs& a) {
     __shared__ int s_w[4];
@@ -1275,7 +1328,7 @@ void launch_cull_clean(Surfels s, const FrameDev* frame, const PoseDev* pose, in
 
 // One run per workgroup and round (its <= kRun slots: two per thread); the runs are dealt round-robin over the grid (the listed runs come in no
 // particular order, expensive -- in view -- and cheap ones mixed).
-template <bool kTap16>
+template <bool kTap16, int kGroup, bool kMaskFree>
 __device__ __forceinline__ void clean_runs_body(const CleanArgs& a) {
     __shared__ int s_cnt[2][4];
     __shared__ int s_red[4][kRunRed];
@@ -1309,8 +1362,8 @@ __device__ __forceinline__ void clean_runs_body(const CleanArgs& a) {
         // nothing on the configs[4] maps, 0.43 ms either way: the pass is bound by the instructions of the test, ~2 000 per surfel in view.)
         float nc0 = 0.f, nc1 = 0.f;
         int dk = 0;
-        const bool keep0 = live0 && clean_test<kTap16>(a, pc0, make_float4(0.f, 0.f, tm0.x, tm0.y), make_float4(0, 0, 0, 0), time, Ri, ti, nc0, dk, &a.src.nr[start + off0]);
-        const bool keep1 = live1 && clean_test<kTap16>(a, pc1, make_float4(0.f, 0.f, tm1.x, tm1.y), make_float4(0, 0, 0, 0), time, Ri, ti, nc1, dk, &a.src.nr[start + off1]);
+        const bool keep0 = live0 && clean_test<kTap16, kGroup, kMaskFree>(a, pc0, make_float4(0.f, 0.f, tm0.x, tm0.y), make_float4(0, 0, 0, 0), time, Ri, ti, nc0, dk, &a.src.nr[start + off0]);
+        const bool keep1 = live1 && clean_test<kTap16, kGroup, kMaskFree>(a, pc1, make_float4(0.f, 0.f, tm1.x, tm1.y), make_float4(0, 0, 0, 0), time, Ri, ti, nc1, dk, &a.src.nr[start + off1]);
         RunAcc acc;
         acc.reset();
         // copy_unstable.vert:131: a surfel stamped -2 ("seen in this frame") leaves the pass stamped with the tick -- only an uploaded map holds one
@@ -1407,8 +1460,8 @@ __device__ __forceinline__ void clean_runs_body(const CleanArgs& a) {
     }
 }
 
-template <bool kTap16>
-__global__ __launch_bounds__(256) void k_clean_runs(const CleanArgs a) { clean_runs_body<kTap16>(a); }
+template <bool kTap16, int kGroup, bool kMaskFree>
+__global__ __launch_bounds__(256) void k_clean_runs(const CleanArgs a) { clean_runs_body<kTap16, kGroup, kMaskFree>(a); }
 
 // workgroups of a k_clean_runs launch for a buffer of ~`elements` surfels: the runs are dealt round-robin, any grid covers any table
 int clean_runs_grid(long elements) {
@@ -1646,7 +1699,8 @@ static CleanArgs clean_args(const CleanIn& in, Surfels src, Surfels dst) {
     a.literal = in.literalWindow ? 1 : 0;
     a.src = src; a.dst = dst; a.frame = in.frame; a.pose = in.pose; a.W = in.W; a.H = in.H; a.k = in.k; a.timeDelta = in.timeDelta;
     a.confThreshold = in.confThreshold; a.outlierCoeff = in.outlierCoeff; a.maskID = in.maskID; a.index = in.index; a.vc = in.vc; a.ct = in.ct;
-    a.packed = in.packed; a.depthT = in.packed ? in.depthT : nullptr;
+    a.packed = in.packed; a.tap16 = in.packed && in.tap16 ? 1 : 0; a.depthT = a.tap16 ? in.depthT : nullptr;
+    a.tapGroup = in.tapGroup; a.maskFree = a.tap16 && in.maskFree ? 1 : 0;
     a.depthF = in.depthF; a.mask = in.mask; a.maskT = in.maskT; a.cand_op = in.cand_op; a.cand_rec = in.cand_rec;
     a.flags = in.flags; a.newconf = in.newconf; a.block_counts = in.block_counts; a.host_count = in.host_count;
     a.host_append = in.host_append; a.seq = in.seq;
@@ -1657,25 +1711,37 @@ static CleanArgs clean_args(const CleanIn& in, Surfels src, Surfels dst) {
 // (0.75 M elements) is fastest on 2 048 (303.6 against 309-313 us per frame on 1 024 and 305.0 on 4 096); from ~1.5 M elements on, 1 024 workgroups
 // with longer slices win: 1280 x 960 on its natural map 847 -> 835 us, the four 3.7 M-element object maps of configs[4] 4.16 -> 4.07-4.12 ms
 // (profiles/r06zo_ab.txt, r06zp_ab.txt).
+// the instance of a clean kernel for the pass's tap form: the 32-byte record or the separate images, or 16-byte taps by group and mask planes
+#define MF_LAUNCH_CLEAN(K, grid, s, a)                                                                                      \
+    do {                                                                                                                    \
+        const int mf_g = (a).tapGroup == 9 ? 9 : (a).tapGroup == 3 ? 3 : 1;                                                 \
+        if (!(a).tap16) hipLaunchKernelGGL((K<false, 1, false>), grid, dim3(256), 0, s, a);                                 \
+        else if ((a).maskFree) {                                                                                            \
+            if (mf_g == 3) hipLaunchKernelGGL((K<true, 3, true>), grid, dim3(256), 0, s, a);                                \
+            else if (mf_g == 9) hipLaunchKernelGGL((K<true, 9, true>), grid, dim3(256), 0, s, a);                           \
+            else hipLaunchKernelGGL((K<true, 1, true>), grid, dim3(256), 0, s, a);                                          \
+        } else {                                                                                                            \
+            if (mf_g == 3) hipLaunchKernelGGL((K<true, 3, false>), grid, dim3(256), 0, s, a);                               \
+            else if (mf_g == 9) hipLaunchKernelGGL((K<true, 9, false>), grid, dim3(256), 0, s, a);                          \
+            else hipLaunchKernelGGL((K<true, 1, false>), grid, dim3(256), 0, s, a);                                         \
+        }                                                                                                                   \
+    } while (0)
 int compact_blocks_for(long elements) { return elements >= 1500000L ? kCompactBlocks / 2 : kCompactBlocks; }
 void launch_clean_small(const CleanIn& in, Surfels src, Surfels dst, hipStream_t s, int blocks) {
     const CleanArgs a = clean_args(in, src, dst);
-    if (a.depthT) hipLaunchKernelGGL(k_clean_small_flags<true>, dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_clean_small_flags<false>, dim3(blocks), dim3(256), 0, s, a);
+    MF_LAUNCH_CLEAN(k_clean_small_flags, dim3(blocks), s, a);
     hipLaunchKernelGGL(k_clean_small_compact, dim3(blocks), dim3(256), 0, s, a);
 }
 void launch_clean_runs(const CleanIn& in, Surfels buf, const VisList* runs, int* ctl, int blocks, hipStream_t s) {
     CleanArgs a = clean_args(in, buf, buf);
     a.run_list = runs ? runs->list : nullptr; a.run_count = runs ? runs->count : nullptr; a.ctl = ctl;
-    if (a.depthT) hipLaunchKernelGGL(k_clean_runs<true>, dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_clean_runs<false>, dim3(blocks), dim3(256), 0, s, a);
+    MF_LAUNCH_CLEAN(k_clean_runs, dim3(blocks), s, a);
 }
 void launch_clean_append(const CleanIn& in, Surfels buf, hipStream_t s) {
     CleanArgs a = clean_args(in, buf, buf);
     a.append = 1;
     // (the candidates are <= P / 4 elements: a grid of one 256-element slice per workgroup, at most kCompactBlocks of them)
-    if (a.depthT) hipLaunchKernelGGL(k_clean_small_flags<true>, dim3(kCompactBlocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_clean_small_flags<false>, dim3(kCompactBlocks), dim3(256), 0, s, a);
+    MF_LAUNCH_CLEAN(k_clean_small_flags, dim3(kCompactBlocks), s, a);
     hipLaunchKernelGGL(k_clean_small_compact, dim3(kCompactBlocks), dim3(256), 0, s, a);
 }
 
@@ -1691,12 +1757,13 @@ __global__ __launch_bounds__(256) void k_obj_index_scatter(const ObjBatch b) {
 }
 __global__ __launch_bounds__(256) void k_obj_index_resolve(const ObjBatch b) {   // (the object models' keys are row-major in both passes)
     const ObjPassArgs& m = b.m[blockIdx.z];
-    index_resolve_same_body<false>(m.a, m.pose, m.keys, b.W * b.H, ResolveOut{m.index, m.ivc, m.inr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, m.frame, nullptr, 0});
+    index_resolve_same_body<false>(m.a, m.pose, m.keys, b.W * b.H, ResolveOut{m.index, m.ivc, m.inr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, m.frame, nullptr, 0, 0});
 }
 __global__ __launch_bounds__(256) void k_obj_index_resolve_packed(const ObjBatch b) {   // the pass that feeds clean(): grid.x = 16 x 16-pixel tiles
     const ObjPassArgs& m = b.m[blockIdx.z];
     index_resolve_transposing_body<true>(b.updateCopy ? m.b : m.a, m.pose, m.keys, b.W, b.H,
-                                         ResolveOut{nullptr, nullptr, nullptr, nullptr, m.iclean, b.depthF, b.mask, b.maskT, b.depthT, m.confThreshold, m.frame, nullptr, 0}, (int)blockIdx.x);
+                                         ResolveOut{nullptr, nullptr, nullptr, nullptr, m.iclean, b.depthF, b.mask, b.maskT, b.depthT, m.confThreshold, m.frame, nullptr, 0, b.depthT ? 1 : 0},
+                                         (int)blockIdx.x);
 }
 template <int kLanes>
 __global__ __launch_bounds__(256) void k_obj_fuse_data(const ObjBatch b) {
@@ -1722,16 +1789,19 @@ __device__ __forceinline__ CleanArgs obj_clean_args(const ObjBatch& b, const Obj
     a.frame = m.frame; a.pose = m.pose; a.W = b.W; a.H = b.H; a.k = b.k; a.timeDelta = b.timeDelta;
     a.confThreshold = m.confThreshold; a.outlierCoeff = b.outlierCoeff; a.maskID = m.maskID; a.transposed = 1; a.literal = b.cleanLiteral;
     a.index = m.index; a.vc = m.ivc; a.ct = nullptr; a.packed = m.iclean; a.depthT = b.depthT; a.depthF = b.depthF; a.mask = b.mask; a.maskT = b.maskT;
+    a.tap16 = b.depthT ? 1 : 0; a.tapGroup = b.cleanTapGroup; a.maskFree = 0;    // (an object model's mask is never its own id everywhere)
     a.cand_op = m.cand_op; a.cand_rec = m.cand_rec; a.flags = m.flags; a.newconf = m.newconf;
     a.block_counts = m.block_counts; a.host_count = m.host_count;
     a.host_append = m.host_append; a.seq = m.clean_seq;
     a.append = append; a.run_list = nullptr; a.run_count = nullptr; a.ctl = m.clean_ctl;
     return a;
 }
-template <bool kTap16>
-__global__ __launch_bounds__(256) void k_obj_clean_runs(const ObjBatch b) { clean_runs_body<kTap16>(obj_clean_args(b, b.m[blockIdx.z], 0)); }
-template <bool kTap16>
-__global__ __launch_bounds__(256) void k_obj_clean_small_flags(const ObjBatch b) { clean_small_flags_body<kTap16>(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1)); }
+template <bool kTap16, int kGroup>
+__global__ __launch_bounds__(256) void k_obj_clean_runs(const ObjBatch b) { clean_runs_body<kTap16, kGroup, false>(obj_clean_args(b, b.m[blockIdx.z], 0)); }
+template <bool kTap16, int kGroup>
+__global__ __launch_bounds__(256) void k_obj_clean_small_flags(const ObjBatch b) {
+    clean_small_flags_body<kTap16, kGroup, false>(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1));
+}
 __global__ __launch_bounds__(256) void k_obj_clean_small_compact(const ObjBatch b) { clean_small_compact_body(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1)); }
 __global__ __launch_bounds__(256) void k_obj_splat_scatter(const ObjBatch b) {
     const ObjPassArgs& m = b.m[blockIdx.z];
@@ -1766,12 +1836,19 @@ void launch_obj_fuse_clean(const ObjBatch& b, int blocks, int clean_blocks, hipS
     hipLaunchKernelGGL(k_obj_index_resolve_packed, dim3(resolve_tiles(b.W, b.H), 1, b.n), dim3(256), 0, s, b);
     // two-launch form src -> dst, or (big models) the buffer's own surfels in place, run by run -- an object model's launch visits every run: its
     // bounding box is the box of ALL its drawn surfels -- and then the frame's candidates appended by the two-launch form
-    if (b.depthT) {    // the 16-byte tap (the resolve pass above wrote it with each model's own threshold and tick)
-        if (!b.cleanSmall) hipLaunchKernelGGL(k_obj_clean_runs<true>, compact, dim3(256), 0, s, b);
-        hipLaunchKernelGGL(k_obj_clean_small_flags<true>, dim3(compact_blocks, 1, b.n), dim3(256), 0, s, b);
+    const dim3 flags(compact_blocks, 1, b.n);
+    if (b.depthT && b.cleanTapGroup == 3) {    // the 16-byte tap (the resolve pass above wrote it with each model's own threshold and tick)
+        if (!b.cleanSmall) hipLaunchKernelGGL((k_obj_clean_runs<true, 3>), compact, dim3(256), 0, s, b);
+        hipLaunchKernelGGL((k_obj_clean_small_flags<true, 3>), flags, dim3(256), 0, s, b);
+    } else if (b.depthT && b.cleanTapGroup == 9) {
+        if (!b.cleanSmall) hipLaunchKernelGGL((k_obj_clean_runs<true, 9>), compact, dim3(256), 0, s, b);
+        hipLaunchKernelGGL((k_obj_clean_small_flags<true, 9>), flags, dim3(256), 0, s, b);
+    } else if (b.depthT) {
+        if (!b.cleanSmall) hipLaunchKernelGGL((k_obj_clean_runs<true, 1>), compact, dim3(256), 0, s, b);
+        hipLaunchKernelGGL((k_obj_clean_small_flags<true, 1>), flags, dim3(256), 0, s, b);
     } else {
-        if (!b.cleanSmall) hipLaunchKernelGGL(k_obj_clean_runs<false>, compact, dim3(256), 0, s, b);
-        hipLaunchKernelGGL(k_obj_clean_small_flags<false>, dim3(compact_blocks, 1, b.n), dim3(256), 0, s, b);
+        if (!b.cleanSmall) hipLaunchKernelGGL((k_obj_clean_runs<false, 1>), compact, dim3(256), 0, s, b);
+        hipLaunchKernelGGL((k_obj_clean_small_flags<false, 1>), flags, dim3(256), 0, s, b);
     }
     hipLaunchKernelGGL(k_obj_clean_small_compact, dim3(compact_blocks, 1, b.n), dim3(256), 0, s, b);
 }
