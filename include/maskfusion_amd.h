@@ -504,76 +504,117 @@ int mf_cloud_visibility_dev(const float* d_points, int32_t stride, int64_t n, co
 /* whether the last tracking step used the fill-in maps (MaskFusion::requiresFillIn, MaskFusion.cpp:630-648) */
 int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
 
-/* The per-frame setters of MaskFusion (Core/MaskFusion.h:132-182,234-263).  Keys: "depthCutoff", "icpWeight",
- * "confidenceThreshold" (background), "outlierCoefficient", "fastOdom", "so3", "rgbOnly" (setRgbOnly: photometric term only), "pyramid", "timeDelta",
- * "maxDepthProcessed", "enableMultipleModels", "trackAllModels", "modelSpawnOffset",
- * "newModelMinRelativeSize", "newModelMaxRelativeSize" (SegmentationPerformer.h:36-37) and the MfSegmentation tunables
- * (MaskFusion.h:234-263 / MfSegmentation.h:42-62): "mfThreshold", "mfWeightDistance", "mfWeightConvexity",
- * "mfMorphEdgeIterations", "mfMorphEdgeRadius", "mfMorphMaskIterations", "mfMorphMaskRadius".
- * Implementation switches (defaults are the product; the alternatives exist for A/B measurements and as executable specifications):
- * "splatTiles" (1), "globalTiles" (1: GlobalProjection of the background through tile lists), "gpuLabels" (1: label stage on the
- * device), "batchTracking" (1: one Gauss-Newton launch serves every tracked model), "earlyBackgroundFusion" (1),
- * "cleanTap16" (1: inside mf_process_frame the index pass that feeds Model::clean writes one 16-byte tap per texel -- {x, y, z', initTime}, z' = NaN
- * unless index > 0, confidence > the model's threshold and z > 0, its sign bit set when lastTime == tick: everything the pass's window uses of a
- * tap, so the results are bit-identical -- and the filtered depth into a plane of its own; 0: the 32-byte record, which the model-level calls
- * mf_model_predict_indices -> mf_model_clean always use), "fuseLanes" (4: the data association handles a candidate on a quad of lanes, one window
- * column per lane, merged in the serial order; 1: one lane per candidate -- same results), read-only "indexPackedTexelBytes" (16 or 32: the form the
- * debug tap "index_packed" holds),
- * "cleanTapGroup" (3: with 16-byte taps Model::clean requests the three taps of a window column together before it looks at the first; 1: one tap
- * after the other; 9: the whole window at once -- the counts are integer sums, the results the same), "maskFreeClean" (1: in a context that takes
- * no masks the background's clean pass and the index pass that feeds it carry no mask / depth plane -- no texel can disagree with model 0 --; 0:
- * the planes travel in every context; a context with masks and the model-level calls always carry them),
- * "cleanLiteralWindow" (1: Model::clean walks its window with copy_unstable.vert's own fp32 trip count, 4 or 5 taps per axis;
- * 0: 4 x 4), "timings", "passTimings" (mf_get_pass_timings), "icpProfile", "objectSmallGrids" (1; 1: the grid-stride
- * surfel kernels of an object model run on a grid sized from its last known surfel count instead of 2048 workgroups), "objectScatterSplat" (1;
- * 1: object models are predicted with the scatter form of the splat instead of tile lists) -- both leave every result bit-identical; measured on
- * MI355X on the 12-model S2 scene: 394 -> 407 frames/s with both (profiles/r03a_bench_2s_object_switches.txt), on since round 3;
- * "bigMapElements" (6 000 000: from this many surfels on a model's buffer is kept as RUNS with a table (Surfels::box): Model::clean works in
- * place on the runs in which its rules can change something (k_cull_clean / k_clean_runs, the frame's new surfels appended behind the last run)
- * and the projection passes visit only the runs that can be in view (k_cull) -- below, the two-launch clean (a dense copy) and whole-buffer passes
- * of rounds 1-4), "inPlaceElements" (1 000 000: from this
- * many surfels on update.vert runs in place -- below, as rounds 1-4's copy with the second index scatter riding on it); which form a model's
- * passes take depends on its size alone and changes no result (tests/test_gpu_switches.py::test_clean_forms_agree), "cullRuns" (1; 0: big maps walk every run of
- * the buffer in every projection pass and in Model::clean -- the executable specification of the culled forms), "slabCulling" (1: the
- * batched Gauss-Newton pixel pass skips the workgroups none of whose pixels can project onto a model's normals -- exact, mf_odometry.hip; 0: every
- * workgroup walks its pixels), "densifyEvery" (0; n > 0: a
- * sparse buffer is compacted every n frames whatever the host's bounds say -- a test switch; by default only when the slots behind the last run or
- * the table entries could run out, before a download, before a model returns to the small-map forms); read-only: "densifyCount" (compactions so
- * far), "cleanRuns" / "visibleRuns" / "backgroundRuns" (runs the last in-place clean visited / on the last visibility list / of the
- * background's table), "unstampedRuns" (live runs of that table that hold a surfel with lastTime <= 0: the in-place clean visits them every frame),
- * "literalFusionWeight" (1: Model::computeFusionWeight's log map takes cos(theta) from the float trace of a float matrix as the reference's
- * text does -- its rotation term is then quantised in steps of ~4.9e-4 rad; 0: the same formula evaluated accurately in double.  See
- * DESIGN.md, finding F5; default 1 since round 3), "frameToFrameRGB" (0; MaskFusion::setFrameToFrameRGB, "-ftf": the photometric term tracks
- * against the previous RAW frame, Model.cpp:399-400,981), "objectBoundingBoxLimit" (1: Model::fuse limits an object model's depth by its
- * bounding box + 5 % as upstream does whenever its GUI draws the models, Model.cpp:480-501; 0: bb_max_z = FLT_MAX, a headless upstream).
- * "fusedRgbPyramid" (1: the frame's intensity pyramid and its derivative / gate images -- photometric term, SO(3) -- as one LDS-tiled launch;
- * 0: imageBGRToIntensity + 2 x pyrDownUcharGauss + computeDerivativeImages as four launches, the executable specification; same bytes).
- * Further switches and taps: "batchObjectPasses" (1: the surfel passes of all object models of a frame as one launch per pass; 0: model by
- * model, the executable specification), "objectStream" (1: inside mf_process_frame those batched launches -- the objects' fuse / clean chain and
- * their prediction -- go to a second stream and run beside the background's chain, joined at the end of the frame; 0: one stream; same bytes),
- * "batchSolveInPixelPass" (1: an iteration of the batched Gauss-Newton loop is ONE launch -- every workgroup of a model finishes the previous
- * iteration in its prologue, as the single-model kernel does; 0: a solve launch and a pixel launch per iteration; same bytes),
- * "fusedPreprocessLaunch" (1: when only the background is tracked model by model, its model-side pyramid is built in the depth filter's launch --
- * two independent kernels of a frame side by side; 0: two launches; same bytes),
- * "deferPredict" (a single-model context that tracks with the geometric term alone, timings off: the prediction of frame t is enqueued at the head
- * of the next mf_process_frame[_dev] call -- or by whatever other call on the context comes first -- instead of at the end of frame t, so that it can
- * share launches with frame t + 1's preprocessing; same bytes.  Work the caller enqueues on mf_get_stream()'s stream sees frame t's prediction only
- * behind the next library call), "fusedBinFilter" / "fusedFramePyramids" (in that head: the prediction's binning pass in the next frame's depth
- * filter's launch / the frame's pyramid and the model-side pyramid in one launch; 0: two launches each; same bytes); read-only: "deferredFrames" /
- * "fusedHeadFrames" (predictions deferred / frames that took the fused head so far),
- * "tilePyramid" (1: in that head every workgroup of the prediction's tile pass also writes its tile of the model-side pyramid, as the pyramid's own
- * launch computes it without fill-in, and that launch becomes a fix-up whose workgroups leave at once unless the frame's fill-in decision is 1;
- * 0: the model-side pyramid as a launch of its own; same bytes), "fusedTilePyramid" (needs "tilePyramid"; 1: the frame's pyramid rides in the tile
- * pass's launch, in workgroups of its own; 0: it shares the fix-up's launch or, with "fusedFramePyramids" 0, runs alone; same bytes); read-only:
- * "pyramidFixupFrames" (fused heads whose fix-up rebuilt the pyramid, i.e. whose tracking step fills in; synchronises the stream),
- * "hostLockstep" (1: mf_process_frame waits for frame k-2 to have run before it enqueues frame k's
- * upload), "hostWaitUpload" (1: ... and for its own upload: single-model frames), "modelApiPackedIndex" (0; 1: mf_model_predict_indices
- * also builds the packed column-major map mf_process_frame feeds Model::clean with), "tileThreads" (512) / "spriteLanes" (4) / "tileHeight" (24; 16, 20, 32: tiles of 16 pixels by that many rows): launch shape of
- * the tile passes (A/B), "splatTileEntries" (test knob: shrinks the tile lists to force their overflow path), "rebuildRunTable" (write-only:
- * rebuilds the background's run table from scratch), "splatProfile" (1: per-tile stamps of the background's tile pass, debug tap
- * "splat_prof").  Read-only (mf_get_param): "visibleRuns" / "backgroundRuns" (runs k_cull listed for the last pass / runs of the
- * background's table), "hostWaitUs" | "hostStageUs" | "hostUploadUs" | "hostEnqueueUs" | "hostCallUs" (host clocks inside
- * mf_process_frame, microseconds per call since mf_set_param("hostProfileReset", 1)). */
+/* The parameters of a context, by key.  One table (maskfusion_amd/csrc/mf_params.inl) holds every key with its type, its legal values and who
+ * may read and write it; the list below follows it row by row.  A flag stores value != 0 and reads back as 0 or 1; an int stores (int)value.
+ * Every read-write key can be read back.  MF_EINVAL -- for an unknown key, a set of a read-only key, a get of a write-only key, a value outside
+ * a key's legal values -- changes nothing and leaves "<key>: <reason>" in mf_last_error.
+ *
+ * Reference parameters: the per-frame setters of MaskFusion (Core/MaskFusion.h:132-182,234-263); their defaults are mf_config's.
+ *   "depthCutoff", "icpWeight" (float)
+ *   "confidenceThreshold" (float; the background's)
+ *   "outlierCoefficient", "maxDepthProcessed" (float)
+ *   "fastOdom", "so3" (int)
+ *   "rgbOnly" (int; setRgbOnly: photometric term only)
+ *   "pyramid", "timeDelta", "enableMultipleModels", "trackAllModels", "modelSpawnOffset" (int)
+ *
+ * Segmentation parameters:
+ *   "newModelMinRelativeSize", "newModelMaxRelativeSize" (float; SegmentationPerformer.h:36-37)
+ *   "mfThreshold", "mfWeightDistance", "mfWeightConvexity" (float), "mfMorphEdgeIterations", "mfMorphEdgeRadius", "mfMorphMaskIterations",
+ *     "mfMorphMaskRadius" (int): the MfSegmentation tunables (MaskFusion.h:234-263 / MfSegmentation.h:42-62)
+ *
+ * Implementation switches (flags unless legal values are given; the defaults, in parentheses, are the product; the alternatives exist for A/B
+ * measurements and as executable specifications):
+ *   "splatTiles" (1)
+ *   "globalTiles" (1: GlobalProjection of the background through tile lists)
+ *   "gpuLabels" (1: label stage on the device)
+ *   "batchTracking" (1: one Gauss-Newton launch serves every tracked model)
+ *   "batchSolveInPixelPass" (1: an iteration of the batched Gauss-Newton loop is ONE launch -- every workgroup of a model finishes the previous
+ *     iteration in its prologue, as the single-model kernel does; 0: a solve launch and a pixel launch per iteration; same bytes)
+ *   "slabCulling" (1: the batched Gauss-Newton pixel pass skips the workgroups none of whose pixels can project onto a model's normals -- exact,
+ *     mf_odometry.hip; 0: every workgroup walks its pixels)
+ *   "earlyBackgroundFusion" (1)
+ *   "cleanTap16" (1: inside mf_process_frame the index pass that feeds Model::clean writes one 16-byte tap per texel -- {x, y, z', initTime}, z' = NaN
+ *     unless index > 0, confidence > the model's threshold and z > 0, its sign bit set when lastTime == tick: everything the pass's window uses of a
+ *     tap, so the results are bit-identical -- and the filtered depth into a plane of its own; 0: the 32-byte record, which the model-level calls
+ *     mf_model_predict_indices -> mf_model_clean always use)
+ *   "cleanTapGroup" (3; legal: 1, 3, 9.  3: with 16-byte taps Model::clean requests the three taps of a window column together before it looks at
+ *     the first; 1: one tap after the other; 9: the whole window at once -- the counts are integer sums, the results the same)
+ *   "maskFreeClean" (1: in a context that takes no masks the background's clean pass and the index pass that feeds it carry no mask / depth plane
+ *     -- no texel can disagree with model 0 --; 0: the planes travel in every context; a context with masks and the model-level calls always carry
+ *     them)
+ *   "fuseLanes" (4; legal: 1, 4.  4: the data association handles a candidate on a quad of lanes, one window column per lane, merged in the serial
+ *     order; 1: one lane per candidate -- same results)
+ *   "cleanLiteralWindow" (1: Model::clean walks its window with copy_unstable.vert's own fp32 trip count, 4 or 5 taps per axis; 0: 4 x 4)
+ *   "objectSmallGrids" (1: the grid-stride surfel kernels of an object model run on a grid sized from its last known surfel count instead of 2048
+ *     workgroups)
+ *   "objectScatterSplat" (1: object models are predicted with the scatter form of the splat instead of tile lists) -- both leave every result
+ *     bit-identical; measured on MI355X on the 12-model S2 scene: 394 -> 407 frames/s with both (profiles/r03a_bench_2s_object_switches.txt), on
+ *     since round 3
+ *   "batchObjectPasses" (1: the surfel passes of all object models of a frame as one launch per pass; 0: model by model, the executable
+ *     specification)
+ *   "objectStream" (1: inside mf_process_frame those batched launches -- the objects' fuse / clean chain and their prediction -- go to a second
+ *     stream and run beside the background's chain, joined at the end of the frame; 0: one stream; same bytes)
+ *   "cullRuns" (1; 0: big maps walk every run of the buffer in every projection pass and in Model::clean -- the executable specification of the
+ *     culled forms)
+ *   "literalFusionWeight" (1: Model::computeFusionWeight's log map takes cos(theta) from the float trace of a float matrix as the reference's text
+ *     does -- its rotation term is then quantised in steps of ~4.9e-4 rad; 0: the same formula evaluated accurately in double.  See DESIGN.md,
+ *     finding F5; default 1 since round 3)
+ *   "frameToFrameRGB" (0; MaskFusion::setFrameToFrameRGB, "-ftf": the photometric term tracks against the previous RAW frame,
+ *     Model.cpp:399-400,981)
+ *   "objectBoundingBoxLimit" (1: Model::fuse limits an object model's depth by its bounding box + 5 % as upstream does whenever its GUI draws the
+ *     models, Model.cpp:480-501; 0: bb_max_z = FLT_MAX, a headless upstream)
+ *   "fusedRgbPyramid" (1: the frame's intensity pyramid and its derivative / gate images -- photometric term, SO(3) -- as one LDS-tiled launch;
+ *     0: imageBGRToIntensity + 2 x pyrDownUcharGauss + computeDerivativeImages as four launches, the executable specification; same bytes)
+ *   "fusedPreprocessLaunch" (1: when only the background is tracked model by model, its model-side pyramid is built in the depth filter's launch
+ *     -- two independent kernels of a frame side by side; 0: two launches; same bytes)
+ *   "deferPredict" (1; a single-model context that tracks with the geometric term alone, timings off: the prediction of frame t is enqueued at the
+ *     head of the next mf_process_frame[_dev] call -- or by whatever other call on the context comes first -- instead of at the end of frame t, so
+ *     that it can share launches with frame t + 1's preprocessing; same bytes.  Work the caller enqueues on mf_get_stream()'s stream sees frame t's
+ *     prediction only behind the next library call)
+ *   "fusedBinFilter" (1) / "fusedFramePyramids" (1) (in that head: the prediction's binning pass in the next frame's depth filter's launch / the
+ *     frame's pyramid and the model-side pyramid in one launch; 0: two launches each; same bytes)
+ *   "tilePyramid" (1: in that head every workgroup of the prediction's tile pass also writes its tile of the model-side pyramid, as the pyramid's
+ *     own launch computes it without fill-in, and that launch becomes a fix-up whose workgroups leave at once unless the frame's fill-in decision
+ *     is 1; 0: the model-side pyramid as a launch of its own; same bytes)
+ *   "fusedTilePyramid" (needs "tilePyramid"; 1: the frame's pyramid rides in the tile pass's launch, in workgroups of its own; 0: it shares the
+ *     fix-up's launch or, with "fusedFramePyramids" 0, runs alone; same bytes)
+ *   "hostInputAsync" (1: mf_process_frame returns when the frame is enqueued; 0: the blocking form of rounds 1-3.  Setting it synchronises both
+ *     streams first)
+ *   "hostLockstep" (1: mf_process_frame waits for frame k-2 to have run before it enqueues frame k's upload)
+ *   "hostWaitUpload" (1: ... and for its own upload: single-model frames)
+ *   "modelApiPackedIndex" (0; 1: mf_model_predict_indices also builds the packed column-major map mf_process_frame feeds Model::clean with)
+ *
+ * Tuning knobs (int):
+ *   "bigMapElements" (6 000 000: from this many surfels on a model's buffer is kept as RUNS with a table (Surfels::box): Model::clean works in
+ *     place on the runs in which its rules can change something (k_cull_clean / k_clean_runs, the frame's new surfels appended behind the last
+ *     run) and the projection passes visit only the runs that can be in view (k_cull) -- below, the two-launch clean (a dense copy) and
+ *     whole-buffer passes of rounds 1-4)
+ *   "inPlaceElements" (1 000 000: from this many surfels on update.vert runs in place -- below, as rounds 1-4's copy with the second index
+ *     scatter riding on it); which form a model's passes take depends on its size alone and changes no result
+ *     (tests/test_gpu_switches.py::test_clean_forms_agree)
+ *   "tileHeight" (24; legal: 16, 20, 24, 32: tiles of 16 pixels by that many rows), "tileThreads" (512; legal: 256, 320, 384, 512, 1024: threads
+ *     per tile workgroup), "spriteLanes" (4; legal: 1, 2, 4, 8, 16: lanes that share a sprite in the tile z-test): launch shape of the tile
+ *     passes (A/B)
+ *
+ * Test knobs and actions:
+ *   "densifyEvery" (int, 0; n > 0: a sparse buffer is compacted every n frames whatever the host's bounds say -- a test switch; by default only
+ *     when the slots behind the last run or the table entries could run out, before a download, before a model returns to the small-map forms)
+ *   "splatTileEntries" (int; legal: 1 up to its initial value.  Test knob: shrinks the tile lists to force their overflow path)
+ *   "timings" (0; mf_get_timings), "passTimings" (0; mf_get_pass_timings; setting it clears the recorded passes), "icpProfile" (0)
+ *   "splatProfile" (0; 1: per-tile stamps of the background's tile pass, debug tap "splat_prof"; MF_ENOMEM when its buffer cannot be allocated)
+ *   "hostProfileReset" (write-only: restarts the host clocks below)
+ *   "rebuildRunTable" (write-only: rebuilds the background's run table from scratch)
+ *
+ * Read-only taps (mf_get_param):
+ *   "indexPackedTexelBytes" (16 or 32: the form the debug tap "index_packed" holds)
+ *   "deferredFrames" / "fusedHeadFrames" (predictions deferred / frames that took the fused head so far)
+ *   "pyramidFixupFrames" (fused heads whose fix-up rebuilt the pyramid, i.e. whose tracking step fills in; synchronises the stream)
+ *   "densifyCount" (compactions so far)
+ *   "cleanRuns" / "visibleRuns" / "backgroundRuns" (runs the last in-place clean visited / runs k_cull listed for the last pass / runs of the
+ *     background's table)
+ *   "unstampedRuns" (live runs of that table that hold a surfel with lastTime <= 0: the in-place clean visits them every frame)
+ *   "hostStageUs" | "hostUploadUs" | "hostEnqueueUs" | "hostCallUs" | "hostWaitUs" (host clocks inside mf_process_frame, microseconds per call
+ *     since mf_set_param("hostProfileReset", 1)) */
 int mf_set_param(mf_ctx* ctx, const char* key, double value);
 int mf_get_param(mf_ctx* ctx, const char* key, double* value);
 

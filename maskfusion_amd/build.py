@@ -12,7 +12,7 @@ LIB = os.path.join(HERE, "libmaskfusion_amd.so")
 SOURCES = ["mf_preproc.hip", "mf_odometry.hip", "mf_rgbd.hip", "mf_surfel.hip", "mf_splat.hip", "mf_segment.hip", "mf_labels.hip", "mf_labels_gpu.hip", "mf_render.hip", "mf_eval.hip", "mf_eval_image.hip", "mf_eval_visibility.hip", "mf_mesh.hip", "mf_eval_trimesh.hip", "mf_trimesh_ray.hip", "mf_context.hip"]
 HEADERS = ["mf_internal.h", "mf_device.h", "mf_labels.h", os.path.join("..", "..", "include", "maskfusion_amd.h"), "mf_rgbd_device.h", "mf_walk.h", "mf_cloud_grid.h", "mf_trimesh.h",
            "mf_bilateral_device.h", "mf_frame_pyramid_device.h", "mf_model_pyramid_device.h",
-           "mf_frame.inl", "mf_model_api.inl", "mf_ktest.inl", "mf_render.inl", "mf_eval.inl"]   # (the .inl files are parts of mf_context.hip)
+           "mf_frame.inl", "mf_model_api.inl", "mf_params.inl", "mf_ktest.inl", "mf_render.inl", "mf_eval.inl"]   # (the .inl files are parts of mf_context.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # per-file additions.  mf_odometry: the SLP vectoriser pairs the 28 upper-triangle products of the ICP row into v_pk_fma_f32 and then
 # spends more v_mov_b32 on assembling the operand pairs than it saves (k_icp_iter<512>: 2643 -> 2432 instructions, 589 -> 286 moves)

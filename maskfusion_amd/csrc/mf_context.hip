@@ -163,19 +163,89 @@ static void render_free(RenderScratch* r);
 struct EvalScratch;                            // mf_eval.inl: the model nearest-neighbour query's scratch, allocated on its first call
 static void eval_free(EvalScratch* e);
 
+// Every implementation switch and tuning knob of a context, in the order of their table (mf_params.inl: key, legal values, side effects of setting
+// one).  The defaults are the product; the other positions exist for A/B measurements and as executable specifications.  A flag is a bool, a
+// number an int: the table addresses the members by offset and type.
+#ifndef MF_DEFAULT_LITERAL_FUSION_WEIGHT
+#define MF_DEFAULT_LITERAL_FUSION_WEIGHT 1             // default since round 3 (finding F5: the reference's own arithmetic); 0 = the accurate double log map
+#endif
+struct Switches {
+    // ---- implementation switches ----
+    bool splat_tiles = true;                           // "splatTiles": models are predicted through tile lists (mf_splat.hip); 0: the scatter form
+    bool global_tiles = true;                          // A/B + test knob ("globalTiles"): 0 = every model through k_global_scatter
+    bool gpu_labels = true;                            // "gpuLabels": the label stage on the device; 0: the host label stage (specification)
+    bool batch_tracking = true;                        // 0: track the models one after the other even when a batch is possible ("batchTracking")
+    bool batch_solve_fused = true;                     // "batchSolveInPixelPass": the batched Gauss-Newton loop as ONE launch per iteration (k_icp_batch_pixels with
+                                                       // k_icp_batch_solve's work as its prologue); 0: two (the executable specification)
+    bool slab_culling = true;                          // "slabCulling": the batched pixel pass skips the workgroups whose pixels cannot project onto a model's normals (exact)
+    bool early_bg_fusion = true;                       // A/B knob ("earlyBackgroundFusion"): 0 = the host visit drains the stream
+    bool clean_tap16 = true;                           // the pass that feeds clean() inside a frame writes 16-byte window taps ("cleanTap16"; 0: the 32-byte record)
+    int clean_tap_group = 3;                           // 16-byte taps a clean pass requests before it looks at one: 1 (the serial walk), 3 (a window column), 9 ("cleanTapGroup")
+    bool mask_free_clean = true;                       // a frame without a mask carries no mask / depth plane into the background's clean pass ("maskFreeClean";
+                                                       // 0: the planes travel in every context)
+    int fuse_lanes = 4;                                // lanes per candidate of the data association ("fuseLanes": 1 or 4)
+    bool clean_literal = true;                         // Model::clean walks its window with the shader text's fp32 trip count ("cleanLiteralWindow"; 0: the exact-arithmetic 4 x 4 window)
+    // A/B switches for object models (a few thousand surfels each; their per-frame cost is launch overhead).  Measured on MI355X, 12-model S2
+    // scene (profiles/r03a_bench_2s_object_switches.txt): 394 frames/s without, 395 / 399 with one, 407 with both -> on since round 3:
+    bool object_small_grids = true;                    // "objectSmallGrids": the grid-stride surfel kernels with a grid sized from the model's last known count
+    bool object_scatter_splat = true;                  // "objectScatterSplat": object models are predicted with the scatter form instead of tile lists
+    bool batch_objects = true;                         // "batchObjectPasses": the surfel passes of all object models of a frame as one launch per pass (grid.z = model);
+                                                       // 0: model by model.  process_frame_impl turns it off when an object's scratch cannot be allocated
+    bool object_stream = true;                         // "objectStream": the batched object passes on a stream of their own, beside the background's chain (mf_ctx::stream_obj);
+                                                       // 0: on the main stream, behind the background's
+    bool cull_runs = true;                             // "cullRuns": 0 = every projection pass streams the whole buffer (A/B switch, executable specification)
+    bool weight_literal = MF_DEFAULT_LITERAL_FUSION_WEIGHT != 0;   // "literalFusionWeight": Model::rodrigues2 with the reference's float trace (finding F5)
+    bool ftf_rgb = false;                              // MaskFusion::frameToFrameRGB ("-ftf"; Model.cpp:399-400,981, setFrameToFrameRGB Core/MaskFusion.cpp:910): the
+                                                       // photometric term tracks against the previous RAW frame
+    bool bbox_limit = true;                            // "objectBoundingBoxLimit": Model::fuse limits an object's depth by lastBoundingBox (Model.cpp:480-501; upstream: whenever
+                                                       // its GUI draws the models); 0: a headless upstream that never renders (bb_max_z = FLT_MAX)
+    bool fused_rgb_pyramid = true;                     // "fusedRgbPyramid": the frame's intensity pyramid + derivative / gate images as one launch (0: four launches, the executable specification)
+    // "fusedPreprocessLaunch": the model-side pyramids of the frame's tracking plan are built in the depth filter's launch (k_bilateral_model_pyramid):
+    // the background's, or every tracked model's of a batched plan (mf_frame.inl: process_frame_impl hands the fact to the tracking loop);
+    // 0: k_bilateral and k_model_pyramid as two launches
+    bool fused_preprocess = true;
+    // "deferPredict": the background's prediction of frame t waits as a record (mf_ctx::pending) and is drawn in the head of frame t + 1, where its
+    // launches are shared with that frame's preprocessing; 0: every prediction at the end of its own frame.  "fusedBinFilter" 0: k_splat_bin and
+    // k_bilateral as two launches in the fused head; "fusedFramePyramids" 0: k_frame_pyramid and k_model_pyramid as two launches
+    bool defer_predict = true, fused_bin_filter = true, fused_frame_pyramids = true;
+    // "tilePyramid": in the fused head the tile pass also writes the model-side pyramid (without fill-in) and the model-side pyramid's launch shrinks to
+    // a fix-up that runs only in frames whose fill-in decision is 1 (0: a launch of its own); "fusedTilePyramid": the frame pyramid rides in the tile
+    // pass's launch too (0: behind the tile pass, not beside it; mf_frame.inl: enqueue_fused_head)
+    bool tile_pyramid = true, fused_tile_pyramid = true;
+    bool host_async = true;                            // "hostInputAsync": mf_process_frame returns when the frame is enqueued (mf_ctx::stream_in); 0: it blocks until the frame is fused (rounds 1-3)
+    // "hostLockstep": the call waits for frame k-2 to have RUN before it enqueues frame k's upload, so the host is at most two
+    // frames ahead and the upload's dependency (the frame that last read the device block) is already satisfied when it is enqueued.  Left
+    // to run three frames ahead, every frame pays ~40 us for cross-queue dependencies that are still open at enqueue time
+    // (profiles/r04o_host_ab.json: 352 -> 324 us per frame; device-resident: 305)
+    bool host_lockstep = true;
+    // "hostWaitUpload" (needs hostLockstep): the call also waits for its OWN upload (~60 us of the ~300 the host has to spare per
+    // frame) before it enqueues the frame, which then needs no cross-queue wait at all: 322 -> 317 us per frame (profiles/r04q_host_ab.json;
+    // device-resident frames: 305).
+    bool host_wait_upload = true;
+    bool model_api_packed = false;                     // "modelApiPackedIndex": mf_model_predict_indices also builds the packed column-major map clean() uses in-frame;
+                                                       // 0: scatter + resolve form (specification)
+    // ---- tuning knobs ----
+    int big_map_elements = 6000000;                    // "bigMapElements": from this many surfels on a model's buffer is kept as runs (Surfels::box): its clean pass works in
+                                                       // place on the runs its rules can touch and its projection passes cull by run; below, the two-launch clean (a dense
+                                                       // copy) and whole-buffer passes
+    int in_place_elements = 1000000;                   // "inPlaceElements": from this many surfels on update.vert runs in place and the second index scatter is a
+                                                       // launch of its own (~18 us per million surfels + ~10 us); below, the copying update with the scatter
+                                                       // riding on it (~30 us per million).  Only with the two-launch clean (<= big_map_elements)
+    SplatTuning splat_tune;                            // "tileHeight" / "tileThreads" / "spriteLanes" of THIS context: launch shape of the tile passes (mf_splat.hip)
+    // ---- test knobs ----
+    int densify_every = 0;                             // "densifyEvery": > 0 = a model's sparse buffer is compacted every so many frames whatever its bounds say (tests)
+    bool timings_on = false, pass_timings_on = false;  // "timings" / "passTimings": HIP events around the stages (mf_get_timings) / the surfel passes (mf_get_pass_timings)
+    bool icp_prof_on = false;                          // "icpProfile"
+    bool splat_prof_on = false;                        // "splatProfile": per-tile shader-clock stamps of k_splat_tile (tools/splat_prof.py); debug tap "splat_prof"
+};
+
 struct mf_ctx {
     mf_config cfg;
+    Switches sw;                       // every implementation switch and tuning knob (mf_params.inl is their table)
     int W, H, P;
     Intr K;
     hipStream_t stream = nullptr;      // the frame's chain: preprocessing, tracking, fusion, prediction
-    bool clean_tap16 = true;                           // the pass that feeds clean() inside a frame writes 16-byte window taps ("cleanTap16"; 0: the 32-byte record)
-    int clean_tap_group = 3;                           // 16-byte taps a clean pass requests before it looks at one: 1, 3 (a window column), 9 ("cleanTapGroup")
-    bool mask_free_clean = true;                       // a frame without a mask carries no mask / depth plane into the background's clean pass ("maskFreeClean")
     bool iclean_is_tap16 = false;                      // the form d_iclean holds (debug tap "index_packed")
-    int fuse_lanes = 4;                                // lanes per candidate of the data association ("fuseLanes": 1 or 4)
-    bool clean_literal = true;                         // Model::clean walks its window with the shader text's fp32 trip count ("cleanLiteralWindow")
-    bool global_tiles = true;                          // A/B + test knob ("globalTiles"): 0 = every model through k_global_scatter
-    bool early_bg_fusion = true;                       // A/B knob ("earlyBackgroundFusion"): 0 = the host visit drains the stream
     hipEvent_t ev_labels = nullptr;                    // the label stage of this frame has written its result words
     long frame_no = 0;
     long bg_fused_frame = -1;          // mf_fuse_background has fused the background of this staged frame (mf_fuse_models then skips it)
@@ -185,17 +255,6 @@ struct mf_ctx {
     int host_tick = 1;
     bool map_ready = false;            // the background map exists (first frame processed, Model::initialise or an uploaded map)
     bool tracked_once = false;         // a tracking step has run (its stage timings are meaningful)
-    bool timings_on = false, icp_prof_on = false;
-    // A/B switches for object models (a few thousand surfels each; their per-frame cost is launch overhead).  Measured on MI355X, 12-model S2
-    // scene (profiles/r03a_bench_2s_object_switches.txt): 394 frames/s without, 395 / 399 with one, 407 with both -> on since round 3:
-    bool object_small_grids = true;                    // "objectSmallGrids": the grid-stride surfel kernels with a grid sized from the model's last known count
-    bool object_scatter_splat = true;                  // "objectScatterSplat": object models are predicted with the scatter form instead of tile lists
-#ifndef MF_DEFAULT_LITERAL_FUSION_WEIGHT
-#define MF_DEFAULT_LITERAL_FUSION_WEIGHT 1             // default since round 3 (finding F5: the reference's own arithmetic); 0 = the accurate double log map
-#endif
-    bool weight_literal = MF_DEFAULT_LITERAL_FUSION_WEIGHT != 0;   // "literalFusionWeight": Model::rodrigues2 with the reference's float trace (finding F5)
-    bool bbox_limit = true;                            // "objectBoundingBoxLimit": Model::fuse limits an object's depth by lastBoundingBox (Model.cpp:480-501; upstream: whenever its GUI draws the models)
-    bool batch_objects = true;                         // "batchObjectPasses": the surfel passes of all object models of a frame as one launch per pass (grid.z = model)
     static constexpr int kObjArgSlots = 8;             // argument arrays of the batched launches: pinned staging + device copy, a small ring (two per frame)
     ObjPassArgs* d_obj_args[kObjArgSlots] = {}; ObjPassArgs* h_obj_args[kObjArgSlots] = {}; hipEvent_t ev_obj_args[kObjArgSlots] = {};
     unsigned obj_arg_slot = 0;
@@ -204,46 +263,26 @@ struct mf_ctx {
     // share read-only inputs (frame, label image, poses).  Fork: behind the label stage (the host has waited for it); join: the end of the frame.
     // obj_s: where the batched object passes are enqueued right now (the main stream outside that window); obj_dep_main: main-stream work the object
     // chain depends on has been enqueued since the fork (a spawn, a compaction) -- the object stream waits for it first.
-    // "fusedPreprocessLaunch": the model-side pyramids of the frame's tracking plan are built in the depth filter's launch (k_bilateral_model_pyramid):
-    // the background's, or every tracked model's of a batched plan (mf_frame.inl: process_frame_impl hands the fact to the tracking loop)
-    bool fused_preprocess = true;
-    // "deferPredict": the background's prediction of frame t waits as a record and is drawn in the head of frame t + 1, where its launches are shared
-    // with that frame's preprocessing ("fusedBinFilter", "fusedFramePyramids"; mf_frame.inl: defer_eligible, settle, enqueue_fused_head).  pending.m:
-    // the model whose prediction is pending (nullptr: none), pending.adv: its end-of-frame bookkeeping with the pose-log slot taken in call t
-    bool defer_predict = true, fused_bin_filter = true, fused_frame_pyramids = true;
-    struct { ModelState* m = nullptr; FrameAdvance adv{nullptr, nullptr, nullptr}; } pending;
-    long deferred_frames = 0, fused_head_frames = 0;   // "deferredFrames" / "fusedHeadFrames" (read-only): predictions deferred / heads taken so far
-    // "tilePyramid": in the fused head the tile pass also writes the model-side pyramid (without fill-in) and the model-side pyramid's launch shrinks to
-    // a fix-up that runs only in frames whose fill-in decision is 1; "fusedTilePyramid": the frame pyramid rides in the tile pass's launch too
-    // (mf_frame.inl: enqueue_fused_head).  d_pyramid_fixups: frames whose fix-up ran, counted on the device ("pyramidFixupFrames", read-only)
-    bool tile_pyramid = true, fused_tile_pyramid = true;
-    int* d_pyramid_fixups = nullptr;
-    bool object_stream = true;
     hipStream_t stream_obj = nullptr, obj_s = nullptr;
     hipEvent_t ev_obj_dep = nullptr, ev_obj_done = nullptr;
     bool obj_dep_main = false;
+    // the background's deferred prediction ("deferPredict"; mf_frame.inl: defer_eligible, settle, enqueue_fused_head).  pending.m: the model whose
+    // prediction is pending (nullptr: none), pending.adv: its end-of-frame bookkeeping with the pose-log slot taken in call t
+    struct { ModelState* m = nullptr; FrameAdvance adv{nullptr, nullptr, nullptr}; } pending;
+    long deferred_frames = 0, fused_head_frames = 0;   // "deferredFrames" / "fusedHeadFrames" (read-only): predictions deferred / heads taken so far
+    // frames whose model-side pyramid fix-up ran ("tilePyramid"), counted on the device ("pyramidFixupFrames", read-only)
+    int* d_pyramid_fixups = nullptr;
     float* d_depthT = nullptr;                         // the filtered depth in d_maskT's order (16-byte taps: the 32-byte record carries it in its spare word)
     float* d_depthT_obj = nullptr;                     // the object chain's own copy, as d_maskT_obj
     uint8_t* d_maskT_obj = nullptr;                    // the object chain's own copy of d_maskT (every packed resolve pass writes the whole plane)
-    bool ftf_rgb = false;                              // MaskFusion::frameToFrameRGB ("-ftf"; Model.cpp:399-400,981): the photometric term tracks against the previous RAW frame
     double host_us[5] = {0, 0, 0, 0, 0}; long host_calls = 0;   // mf_process_frame's host time: wait for the slot + staging copy | upload enqueue | frame enqueue | whole call | the wait alone ("hostStageUs" ... "hostWaitUs")
-    // "hostLockstep" (default on): the call waits for frame k-2 to have RUN before it enqueues frame k's upload, so the host is at most two
-    // frames ahead and the upload's dependency (the frame that last read the device block) is already satisfied when it is enqueued.  Left
-    // to run three frames ahead, every frame pays ~40 us for cross-queue dependencies that are still open at enqueue time
-    // (profiles/r04o_host_ab.json: 352 -> 324 us per frame; device-resident: 305)
-    bool host_lockstep = true;
-    // "hostWaitUpload" (default on, needs hostLockstep): the call also waits for its OWN upload (~60 us of the ~300 the host has to spare per
-    // frame) before it enqueues the frame, which then needs no cross-queue wait at all: 322 -> 317 us per frame (profiles/r04q_host_ab.json;
-    // device-resident frames: 305).
-    bool host_wait_upload = true;
 
     // frame-level
     uint8_t* d_rgb = nullptr; float* d_depth = nullptr; uint8_t* d_mask_in = nullptr; uint8_t* d_zero_mask = nullptr;
-    // mf_process_frame (host pointers, the reference's FrameData boundary) without a synchronisation per frame ("hostInputAsync", default on):
+    // mf_process_frame (host pointers, the reference's FrameData boundary) without a synchronisation per frame ("hostInputAsync"):
     // the caller's buffers are copied into a pinned staging slot (so they may be reused at once), the slot goes to the device on its own
     // stream under the previous frame's kernels, and the call returns when the frame is enqueued; every getter synchronises, as they do
     // behind mf_process_frame_dev.  Two slots each: frame k+2 reuses what frame k used.
-    bool host_async = true;
     hipStream_t stream_in = nullptr;
     uint8_t* h_in[2] = {nullptr, nullptr};                 // pinned: depth (4P) | rgb (3P) | mask (P), each part 256-B aligned: ONE upload per frame
     uint8_t* d_in_block[2] = {nullptr, nullptr};           // the same layout in HBM; d_in_* below are views into it
@@ -265,14 +304,10 @@ struct mf_ctx {
     RgbCorr* d_corres = nullptr; float* d_rgb_partials[2] = {nullptr, nullptr}; int2* d_cnt[2] = {nullptr, nullptr};
     So3Result* d_so3 = nullptr; char* d_so3_scratch = nullptr;
     // tiled splat prediction (mf_splat.hip)
-    SplatTuning splat_tune;                // "spriteLanes" / "tileThreads" of THIS context
-    int* d_tile_count = nullptr; int* d_tile_entries = nullptr; int tile_entries_cap = 0; int tile_entries_alloc = 0; int splat_tiles = 1;
+    int* d_tile_count = nullptr; int* d_tile_entries = nullptr; int tile_entries_cap = 0; int tile_entries_alloc = 0;
     float4* d_splat_rec0 = nullptr; float4* d_splat_rec1 = nullptr; uint2* d_splat_bbox = nullptr;   // per-surfel sprite set-up
     const uint8_t* cur_rgb = nullptr;      // device rgb of the frame being processed (fill-in intensity at predict time)
     const float* cur_depth = nullptr;      // device raw depth of the frame being processed / staged (Model-level entry points)
-    bool batch_solve_fused = true;         // "batchSolveInPixelPass": the batched Gauss-Newton loop as ONE launch per iteration (k_icp_batch_pixels with k_icp_batch_solve's work as its prologue); 0: two
-    int batch_tracking = 1;                // 0: track the models one after the other even when a batch is possible ("batchTracking")
-    int model_api_packed = 0;              // mf_model_predict_indices also builds the packed column-major map clean() uses in-frame
     std::vector<int32_t> mask_classes;     // FrameData::classIDs for mf_process_frame_dev (mf_set_mask_class_ids)
     std::vector<int> trackable;            // MaskFusion::trackableClassIds (empty: every class is trackable)
     // pose logs of dropped models (MaskFusion::inactiveModels, exportPoses).  A drop must not stall the frame it happens in (a scene of tracked
@@ -298,25 +333,14 @@ struct mf_ctx {
     int* d_vis_list = nullptr; int* d_vis_count = nullptr; int* d_cull_ctl = nullptr; int vis_max_runs = 0;
     struct { const void* model = nullptr; long frame = -1; int cur = -1; unsigned gen = 0; float max_depth = 0.f; int time_delta = 0; } vis_tag;
     int densify_count = 0;                 // compactions of sparse buffers so far ("densifyCount", read-only: tests / bench)
-    bool fused_rgb_pyramid = true;         // "fusedRgbPyramid": the frame's intensity pyramid + derivative / gate images as one launch (0: four launches, the executable specification)
     float2* d_row_z = nullptr;             // batched Gauss-Newton loop: depth range of every row of the frame's vertex maps (launch_row_zrange)
-    bool slab_culling = true;              // "slabCulling": the batched pixel pass skips the workgroups whose pixels cannot project onto a model's normals (exact)
-    int densify_every = 0;                 // "densifyEvery": > 0 = a model's sparse buffer is compacted every so many frames whatever its bounds say (tests)
-    bool cull_runs = true;                 // "cullRuns": 0 = every projection pass streams the whole buffer (A/B switch, executable specification)
-    int big_map_elements = 6000000;        // "bigMapElements": from this many surfels on a model's buffer is kept as runs (Surfels::box): its clean pass works in
-                                           // place on the runs its rules can touch and its projection passes cull by run; below, the two-launch clean (a dense
-                                           // copy) and whole-buffer passes
-    int in_place_elements = 1000000;       // "inPlaceElements": from this many surfels on update.vert runs in place and the second index scatter is a
-                                           // launch of its own (~18 us per million surfels + ~10 us); below, the copying update with the scatter
-                                           // riding on it (~30 us per million).  Only with the two-launch clean (<= big_map_elements)
     unsigned long long* d_icp_prof = nullptr;
-    unsigned long long* d_splat_prof = nullptr; bool splat_prof_on = false;   // "splatProfile": [tiles][8] stamps of the background's tile pass
+    unsigned long long* d_splat_prof = nullptr;   // "splatProfile": [tiles][8] stamps of the background's tile pass
     // multi-model coupling
     float* d_edge = nullptr; uint8_t* d_bin = nullptr; uint8_t* d_tmp_u8 = nullptr; uint8_t* d_proj_ids = nullptr;
     uint8_t* h_bin = nullptr; uint8_t* h_ids = nullptr; float* h_depth = nullptr; uint8_t* h_mask = nullptr; uint8_t* h_full = nullptr;
     std::vector<uint8_t> ignoreMap;
     std::unique_ptr<LabelsScratch> labels;   // device label stage ("gpuLabels", default on)
-    int gpu_labels = 1;
     SegParams seg;
     int nextID = 0, spawnOffset = 0;
     int cap_max = 0;
@@ -329,7 +353,6 @@ struct mf_ctx {
     hipEvent_t ev_icp[2] = {nullptr, nullptr};   // first / after-last Gauss-Newton launch of the background model
     // "passTimings": GPU milliseconds of the surfel passes of the last frame, pass by pass (mf_get_pass_timings; labels in maskfusion_amd.h) -- an
     // event pair around each, created on first use; what bench.py's configs[4] line builds its per-pass roofline rows from IN THE TIMED RUN
-    bool pass_timings_on = false;
     hipEvent_t ev_pass[MF_N_PASSES][2] = {};
     bool pass_recorded[MF_N_PASSES] = {};
     float pass_ms[MF_N_PASSES] = {};
@@ -498,7 +521,7 @@ static int create_model(mf_ctx* c, int id, float confThr, bool allowFillIn, int 
         t.rect = m->d_track_rect;
         m->track_host = t;
     }
-    hipLaunchKernelGGL(k_pose_identity, dim3(1), dim3(64), 0, c->stream, m->d_pose, c->weight_literal ? 1 : 0);
+    hipLaunchKernelGGL(k_pose_identity, dim3(1), dim3(64), 0, c->stream, m->d_pose, c->sw.weight_literal ? 1 : 0);
     hipLaunchKernelGGL(k_frame_init, dim3(1), dim3(64), 0, c->stream, m->d_frame, c->host_tick);
     if (hipHostMalloc((void**)&m->h_pose, sizeof(PoseDev)) != hipSuccess || hipHostMalloc((void**)&m->h_frame, sizeof(FrameDev)) != hipSuccess ||
         hipHostMalloc((void**)&m->h_count, sizeof(int)) != hipSuccess || hipHostMalloc((void**)&m->h_append, sizeof(unsigned long long)) != hipSuccess)
@@ -508,7 +531,7 @@ static int create_model(mf_ctx* c, int id, float confThr, bool allowFillIn, int 
     for (int k = 0; k < 9; ++k) m->h_pose->R[k] = m->h_pose->Ri[k] = (k % 4 == 0) ? 1.f : 0.f;
     m->h_pose->alive = 1;
     m->h_pose->fusionWeight = 1.f;                         // pose == lastPose: computeFusionWeight(1) = 1 before the first tracking step
-    m->h_pose->weightLiteral = c->weight_literal ? 1 : 0;
+    m->h_pose->weightLiteral = c->sw.weight_literal ? 1 : 0;
     memset(m->h_frame, 0, sizeof(FrameDev));
     m->h_frame->tick = c->host_tick;
     *m->h_count = 0;
@@ -726,7 +749,7 @@ extern "C" int mf_preallocate_models(mf_ctx* c, uint32_t count) {
     if (!c) return MF_EINVAL;
     for (uint32_t i = 0; i < count; ++i) {
         std::unique_ptr<ModelState> m;
-        int rc = create_model(c, -1, c->cfg.conf_object, false, surfel_capacity(c->cfg.num_osurfels), m, c->batch_objects);
+        int rc = create_model(c, -1, c->cfg.conf_object, false, surfel_capacity(c->cfg.num_osurfels), m, c->sw.batch_objects);
         if (rc != MF_OK) return rc;
         c->pool.push_back(std::move(m));
     }
@@ -1065,208 +1088,7 @@ extern "C" int mf_download_map(mf_ctx* c, int32_t model, float* out, uint32_t ma
 // ------------------------------------------------------------------------------------------------
 // parameters
 // ------------------------------------------------------------------------------------------------
-struct ParamRef { const char* key; int kind; size_t off; };  // kind 0 float, 1 int
-static const ParamRef kParams[] = {
-    {"depthCutoff", 0, offsetof(mf_config, depth_cutoff)},
-    {"icpWeight", 0, offsetof(mf_config, icp_weight)},
-    {"outlierCoefficient", 0, offsetof(mf_config, outlier_coefficient)},
-    {"maxDepthProcessed", 0, offsetof(mf_config, max_depth_processed)},
-    {"fastOdom", 1, offsetof(mf_config, fast_odom)},
-    {"so3", 1, offsetof(mf_config, so3)},
-    {"rgbOnly", 1, offsetof(mf_config, rgb_only)},
-    {"pyramid", 1, offsetof(mf_config, pyramid)},
-    {"timeDelta", 1, offsetof(mf_config, time_delta)},
-    {"enableMultipleModels", 1, offsetof(mf_config, enable_multiple_models)},
-    {"trackAllModels", 1, offsetof(mf_config, track_all_models)},
-    {"modelSpawnOffset", 1, offsetof(mf_config, model_spawn_offset)},
-};
-struct SegRef { const char* key; int kind; size_t off; };  // kind 0 float, 1 int
-static const SegRef kSegParams[] = {
-    {"mfThreshold", 0, offsetof(SegParams, threshold)},
-    {"mfWeightDistance", 0, offsetof(SegParams, weightDistance)},
-    {"mfWeightConvexity", 0, offsetof(SegParams, weightConvexity)},
-    {"mfMorphEdgeIterations", 1, offsetof(SegParams, morphEdgeIterations)},
-    {"mfMorphEdgeRadius", 1, offsetof(SegParams, morphEdgeRadius)},
-    {"mfMorphMaskIterations", 1, offsetof(SegParams, morphMaskIterations)},
-    {"mfMorphMaskRadius", 1, offsetof(SegParams, morphMaskRadius)},
-    {"newModelMinRelativeSize", 0, offsetof(SegParams, minRelSizeNew)},
-    {"newModelMaxRelativeSize", 0, offsetof(SegParams, maxRelSizeNew)},
-};
-
-extern "C" int mf_set_param(mf_ctx* c, const char* key, double value) {
-    settle(c);
-    if (!c || !key) return MF_EINVAL;
-    if (!strcmp(key, "deferPredict")) { c->defer_predict = value != 0; return MF_OK; }   // 0: every prediction at the end of its own frame
-    if (!strcmp(key, "fusedBinFilter")) { c->fused_bin_filter = value != 0; return MF_OK; }   // 0: k_splat_bin and k_bilateral as two launches in the fused head
-    if (!strcmp(key, "fusedFramePyramids")) { c->fused_frame_pyramids = value != 0; return MF_OK; }   // 0: k_frame_pyramid and k_model_pyramid as two launches
-    if (!strcmp(key, "tilePyramid")) { c->tile_pyramid = value != 0; return MF_OK; }   // 0: the model-side pyramid as a launch of its own in the fused head
-    if (!strcmp(key, "fusedTilePyramid")) { c->fused_tile_pyramid = value != 0; return MF_OK; }   // 0: the frame pyramid behind the tile pass, not beside it
-    if (!strcmp(key, "hostProfileReset")) { for (double& v : c->host_us) v = 0; c->host_calls = 0; return MF_OK; }
-    if (!strcmp(key, "timings")) { c->timings_on = value != 0; return MF_OK; }
-    if (!strcmp(key, "passTimings")) {
-        c->pass_timings_on = value != 0;
-        for (int q = 0; q < MF_N_PASSES; ++q) { c->pass_recorded[q] = false; c->pass_ms[q] = 0.f; }
-        return MF_OK;
-    }
-    if (!strcmp(key, "icpProfile")) { c->icp_prof_on = value != 0; return MF_OK; }
-    if (!strcmp(key, "hostInputAsync")) {   // 0: mf_process_frame blocks until the frame is fused (rounds 1-3); 1: returns when it is enqueued
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipStreamSynchronize(c->stream_in) != hipSuccess) return MF_EHIP;
-        c->host_async = value != 0; return MF_OK;
-    }
-    if (!strcmp(key, "hostLockstep")) { c->host_lockstep = value != 0; return MF_OK; }
-    if (!strcmp(key, "hostWaitUpload")) { c->host_wait_upload = value != 0; return MF_OK; }
-    if (!strcmp(key, "splatProfile")) {   // per-tile shader-clock stamps of k_splat_tile (tools/splat_prof.py); debug tap "splat_prof"
-        if (value != 0 && !c->d_splat_prof) {
-            if (hipMalloc(&c->d_splat_prof, splat_tiles_scratch_ints(c->W, c->H) * 8 * sizeof(unsigned long long)) != hipSuccess) return MF_ENOMEM;
-        }
-        c->splat_prof_on = value != 0;
-        return MF_OK;
-    }
-    if (!strcmp(key, "gpuLabels")) { c->gpu_labels = value != 0; return MF_OK; }   // 0: host label stage (specification)
-    if (!strcmp(key, "splatTiles")) { c->splat_tiles = value != 0; return MF_OK; }
-    if (!strcmp(key, "splatTileEntries")) {   // test knob: shrink the tile lists (never beyond what was allocated) to force the overflow path
-        const long long v = (long long)value;
-        if (v < 1 || v > c->tile_entries_alloc) return MF_EINVAL;
-        c->tile_entries_cap = (int)v;
-        return MF_OK;
-    }
-    if (!strcmp(key, "batchTracking")) { c->batch_tracking = value != 0; return MF_OK; }
-    if (!strcmp(key, "frameToFrameRGB")) { c->ftf_rgb = value != 0; return MF_OK; }         // MaskFusion::setFrameToFrameRGB (Core/MaskFusion.cpp:910)
-    if (!strcmp(key, "batchSolveInPixelPass")) { c->batch_solve_fused = value != 0; return MF_OK; }   // 0: k_icp_batch_solve + k_icp_batch_pixels per iteration (the executable specification)
-    if (!strcmp(key, "fusedPreprocessLaunch")) { c->fused_preprocess = value != 0; return MF_OK; }   // 0: k_bilateral and k_model_pyramid as two launches
-    if (!strcmp(key, "objectStream")) { c->object_stream = value != 0; return MF_OK; }   // 0: the object models' batched passes on the main stream, behind the background's
-    if (!strcmp(key, "batchObjectPasses")) { c->batch_objects = value != 0; return MF_OK; }  // 0: the object models' surfel passes model by model
-    if (!strcmp(key, "objectBoundingBoxLimit")) { c->bbox_limit = value != 0; return MF_OK; }   // 0: a headless upstream that never renders (bb_max_z = FLT_MAX)
-    if (!strcmp(key, "literalFusionWeight")) {
-        c->weight_literal = value != 0;
-        for (auto& m : c->models) hipLaunchKernelGGL(k_set_weight_literal, dim3(1), dim3(64), 0, c->stream, m->d_pose, c->weight_literal ? 1 : 0, m->h_pose);
-        for (auto& m : c->pool) hipLaunchKernelGGL(k_set_weight_literal, dim3(1), dim3(64), 0, c->stream, m->d_pose, c->weight_literal ? 1 : 0, m->h_pose);
-        return check_launch(c);
-    }
-    if (!strcmp(key, "objectSmallGrids")) { c->object_small_grids = value != 0; return MF_OK; }
-    if (!strcmp(key, "objectScatterSplat")) { c->object_scatter_splat = value != 0; return MF_OK; }
-    if (!strcmp(key, "globalTiles")) { c->global_tiles = value != 0; return MF_OK; }
-    if (!strcmp(key, "cullRuns")) { c->cull_runs = value != 0; c->vis_tag.model = nullptr; return MF_OK; }
-    if (!strcmp(key, "densifyEvery")) { c->densify_every = (int)value; return MF_OK; }
-    if (!strcmp(key, "slabCulling")) { c->slab_culling = value != 0; return MF_OK; }
-    if (!strcmp(key, "bigMapElements")) { c->big_map_elements = (int)value; c->vis_tag.model = nullptr; return MF_OK; }
-    if (!strcmp(key, "fusedRgbPyramid")) { c->fused_rgb_pyramid = value != 0; return MF_OK; }
-    if (!strcmp(key, "inPlaceElements")) { c->in_place_elements = (int)value; return MF_OK; }
-    if (!strcmp(key, "rebuildRunTable")) {   // tooling: the background's run table from scratch (what an upload / Model::initialise does)
-        // fixed runs over slots [0, count) describe a DENSE buffer only: a sparse one is compacted first, and the host's bounds start afresh
-        ModelState& bg = *c->models[0];
-        require_dense(c, bg);
-        MF_HIP(c, hipStreamSynchronize(c->stream));   // (the exact count: the pinned mirror as of the last clean pass / the compaction)
-        launch_run_table(bg.surf[bg.cur], bg.d_frame, c->stream);
-        bg.fresh_table(bg.cur, (long)*bg.h_count);
-        c->vis_tag.model = nullptr;
-        return check_launch(c);
-    }
-    if (!strcmp(key, "cleanTapGroup")) {   // 1: the serial walk
-        if (value != 1 && value != 3 && value != 9) { c->err = "cleanTapGroup is 1, 3 or 9"; return MF_EINVAL; }
-        c->clean_tap_group = (int)value; return MF_OK;
-    }
-    if (!strcmp(key, "maskFreeClean")) { c->mask_free_clean = value != 0; return MF_OK; }   // 0: the planes travel in every context
-    if (!strcmp(key, "cleanTap16")) { c->clean_tap16 = value != 0; return MF_OK; }   // 0: the 32-byte record in every clean pass
-    if (!strcmp(key, "fuseLanes")) {
-        if ((int)value != 1 && (int)value != 4) { c->err = "fuseLanes: 1 or 4"; return MF_EINVAL; }
-        c->fuse_lanes = (int)value;
-        return MF_OK;
-    }
-    if (!strcmp(key, "cleanLiteralWindow")) { c->clean_literal = value != 0; return MF_OK; }   // 0: the exact-arithmetic 4 x 4 window
-    if (!strcmp(key, "earlyBackgroundFusion")) { c->early_bg_fusion = value != 0; return MF_OK; }
-    if (!strcmp(key, "modelApiPackedIndex")) { c->model_api_packed = value != 0; return MF_OK; }   // 0: scatter + resolve form (specification)
-    if (!strcmp(key, "tileHeight")) { c->splat_tune.tile_h = (int)value; return MF_OK; }   // A/B: 16 x 24 (default), 16 x 20 or 16 x 16 pixel tiles
-    if (!strcmp(key, "tileThreads")) { c->splat_tune.tile_threads = (int)value; return MF_OK; }   // A/B: threads per tile workgroup of the tile passes
-    if (!strcmp(key, "spriteLanes")) { c->splat_tune.sprite_lanes = (int)value; return MF_OK; }   // A/B: lanes per sprite in the tile z-test (default 4)
-    if (!strcmp(key, "confidenceThreshold")) { c->cfg.conf_global = (float)value; c->models[0]->confThr = (float)value; return MF_OK; }
-    for (const ParamRef& p : kParams)
-        if (!strcmp(key, p.key)) {
-            char* base = reinterpret_cast<char*>(&c->cfg);
-            if (p.kind == 0) *reinterpret_cast<float*>(base + p.off) = (float)value;
-            else *reinterpret_cast<int32_t*>(base + p.off) = (int32_t)value;
-            return MF_OK;
-        }
-    for (const SegRef& p : kSegParams)
-        if (!strcmp(key, p.key)) {
-            char* base = reinterpret_cast<char*>(&c->seg);
-            if (p.kind == 0) *reinterpret_cast<float*>(base + p.off) = (float)value;
-            else *reinterpret_cast<int*>(base + p.off) = (int)value;
-            return MF_OK;
-        }
-    c->err = std::string("unknown parameter: ") + key;
-    return MF_EINVAL;
-}
-extern "C" int mf_get_param(mf_ctx* c, const char* key, double* value) {
-    settle(c);
-    if (!c || !key || !value) return MF_EINVAL;
-    if (!strcmp(key, "confidenceThreshold")) { *value = c->models[0]->confThr; return MF_OK; }
-    if (!strcmp(key, "splatTileEntries")) { *value = c->tile_entries_cap; return MF_OK; }
-    if (!strcmp(key, "cullRuns")) { *value = c->cull_runs ? 1 : 0; return MF_OK; }
-    if (!strcmp(key, "cleanTap16")) { *value = c->clean_tap16 ? 1 : 0; return MF_OK; }
-    if (!strcmp(key, "cleanTapGroup")) { *value = c->clean_tap_group; return MF_OK; }
-    if (!strcmp(key, "maskFreeClean")) { *value = c->mask_free_clean ? 1 : 0; return MF_OK; }
-    if (!strcmp(key, "fuseLanes")) { *value = c->fuse_lanes; return MF_OK; }
-    if (!strcmp(key, "indexPackedTexelBytes")) { *value = c->iclean_is_tap16 ? 16 : 32; return MF_OK; }   // the form "index_packed" holds
-    if (!strcmp(key, "deferPredict")) { *value = c->defer_predict ? 1 : 0; return MF_OK; }
-    if (!strcmp(key, "fusedBinFilter")) { *value = c->fused_bin_filter ? 1 : 0; return MF_OK; }
-    if (!strcmp(key, "fusedFramePyramids")) { *value = c->fused_frame_pyramids ? 1 : 0; return MF_OK; }
-    if (!strcmp(key, "tilePyramid")) { *value = c->tile_pyramid ? 1 : 0; return MF_OK; }
-    if (!strcmp(key, "fusedTilePyramid")) { *value = c->fused_tile_pyramid ? 1 : 0; return MF_OK; }
-    if (!strcmp(key, "pyramidFixupFrames")) {   // fused heads whose fill-in decision was 1: the fix-up launch rebuilt the model-side pyramid there
-        int v = 0;
-        MF_HIP(c, hipStreamSynchronize(c->stream));
-        MF_HIP(c, hipMemcpy(&v, c->d_pyramid_fixups, sizeof(int), hipMemcpyDeviceToHost));
-        *value = v;
-        return MF_OK;
-    }
-    if (!strcmp(key, "deferredFrames")) { *value = (double)c->deferred_frames; return MF_OK; }
-    if (!strcmp(key, "fusedHeadFrames")) { *value = (double)c->fused_head_frames; return MF_OK; }
-    if (!strcmp(key, "densifyCount")) { *value = (float)c->densify_count; return MF_OK; }
-    if (!strcmp(key, "unstampedRuns")) {   // test tap: live runs of the background's table that carry "holds a time stamp <= 0" (k_cull_clean lists them)
-        MF_HIP(c, hipStreamSynchronize(c->stream));
-        ModelState& bg = *c->models[0];
-        FrameDev f; MF_HIP(c, hipMemcpy(&f, bg.d_frame, sizeof(FrameDev), hipMemcpyDeviceToHost));
-        const size_t cap_runs = run_table_runs((long)bg.cap, (long)c->P);
-        const size_t runs = bg.table_valid ? std::min((size_t)std::max(f.runs, 0), cap_runs) : 0;
-        std::vector<int4> box(kBoxStride * runs);
-        if (runs) MF_HIP(c, hipMemcpy(box.data(), bg.surf[bg.cur].box, box.size() * sizeof(int4), hipMemcpyDeviceToHost));
-        int v = 0;
-        for (size_t r = 0; r < runs; ++r) v += (box[kBoxStride * r + 2].x > 0 && box[kBoxStride * r + 2].z != 0) ? 1 : 0;
-        *value = v;
-        return MF_OK;
-    }
-    if (!strcmp(key, "visibleRuns") || !strcmp(key, "backgroundRuns") || !strcmp(key, "cleanRuns")) {   // test taps: size of the last visibility list / of the
-        MF_HIP(c, hipStreamSynchronize(c->stream));                                                      // background's run table / of the last clean list
-        int v = 0;
-        if (!strcmp(key, "visibleRuns")) MF_HIP(c, hipMemcpy(&v, c->d_vis_count, sizeof(int), hipMemcpyDeviceToHost));
-        else if (!strcmp(key, "cleanRuns")) MF_HIP(c, hipMemcpy(&v, c->d_clean_count, sizeof(int), hipMemcpyDeviceToHost));
-        else { FrameDev f; MF_HIP(c, hipMemcpy(&f, c->models[0]->d_frame, sizeof(FrameDev), hipMemcpyDeviceToHost)); v = f.runs; }
-        *value = v;
-        return MF_OK;
-    }
-    // mean host microseconds per mf_process_frame call since the context was created: staging copy | upload enqueue | frame enqueue | whole call
-    if (!strcmp(key, "hostStageUs")) { *value = c->host_calls ? c->host_us[0] / c->host_calls : 0; return MF_OK; }
-    if (!strcmp(key, "hostUploadUs")) { *value = c->host_calls ? c->host_us[1] / c->host_calls : 0; return MF_OK; }
-    if (!strcmp(key, "hostEnqueueUs")) { *value = c->host_calls ? c->host_us[2] / c->host_calls : 0; return MF_OK; }
-    if (!strcmp(key, "hostCallUs")) { *value = c->host_calls ? c->host_us[3] / c->host_calls : 0; return MF_OK; }
-    if (!strcmp(key, "hostWaitUs")) { *value = c->host_calls ? c->host_us[4] / c->host_calls : 0; return MF_OK; }
-    if (!strcmp(key, "frameToFrameRGB")) { *value = c->ftf_rgb ? 1 : 0; return MF_OK; }
-    if (!strcmp(key, "objectBoundingBoxLimit")) { *value = c->bbox_limit ? 1 : 0; return MF_OK; }
-    for (const ParamRef& p : kParams)
-        if (!strcmp(key, p.key)) {
-            const char* base = reinterpret_cast<const char*>(&c->cfg);
-            *value = p.kind == 0 ? (double)*reinterpret_cast<const float*>(base + p.off) : (double)*reinterpret_cast<const int32_t*>(base + p.off);
-            return MF_OK;
-        }
-    for (const SegRef& p : kSegParams)
-        if (!strcmp(key, p.key)) {
-            const char* base = reinterpret_cast<const char*>(&c->seg);
-            *value = p.kind == 0 ? (double)*reinterpret_cast<const float*>(base + p.off) : (double)*reinterpret_cast<const int*>(base + p.off);
-            return MF_OK;
-        }
-    return MF_EINVAL;
-}
+#include "mf_params.inl"     // the table of the keys, mf_set_param, mf_get_param
 
 extern "C" int mf_get_timings(mf_ctx* c, float* ms) {
     settle(c);

@@ -4,20 +4,20 @@
 // four files by subject; mf_context.hip includes them in this order)
 
 static void mark(mf_ctx* c, int i, hipStream_t s = nullptr) {
-    if (c->timings_on) (void)hipEventRecord(c->ev[i], s ? s : c->stream);
+    if (c->sw.timings_on) (void)hipEventRecord(c->ev[i], s ? s : c->stream);
 }
 // "passTimings": an event pair around the launches of one surfel pass (labels: maskfusion_amd.h, MF_PASS_*); a pass that runs several times in a
 // frame (object models handled one by one) keeps its last run
 struct PassTimer {
     mf_ctx* c; int id; hipStream_t s;
     PassTimer(mf_ctx* c_, int id_, hipStream_t s_ = nullptr) : c(c_), id(id_), s(s_ ? s_ : c_->stream) {
-        if (!c->pass_timings_on || id < 0) return;
+        if (!c->sw.pass_timings_on || id < 0) return;
         for (int q = 0; q < 2; ++q)
             if (!c->ev_pass[id][q] && hipEventCreate(&c->ev_pass[id][q]) != hipSuccess) { (void)hipGetLastError(); c->ev_pass[id][q] = nullptr; }
         if (c->ev_pass[id][0]) (void)hipEventRecord(c->ev_pass[id][0], s);
     }
     ~PassTimer() {
-        if (!c->pass_timings_on || id < 0 || !c->ev_pass[id][0] || !c->ev_pass[id][1]) return;
+        if (!c->sw.pass_timings_on || id < 0 || !c->ev_pass[id][0] || !c->ev_pass[id][1]) return;
         (void)hipEventRecord(c->ev_pass[id][1], s);
         c->pass_recorded[id] = true;
     }
@@ -31,7 +31,7 @@ struct ObjStreamWindow {
     mf_ctx* c; bool open = false;
     explicit ObjStreamWindow(mf_ctx* c_) : c(c_) {}
     void begin() {
-        if (open || !c->object_stream || !c->stream_obj || c->timings_on) return;   // (the stage timings bracket the main stream: one stream while they are on)
+        if (open || !c->sw.object_stream || !c->stream_obj || c->sw.timings_on) return;   // (the stage timings bracket the main stream: one stream while they are on)
         open = true;
         c->obj_s = c->stream_obj;
         c->obj_dep_main = false;
@@ -89,7 +89,7 @@ static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, floa
     if (rgb) {
         // initRGBModel + initRGB (Model.cpp:395-406; Q1: both depth pyramids come from the vertex map initICPModel was given)
         launch_rgbd_last_l0(m.d_predV, m.allowFillIn ? fillDepth : nullptr, m.d_predGray, m.d_fillGray, m.d_frame, c->d_lastDepth[0],
-                            c->d_lastImage[0], W * H, s, (c->ftf_rgb && m.allowFillIn) ? 1 : 0);
+                            c->d_lastImage[0], W * H, s, (c->sw.ftf_rgb && m.allowFillIn) ? 1 : 0);
         for (int i = 0; i + 1 < 3; ++i) {   // one level of the depth pyramid and of the intensity pyramid per launch (independent of each other)
             SmallJobs jobs;
             jobs.n = 2;
@@ -100,7 +100,7 @@ static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, floa
     }
     const int iters[3] = {g.fast_odom ? 3 : 10, g.pyramid ? 5 : 0, g.pyramid ? 4 : 0};  // RGBDOdometry.cpp:327-329
     const float sobelScale = 1.0f / 8.0f;                                                // 1 / 2^sobelSize, :31-32
-    const bool timed = c->timings_on && &m == c->models[0].get();
+    const bool timed = c->sw.timings_on && &m == c->models[0].get();
     if (timed) { (void)hipEventRecord(c->ev_icp[0], s); c->tracked_once = true; c->icp_mid_recorded = false; }
     int k = 0, nb_prev = 0, prev_level = -1;
     // every launch of the loop and its finalize
@@ -120,7 +120,7 @@ static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, floa
             l.state_in = &m.d_gn[k & 1]; l.state_out = &m.d_gn[(k + 1) & 1];
             l.log_out = (k > 0) ? m.d_icp_log + 32 * (k - 1) : nullptr;
             l.trace = rgb ? nullptr : m.d_gn_trace; l.it = k;
-            l.prof_out = (c->icp_prof_on && m.id == 0 && !rgb) ? c->d_icp_prof + 16 * k : nullptr;
+            l.prof_out = (c->sw.icp_prof_on && m.id == 0 && !rgb) ? c->d_icp_prof + 16 * k : nullptr;
             l.pose_in = (k == 0) ? m.d_pose : nullptr;
             l.so3_in = (k == 0) ? so3_seed : nullptr;
             if (!rgb) {
@@ -186,20 +186,20 @@ static void enqueue_track_batch(mf_ctx* c, const std::vector<ModelState*>& ms, c
                                   c->d_so3, c->d_so3_scratch, s);
     const So3Result* so3_seed = so3 ? c->d_so3 : nullptr;
     const int iters[3] = {g.fast_odom ? 3 : 10, g.pyramid ? 5 : 0, g.pyramid ? 4 : 0};
-    const bool timed = c->timings_on && ms[0] == c->models[0].get();
+    const bool timed = c->sw.timings_on && ms[0] == c->models[0].get();
     if (timed) { (void)hipEventRecord(c->ev_icp[0], s); c->tracked_once = true; c->icp_mid_recorded = false; }
     // slab culling of the pixel pass (mf_odometry.hip: k_icp_batch_pixels): the depth range of every row of the frame's vertex maps, once per frame
-    if (c->slab_culling) launch_row_zrange(c->d_vmap[set], W, H, c->d_row_z, s);
+    if (c->sw.slab_culling) launch_row_zrange(c->d_vmap[set], W, H, c->d_row_z, s);
     const int row_base[3] = {0, H, H + (H >> 1)};
     int it = 0, nb_prev = 0;
     for (int lvl = 2; lvl >= 0; --lvl) {
         const float div = (float)(1 << lvl);
         for (int j = 0; j < iters[lvl]; ++j) {
             // one launch per iteration ("batchSolveInPixelPass", default): the pixel pass finishes the previous iteration in its prologue; else two
-            if (!c->batch_solve_fused) launch_icp_batch_solve(b, it, nb_prev, it == 0 ? so3_seed : nullptr, s);
+            if (!c->sw.batch_solve_fused) launch_icp_batch_solve(b, it, nb_prev, it == 0 ? so3_seed : nullptr, s);
             launch_icp_batch_pixels(b, it, lvl, c->d_vmap[set][lvl], c->d_nmap[set][lvl], W >> lvl, H >> lvl,
                                     Intr{g.fx / div, g.fy / div, g.cx / div, g.cy / div}, 0.10f, sinf(20.f * 3.14159254f / 180.f), s,
-                                    c->slab_culling ? c->d_row_z + row_base[lvl] : nullptr, c->batch_solve_fused, nb_prev, it == 0 ? so3_seed : nullptr);
+                                    c->sw.slab_culling ? c->d_row_z + row_base[lvl] : nullptr, c->sw.batch_solve_fused, nb_prev, it == 0 ? so3_seed : nullptr);
             nb_prev = icp_batch_blocks(W >> lvl, H >> lvl, b.n);
             ++it;
         }
@@ -213,7 +213,7 @@ static void enqueue_track_batch(mf_ctx* c, const std::vector<ModelState*>& ms, c
 // "objectSmallGrids" -- twice what its last known surfel count needs (the count lives on the device; *h_count is its pinned mirror as of the
 // last clean pass: a stale value only costs a few more trips round the grid-stride loop, never a result)
 static int surfel_blocks(const mf_ctx* c, const ModelState& m) {
-    if (!c->object_small_grids || m.id == 0) return kSurfelGridBlocks;
+    if (!c->sw.object_small_grids || m.id == 0) return kSurfelGridBlocks;
     const long n = 2L * (long)*m.h_count + 4096;
     const long b = (n + 255) / 256;
     return (int)(b < 32 ? 32 : (b > kSurfelGridBlocks ? kSurfelGridBlocks : b));
@@ -226,7 +226,7 @@ static int surfel_blocks(const mf_ctx* c, const ModelState& m) {
 static const VisList* ensure_vis(mf_ctx* c, ModelState& m, VisList& out) {
     // (a small map is cheaper to stream than to cull: the test is a launch of its own on a chain of launches that are each a few microseconds.
     // The count is the pinned mirror as of the model's last clean pass; which side of the threshold a frame falls on changes no result)
-    if (!c->cull_runs || !m.table_valid || (!m.sparse && *m.h_count < c->big_map_elements)) return nullptr;
+    if (!c->sw.cull_runs || !m.table_valid || (!m.sparse && *m.h_count < c->sw.big_map_elements)) return nullptr;
     const mf_config& g = c->cfg;
     const float max_depth = fmaxf(g.depth_cutoff, g.max_depth_processed);
     out.list = c->d_vis_list; out.count = c->d_vis_count;
@@ -242,10 +242,10 @@ static const VisList* ensure_vis(mf_ctx* c, ModelState& m, VisList& out) {
 }
 
 // which clean form model m gets this frame: the two-launch form (a dense copy) below "bigMapElements", in place on the buffer's runs from there on
-static bool clean_small(const mf_ctx* c, const ModelState& m) { return (long)*m.h_count + (long)c->P / 4 < (long)c->big_map_elements; }
+static bool clean_small(const mf_ctx* c, const ModelState& m) { return (long)*m.h_count + (long)c->P / 4 < (long)c->sw.big_map_elements; }
 // which update form: the copying one (second index scatter riding on it) below "inPlaceElements"; it pairs with the two-launch clean only
 static bool update_copy(const mf_ctx* c, const ModelState& m) {
-    return clean_small(c, m) && (long)*m.h_count + (long)c->P / 4 < (long)c->in_place_elements;
+    return clean_small(c, m) && (long)*m.h_count + (long)c->P / 4 < (long)c->sw.in_place_elements;
 }
 // what a frame can append to a buffer: candidates (data.vert:117 takes every other pixel of every other row) and table entries for them
 static long cand_max(const mf_ctx* c) { return (long)((c->W + 1) / 2) * (long)((c->H + 1) / 2); }
@@ -273,7 +273,7 @@ static void require_dense(mf_ctx* c, ModelState& m) { if (m.sparse) densify(c, m
 static int prepare_in_place(mf_ctx* c, ModelState& m, bool& ok) {
     const long cm = cand_max(c), nr = new_runs_max(c), table = (long)run_table_runs((long)m.cap, (long)c->P);
     ok = true;
-    const bool every = c->densify_every > 0 && m.sparse && (c->frame_no % c->densify_every) == 0;   // ("densifyEvery": tests)
+    const bool every = c->sw.densify_every > 0 && m.sparse && (c->frame_no % c->sw.densify_every) == 0;   // ("densifyEvery": tests)
     // The host's own bounds grow by a frame's worth of CANDIDATES per pass, the buffer by the few that survive.  The device leaves where the buffer
     // really ended behind every pass in pinned memory (append_mirror): bounds from the newest pass that has run are P / 4 per pass still in flight.
     long pub = every ? -1 : m.phys_ub, rub = every ? -1 : m.runs_ub;
@@ -331,19 +331,19 @@ static void after_clean(mf_ctx* c, ModelState& m, bool in_place, int live) {
 // A frame without a mask (mf_process_frame of a single-model context: every byte of c->d_zero_mask is 0) cannot disagree with the background, id 0:
 // with 16-byte taps the resolve pass then leaves the planes depthT / maskT alone and the clean pass reads neither ("maskFreeClean")
 static bool mask_free(const mf_ctx* c, const ModelState& m, const uint8_t* mask, bool tap16) {
-    return c->mask_free_clean && tap16 && mask == c->d_zero_mask && m.id == 0;
+    return c->sw.mask_free_clean && tap16 && mask == c->d_zero_mask && m.id == 0;
 }
 static CleanIn clean_in(mf_ctx* c, ModelState& m, int time_delta, bool packed, const float* depthF, const uint8_t* mask, bool tap16 = false) {
     CleanIn in;
     in.frame = m.d_frame; in.pose = m.d_pose; in.W = c->W; in.H = c->H; in.k = c->K; in.timeDelta = time_delta; in.confThreshold = m.confThr;
     in.outlierCoeff = c->cfg.outlier_coefficient; in.maskID = m.id;
     in.index = c->d_index; in.vc = c->d_ivc; in.ct = c->d_ict; in.packed = packed ? c->d_iclean : nullptr; in.maskT = c->d_maskT;
-    in.tap16 = packed && tap16; in.tapGroup = c->clean_tap_group; in.maskFree = mask_free(c, m, mask, in.tap16);
+    in.tap16 = packed && tap16; in.tapGroup = c->sw.clean_tap_group; in.maskFree = mask_free(c, m, mask, in.tap16);
     in.depthT = in.tap16 && !in.maskFree ? c->d_depthT : nullptr;
     in.depthF = depthF; in.mask = mask; in.cand_op = c->d_cand_op; in.cand_rec = c->d_cand_rec;
     in.flags = c->d_flags; in.newconf = c->d_newconf; in.block_counts = c->d_block_counts; in.host_count = m.h_count;
     in.host_append = append_mirror_fits(c, m) ? m.h_append : nullptr; in.seq = m.clean_seq + 1;     // (after_clean counts the pass)
-    in.transposed = packed; in.literalWindow = c->clean_literal;
+    in.transposed = packed; in.literalWindow = c->sw.clean_literal;
     return in;
 }
 // Model::clean of m in place (m has a run table): the buffer's own surfels run by run, then the frame's candidates appended.  cull: visit only the
@@ -377,7 +377,7 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
     const int blocks = surfel_blocks(c, m);
     const bool timed = m.id == 0;       // "passTimings": the background's passes one by one
     // the pass that feeds clean writes 16-byte taps: resolve and clean are enqueued here, with one tick and one threshold
-    const bool tap16 = c->clean_tap16 && secondIndexPass;
+    const bool tap16 = c->sw.clean_tap16 && secondIndexPass;
     float* const depthT = tap16 ? c->d_depthT : nullptr;
     if (secondIndexPass) c->iclean_is_tap16 = tap16;
     VisList vl;
@@ -395,12 +395,12 @@ static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, co
     {
         PassTimer t(c, timed ? MF_PASS_BG_FUSE_DATA : -1);
         launch_fuse_data(d_rgb, d_depth, depthF, mask, m.id, m.d_frame, m.d_pose, weightMultiplier, fminf(fuseDepthCutoff, m.maxDepth), W, H,
-                         c->K, c->d_index, c->d_ivc, c->d_inr, c->d_cand_op, c->d_cand_rec, c->d_upd_first, c->d_cand_best, s, c->bbox_limit ? 1 : 0, c->fuse_lanes);
+                         c->K, c->d_index, c->d_ivc, c->d_inr, c->d_cand_op, c->d_cand_rec, c->d_upd_first, c->d_cand_best, s, c->sw.bbox_limit ? 1 : 0, c->sw.fuse_lanes);
     }
     if (marks) mark(c, 5);
     // the in-place clean of the background visits only the runs its rules can touch (k_cull_clean); the resolve pass that feeds clean gathers
     // the frame's statistics for that test
-    const bool in_place = form.in_place, cull_clean = in_place && c->cull_runs && secondIndexPass && m.id == 0;
+    const bool in_place = form.in_place, cull_clean = in_place && c->sw.cull_runs && secondIndexPass && m.id == 0;
     int live = src;      // the buffer that holds the updated surfels
     if (form.update_copy) {
         // small map (rounds 1-4's pass): update.vert as a copy src -> dst with the second index scatter (:556) riding on it; clean goes
@@ -454,15 +454,15 @@ static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advanc
                             const SplatPyramidJob* pyramid = nullptr) {
     PassTimer timer(c, m.id == 0 ? MF_PASS_BG_PREDICT : -1);
     m.pred_gray_valid = photometric_on(c);
-    if (c->splat_tiles && !(c->object_scatter_splat && m.id != 0)) {
+    if (c->sw.splat_tiles && !(c->sw.object_scatter_splat && m.id != 0)) {
         const bool gray = photometric_on(c);
         VisList vl;
         const VisList* vis = ensure_vis(c, m, vl);
         if (launch_splat_tiled(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, c->cfg.max_depth_processed, m.confThr,
                                c->cfg.time_delta, c->d_tile_count, c->d_tile_entries, c->tile_entries_cap, c->d_splat_rec0, c->d_splat_rec1,
                                c->d_splat_bbox, m.d_predV, m.d_predN, m.d_predImage, m.d_predTime, c->cur_rgb,
-                               gray ? m.d_predGray : nullptr, gray ? m.d_fillGray : nullptr, c->stream, advance, c->ftf_rgb ? 1 : 0,
-                               (c->splat_prof_on && m.id == 0) ? c->d_splat_prof : nullptr, c->splat_tune, vis, filter, pyramid) == 0)
+                               gray ? m.d_predGray : nullptr, gray ? m.d_fillGray : nullptr, c->stream, advance, c->sw.ftf_rgb ? 1 : 0,
+                               (c->sw.splat_prof_on && m.id == 0) ? c->d_splat_prof : nullptr, c->sw.splat_tune, vis, filter, pyramid) == 0)
             return;
     }
     if (filter) launch_bilateral(filter->depth, filter->out, c->W, c->H, c->stream);   // (not reached: a deferred prediction is a tiled one)
@@ -470,7 +470,7 @@ static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advanc
                          c->cfg.time_delta, c->d_keys, c->stream, surfel_blocks(c, m));
     const bool gray = photometric_on(c) ;
     launch_splat_resolve(m.surf[m.cur], m.d_pose, c->d_keys, c->W, c->H, c->K, m.d_predV, m.d_predN, m.d_predImage, m.d_predTime,
-                         m.d_frame, c->cur_rgb, gray ? m.d_predGray : nullptr, gray ? m.d_fillGray : nullptr, c->stream, c->ftf_rgb ? 1 : 0);
+                         m.d_frame, c->cur_rgb, gray ? m.d_predGray : nullptr, gray ? m.d_fillGray : nullptr, c->stream, c->sw.ftf_rgb ? 1 : 0);
     if (advance) launch_frame_advance(m.d_frame, c->W, c->H, advance->host_mirror, m.d_pose, advance->bg_pose, advance->log_slot, c->stream);
 }
 
@@ -479,8 +479,8 @@ static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advanc
 // context that tracks with the geometric term alone -- the tile pass then reads no caller-owned image -- through the tiled form, with no timings on
 // (the stage and pass timings bracket the prediction where it is enqueued today).  The host-side bookkeeping of the frame stays in call t.
 static bool defer_eligible(const mf_ctx* c) {
-    return c->defer_predict && c->cfg.enable_multiple_models == 0 && c->models.size() == 1 && !photometric_on(c) && c->cfg.so3 == 0 && c->splat_tiles &&
-           splat_tiled_applies(c->W, c->H, c->splat_tune) && !c->timings_on && !c->pass_timings_on && !c->splat_prof_on;
+    return c->sw.defer_predict && c->cfg.enable_multiple_models == 0 && c->models.size() == 1 && !photometric_on(c) && c->cfg.so3 == 0 && c->sw.splat_tiles &&
+           splat_tiled_applies(c->W, c->H, c->sw.splat_tune) && !c->sw.timings_on && !c->sw.pass_timings_on && !c->sw.splat_prof_on;
 }
 // Enqueues a pending prediction exactly as the end of its frame would have, and clears the record.  The first statement of every entry point that
 // takes a context (but the two process-frame entries, which may draw it in their fused head, and mf_destroy, which drops it): whatever reads or
@@ -527,11 +527,11 @@ static int make_obj_batch(mf_ctx* c, const std::vector<ModelState*>& ms, const s
     MF_HIP(c, hipEventRecord(c->ev_obj_args[slot], s));
     b.m = c->d_obj_args[slot]; b.n = (int)ms.size();
     b.W = c->W; b.H = c->H; b.k = c->K; b.maxDepthProcessed = g.max_depth_processed; b.globalMaxDepth = g.depth_cutoff; b.timeDelta = g.time_delta;
-    b.outlierCoeff = g.outlier_coefficient; b.cleanLiteral = c->clean_literal ? 1 : 0; b.bboxLimit = c->bbox_limit ? 1 : 0; b.cleanSmall = 0; b.updateCopy = 0;
+    b.outlierCoeff = g.outlier_coefficient; b.cleanLiteral = c->sw.clean_literal ? 1 : 0; b.bboxLimit = c->sw.bbox_limit ? 1 : 0; b.cleanSmall = 0; b.updateCopy = 0;
     b.denseSprites = 0;
-    for (ModelState* m : ms) if ((long)*m->h_count >= (long)c->in_place_elements) b.denseSprites = 1;
+    for (ModelState* m : ms) if ((long)*m->h_count >= (long)c->sw.in_place_elements) b.denseSprites = 1;
     b.rgb = d_rgb; b.depthRaw = d_depth; b.depthF = depthF; b.mask = mask; b.maskT = s == c->stream ? c->d_maskT : c->d_maskT_obj;
-    b.depthT = !c->clean_tap16 ? nullptr : s == c->stream ? c->d_depthT : c->d_depthT_obj; b.fuseLanes = c->fuse_lanes; b.cleanTapGroup = c->clean_tap_group; b.bg_pose = c->models[0]->d_pose; b.global_keys = c->d_keys;
+    b.depthT = !c->sw.clean_tap16 ? nullptr : s == c->stream ? c->d_depthT : c->d_depthT_obj; b.fuseLanes = c->sw.fuse_lanes; b.cleanTapGroup = c->sw.clean_tap_group; b.bg_pose = c->models[0]->d_pose; b.global_keys = c->d_keys;
     return MF_OK;
 }
 // every object model of the list, with its position in the list (the GlobalProjection payload)
@@ -539,7 +539,7 @@ static void object_models(mf_ctx* c, std::vector<ModelState*>& ms, std::vector<i
     ms.clear(); orders.clear();
     for (size_t i = 1; i < c->models.size(); ++i) { ms.push_back(c->models[i].get()); orders.push_back((int)i); }
 }
-static bool batch_objects_now(const mf_ctx* c) { return c->batch_objects && c->models.size() >= 3 && c->models.size() <= 65; }
+static bool batch_objects_now(const mf_ctx* c) { return c->sw.batch_objects && c->models.size() >= 3 && c->models.size() <= 65; }
 
 static int check_launch(mf_ctx* c) {
     hipError_t e = hipGetLastError();
@@ -574,7 +574,7 @@ static void tracking_plan(mf_ctx* c, size_t first, bool track_all, TrackingPlan&
         if ((!m.isStatic || track_all) && trackable) p.tracked.push_back(&m);   // jump rule of :268-272 in the finalize step
         else p.follow.push_back(&m);
     }
-    p.batch = !photometric_on(c) && p.tracked.size() >= 2 && (int)p.tracked.size() <= kMaxTrackBatch && c->batch_tracking;
+    p.batch = !photometric_on(c) && p.tracked.size() >= 2 && (int)p.tracked.size() <= kMaxTrackBatch && c->sw.batch_tracking;
 }
 
 // filterDepth (Core/MaskFusion.cpp:217) + Model::generateCUDATextures (Model.cpp:350-389) + the frame's intensity pyramid and
@@ -611,7 +611,7 @@ static int enqueue_preprocess(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
         // imageBGRToIntensity + pyrDownUcharGauss of the frame (initRGB / initFirstRGB) and, for the photometric term,
         // computeDerivativeImages (RGBDOdometry.cpp:245-250)
         const float min_scale[3] = {rgb_min_scale(0), rgb_min_scale(1), rgb_min_scale(2)};
-        if (c->fused_rgb_pyramid && launch_rgb_pyramid(d_rgb, W, H, c->d_gray[set], c->d_dIdx, c->d_dIdy, c->d_rgb_gate, min_scale, photometric_on(c), sp)) {
+        if (c->sw.fused_rgb_pyramid && launch_rgb_pyramid(d_rgb, W, H, c->d_gray[set], c->d_dIdx, c->d_dIdy, c->d_rgb_gate, min_scale, photometric_on(c), sp)) {
             c->gray_frame[set] = k;   // one launch: the three intensity levels and (photometric term) their derivative / gate images
             if (photometric_on(c)) c->deriv_frame = k;
         } else {
@@ -654,8 +654,8 @@ static void enqueue_fused_head(mf_ctx* c, const uint8_t* d_rgb, const float* d_d
     c->pending.m = nullptr;
     const int set = (int)(k & 1);
     float* depthF = c->d_depthF[k % 3];
-    const SplatFilterJob job{d_depth, depthF, c->fused_bin_filter ? 1 : 0};
-    const bool tile_pyr = c->tile_pyramid, tile_frame = tile_pyr && c->fused_tile_pyramid;
+    const SplatFilterJob job{d_depth, depthF, c->sw.fused_bin_filter ? 1 : 0};
+    const bool tile_pyr = c->sw.tile_pyramid, tile_frame = tile_pyr && c->sw.fused_tile_pyramid;
     SplatPyramidJob pj;
     for (int i = 0; i < 3; ++i) { pj.vm[i] = m->d_vmap_g[i]; pj.nm[i] = m->d_nmap_g[i]; pj.frame_vmap[i] = c->d_vmap[set][i]; pj.frame_nmap[i] = c->d_nmap[set][i]; }
     pj.frame_depth = tile_frame ? depthF : nullptr; pj.frame_cutoff = c->cfg.depth_cutoff;
@@ -665,7 +665,7 @@ static void enqueue_fused_head(mf_ctx* c, const uint8_t* d_rgb, const float* d_d
     const bool model_launch = !tile_pyr || fill != nullptr;                // (without fill-in the epilogue's pyramid is final)
     if (tile_frame) {
         if (model_launch) launch_model_pyramid(m->d_predV, m->d_predN, fill, m->d_frame, m->d_pose, nullptr, m->d_vmap_g, m->d_nmap_g, c->W, c->H, c->K, c->stream, fixup);   // C'
-    } else if (c->fused_frame_pyramids && model_launch) {
+    } else if (c->sw.fused_frame_pyramids && model_launch) {
         launch_frame_model_pyramid(depthF, c->d_vmap[set], c->d_nmap[set], c->cfg.depth_cutoff, m->d_predV, m->d_predN, fill, m->d_frame, m->d_pose,
                                    m->d_vmap_g, m->d_nmap_g, c->W, c->H, c->K, c->stream, fixup);   // C
     } else {
@@ -685,11 +685,11 @@ static int download_pose_log(mf_ctx* c, ModelState& m, std::vector<int64_t>& ts,
 static void enqueue_global_projection(mf_ctx* c, ModelState& m, int order) {
     const mf_config& g = c->cfg;
     PassTimer timer(c, m.id == 0 ? MF_PASS_BG_GLOBAL : -1);
-    if (m.id == 0 && c->splat_tiles && c->global_tiles) {
+    if (m.id == 0 && c->sw.splat_tiles && c->sw.global_tiles) {
         VisList vl;
         const VisList* vis = ensure_vis(c, m, vl);
         if (launch_global_tiled(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, g.depth_cutoff, 12.0f, g.time_delta, order, m.id, c->d_tile_count,
-                                c->d_tile_entries, c->tile_entries_cap, c->d_splat_rec0, c->d_splat_rec1, c->d_splat_bbox, c->d_keys, c->stream, c->splat_tune,
+                                c->d_tile_entries, c->tile_entries_cap, c->d_splat_rec0, c->d_splat_rec1, c->d_splat_bbox, c->d_keys, c->stream, c->sw.splat_tune,
                                 vis) == 0)
             return;
     }
@@ -710,7 +710,7 @@ static int spawn_object(mf_ctx* c, int id, int classID) {
         nm->confThr = g.conf_object;
         nm->age = 0; nm->isStatic = true; nm->log_ts.clear();
         nm->reset_empty();
-        hipLaunchKernelGGL(k_pose_identity, dim3(1), dim3(64), 0, s, nm->d_pose, c->weight_literal ? 1 : 0);
+        hipLaunchKernelGGL(k_pose_identity, dim3(1), dim3(64), 0, s, nm->d_pose, c->sw.weight_literal ? 1 : 0);
         hipLaunchKernelGGL(k_frame_init, dim3(1), dim3(64), 0, s, nm->d_frame, c->host_tick);
         nm->h_frame->tick = c->host_tick;
     } else {
@@ -722,9 +722,9 @@ static int spawn_object(mf_ctx* c, int id, int classID) {
     c->models.push_back(std::move(nm));
     // the private scratch of the batched object passes (>= 2 objects) is allocated HERE, outside the enqueue path of a frame (hipMalloc
     // synchronises the device); a failure only switches the batched passes off -- the model-by-model passes need no private scratch
-    if (c->batch_objects && c->models.size() >= 3)
+    if (c->sw.batch_objects && c->models.size() >= 3)
         for (size_t i = 1; i < c->models.size(); ++i)
-            if (ensure_obj_scratch(c, *c->models[i]) != MF_OK) { (void)hipGetLastError(); c->batch_objects = false; c->err.clear(); break; }
+            if (ensure_obj_scratch(c, *c->models[i]) != MF_OK) { (void)hipGetLastError(); c->sw.batch_objects = false; c->err.clear(); break; }
     return MF_OK;
 }
 
@@ -924,7 +924,7 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
     bool bg_fused = false;
     // "passTimings" reports the passes of THIS frame: one that does not run in it (a compaction, bgAppend in the two-launch form, the batched object
     // passes) reads 0, not the duration of its last run
-    if (c->pass_timings_on)
+    if (c->sw.pass_timings_on)
         for (int q = 0; q < MF_N_PASSES; ++q) { c->pass_recorded[q] = false; c->pass_ms[q] = 0.f; }
     c->mm_marked = false;
     ObjStreamWindow obj_window(c);   // (joins on every way out of this function)
@@ -933,7 +933,7 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
     // pyramids ride in the depth filter's launch ("fusedPreprocessLaunch"), and the loop is told so
     TrackingPlan plan;
     tracking_plan(c, 0, g.track_all_models != 0, plan);
-    const bool pyr_built = c->fused_preprocess && c->map_ready && !(in_pose16 && !bootstrap);
+    const bool pyr_built = c->sw.fused_preprocess && c->map_ready && !(in_pose16 && !bootstrap);
     // a pending prediction ("deferPredict") is drawn in this frame's head when the frame tracks the background alone; any other frame settles first
     const bool fused_head = c->pending.m && pyr_built && !plan.batch && plan.tracked.size() == 1 && plan.tracked.front() == c->pending.m;
     if (fused_head) {
@@ -991,7 +991,7 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
                 for (size_t i = 0; i < c->models.size(); ++i) enqueue_global_projection(c, *c->models[i], (int)i);
             }
             launch_global_resolve(c->d_keys, c->d_proj_ids, P, s);
-            if (c->timings_on) (void)hipEventRecord(c->ev_mm[0], s);
+            if (c->sw.timings_on) (void)hipEventRecord(c->ev_mm[0], s);
             // MfSegmentation::performSegmentation, device half (MfSegmentation.cpp:149-208)
             launch_edge_map(c->d_vmap[set][0], c->d_nmap[set][0], c->d_edge, W, H, c->seg.weightDistance, c->seg.weightConvexity, s);
             launch_edge_binary(c->d_edge, c->d_bin, c->d_tmp_u8, W, H, c->seg.threshold, c->seg.morphEdgeRadius,
@@ -999,7 +999,7 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
             const bool haveMasks = d_mask_in && class_ids && n_masks > 0;
             static const int32_t kNoClass[1] = {0};
             SegResult res;
-            if (c->gpu_labels) {
+            if (c->sw.gpu_labels) {
                 // label stage on the device (mf_labels_gpu.hip): the model table still holds the objects the jump rule may
                 // have dropped in this frame -- the kernels read their `alive` flags -- and the only host visit of the frame
                 // reads back the new-model decision and those flags
@@ -1020,17 +1020,17 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
                 // surfels; upstream fuses the new model first, MaskFusion.cpp:342-353,539-565.)
                 if (!c->ev_labels) MF_HIP(c, hipEventCreateWithFlags(&c->ev_labels, hipEventDisableTiming));
                 MF_HIP(c, hipEventRecord(c->ev_labels, s));
-                if (c->timings_on) (void)hipEventRecord(c->ev_mm[1], s);
-                if (!g.rgb_only && c->early_bg_fusion) {
+                if (c->sw.timings_on) (void)hipEventRecord(c->ev_mm[1], s);
+                if (!g.rgb_only && c->sw.early_bg_fusion) {
                     int rc2 = enqueue_fuse_clean(c, bg, d_rgb, d_depth, depthF, mask, g.depth_cutoff, weight_multiplier, true, true);
                     if (rc2 != MF_OK) return rc2;
                     bg_fused = true;
                 }
-                if (c->timings_on) (void)hipEventRecord(c->ev_mm[2], s);
+                if (c->sw.timings_on) (void)hipEventRecord(c->ev_mm[2], s);
                 const auto t_wait0 = std::chrono::steady_clock::now();
                 MF_HIP(c, hipEventSynchronize(c->ev_labels));
                 c->mm_host_wait_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_wait0).count();
-                if (c->timings_on) { (void)hipEventRecord(c->ev_mm[3], s); c->mm_marked = true; }
+                if (c->sw.timings_on) { (void)hipEventRecord(c->ev_mm[3], s); c->mm_marked = true; }
                 if (c->labels->h_result[2]) { c->err = "label stage: vote tables overflowed (too many components x masks)"; return MF_ESTATE; }
                 res.hasNewLabel = c->labels->h_result[0] != 0;
                 res.newClassID = c->labels->h_result[1];
@@ -1051,7 +1051,7 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
                     if (rc != MF_OK) return rc;
                 } else ++i;
             }
-            if (!c->gpu_labels) {
+            if (!c->sw.gpu_labels) {
                 if (c->spawnOffset < g.model_spawn_offset) c->spawnOffset++;  // :294
                 std::vector<SegModelInfo> infos;
                 for (auto& m : c->models) infos.push_back(SegModelInfo{m->id, m->classID});
@@ -1120,12 +1120,12 @@ extern "C" int mf_sync(mf_ctx* c) {
     settle(c);
     if (!c) return MF_EINVAL;
     MF_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->pass_timings_on)
+    if (c->sw.pass_timings_on)
         for (int q = 0; q < MF_N_PASSES; ++q) {
             float ms = 0.f;
             if (c->pass_recorded[q] && hipEventElapsedTime(&ms, c->ev_pass[q][0], c->ev_pass[q][1]) == hipSuccess) c->pass_ms[q] = ms;
         }
-    if (c->timings_on) {
+    if (c->sw.timings_on) {
         // event i marks the START of stage i; stage i lasts until event i+1 (labels: see the header)
         float t[MF_N_TIMINGS] = {};
         for (int i = 0; i < 8; ++i) {
@@ -1159,7 +1159,7 @@ extern "C" int mf_process_frame(mf_ctx* c, const uint8_t* rgb, const float* dept
                                 int32_t n_masks, int64_t timestamp, const float* in_pose16, float weight_multiplier, int32_t bootstrap) {
     if (!c || !rgb || !depth) return MF_EINVAL;
     if (bootstrap && !in_pose16) { c->err = "bootstrap needs in_pose (MaskFusion.cpp:281)"; return MF_EINVAL; }
-    if (c->host_async) {
+    if (c->sw.host_async) {
         // pinned double buffer + asynchronous upload: no hipStreamSynchronize per frame on the boundary a drop-in
         // user sees (MaskFusion.cpp:212-216 uploads FrameData every frame)
         const size_t P = (size_t)c->P;
@@ -1173,14 +1173,14 @@ extern "C" int mf_process_frame(mf_ctx* c, const uint8_t* rgb, const float* dept
         if (mask) memcpy(h + c->in_off_mask, mask, P);
         const auto t_1 = std::chrono::steady_clock::now();
         hipStream_t sup = c->stream_in;
-        if (c->host_lockstep) MF_HIP(c, hipEventSynchronize(c->ev_in_consumed[slot]));   // (frame k-2 has run: at most two frames are queued)
+        if (c->sw.host_lockstep) MF_HIP(c, hipEventSynchronize(c->ev_in_consumed[slot]));   // (frame k-2 has run: at most two frames are queued)
         MF_HIP(c, hipStreamWaitEvent(sup, c->ev_in_consumed[slot], 0));                  // the frame that read this device block is done
         const size_t up_bytes = mask ? c->in_off_mask + P : c->in_off_rgb + P * 3;
         MF_HIP(c, hipMemcpyAsync(c->d_in_block[slot], h, up_bytes, hipMemcpyHostToDevice, sup));
         MF_HIP(c, hipEventRecord(c->ev_in_copied[slot], sup));
         // (single-model frames: ~60 us of the ~300 the host has to spare.  A multi-model call synchronises in mid-frame for the label stage's
         // decision and has no time to spare: its upload stays a cross-queue wait under the previous frame's tail)
-        if (c->host_wait_upload && c->host_lockstep && c->cfg.enable_multiple_models == 0) MF_HIP(c, hipEventSynchronize(c->ev_in_copied[slot]));
+        if (c->sw.host_wait_upload && c->sw.host_lockstep && c->cfg.enable_multiple_models == 0) MF_HIP(c, hipEventSynchronize(c->ev_in_copied[slot]));
         else MF_HIP(c, hipStreamWaitEvent(c->stream, c->ev_in_copied[slot], 0));
         const auto t_2 = std::chrono::steady_clock::now();
         int rc = process_frame_impl(c, c->d_in_rgb[slot], c->d_in_depth[slot], mask ? c->d_in_mask[slot] : nullptr, class_ids, n_masks,

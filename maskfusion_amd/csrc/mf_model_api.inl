@@ -145,8 +145,8 @@ extern "C" int mf_model_perform_tracking(mf_ctx* c, int32_t model, int32_t frame
         }
     }
     const mf_config keep = c->cfg;
-    const bool keep_ftf = c->ftf_rgb;
-    c->ftf_rgb = frame_to_frame_rgb != 0;   // which image initRGBModel takes (Model.cpp:399-400); the fill-in image itself was built by the last prediction
+    const bool keep_ftf = c->sw.ftf_rgb;
+    c->sw.ftf_rgb = frame_to_frame_rgb != 0;   // which image initRGBModel takes (Model.cpp:399-400); the fill-in image itself was built by the last prediction
     c->cfg.rgb_only = rgb_only; c->cfg.icp_weight = icp_weight; c->cfg.pyramid = pyramid; c->cfg.fast_odom = fast_odom; c->cfg.so3 = so3;
     c->cfg.max_depth_processed = max_depth_processed;
     // tryFillIn = MaskFusion::requiresFillIn(model) (:630-648): the decision itself is taken on the device from the coverage of the
@@ -154,7 +154,7 @@ extern "C" int mf_model_perform_tracking(mf_ctx* c, int32_t model, int32_t frame
     // object models carry the 0.2 m jump rule of the caller (MaskFusion.cpp:268-272): pose->alive = 0 marks "remove this model"
     enqueue_track(c, *m, (try_fill_in && m->allowFillIn) ? c->d_depthF[(k + 2) % 3] : nullptr, model == 0 ? 0.f : 0.2f, k, false);
     c->cfg = keep;
-    c->ftf_rgb = keep_ftf;
+    c->sw.ftf_rgb = keep_ftf;
     return check_launch(c);
 }
 
@@ -167,7 +167,7 @@ extern "C" int mf_model_predict_indices(mf_ctx* c, int32_t model, int32_t time, 
     set_model_tick(c, *m, time);
     launch_index_scatter(m->surf[m->cur], m->d_frame, m->d_pose, c->W, c->H, c->K, max_depth, time_delta, c->d_keys, true, s);
     launch_index_resolve(m->surf[m->cur], m->d_frame, m->d_pose, c->d_keys, c->W, c->H, c->d_index, c->d_ivc, c->d_inr, c->d_ict, nullptr, nullptr, nullptr, nullptr, true, s);
-    if (c->model_api_packed) {   // the layout mf_process_frame feeds clean() with: packed records, column-major
+    if (c->sw.model_api_packed) {   // the layout mf_process_frame feeds clean() with: packed records, column-major
         launch_index_scatter(m->surf[m->cur], m->d_frame, m->d_pose, c->W, c->H, c->K, max_depth, time_delta, c->d_keys, true, s);
         launch_index_resolve(m->surf[m->cur], m->d_frame, m->d_pose, c->d_keys, c->W, c->H, nullptr, nullptr, nullptr, nullptr, c->d_iclean, c->d_depthF[staged_frame(c) % 3],
                              current_mask(c), c->d_maskT, true, s);
@@ -188,7 +188,7 @@ extern "C" int mf_model_fuse(mf_ctx* c, int32_t model, int32_t time, float depth
     set_model_tick(c, *m, time);
     launch_fuse_data(c->cur_rgb, c->cur_depth, c->d_depthF[k % 3], current_mask(c), m->id, m->d_frame, m->d_pose, weight_multiplier,
                      fminf(depth_cutoff, m->maxDepth), c->W, c->H, c->K, c->d_index, c->d_ivc, c->d_inr, c->d_cand_op, c->d_cand_rec,
-                     c->d_upd_first, c->d_cand_best, s, c->bbox_limit ? 1 : 0, c->fuse_lanes);
+                     c->d_upd_first, c->d_cand_best, s, c->sw.bbox_limit ? 1 : 0, c->sw.fuse_lanes);
     launch_fuse_update(m->surf[m->cur], m->d_frame, c->d_upd_first, c->d_cand_op, c->d_cand_best, c->d_cand_rec, c->W, c->H, s);   // in place
     // merged surfels moved and were seen now: the boxes and time stamps of their runs are refreshed (inside mf_process_frame the clean pass that
     // follows rewrites the entries of every run it visits -- and it visits every run a merge can have touched)
@@ -206,7 +206,7 @@ extern "C" int mf_model_clean(mf_ctx* c, int32_t model, int32_t time, int32_t ti
     if (!m || c->frame_no == 0) return MF_EINVAL;
     const long k = staged_frame(c);
     set_model_tick(c, *m, time);
-    const bool packed = c->model_api_packed != 0;
+    const bool packed = c->sw.model_api_packed != 0;
     CleanForm form;
     int rc = prepare_clean(c, &m, 1, !clean_small(c, *m), form);
     if (rc != MF_OK) return rc;

@@ -21,7 +21,7 @@
 namespace mf {
 
 constexpr int kTile = 16;                // tile width in pixels
-constexpr int kTileHMax = 32;            // tile height: 24 (default since round 6), 16, 20 or 32 pixels ("tileHeight", SplatTuning::tile_h) -- a launch parameter.
+constexpr int kTileHMax = 32;            // the tallest tile: the height is a launch parameter ("tileHeight", SplatTuning::tile_h; 24 since round 6).
                                          // 1 200 workgroups of 16 x 16 tiles at VGA are more than the 1 024 that are resident at once; 800 of 16 x 24 are one
                                          // round: prediction stage 53.0 -> 50.8 us at VGA, the 1280 x 960 frame 861 -> 848 us (profiles/r06zj_ab.txt); 16 x 32: 52.6 us at VGA, 843 us at
                                          // 1280 x 960, configs[4] unchanged (r06zk_ab.txt)
@@ -69,16 +69,18 @@ __device__ __forceinline__ bool splat_setup(const Surfels& src, int i, float tim
     return true;
 }
 
-// lanes that share one sprite in the tile z-test (1, 2, 4, 8, 16; mf_set_param "spriteLanes"): an A/B switch for measurements, per context
+// The three knobs of SplatTuning.  Their legal values are the rows of mf_params.inl (mf_set_param refuses everything else); what follows only guards
+// the launches against a SplatTuning filled in by hand: anything else takes the default.
+// lanes that share one sprite in the tile z-test (mf_set_param "spriteLanes"): an A/B switch for measurements, per context
 // (SplatTuning travels with the launch; rounds 2-3 kept both knobs in process-wide statics that one context's setting changed for all)
 int splat_sprite_lanes(int n) { return (n == 1 || n == 2 || n == 8 || n == 16) ? n : 4; }
-// threads per tile workgroup (256, 512, 1024; "tileThreads"): a tile has 256 pixels, the threads beyond them only walk the sprite list.
+// threads per tile workgroup ("tileThreads"): a tile has 256 pixels, the threads beyond them only walk the sprite list.
 // 1200 tiles of 256 threads are 4.7 wavefronts per SIMD on 256 CUs -- too few to hide the list's dependent gathers and the division
 // chain of the pixel test (tools/splat_prof.py: a tile workgroup lives ~32 k cycles, ~4 k of them issuing)
 // Measured (profiles/r03k_*, prediction stage incl. binning): 256 threads 62.6 us, 512 threads 58.0 us, 1024 threads 65.9 us (4 lanes per
 // sprite each) -- 512 is the default.
 int splat_tile_threads(int n) { return (n == 256 || n == 320 || n == 384 || n == 1024) ? n : 512; }
-// tile height ("tileHeight"): 16, 20 or 24 rows of 16 pixels; the tile's pixels need a thread each
+// tile height ("tileHeight"): that many rows of 16 pixels; the tile's pixels need a thread each
 int splat_tile_height(int h) { return (h == 16 || h == 20 || h == 32) ? h : 24; }
 
 struct BinArgs {

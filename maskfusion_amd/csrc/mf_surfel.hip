@@ -1711,37 +1711,37 @@ static CleanArgs clean_args(const CleanIn& in, Surfels src, Surfels dst) {
 // (0.75 M elements) is fastest on 2 048 (303.6 against 309-313 us per frame on 1 024 and 305.0 on 4 096); from ~1.5 M elements on, 1 024 workgroups
 // with longer slices win: 1280 x 960 on its natural map 847 -> 835 us, the four 3.7 M-element object maps of configs[4] 4.16 -> 4.07-4.12 ms
 // (profiles/r06zo_ab.txt, r06zp_ab.txt).
-// the instance of a clean kernel for the pass's tap form: the 32-byte record or the separate images, or 16-byte taps by group and mask planes
-#define MF_LAUNCH_CLEAN(K, grid, s, a)                                                                                      \
+// The instance of a clean kernel K<kTap16, kGroup, kMaskFree> for a pass's tap form: the 32-byte record or the separate images, or 16-byte taps by
+// group ("cleanTapGroup": 1, 3 or 9 -- mf_set_param refuses everything else), without the mask planes where the pass drops them.  kMayDrop is a
+// compile-time constant: the object batch passes false and no mask-free instance of its kernels exists.
+#define MF_LAUNCH_CLEAN_GROUP(K, kMaskFree, group, grid, s, arg)                                                            \
     do {                                                                                                                    \
-        const int mf_g = (a).tapGroup == 9 ? 9 : (a).tapGroup == 3 ? 3 : 1;                                                 \
-        if (!(a).tap16) hipLaunchKernelGGL((K<false, 1, false>), grid, dim3(256), 0, s, a);                                 \
-        else if ((a).maskFree) {                                                                                            \
-            if (mf_g == 3) hipLaunchKernelGGL((K<true, 3, true>), grid, dim3(256), 0, s, a);                                \
-            else if (mf_g == 9) hipLaunchKernelGGL((K<true, 9, true>), grid, dim3(256), 0, s, a);                           \
-            else hipLaunchKernelGGL((K<true, 1, true>), grid, dim3(256), 0, s, a);                                          \
-        } else {                                                                                                            \
-            if (mf_g == 3) hipLaunchKernelGGL((K<true, 3, false>), grid, dim3(256), 0, s, a);                               \
-            else if (mf_g == 9) hipLaunchKernelGGL((K<true, 9, false>), grid, dim3(256), 0, s, a);                          \
-            else hipLaunchKernelGGL((K<true, 1, false>), grid, dim3(256), 0, s, a);                                         \
-        }                                                                                                                   \
+        if ((group) == 3) hipLaunchKernelGGL((K<true, 3, kMaskFree>), grid, dim3(256), 0, s, arg);                          \
+        else if ((group) == 9) hipLaunchKernelGGL((K<true, 9, kMaskFree>), grid, dim3(256), 0, s, arg);                     \
+        else hipLaunchKernelGGL((K<true, 1, kMaskFree>), grid, dim3(256), 0, s, arg);                                       \
+    } while (0)
+#define MF_LAUNCH_CLEAN(K, kMayDrop, tap16, group, maskFree, grid, s, arg)                                                  \
+    do {                                                                                                                    \
+        if (!(tap16)) hipLaunchKernelGGL((K<false, 1, false>), grid, dim3(256), 0, s, arg);                                 \
+        else if (kMayDrop && (maskFree)) MF_LAUNCH_CLEAN_GROUP(K, kMayDrop, group, grid, s, arg);                           \
+        else MF_LAUNCH_CLEAN_GROUP(K, false, group, grid, s, arg);                                                          \
     } while (0)
 int compact_blocks_for(long elements) { return elements >= 1500000L ? kCompactBlocks / 2 : kCompactBlocks; }
 void launch_clean_small(const CleanIn& in, Surfels src, Surfels dst, hipStream_t s, int blocks) {
     const CleanArgs a = clean_args(in, src, dst);
-    MF_LAUNCH_CLEAN(k_clean_small_flags, dim3(blocks), s, a);
+    MF_LAUNCH_CLEAN(k_clean_small_flags, true, a.tap16, a.tapGroup, a.maskFree, dim3(blocks), s, a);
     hipLaunchKernelGGL(k_clean_small_compact, dim3(blocks), dim3(256), 0, s, a);
 }
 void launch_clean_runs(const CleanIn& in, Surfels buf, const VisList* runs, int* ctl, int blocks, hipStream_t s) {
     CleanArgs a = clean_args(in, buf, buf);
     a.run_list = runs ? runs->list : nullptr; a.run_count = runs ? runs->count : nullptr; a.ctl = ctl;
-    MF_LAUNCH_CLEAN(k_clean_runs, dim3(blocks), s, a);
+    MF_LAUNCH_CLEAN(k_clean_runs, true, a.tap16, a.tapGroup, a.maskFree, dim3(blocks), s, a);
 }
 void launch_clean_append(const CleanIn& in, Surfels buf, hipStream_t s) {
     CleanArgs a = clean_args(in, buf, buf);
     a.append = 1;
     // (the candidates are <= P / 4 elements: a grid of one 256-element slice per workgroup, at most kCompactBlocks of them)
-    MF_LAUNCH_CLEAN(k_clean_small_flags, dim3(kCompactBlocks), s, a);
+    MF_LAUNCH_CLEAN(k_clean_small_flags, true, a.tap16, a.tapGroup, a.maskFree, dim3(kCompactBlocks), s, a);
     hipLaunchKernelGGL(k_clean_small_compact, dim3(kCompactBlocks), dim3(256), 0, s, a);
 }
 
@@ -1796,11 +1796,11 @@ __device__ __forceinline__ CleanArgs obj_clean_args(const ObjBatch& b, const Obj
     a.append = append; a.run_list = nullptr; a.run_count = nullptr; a.ctl = m.clean_ctl;
     return a;
 }
-template <bool kTap16, int kGroup>
-__global__ __launch_bounds__(256) void k_obj_clean_runs(const ObjBatch b) { clean_runs_body<kTap16, kGroup, false>(obj_clean_args(b, b.m[blockIdx.z], 0)); }
-template <bool kTap16, int kGroup>
+template <bool kTap16, int kGroup, bool kMaskFree>   // (kMaskFree: always false, as obj_clean_args says)
+__global__ __launch_bounds__(256) void k_obj_clean_runs(const ObjBatch b) { clean_runs_body<kTap16, kGroup, kMaskFree>(obj_clean_args(b, b.m[blockIdx.z], 0)); }
+template <bool kTap16, int kGroup, bool kMaskFree>
 __global__ __launch_bounds__(256) void k_obj_clean_small_flags(const ObjBatch b) {
-    clean_small_flags_body<kTap16, kGroup, false>(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1));
+    clean_small_flags_body<kTap16, kGroup, kMaskFree>(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1));
 }
 __global__ __launch_bounds__(256) void k_obj_clean_small_compact(const ObjBatch b) { clean_small_compact_body(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1)); }
 __global__ __launch_bounds__(256) void k_obj_splat_scatter(const ObjBatch b) {
@@ -1837,19 +1837,9 @@ void launch_obj_fuse_clean(const ObjBatch& b, int blocks, int clean_blocks, hipS
     // two-launch form src -> dst, or (big models) the buffer's own surfels in place, run by run -- an object model's launch visits every run: its
     // bounding box is the box of ALL its drawn surfels -- and then the frame's candidates appended by the two-launch form
     const dim3 flags(compact_blocks, 1, b.n);
-    if (b.depthT && b.cleanTapGroup == 3) {    // the 16-byte tap (the resolve pass above wrote it with each model's own threshold and tick)
-        if (!b.cleanSmall) hipLaunchKernelGGL((k_obj_clean_runs<true, 3>), compact, dim3(256), 0, s, b);
-        hipLaunchKernelGGL((k_obj_clean_small_flags<true, 3>), flags, dim3(256), 0, s, b);
-    } else if (b.depthT && b.cleanTapGroup == 9) {
-        if (!b.cleanSmall) hipLaunchKernelGGL((k_obj_clean_runs<true, 9>), compact, dim3(256), 0, s, b);
-        hipLaunchKernelGGL((k_obj_clean_small_flags<true, 9>), flags, dim3(256), 0, s, b);
-    } else if (b.depthT) {
-        if (!b.cleanSmall) hipLaunchKernelGGL((k_obj_clean_runs<true, 1>), compact, dim3(256), 0, s, b);
-        hipLaunchKernelGGL((k_obj_clean_small_flags<true, 1>), flags, dim3(256), 0, s, b);
-    } else {
-        if (!b.cleanSmall) hipLaunchKernelGGL((k_obj_clean_runs<false, 1>), compact, dim3(256), 0, s, b);
-        hipLaunchKernelGGL((k_obj_clean_small_flags<false, 1>), flags, dim3(256), 0, s, b);
-    }
+    const bool tap16 = b.depthT != nullptr;    // the 16-byte tap (the resolve pass above wrote it with each model's own threshold and tick)
+    if (!b.cleanSmall) MF_LAUNCH_CLEAN(k_obj_clean_runs, false, tap16, b.cleanTapGroup, false, compact, s, b);
+    MF_LAUNCH_CLEAN(k_obj_clean_small_flags, false, tap16, b.cleanTapGroup, false, flags, s, b);
     hipLaunchKernelGGL(k_obj_clean_small_compact, dim3(compact_blocks, 1, b.n), dim3(256), 0, s, b);
 }
 void launch_obj_predict_advance(const ObjBatch& b, int blocks, hipStream_t s) {

@@ -110,11 +110,16 @@ def test_cpp_facade_host_semantics_without_gpu(tmp_path):
 
 
 def test_every_parameter_key_is_documented_in_the_header():
-    """every key mf_set_param / mf_get_param compares against appears in include/maskfusion_amd.h (rounds 3-5 added switches faster than the
-    header learnt of them)"""
+    """every key of mf_set_param / mf_get_param -- a row of the table in mf_params.inl -- appears in include/maskfusion_amd.h (rounds 3-5 added
+    switches faster than the header learnt of them), and no key is compared against anywhere else"""
     import re
-    src = open(os.path.join(ROOT, "maskfusion_amd", "csrc", "mf_context.hip")).read()
+    csrc = os.path.join(ROOT, "maskfusion_amd", "csrc")
+    table = open(os.path.join(csrc, "mf_params.inl")).read()
     header = open(os.path.join(ROOT, "include", "maskfusion_amd.h")).read()
-    keys = set(re.findall(r'strcmp\(key, "([A-Za-z0-9_]+)"\)', src)) | set(re.findall(r'\{"([A-Za-z0-9_]+)", \d, offsetof', src))
+    rows = re.findall(r'^    \{"([A-Za-z0-9_]+)", kIn(?:Cfg|Seg|Sw)|^    \{"([A-Za-z0-9_]+)", kComputed', table, re.M)
+    keys = [a or b for a, b in rows]
+    assert len(keys) == len(set(keys)), sorted(k for k in keys if keys.count(k) > 1)
     missing = sorted(k for k in keys if f'"{k}"' not in header)
-    assert len(keys) > 30 and not missing, missing
+    assert len(keys) >= 80 and not missing, missing
+    for name in (n for n in os.listdir(csrc) if n.endswith((".hip", ".inl", ".h"))):
+        assert not re.search(r'strcmp\(key, "', open(os.path.join(csrc, name)).read()), name
