@@ -865,6 +865,10 @@ int mf_k_icp_step(const float* Rcurr9, const float* tcurr3, const float* d_vmap_
                   const float* Rprev_inv9, const float* tprev3, float fx, float fy, float cx, float cy,
                   const float* d_vmap_g_prev, const float* d_nmap_g_prev, float dist_thresh, float angle_thresh,
                   int32_t W, int32_t H, float* d_out32, void* stream);
+/* The launch form the geometric Gauss-Newton kernel takes for a pyramid level of W x H pixels (host only, no GPU involved):
+ * out = {threads per workgroup, pixel slots per thread, workgroups, pixels per workgroup, workgroups that hold at least one
+ * pixel}.  Read from the functions the launch itself calls, so that a test can name the form its image sizes select. */
+int mf_k_icp_launch_form(int32_t W, int32_t H, int32_t out[5]);
 
 #ifdef __cplusplus
 }

@@ -81,10 +81,10 @@ static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, floa
     const bool rgb = photometric_on(c);
     const bool icp = !g.rgb_only && g.icp_weight > 0.f;
     // the previous frame's intensity pyramid is RGBDOdometry::lastNextImage (identical for every tracked model)
-    const bool so3 = g.so3 != 0 && c->gray_frame[set ^ 1] == frame_k - 1 && c->gray_frame[set] == frame_k;
-    if (so3)
-        (void)launch_so3_prealign(c->d_gray[set ^ 1][2], c->d_gray[set][2], W >> 2, H >> 2, Intr{g.fx / 4, g.fy / 4, g.cx / 4, g.cy / 4},
-                                  c->d_so3, c->d_so3_scratch, s);
+    bool so3 = g.so3 != 0 && c->gray_frame[set ^ 1] == frame_k - 1 && c->gray_frame[set] == frame_k;
+    if (so3)   // (a pre-alignment that did not run leaves no seed: the loop then starts from the identity, as with the switch off)
+        so3 = launch_so3_prealign(c->d_gray[set ^ 1][2], c->d_gray[set][2], W >> 2, H >> 2, Intr{g.fx / 4, g.fy / 4, g.cx / 4, g.cy / 4},
+                                  c->d_so3, c->d_so3_scratch, s) == 0;
     const So3Result* so3_seed = so3 ? c->d_so3 : nullptr;
     if (rgb) {
         // initRGBModel + initRGB (Model.cpp:395-406; Q1: both depth pyramids come from the vertex map initICPModel was given)
@@ -180,10 +180,10 @@ static void enqueue_track_batch(mf_ctx* c, const std::vector<ModelState*>& ms, c
     hipStream_t s = c->stream;
     const TrackBatch b = track_batch_of(ms);
     if (!pyr_built) launch_model_pyramid_batch(b, fillDepth, W, H, c->K, s);
-    const bool so3 = g.so3 != 0 && c->gray_frame[set ^ 1] == frame_k - 1 && c->gray_frame[set] == frame_k;
-    if (so3)   // one pre-alignment serves every model: it only looks at the two frames (RGBDOdometry.cpp:264-324)
-        (void)launch_so3_prealign(c->d_gray[set ^ 1][2], c->d_gray[set][2], W >> 2, H >> 2, Intr{g.fx / 4, g.fy / 4, g.cx / 4, g.cy / 4},
-                                  c->d_so3, c->d_so3_scratch, s);
+    bool so3 = g.so3 != 0 && c->gray_frame[set ^ 1] == frame_k - 1 && c->gray_frame[set] == frame_k;
+    if (so3)   // one pre-alignment serves every model: it only looks at the two frames (RGBDOdometry.cpp:264-324); one that did not run leaves no seed
+        so3 = launch_so3_prealign(c->d_gray[set ^ 1][2], c->d_gray[set][2], W >> 2, H >> 2, Intr{g.fx / 4, g.fy / 4, g.cx / 4, g.cy / 4},
+                                  c->d_so3, c->d_so3_scratch, s) == 0;
     const So3Result* so3_seed = so3 ? c->d_so3 : nullptr;
     const int iters[3] = {g.fast_odom ? 3 : 10, g.pyramid ? 5 : 0, g.pyramid ? 4 : 0};
     const bool timed = c->sw.timings_on && ms[0] == c->models[0].get();

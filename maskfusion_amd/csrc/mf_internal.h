@@ -176,6 +176,10 @@ struct IcpLaunch {
 };
 int icp_grid_blocks(int W, int H);       // workgroups of the RGB-D iteration kernels for this level
 int icp_geo_grid_blocks(int W, int H);   // workgroups of the geometric kernel k_icp_iter (more of them at the coarse levels: one pixel slot per thread)
+// the launch form of k_icp_iter for a level: threads per workgroup, pixel slots per thread, workgroups, pixels per workgroup (chunk), and how many
+// of the workgroups hold at least one pixel (chunks round up to 64 pixels, so the last workgroups of a capped grid can lie past the image)
+struct IcpForm { int threads, slots, blocks, chunk, live; };
+IcpForm icp_launch_form(int W, int H);
 void launch_icp_iteration(const IcpLaunch& a, hipStream_t s);
 // ---- the same loop for SEVERAL models at once (MaskFusion.cpp:247-276 tracks them one after the other): one launch serves
 // iteration k of every tracked model.  Split in two kernels per iteration -- "solve" (one workgroup per model: reduce the
@@ -238,7 +242,8 @@ bool launch_rgb_pyramid(const uint8_t* rgb, int W, int H, uint8_t* const gray[3]
 // frameToFrameRGB != 0 (and a fill-in image given): initRGBModel takes the fill-in image whatever the fill-in decision (Model.cpp:399-400)
 void launch_rgbd_last_l0(const float4* predV, const float* fillDepth, const uint8_t* predGray, const uint8_t* fillGray,
                          const FrameDev* frame, float* depth0, uint8_t* image0, int n, hipStream_t s, int frameToFrameRGB = 0);
-// scratch: so3_scratch_bytes(W2, H2) of device memory; returns -1 if the image needs more workgroups than the staging allows
+// scratch: so3_scratch_bytes(W2, H2) of device memory; any image size (at most 512 workgroups, which stride over a larger image).
+// Returns 0, or -1 if nothing was launched (*out is then not written and must not be used as a seed)
 size_t so3_scratch_bytes(int W2, int H2);
 int launch_so3_prealign(const uint8_t* lastImage2, const uint8_t* nextImage2, int W2, int H2, Intr k2, So3Result* out, void* scratch,
                         hipStream_t s);

@@ -205,6 +205,12 @@ extern "C" int mf_k_gn_solve(const double* sys29, const double* result_rt16, con
     const int rc = gn_solve_standalone(sys29, result_rt16, Rprev9, tprev3, x6_serial, x6_wave, result_rt16_out, Rcurr9, tcurr3, stats2, (hipStream_t)stream);
     return rc == 0 ? MF_OK : (rc == -1 ? MF_ENOMEM : MF_EHIP);
 }
+extern "C" int mf_k_icp_launch_form(int32_t W, int32_t H, int32_t out[5]) {
+    if (!out || W <= 0 || H <= 0) return MF_EINVAL;
+    const IcpForm f = icp_launch_form(W, H);
+    out[0] = f.threads; out[1] = f.slots; out[2] = f.blocks; out[3] = f.chunk; out[4] = f.live;
+    return MF_OK;
+}
 extern "C" int mf_k_icp_step(const float* Rcurr9, const float* tcurr3, const float* d_vc, const float* d_nc, const float* Rpi9,
                              const float* tprev3, float fx, float fy, float cx, float cy, const float* d_vp, const float* d_np,
                              float dist_thresh, float angle_thresh, int32_t W, int32_t H, float* d_out32, void* stream) {

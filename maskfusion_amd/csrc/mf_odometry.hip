@@ -761,12 +761,29 @@ int icp_grid_blocks(int W, int H) { return icp_blocks_capped(W, H, kIcpMaxBlocks
 // a VGA frame) gets one workgroup per 256 pixels up to 320 of them -- level 1: 300 workgroups, ONE pixel slot per thread, two workgroups on
 // 44 of the 256 CUs (23 KB of LDS and 4 wavefronts each) -- instead of 240 chunks of 320 pixels whose second slot kept one wavefront in
 // four busy and the other three waiting for it (round 4: the pixel phase is VALU-bound, a slot costs what it costs however few lanes use it).
-int icp_geo_grid_blocks(int W, int H) { return icp_blocks_capped(W, H, 320); }
+constexpr int kIcpGeoCap256 = 320;
+int icp_geo_grid_blocks(int W, int H) { return icp_blocks_capped(W, H, kIcpGeoCap256); }
 
 // pixel slots per thread the launch needs: ceil(chunk / threads), 1..kIcpPx
 int icp_pixel_slots(int W, int H) {
     const int P = W * H, T = icp_threads_for(P);
     return (icp_chunk(P, icp_geo_grid_blocks(W, H)) + T - 1) / T;
+}
+// A 256-thread level never needs a third slot: it has at most (kIcpMaxBlocks - 1) * kIcpThreads pixels (icp_threads_for), and once its grid is
+// capped the chunk is that over kIcpGeoCap256 workgroups, rounded up to 64 -- 384 pixels.  So the 256-thread dispatch has two forms.
+static_assert(((((kIcpMaxBlocks - 1) * kIcpThreads + kIcpGeoCap256 - 1) / kIcpGeoCap256 + 63) / 64) * 64 <= 2 * 256,
+              "a 256-thread level would need k_icp_iter<256, 3>");
+
+// the form launch_icp_iteration gives a level of W x H pixels (what it launches, and what mf_k_icp_launch_form reports)
+IcpForm icp_launch_form(int W, int H) {
+    IcpForm f;
+    const int P = W * H;
+    f.threads = icp_threads_for(P);
+    f.slots = icp_pixel_slots(W, H);
+    f.blocks = icp_geo_grid_blocks(W, H);
+    f.chunk = icp_chunk(P, f.blocks);
+    f.live = (P + f.chunk - 1) / f.chunk;   // workgroups whose chunk starts inside the image
+    return f;
 }
 
 void launch_icp_iteration(const IcpLaunch& l, hipStream_t s) {
@@ -777,12 +794,12 @@ void launch_icp_iteration(const IcpLaunch& l, hipStream_t s) {
     a.st_in = l.state_in; a.st_out = l.state_out; a.log_out = l.log_out; a.prof_out = l.prof_out; a.pose_in = l.pose_in;
     a.trace = l.trace; a.it = l.it;
     a.so3_in = l.so3_in;
-    const dim3 grid(icp_geo_grid_blocks(l.W, l.H));
-    const int px = icp_pixel_slots(l.W, l.H);
-    if (icp_threads_for(l.W * l.H) == 256) {
+    const IcpForm f = icp_launch_form(l.W, l.H);
+    const dim3 grid(f.blocks);
+    const int px = f.slots;
+    if (f.threads == 256) {
         if (px <= 1) hipLaunchKernelGGL((k_icp_iter<256, 1>), grid, dim3(256), 0, s, a);
-        else if (px == 2) hipLaunchKernelGGL((k_icp_iter<256, 2>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_icp_iter<256, kIcpPx>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_icp_iter<256, 2>), grid, dim3(256), 0, s, a);   // (never three: the static_assert above)
     } else {
         if (px <= 2) hipLaunchKernelGGL((k_icp_iter<kIcpThreads, 2>), grid, dim3(kIcpThreads), 0, s, a);
         else hipLaunchKernelGGL((k_icp_iter<kIcpThreads, kIcpPx>), grid, dim3(kIcpThreads), 0, s, a);

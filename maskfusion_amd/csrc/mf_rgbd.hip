@@ -400,6 +400,12 @@ __device__ __forceinline__ void so3_prologue(const So3State* __restrict__ st_in,
 }
 
 constexpr int kSo3MaxBlocks = 512;   // LDS staging of the previous launch's partials
+// workgroups of k_so3_iter: one pixel per thread up to kSo3MaxBlocks * kSo3Threads pixels; beyond that the grid stays at kSo3MaxBlocks and every thread
+// strides over its share of the image
+static int so3_blocks(int W2, int H2) {
+    const size_t nb = ((size_t)W2 * H2 + kSo3Threads - 1) / kSo3Threads;
+    return (int)(nb < (size_t)kSo3MaxBlocks ? nb : (size_t)kSo3MaxBlocks);
+}
 
 __global__ __launch_bounds__(kSo3Threads) void k_so3_iter(const uint8_t* __restrict__ lastImage, const uint8_t* __restrict__ nextImage,
                                                            int W, int H, Intr k, const So3State* __restrict__ st_in,
@@ -422,8 +428,8 @@ __global__ __launch_bounds__(kSo3Threads) void k_so3_iter(const uint8_t* __restr
     float acc[11];
 #pragma unroll
     for (int q = 0; q < 11; ++q) acc[q] = 0.f;
-    const int p = blockIdx.x * kSo3Threads + tid;
-    if (p < W * H) {
+    // (a grid below the cap makes one trip: one pixel per thread, the sums of the one-pixel form in the same order)
+    for (int p = blockIdx.x * kSo3Threads + tid; p < W * H; p += (int)gridDim.x * kSo3Threads) {
         const int y = p / W, x = p - y * W;
         so3_px(lastImage, nextImage, W, H, s_basis, x, y, acc);
     }
@@ -456,14 +462,14 @@ __global__ __launch_bounds__(kSo3Threads) void k_so3_final(const So3State* __res
 }
 
 size_t so3_scratch_bytes(int W2, int H2) {
-    const size_t nb = ((size_t)W2 * H2 + kSo3Threads - 1) / kSo3Threads;
+    const size_t nb = (size_t)so3_blocks(W2, H2);
     return 2 * sizeof(So3State) + 2 * nb * kSo3Slots * sizeof(float) + 64;
 }
 
 int launch_so3_prealign(const uint8_t* lastImage2, const uint8_t* nextImage2, int W2, int H2, Intr k2, So3Result* out, void* scratch,
                         hipStream_t s) {
-    const int nb = (W2 * H2 + kSo3Threads - 1) / kSo3Threads;
-    if (nb > kSo3MaxBlocks) return -1;
+    const int nb = so3_blocks(W2, H2);
+    if (nb < 1) return -1;   // no pixels: nothing runs and *out is not written
     So3State* st = reinterpret_cast<So3State*>(scratch);
     float* part = reinterpret_cast<float*>(st + 2);
     for (int j = 0; j < 10; ++j)   // RGBDOdometry.cpp:283: at most ten iterations

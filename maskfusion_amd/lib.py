@@ -204,6 +204,7 @@ SYMBOLS = {
     "mf_k_icp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                 C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
                                 C.c_int32, C.c_void_p, C.c_void_p]),
+    "mf_k_icp_launch_form": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

@@ -43,3 +43,19 @@ def scene_frames(n, W=640, H=480, noise=False, n_objects=0):
     f = 528.0 * W / 640.0
     st = synth.Stream(W=W, H=H, fx=f, fy=f, cx=W / 2.0, cy=H / 2.0, noise=noise, n_objects=n_objects)
     return st, [st.frame(k) for k in range(n)]
+
+
+def model_maps(oracle, st, depth):
+    """Model-side float4 maps as the oracle builds them from a (fake) prediction = back-projection of `depth` (as test_gpu_kernels.py's)."""
+    H, W = depth.shape
+    v = oracle.create_vmap(depth, st.fx, st.fy, st.cx, st.cy, 20.0)
+    n = oracle.create_nmap(v)
+    v4 = np.zeros((H, W, 4), np.float32)
+    n4 = np.zeros((H, W, 4), np.float32)
+    valid = ~np.isnan(v[0]) & ~np.isnan(n[0])
+    for c in range(3):
+        v4[..., c] = np.where(valid, v[c], 0)
+        n4[..., c] = np.where(valid, n[c], 0)
+    v4[..., 3] = 1
+    n4[..., 3] = 0.01
+    return v4, n4
