@@ -73,12 +73,7 @@ struct ModelState : SurfelBufferState {
     float* d_icp_log = nullptr;            // [20][32] reduced systems of the model's last tracking step, one row per iteration (debug tap "icp_log")
     double* d_gn_trace = nullptr;          // [20][kGnTraceRow] systems in fp64 + the state every iteration used (debug tap "gn_trace"; geometric loop)
     // object models: private scratch of the surfel passes, so that the passes of ALL objects of a frame can be one launch each ("batchObjectPasses")
-    struct ObjScratch {
-        unsigned long long* keys = nullptr; int* index = nullptr; float4* ivc = nullptr; float4* inr = nullptr; float4* iclean = nullptr;
-        uint8_t* cand_op = nullptr; float4* cand_rec = nullptr; int* upd_first = nullptr; int* cand_best = nullptr;
-        int* clean_ctl = nullptr;
-        uint8_t* flags = nullptr; float* newconf = nullptr; int* block_counts = nullptr;   // the two-launch clean form (small maps)
-    } scr;
+    SurfelScratch scr = {};                // (ensure_obj_scratch; empty until then)
     float* d_poselog = nullptr;            // Model::poseLog on the device: ring of [cap][8] floats (t, q xyzw, pad)
     std::vector<int64_t> log_ts;           // timestamps of the entries (host side of PoseLogItem)
     PoseDev* h_pose = nullptr; FrameDev* h_frame = nullptr; int* h_count = nullptr;
@@ -245,7 +240,7 @@ struct mf_ctx {
     int W, H, P;
     Intr K;
     hipStream_t stream = nullptr;      // the frame's chain: preprocessing, tracking, fusion, prediction
-    bool iclean_is_tap16 = false;                      // the form d_iclean holds (debug tap "index_packed")
+    bool iclean_is_tap16 = false;                      // the form scr.iclean holds (debug tap "index_packed")
     hipEvent_t ev_labels = nullptr;                    // the label stage of this frame has written its result words
     long frame_no = 0;
     long bg_fused_frame = -1;          // mf_fuse_background has fused the background of this staged frame (mf_fuse_models then skips it)
@@ -256,7 +251,7 @@ struct mf_ctx {
     bool map_ready = false;            // the background map exists (first frame processed, Model::initialise or an uploaded map)
     bool tracked_once = false;         // a tracking step has run (its stage timings are meaningful)
     static constexpr int kObjArgSlots = 8;             // argument arrays of the batched launches: pinned staging + device copy, a small ring (two per frame)
-    ObjPassArgs* d_obj_args[kObjArgSlots] = {}; ObjPassArgs* h_obj_args[kObjArgSlots] = {}; hipEvent_t ev_obj_args[kObjArgSlots] = {};
+    PassModel* d_obj_args[kObjArgSlots] = {}; PassModel* h_obj_args[kObjArgSlots] = {}; hipEvent_t ev_obj_args[kObjArgSlots] = {};
     unsigned obj_arg_slot = 0;
     // "objectStream": inside mf_process_frame the batched passes of the object models (fuse / clean chain, prediction) go to a stream of their own
     // and run BESIDE the background's chain on the main stream -- the two touch disjoint buffers (an object model's private scratch, its own maps) and
@@ -317,16 +312,9 @@ struct mf_ctx {
     std::vector<RetiredLog> retired;
     float* d_retired = nullptr; size_t retired_cap = 0, retired_used = 0;   // [retired_cap][8] floats
     std::vector<std::unique_ptr<ModelState>> pool;   // MaskFusion::preallocatedModels (buffers allocated ahead of the spawn)
-    unsigned long long* d_keys = nullptr;
-    int* d_index = nullptr; float4* d_ivc = nullptr; float4* d_ict = nullptr; float4* d_inr = nullptr;
-    float4* d_iclean = nullptr;            // packed column-major index map of the clean pass: 2 x float4 per texel (the spare word carries the filtered depth),
-                                           // or one float4 per texel (16-byte taps, "cleanTap16") in its first half
-    uint8_t* d_maskT = nullptr;            // the frame's mask in the same column-major order (launch_index_resolve writes it, clean reads it)
-    uint8_t* d_cand_op = nullptr; float4* d_cand_rec = nullptr; int* d_upd_first = nullptr;
-    uint8_t* d_flags = nullptr; float* d_newconf = nullptr; int* d_block_counts = nullptr;
-    int* d_cand_best = nullptr;            // surfel a merge candidate was associated with (fuse_data -> fuse_update)
-    int* d_clean_ctl = nullptr;            // Model::clean in place (mf_surfel.hip): finished-workgroup counter of k_clean_runs
-    int* d_clean_list = nullptr; int* d_clean_count = nullptr;   // ... the runs it has to visit (k_cull_clean)
+    SurfelScratch scr = {};                // the shared scratch of the surfel passes (mf_internal.h); scr.keys is also GlobalProjection's key image
+    uint8_t* d_maskT = nullptr;            // the frame's mask in the packed map's column-major order (launch_index_resolve_packed writes it, clean reads it)
+    int* d_clean_list = nullptr; int* d_clean_count = nullptr;   // Model::clean in place (mf_surfel.hip): the runs it has to visit (k_cull_clean)
     int* d_decay_stats = nullptr;          // ... and the frame's mask-disagreement depth ranges the culling rests on (ResolveOut::decay_stats), armed between frames
     int* d_run_offs = nullptr;             // compaction of a sparse buffer (launch_densify): exclusive scan of the run lengths
     // visibility list of the projection passes (Surfels::box, k_cull): the runs of ONE buffer that can be in view under ONE pose; vis_tag says whose
@@ -440,33 +428,36 @@ static int surfel_capacity(int num) {  // Model::TEXTURE_DIMENSION_*^2 (Core/Mod
     return dim * dim;
 }
 
+// One set of the surfel passes' scratch (mf_internal.h: SurfelScratch) for maps of up to `cap` surfels: the context's shared set (with_ict) and an
+// object model's own
+static int alloc_surfel_scratch(mf_ctx* c, std::vector<void*>& owner, size_t cap, bool with_ict, SurfelScratch& scr) {
+    const size_t P = (size_t)c->P;
+    int rc;
+#define A(call) do { rc = (call); if (rc != MF_OK) return rc; } while (0)
+    A(dev_alloc(c, owner, &scr.keys, P, 0xFF));
+    A(dev_alloc(c, owner, &scr.index, P));
+    A(dev_alloc(c, owner, &scr.ivc, P));
+    A(dev_alloc(c, owner, &scr.inr, P));
+    if (with_ict) A(dev_alloc(c, owner, &scr.ict, P));
+    A(dev_alloc(c, owner, &scr.iclean, P * 2));
+    A(dev_alloc(c, owner, &scr.cand_op, P));
+    A(dev_alloc(c, owner, &scr.cand_rec, P * 3));
+    A(dev_alloc(c, owner, &scr.upd_first, cap));
+    A(dev_alloc(c, owner, &scr.cand_best, P));
+    A(dev_alloc(c, owner, &scr.clean_ctl, (size_t)kCleanCtlInts));
+    A(dev_alloc(c, owner, &scr.flags, cap + P));
+    A(dev_alloc(c, owner, &scr.newconf, cap + P));
+    A(dev_alloc(c, owner, &scr.block_counts, (size_t)kCompactBlocks));
+#undef A
+    launch_fill_int(scr.upd_first, kNoUpdate, (int)cap, c->stream);
+    return MF_OK;
+}
 // Model::Model (Core/Model/Model.cpp:115-223): buffers of one model
 // An object model's private scratch of the batched surfel passes: its own index maps / key image / candidate records, 141 B per pixel + 9 B per
 // surfel slot (43 MB at VGA, 173 MB at 1280x960).  Only the batched passes ("batchObjectPasses", >= 2 objects) touch it, so it is allocated when
 // a model first takes part in one -- or ahead of time for preallocated models, whose point is that nothing is allocated at spawn time
 // (every object model used to carry it from its creation on, batched or not).
-static int ensure_obj_scratch(mf_ctx* c, ModelState& m) {
-    if (m.scr.keys) return MF_OK;
-    const size_t P = (size_t)c->P, cap = (size_t)m.cap;
-    int rc;
-#define A(call) do { rc = (call); if (rc != MF_OK) return rc; } while (0)
-    A(dev_alloc(c, m.allocs, &m.scr.keys, P, 0xFF));
-    A(dev_alloc(c, m.allocs, &m.scr.index, P));
-    A(dev_alloc(c, m.allocs, &m.scr.ivc, P));
-    A(dev_alloc(c, m.allocs, &m.scr.inr, P));
-    A(dev_alloc(c, m.allocs, &m.scr.iclean, P * 2));
-    A(dev_alloc(c, m.allocs, &m.scr.cand_op, P));
-    A(dev_alloc(c, m.allocs, &m.scr.cand_rec, P * 3));
-    A(dev_alloc(c, m.allocs, &m.scr.upd_first, cap));
-    A(dev_alloc(c, m.allocs, &m.scr.cand_best, P));
-    A(dev_alloc(c, m.allocs, &m.scr.clean_ctl, (size_t)kCleanCtlInts));
-    A(dev_alloc(c, m.allocs, &m.scr.flags, cap + P));
-    A(dev_alloc(c, m.allocs, &m.scr.newconf, cap + P));
-    A(dev_alloc(c, m.allocs, &m.scr.block_counts, (size_t)kCompactBlocks));
-#undef A
-    launch_fill_int(m.scr.upd_first, kNoUpdate, (int)cap, c->stream);
-    return MF_OK;
-}
+static int ensure_obj_scratch(mf_ctx* c, ModelState& m) { return m.scr.keys ? MF_OK : alloc_surfel_scratch(c, m.allocs, (size_t)m.cap, false, m.scr); }
 
 static int create_model(mf_ctx* c, int id, float confThr, bool allowFillIn, int cap, std::unique_ptr<ModelState>& out, bool with_scratch = false) {
     std::unique_ptr<ModelState> m(new ModelState());
@@ -633,24 +624,11 @@ extern "C" int mf_create(const mf_config* cfg, mf_ctx** out) {
         A(dev_alloc(c, c->allocs, &c->d_splat_rec1, maxcap));
         A(dev_alloc(c, c->allocs, &c->d_splat_bbox, maxcap));
     }
-    A(dev_alloc(c, c->allocs, &c->d_keys, (size_t)P, 0xFF));
-    A(dev_alloc(c, c->allocs, &c->d_index, (size_t)P));
-    A(dev_alloc(c, c->allocs, &c->d_ivc, (size_t)P));
-    A(dev_alloc(c, c->allocs, &c->d_ict, (size_t)P));
-    A(dev_alloc(c, c->allocs, &c->d_iclean, (size_t)P * 2));
+    A(alloc_surfel_scratch(c, c->allocs, (size_t)c->cap_max, true, c->scr));
     A(dev_alloc(c, c->allocs, &c->d_maskT, (size_t)P));
     A(dev_alloc(c, c->allocs, &c->d_maskT_obj, (size_t)P));
     A(dev_alloc(c, c->allocs, &c->d_depthT, (size_t)P));
     A(dev_alloc(c, c->allocs, &c->d_depthT_obj, (size_t)P));
-    A(dev_alloc(c, c->allocs, &c->d_inr, (size_t)P));
-    A(dev_alloc(c, c->allocs, &c->d_cand_op, (size_t)P));
-    A(dev_alloc(c, c->allocs, &c->d_cand_rec, (size_t)P * 3));
-    A(dev_alloc(c, c->allocs, &c->d_upd_first, (size_t)c->cap_max));
-    A(dev_alloc(c, c->allocs, &c->d_flags, (size_t)c->cap_max + P));
-    A(dev_alloc(c, c->allocs, &c->d_newconf, (size_t)c->cap_max + P));
-    A(dev_alloc(c, c->allocs, &c->d_block_counts, (size_t)kCompactBlocks));
-    A(dev_alloc(c, c->allocs, &c->d_cand_best, (size_t)P));
-    A(dev_alloc(c, c->allocs, &c->d_clean_ctl, (size_t)kCleanCtlInts));
     A(dev_alloc(c, c->allocs, &c->d_row_z, (size_t)(c->H + (c->H >> 1) + (c->H >> 2))));
     c->vis_max_runs = (int)run_table_runs((long)c->cap_max, (long)P);
     A(dev_alloc(c, c->allocs, &c->d_vis_list, (size_t)c->vis_max_runs));
@@ -671,7 +649,6 @@ extern "C" int mf_create(const mf_config* cfg, mf_ctx** out) {
     A(host_alloc(c, &c->h_depth, (size_t)P));
     A(host_alloc(c, &c->h_mask, (size_t)P));
     A(host_alloc(c, &c->h_full, (size_t)P));
-    launch_fill_int(c->d_upd_first, kNoUpdate, c->cap_max, c->stream);
     // globalModel = Model(getNextModelID(true), initConfidenceGlobal, fillIn = true) (Core/MaskFusion.cpp:80)
     std::unique_ptr<ModelState> bg;
     A(create_model(c, c->nextID++, cfg->conf_global, true, cap_bg, bg));
@@ -688,8 +665,8 @@ extern "C" int mf_create(const mf_config* cfg, mf_ctx** out) {
         if (hipEventCreate(&c->ev_mm[i]) != hipSuccess) return fail(MF_EHIP);
     if (hipEventCreate(&c->ev_icp_mid) != hipSuccess) return fail(MF_EHIP);
     for (int i = 0; i < mf_ctx::kObjArgSlots; ++i) {
-        if (hipMalloc((void**)&c->d_obj_args[i], sizeof(ObjPassArgs) * 64) != hipSuccess ||
-            hipHostMalloc((void**)&c->h_obj_args[i], sizeof(ObjPassArgs) * 64) != hipSuccess ||
+        if (hipMalloc((void**)&c->d_obj_args[i], sizeof(PassModel) * 64) != hipSuccess ||
+            hipHostMalloc((void**)&c->h_obj_args[i], sizeof(PassModel) * 64) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_obj_args[i], hipEventDisableTiming) != hipSuccess)
             return fail(MF_ENOMEM);
     }
@@ -1144,15 +1121,15 @@ static int debug_read_impl(mf_ctx* c, ModelState& mdl, const char* what, void* o
     else if (w == "pred_normal") { src = mdl.d_predN; bytes = P * 16; }
     else if (w == "pred_image") { src = mdl.d_predImage; bytes = P * 4; }
     else if (w == "pred_time") { src = mdl.d_predTime; bytes = P * 2; }
-    else if (w == "index") { src = c->d_index; bytes = P * 4; }
-    else if (w == "index_vc") { src = c->d_ivc; bytes = P * 16; }
-    else if (w == "index_nr") { src = c->d_inr; bytes = P * 16; }
-    else if (w == "index_ct") { src = c->d_ict; bytes = P * 16; }
-    else if (w == "index_packed") { src = c->d_iclean; bytes = c->iclean_is_tap16 ? P * 16 : P * 32; variable = true; }
-    else if (w == "cand_op") { src = c->d_cand_op; bytes = P; variable = true; }
-    else if (w == "cand_rec") { src = c->d_cand_rec; bytes = P * 48; variable = true; }
-    else if (w == "clean_flags") { src = c->d_flags; bytes = (size_t)c->cap_max + P; variable = true; }
-    else if (w == "clean_newconf") { src = c->d_newconf; bytes = ((size_t)c->cap_max + P) * 4; variable = true; }
+    else if (w == "index") { src = c->scr.index; bytes = P * 4; }
+    else if (w == "index_vc") { src = c->scr.ivc; bytes = P * 16; }
+    else if (w == "index_nr") { src = c->scr.inr; bytes = P * 16; }
+    else if (w == "index_ct") { src = c->scr.ict; bytes = P * 16; }
+    else if (w == "index_packed") { src = c->scr.iclean; bytes = c->iclean_is_tap16 ? P * 16 : P * 32; variable = true; }
+    else if (w == "cand_op") { src = c->scr.cand_op; bytes = P; variable = true; }
+    else if (w == "cand_rec") { src = c->scr.cand_rec; bytes = P * 48; variable = true; }
+    else if (w == "clean_flags") { src = c->scr.flags; bytes = (size_t)c->cap_max + P; variable = true; }
+    else if (w == "clean_newconf") { src = c->scr.newconf; bytes = ((size_t)c->cap_max + P) * 4; variable = true; }
     else if (w == "icp_log") { src = mdl.d_icp_log; bytes = 19 * 32 * 4; }
     else if (w == "gn_trace") { src = mdl.d_gn_trace; bytes = 20 * kGnTraceRow * 8; }
     else if (w == "icp_prof") { src = c->d_icp_prof; bytes = 19 * 16 * 8; }

@@ -326,119 +326,134 @@ static void after_clean(mf_ctx* c, ModelState& m, bool in_place, int live) {
     if (in_place) m.cleaned_in_place(cand_max(c), new_runs_max(c));
     else m.became_dense(live);
 }
-// the arguments every clean form of model m shares (shared scratch of the single-model path)
-// tap16: the packed map holds the 16-byte taps a resolve pass of the SAME enqueue wrote with this model's threshold and tick
+// What a frame's surfel passes share (mf_internal.h: PassFrame), for the model-by-model launches and for the object batch alike.
+// tap16: the packed maps hold the 16-byte taps a resolve pass of the SAME enqueue writes, with each model's threshold and tick.  s: the stream the
+// passes run on -- the object stream has frame planes of its own
+static PassFrame pass_frame(const mf_ctx* c, const uint8_t* d_rgb, const float* d_depth, const float* depthF, const uint8_t* mask, bool tap16, hipStream_t s) {
+    const mf_config& g = c->cfg;
+    PassFrame f;
+    f.W = c->W; f.H = c->H; f.k = c->K; f.maxDepthProcessed = g.max_depth_processed; f.globalMaxDepth = g.depth_cutoff; f.timeDelta = g.time_delta;
+    f.outlierCoeff = g.outlier_coefficient; f.cleanLiteral = c->sw.clean_literal ? 1 : 0; f.bboxLimit = c->sw.bbox_limit ? 1 : 0;
+    f.fuseLanes = c->sw.fuse_lanes; f.cleanTapGroup = c->sw.clean_tap_group;
+    f.rgb = d_rgb; f.depthRaw = d_depth; f.depthF = depthF; f.mask = mask; f.bg_pose = c->models[0]->d_pose;
+    f.maskT = s == c->stream ? c->d_maskT : c->d_maskT_obj; f.depthT = !tap16 ? nullptr : s == c->stream ? c->d_depthT : c->d_depthT_obj;
+    f.global_keys = c->scr.keys;
+    return f;
+}
+// ... and what model m brings (PassModel) with the scratch it works in: the context's shared set, or its own in the batch.  Taken AFTER the
+// frame's compactions: they change the live buffer.  (log_slot / global_payload: filled by make_obj_batch, the only path that reads them)
+static PassModel pass_model(mf_ctx* c, ModelState& m, const SurfelScratch& scr, float weightMultiplier, float depthCutoff) {
+    PassModel a;
+    a.a = m.surf[m.cur]; a.b = m.surf[1 - m.cur];
+    a.frame = m.d_frame; a.pose = m.d_pose;
+    // Model::fuse maxDepth uniform: min(depthCutoff, model.maxDepth, bb_max_z) (Model.cpp:527); bb_max_z from the model's bounding box on the device
+    a.maskID = m.id; a.confThreshold = m.confThr; a.fuseMaxDepth = fminf(depthCutoff, m.maxDepth); a.weightMultiplier = weightMultiplier;
+    a.scr = scr; a.host_count = m.h_count;
+    a.host_append = append_mirror_fits(c, m) ? m.h_append : nullptr; a.clean_seq = m.clean_seq + 1;     // (after_clean counts the pass)
+    a.predV = m.d_predV; a.predN = m.d_predN; a.predImage = m.d_predImage; a.predTime = m.d_predTime; a.predGray = photometric_on(c) ? m.d_predGray : nullptr;
+    a.host_frame = m.h_frame; a.log_slot = nullptr; a.global_payload = 0;
+    return a;
+}
 // A frame without a mask (mf_process_frame of a single-model context: every byte of c->d_zero_mask is 0) cannot disagree with the background, id 0:
 // with 16-byte taps the resolve pass then leaves the planes depthT / maskT alone and the clean pass reads neither ("maskFreeClean")
 static bool mask_free(const mf_ctx* c, const ModelState& m, const uint8_t* mask, bool tap16) {
     return c->sw.mask_free_clean && tap16 && mask == c->d_zero_mask && m.id == 0;
 }
-static CleanIn clean_in(mf_ctx* c, ModelState& m, int time_delta, bool packed, const float* depthF, const uint8_t* mask, bool tap16 = false) {
-    CleanIn in;
-    in.frame = m.d_frame; in.pose = m.d_pose; in.W = c->W; in.H = c->H; in.k = c->K; in.timeDelta = time_delta; in.confThreshold = m.confThr;
-    in.outlierCoeff = c->cfg.outlier_coefficient; in.maskID = m.id;
-    in.index = c->d_index; in.vc = c->d_ivc; in.ct = c->d_ict; in.packed = packed ? c->d_iclean : nullptr; in.maskT = c->d_maskT;
-    in.tap16 = packed && tap16; in.tapGroup = c->sw.clean_tap_group; in.maskFree = mask_free(c, m, mask, in.tap16);
-    in.depthT = in.tap16 && !in.maskFree ? c->d_depthT : nullptr;
-    in.depthF = depthF; in.mask = mask; in.cand_op = c->d_cand_op; in.cand_rec = c->d_cand_rec;
-    in.flags = c->d_flags; in.newconf = c->d_newconf; in.block_counts = c->d_block_counts; in.host_count = m.h_count;
-    in.host_append = append_mirror_fits(c, m) ? m.h_append : nullptr; in.seq = m.clean_seq + 1;     // (after_clean counts the pass)
-    in.transposed = packed; in.literalWindow = c->sw.clean_literal;
-    return in;
+// The clean pass of a model handled on its own where no packed map was written for it (a freshly spawned model's first clean -- no second index
+// pass --, the model API without "modelApiPacked"): the window reads the row-major index / vertConf / colorTime images of the first index pass
+static CleanArgs unpacked(CleanArgs a) {
+    a.packed = nullptr; a.transposed = 0;
+    return a;
 }
-// Model::clean of m in place (m has a run table): the buffer's own surfels run by run, then the frame's candidates appended.  cull: visit only the
-// runs in which a rule of the pass can apply (k_cull_clean; needs the decay statistics of THIS frame's packed resolve pass) -- the background;
-// an object model's launch visits every run (its bounding box is the box of all its drawn surfels)
-static void enqueue_clean_in_place(mf_ctx* c, ModelState& m, const CleanIn& in, bool cull, bool timed = false) {
+// Model::clean of m in place (m has a run table; a: a.src = a.dst = its buffer): the buffer's own surfels run by run, then the frame's candidates
+// appended.  cull: visit only the runs in which a rule of the pass can apply (k_cull_clean; needs the decay statistics of THIS frame's packed
+// resolve pass) -- the background; an object model's launch visits every run (its bounding box is the box of all its drawn surfels)
+static void enqueue_clean_in_place(mf_ctx* c, ModelState& m, const CleanArgs& a, bool cull, bool timed = false) {
     VisList cl{c->d_clean_list, c->d_clean_count};
     {
         PassTimer t(c, timed ? MF_PASS_BG_CLEAN : -1);
         if (cull)
-            launch_cull_clean(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, in.timeDelta, in.confThreshold, c->d_decay_stats, c->d_clean_list,
+            launch_cull_clean(a.src, a.frame, a.pose, a.W, a.H, a.k, a.timeDelta, a.confThreshold, c->d_decay_stats, c->d_clean_list,
                               c->d_clean_count, c->d_cull_ctl, (int)run_table_runs((long)m.cap, (long)c->P), c->stream);
-        launch_clean_runs(in, m.surf[m.cur], cull ? &cl : nullptr, c->d_clean_ctl, clean_runs_grid((long)*m.h_count + kRun), c->stream);
+        launch_clean_runs(a, cull ? &cl : nullptr, clean_runs_grid((long)*m.h_count + kRun), c->stream);
     }
     PassTimer t(c, timed ? MF_PASS_BG_APPEND : -1);
-    launch_clean_append(in, m.surf[m.cur], c->stream);
+    launch_clean_append(a, c->stream);
 }
 
 // predictIndices -> fuse -> [predictIndices] -> clean for one model (Core/MaskFusion.cpp:541-563 / :344-353)
 static int enqueue_fuse_clean(mf_ctx* c, ModelState& m, const uint8_t* d_rgb, const float* d_depth, const float* depthF,
                               const uint8_t* mask, float fuseDepthCutoff, float weightMultiplier, bool secondIndexPass, bool marks) {
-    const mf_config& g = c->cfg;
-    const int W = c->W, H = c->H;
     hipStream_t s = c->stream;
     // Which forms a model's passes take is a matter of its size alone (mf_context.hip: in_place_elements / big_map_elements); the results are the same.
     ModelState* const one = &m;
     CleanForm form;
     int rc = prepare_clean(c, &one, 1, !clean_small(c, m), form);
     if (rc != MF_OK) return rc;
-    const int src = m.cur, dst = 1 - m.cur;
     const int blocks = surfel_blocks(c, m);
     const bool timed = m.id == 0;       // "passTimings": the background's passes one by one
     // the pass that feeds clean writes 16-byte taps: resolve and clean are enqueued here, with one tick and one threshold
     const bool tap16 = c->sw.clean_tap16 && secondIndexPass;
-    float* const depthT = tap16 ? c->d_depthT : nullptr;
     if (secondIndexPass) c->iclean_is_tap16 = tap16;
+    // the same two structs the object batch fills (make_obj_batch), with the context's shared scratch
+    const PassFrame f = pass_frame(c, d_rgb, d_depth, depthF, mask, tap16, s);
+    const PassModel pm = pass_model(c, m, c->scr, weightMultiplier, fuseDepthCutoff);
+    const bool maskFree = mask_free(c, m, mask, tap16);
     VisList vl;
     const VisList* vis = nullptr;
     {
         PassTimer t(c, timed ? MF_PASS_BG_INDEX : -1);
         vis = ensure_vis(c, m, vl);
         // (column-major key images in both index passes of a model handled on its own: index_scatter_one; the resolve of this pass transposes)
-        launch_index_scatter(m.surf[src], m.d_frame, m.d_pose, W, H, c->K, g.max_depth_processed, g.time_delta, c->d_keys, true, s, blocks, vis);
-        launch_index_resolve(m.surf[src], m.d_frame, m.d_pose, c->d_keys, W, H, c->d_index, c->d_ivc, c->d_inr, secondIndexPass ? nullptr : c->d_ict,
-                             nullptr, nullptr, nullptr, nullptr, true, s);
+        launch_index_scatter(pm.a, f, pm, s, blocks, vis);
+        launch_index_resolve_maps(pm.a, f, pm, !secondIndexPass, s);
     }
     if (marks) mark(c, 4);
-    // Model::fuse maxDepth uniform: min(depthCutoff, model.maxDepth, bb_max_z) (Model.cpp:527); bb_max_z from the model's bounding box on the device
     {
         PassTimer t(c, timed ? MF_PASS_BG_FUSE_DATA : -1);
-        launch_fuse_data(d_rgb, d_depth, depthF, mask, m.id, m.d_frame, m.d_pose, weightMultiplier, fminf(fuseDepthCutoff, m.maxDepth), W, H,
-                         c->K, c->d_index, c->d_ivc, c->d_inr, c->d_cand_op, c->d_cand_rec, c->d_upd_first, c->d_cand_best, s, c->sw.bbox_limit ? 1 : 0, c->sw.fuse_lanes);
+        launch_fuse_data(fuse_data_args(f, pm), f.fuseLanes, s);
     }
     if (marks) mark(c, 5);
     // the in-place clean of the background visits only the runs its rules can touch (k_cull_clean); the resolve pass that feeds clean gathers
     // the frame's statistics for that test
     const bool in_place = form.in_place, cull_clean = in_place && c->sw.cull_runs && secondIndexPass && m.id == 0;
-    int live = src;      // the buffer that holds the updated surfels
+    int live = m.cur;      // the buffer that holds the updated surfels
     if (form.update_copy) {
-        // small map (rounds 1-4's pass): update.vert as a copy src -> dst with the second index scatter (:556) riding on it; clean goes
-        // dst -> src: two swaps leave the live buffer where it was
+        // small map (rounds 1-4's pass): update.vert as a copy a -> b with the second index scatter (:556) riding on it; clean goes
+        // b -> a: two swaps leave the live buffer where it was
         {
             PassTimer t(c, timed ? MF_PASS_BG_FUSE_UPDATE : -1);
-            launch_fuse_update_copy(m.surf[src], m.surf[dst], m.d_frame, c->d_upd_first, c->d_cand_rec, m.d_pose, W, H, c->K, g.max_depth_processed,
-                                    g.time_delta, secondIndexPass ? c->d_keys : nullptr, true, s, blocks);
+            launch_fuse_update_copy(pm.a, pm.b, f, pm, secondIndexPass, s, blocks);
         }
-        live = dst;
+        live = 1 - m.cur;
         if (marks) mark(c, 6);
         if (secondIndexPass) {
             PassTimer t(c, timed ? MF_PASS_BG_INDEX2 : -1);
-            launch_index_resolve(m.surf[live], m.d_frame, m.d_pose, c->d_keys, W, H, nullptr, nullptr, nullptr, nullptr, c->d_iclean, depthF, mask, c->d_maskT, true, s,
-                                 nullptr, 0, depthT, m.confThr, mask_free(c, m, mask, tap16));
+            launch_index_resolve_packed(m.surf[live], f, pm, s, maskFree);
         }
     } else {
         // update.vert in place -- only the surfels a candidate merged into are touched (the reference copies the whole buffer,
         // Model.cpp:583-646) --, then the second index pass (over the runs in view where the buffer has a run table)
         {
             PassTimer t(c, timed ? MF_PASS_BG_FUSE_UPDATE : -1);
-            launch_fuse_update(m.surf[src], m.d_frame, c->d_upd_first, c->d_cand_op, c->d_cand_best, c->d_cand_rec, W, H, s);
+            launch_fuse_update(pm.a, f, pm, s);
         }
         if (marks) mark(c, 6);
         if (secondIndexPass) {   // predictIndices on the updated buffer (:556); its resolve writes the packed, column-major map of clean's window gathers
             PassTimer t(c, timed ? MF_PASS_BG_INDEX2 : -1);
-            launch_index_scatter(m.surf[src], m.d_frame, m.d_pose, W, H, c->K, g.max_depth_processed, g.time_delta, c->d_keys, true, s, blocks, vis);
-            launch_index_resolve(m.surf[src], m.d_frame, m.d_pose, c->d_keys, W, H, nullptr, nullptr, nullptr, nullptr, c->d_iclean, depthF, mask, c->d_maskT, true, s,
-                                 cull_clean ? c->d_decay_stats : nullptr, m.id, depthT, m.confThr, mask_free(c, m, mask, tap16));
+            launch_index_scatter(pm.a, f, pm, s, blocks, vis);
+            launch_index_resolve_packed(pm.a, f, pm, s, maskFree, cull_clean ? c->d_decay_stats : nullptr);
         }
     }
     // clean: two launches live -> the other buffer (a dense copy) below big_map_elements; from there on in place, run by run
-    const CleanIn in = clean_in(c, m, g.time_delta, secondIndexPass, depthF, mask, tap16);
+    const int clean_dst = in_place ? live : 1 - live;
+    CleanArgs a = clean_args(f, pm, m.surf[live], m.surf[clean_dst], 0, maskFree);
+    if (!secondIndexPass) a = unpacked(a);
     if (in_place) {
-        enqueue_clean_in_place(c, m, in, cull_clean, timed);
+        enqueue_clean_in_place(c, m, a, cull_clean, timed);
     } else {
         PassTimer t(c, timed ? MF_PASS_BG_CLEAN : -1);
-        launch_clean_small(in, m.surf[live], m.surf[1 - live], s, compact_blocks_for((long)*m.h_count + cand_max(c)));
+        launch_clean_small(a, s, compact_blocks_for((long)*m.h_count + cand_max(c)));
     }
     after_clean(c, m, in_place, 1 - live);
     return MF_OK;
@@ -467,9 +482,9 @@ static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advanc
     }
     if (filter) launch_bilateral(filter->depth, filter->out, c->W, c->H, c->stream);   // (not reached: a deferred prediction is a tiled one)
     launch_splat_scatter(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, c->cfg.max_depth_processed, m.confThr,
-                         c->cfg.time_delta, c->d_keys, c->stream, surfel_blocks(c, m));
+                         c->cfg.time_delta, c->scr.keys, c->stream, surfel_blocks(c, m));
     const bool gray = photometric_on(c) ;
-    launch_splat_resolve(m.surf[m.cur], m.d_pose, c->d_keys, c->W, c->H, c->K, m.d_predV, m.d_predN, m.d_predImage, m.d_predTime,
+    launch_splat_resolve(m.surf[m.cur], m.d_pose, c->scr.keys, c->W, c->H, c->K, m.d_predV, m.d_predN, m.d_predImage, m.d_predTime,
                          m.d_frame, c->cur_rgb, gray ? m.d_predGray : nullptr, gray ? m.d_fillGray : nullptr, c->stream, c->sw.ftf_rgb ? 1 : 0);
     if (advance) launch_frame_advance(m.d_frame, c->W, c->H, advance->host_mirror, m.d_pose, advance->bg_pose, advance->log_slot, c->stream);
 }
@@ -499,39 +514,27 @@ static void settle(mf_ctx* c) {
 static int make_obj_batch(mf_ctx* c, const std::vector<ModelState*>& ms, const std::vector<int>& orders, const uint8_t* d_rgb, const float* d_depth,
                           const float* depthF, const uint8_t* mask, float weightMultiplier, const std::vector<float*>* log_slots, ObjBatch& b, int& blocks,
                           hipStream_t s = nullptr) {
-    const mf_config& g = c->cfg;
     if (!s) s = c->stream;
     const int slot = (int)(c->obj_arg_slot++ % mf_ctx::kObjArgSlots);
     MF_HIP(c, hipEventSynchronize(c->ev_obj_args[slot]));
-    ObjPassArgs* h = c->h_obj_args[slot];
-    const bool gray = photometric_on(c);
+    PassModel* h = c->h_obj_args[slot];
     blocks = 32;
+    b.denseSprites = 0;
     for (size_t i = 0; i < ms.size(); ++i) {
         ModelState& m = *ms[i];
-        ObjPassArgs& a = h[i];
         if (!m.scr.keys) { int rc = ensure_obj_scratch(c, m); if (rc != MF_OK) return rc; }   // first batched pass of a model created at spawn time
-        a.a = m.surf[m.cur]; a.b = m.surf[1 - m.cur];
-        a.frame = m.d_frame; a.pose = m.d_pose;
-        a.maskID = m.id; a.confThreshold = m.confThr; a.fuseMaxDepth = fminf(g.depth_cutoff, m.maxDepth); a.weightMultiplier = weightMultiplier;
-        a.keys = m.scr.keys; a.index = m.scr.index; a.ivc = m.scr.ivc; a.inr = m.scr.inr; a.iclean = m.scr.iclean;
-        a.cand_op = m.scr.cand_op; a.cand_rec = m.scr.cand_rec; a.upd_first = m.scr.upd_first; a.cand_best = m.scr.cand_best;
-        a.clean_ctl = m.scr.clean_ctl; a.host_count = m.h_count;
-        a.host_append = append_mirror_fits(c, m) ? m.h_append : nullptr; a.clean_seq = m.clean_seq + 1;
-        a.flags = m.scr.flags; a.newconf = m.scr.newconf; a.block_counts = m.scr.block_counts;
-        a.predV = m.d_predV; a.predN = m.d_predN; a.predImage = m.d_predImage; a.predTime = m.d_predTime; a.predGray = gray ? m.d_predGray : nullptr;
-        a.host_frame = m.h_frame; a.log_slot = log_slots ? (*log_slots)[i] : nullptr;
-        a.global_payload = ((unsigned)orders[i] << 8) | ((unsigned)m.id & 255u);
+        h[i] = pass_model(c, m, m.scr, weightMultiplier, c->cfg.depth_cutoff);
+        h[i].log_slot = log_slots ? (*log_slots)[i] : nullptr;
+        h[i].global_payload = ((unsigned)orders[i] << 8) | ((unsigned)m.id & 255u);
         blocks = std::max(blocks, surfel_blocks(c, m));
+        if ((long)*m.h_count >= (long)c->sw.in_place_elements) b.denseSprites = 1;
     }
-    MF_HIP(c, hipMemcpyAsync(c->d_obj_args[slot], h, sizeof(ObjPassArgs) * ms.size(), hipMemcpyHostToDevice, s));
+    MF_HIP(c, hipMemcpyAsync(c->d_obj_args[slot], h, sizeof(PassModel) * ms.size(), hipMemcpyHostToDevice, s));
     MF_HIP(c, hipEventRecord(c->ev_obj_args[slot], s));
+    // (ObjBatch IS a PassFrame, so that the kernels read b.W and hand b to the builders as it is: the frame part is assigned through the base)
+    static_cast<PassFrame&>(b) = pass_frame(c, d_rgb, d_depth, depthF, mask, c->sw.clean_tap16, s);
     b.m = c->d_obj_args[slot]; b.n = (int)ms.size();
-    b.W = c->W; b.H = c->H; b.k = c->K; b.maxDepthProcessed = g.max_depth_processed; b.globalMaxDepth = g.depth_cutoff; b.timeDelta = g.time_delta;
-    b.outlierCoeff = g.outlier_coefficient; b.cleanLiteral = c->sw.clean_literal ? 1 : 0; b.bboxLimit = c->sw.bbox_limit ? 1 : 0; b.cleanSmall = 0; b.updateCopy = 0;
-    b.denseSprites = 0;
-    for (ModelState* m : ms) if ((long)*m->h_count >= (long)c->sw.in_place_elements) b.denseSprites = 1;
-    b.rgb = d_rgb; b.depthRaw = d_depth; b.depthF = depthF; b.mask = mask; b.maskT = s == c->stream ? c->d_maskT : c->d_maskT_obj;
-    b.depthT = !c->sw.clean_tap16 ? nullptr : s == c->stream ? c->d_depthT : c->d_depthT_obj; b.fuseLanes = c->sw.fuse_lanes; b.cleanTapGroup = c->sw.clean_tap_group; b.bg_pose = c->models[0]->d_pose; b.global_keys = c->d_keys;
+    b.cleanSmall = 0; b.updateCopy = 0;     // (the caller's, where the fuse / clean launches run)
     return MF_OK;
 }
 // every object model of the list, with its position in the list (the GlobalProjection payload)
@@ -689,11 +692,11 @@ static void enqueue_global_projection(mf_ctx* c, ModelState& m, int order) {
         VisList vl;
         const VisList* vis = ensure_vis(c, m, vl);
         if (launch_global_tiled(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, g.depth_cutoff, 12.0f, g.time_delta, order, m.id, c->d_tile_count,
-                                c->d_tile_entries, c->tile_entries_cap, c->d_splat_rec0, c->d_splat_rec1, c->d_splat_bbox, c->d_keys, c->stream, c->sw.splat_tune,
+                                c->d_tile_entries, c->tile_entries_cap, c->d_splat_rec0, c->d_splat_rec1, c->d_splat_bbox, c->scr.keys, c->stream, c->sw.splat_tune,
                                 vis) == 0)
             return;
     }
-    launch_global_scatter(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, g.depth_cutoff, 12.0f, g.time_delta, order, m.id, c->d_keys,
+    launch_global_scatter(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, g.depth_cutoff, 12.0f, g.time_delta, order, m.id, c->scr.keys,
                           c->stream, surfel_blocks(c, m));
 }
 
@@ -948,8 +951,8 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
         c->map_ready = true;
         mark(c, 2); mark(c, 3); mark(c, 4); mark(c, 5); mark(c, 6);
         // :235-238
-        launch_init_surfels(d_rgb, d_depth, depthF, W, H, c->K, g.max_depth_processed, bg.d_frame, c->d_cand_rec, c->d_flags, s);
-        launch_compact_records(c->d_cand_rec, c->d_flags, P, bg.surf[0], bg.d_frame, c->d_block_counts, bg.h_count, s);
+        launch_init_surfels(d_rgb, d_depth, depthF, W, H, c->K, g.max_depth_processed, bg.d_frame, c->scr.cand_rec, c->scr.flags, s);
+        launch_compact_records(c->scr.cand_rec, c->scr.flags, P, bg.surf[0], bg.d_frame, c->scr.block_counts, bg.h_count, s);
         launch_run_table(bg.surf[0], bg.d_frame, s);
         bg.fresh_table(0, (long)P);
         mark(c, 7);
@@ -990,7 +993,7 @@ static int process_frame_impl(mf_ctx* c, const uint8_t* d_rgb, const float* d_de
             } else {
                 for (size_t i = 0; i < c->models.size(); ++i) enqueue_global_projection(c, *c->models[i], (int)i);
             }
-            launch_global_resolve(c->d_keys, c->d_proj_ids, P, s);
+            launch_global_resolve(c->scr.keys, c->d_proj_ids, P, s);
             if (c->sw.timings_on) (void)hipEventRecord(c->ev_mm[0], s);
             // MfSegmentation::performSegmentation, device half (MfSegmentation.cpp:149-208)
             launch_edge_map(c->d_vmap[set][0], c->d_nmap[set][0], c->d_edge, W, H, c->seg.weightDistance, c->seg.weightConvexity, s);

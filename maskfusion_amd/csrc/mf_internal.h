@@ -271,10 +271,65 @@ void launch_init_surfels(const uint8_t* rgb, const float* depthRaw, const float*
 // Grid of the four grid-stride surfel kernels below: 2048 workgroups by default; a model that is known to be small (an object model
 // of a few thousand surfels) may be launched with fewer -- the loops are grid-stride, the result does not depend on the grid.
 constexpr int kSurfelGridBlocks = 2048;
+// ---- the arguments of a frame's surfel passes: index map, data association, update, second index map, clean, prediction ----
+// Each pass exists as a launch for ONE model (mf_frame.inl: enqueue_fuse_clean, mf_model_api.inl) and as a launch for ALL object models of a
+// frame (grid.z = model, mf_surfel.hip: k_obj_*); both forms describe their work with the same three structs, filled by the same functions
+// (mf_frame.inl: pass_frame, pass_model), and build every kernel-argument struct from them with the builders below.
+// The per-model scratch of the passes.  The context owns one set, shared by the model-by-model launches (the reference's per-model passes never
+// overlap in time); an object model that takes part in the batched launches brings its own (mf_context.hip: alloc_surfel_scratch knows the sizes).
+struct SurfelScratch {
+    unsigned long long* keys;                         // [P] z-test key image, kEmptyKey between passes
+    int* index; float4* ivc; float4* inr;             // [P] row-major index map of the pass that feeds fuse
+    float4* ict;                                      // [P] its colorTime image -- the shared set only: nullptr for an object model's own
+    float4* iclean;                                   // [2 P] packed column-major index map of the pass that feeds clean: 2 x float4 per texel (the spare
+                                                      // word carries the filtered depth), or one float4 per texel (16-byte taps, "cleanTap16") in its first half
+    uint8_t* cand_op; float4* cand_rec;               // [P], [3 P] the frame's candidates (association pass)
+    int* upd_first;                                   // [capacity] winning merge candidate per surfel, kNoUpdate between passes
+    int* cand_best;                                   // [P] surfel a merge candidate was associated with (fuse_data -> fuse_update)
+    int* clean_ctl;                                   // [kCleanCtlInts] k_clean_runs' finished-workgroup counter, zero between launches
+    uint8_t* flags; float* newconf; int* block_counts;   // [capacity + P] x 2, [kCompactBlocks]: the two-launch clean form's intermediates
+};
+// What the passes of a frame share, whichever model they serve
+struct PassFrame {
+    int W, H; Intr k; float maxDepthProcessed, globalMaxDepth; int timeDelta; float outlierCoeff;
+    int cleanLiteral;                  // the clean window walked with the shader's own fp32 trip count
+    int bboxLimit;                     // object models limit their fusion depth by lastBoundingBox ("objectBoundingBoxLimit")
+    int fuseLanes;                     // lanes per candidate of the association pass: 1 or 4
+    int cleanTapGroup;                 // 16-byte taps requested together: 1, 3 (a window column) or 9 ("cleanTapGroup")
+    const uint8_t* rgb; const float* depthRaw; const float* depthF; const uint8_t* mask; const PoseDev* bg_pose;
+    uint8_t* maskT;                    // the mask in column-major order, beside the packed maps (every model's resolve writes the same bytes)
+    float* depthT;                     // != nullptr: the packed maps hold 16-byte taps, and this plane the filtered depth in column-major order (as maskT)
+    unsigned long long* global_keys;   // GlobalProjection's key image (the shared set's)
+};
+// What a model brings to them
+struct PassModel {
+    Surfels a, b;                      // live buffer when the frame's fusion starts / the other one (small models: fuse a -> b, clean b -> a; from
+                                       // inPlaceElements on: fuse in place in a, clean a -> b, then b is live; big ones: everything in place in a)
+    FrameDev* frame; PoseDev* pose;
+    int maskID; float confThreshold, fuseMaxDepth, weightMultiplier;
+    SurfelScratch scr;                 // the shared set (a model handled on its own) or the model's own (the batch)
+    int* host_count;                   // pinned mirror of the surfel count
+    unsigned long long* host_append; unsigned clean_seq;   // in place: pinned mirror of where the buffer ends after THIS clean pass, tagged with the pass's
+                                                           // sequence number (append_mirror() below); nullptr: none
+    float4* predV; float4* predN; uchar4* predImage; uint16_t* predTime; uint8_t* predGray;
+    FrameDev* host_frame; float* log_slot;
+    unsigned global_payload;           // GlobalProjection: order << 8 | id
+};
+// The surfel passes of ALL object models of a frame, one launch per pass (grid.z = model).  An object model holds a few thousand surfels: each of
+// its ~11 per-frame launches is pure launch latency (~85 us per object and frame in round 2's profile).  The batched kernels are the single-model
+// kernels' bodies called with the frame's arguments and one model's, picked from a device array by blockIdx.z.  One launch has one form:
+struct ObjBatch : PassFrame {
+    const PassModel* m; int n;
+    int denseSprites;                  // 1: a model of the batch is above inPlaceElements -- the sprite passes (prediction, GlobalProjection) run one thread
+                                       // per surfel: such a map holds sub-pixel sprites, and four lanes per surfel repeat its set-up four times
+    int updateCopy;                    // 1: every model of the batch is below inPlaceElements -- update.vert as a copy a -> b, clean b -> a
+    int cleanSmall;                    // 1: the two-launch clean form src -> dst; 0: every model of the batch has a run table -- clean in place
+};
+
+// The launches below take the key image, maps and records from m.scr, the size, limits and frame planes from f; their key images are column-major
+// (index_scatter_one; the batched object kernels scatter row-major).
 // vis: nullptr = every surfel; else the runs launch_cull found possibly visible
-void launch_index_scatter(Surfels src, const FrameDev* frame, const PoseDev* pose, int W, int H, Intr k,
-                          float maxDepth, int timeDelta, unsigned long long* keys, bool transposed /* column-major key image */, hipStream_t s,
-                          int blocks = kSurfelGridBlocks, const VisList* vis = nullptr);
+void launch_index_scatter(Surfels src, const PassFrame& f, const PassModel& m, hipStream_t s, int blocks = kSurfelGridBlocks, const VisList* vis = nullptr);
 // run table of a DENSE buffer s (slots [0, frame->count)): fixed runs of kRun slots (after Model::initialise / an uploaded map / a compaction; the
 // in-place clean pass maintains it afterwards).  refresh: s has a table -- only the entries' contents are recomputed from the surfels
 void launch_run_table(Surfels s, FrameDev* frame, hipStream_t st, bool refresh = false);
@@ -284,50 +339,74 @@ size_t run_table_entries(long capacity, long pixels);   // int4 entries of that 
 // timeDelta: their indices -> list (any order), their number -> count[0]; ctl: 2 ints, zero between launches
 void launch_cull(Surfels s, const FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth, int timeDelta, int* list, int* count,
                  int* ctl, int max_runs, hipStream_t st);
-// packed == nullptr: index / vertConf / normRad (+ colorTime if ct != nullptr) images; else one 32 B record per texel.  decay_stats (with packed,
-// optional): kDecayStats ints the pass accumulates the frame's mask-disagreement depth ranges into for launch_cull_clean (armed by
-// launch_arm_decay_stats / k_cull_clean; maskID: the model's id)
-void launch_index_resolve(Surfels src, const FrameDev* frame, const PoseDev* pose, unsigned long long* keys, int W, int H, int* index,
-                          float4* vc, float4* nr, float4* ct /*or null*/, float4* packed /*or null: the packed column-major map instead of the row-major maps*/,
-                          const float* depthF, const uint8_t* mask, uint8_t* maskT /* with packed: the frame planes that travel with it */,
-                          bool keys_transposed /* the order the scatter used */, hipStream_t s, int* decay_stats = nullptr, int maskID = 0,
-                          float* depthT = nullptr /* with packed: the 16-byte tap {x, y, z', initTime} per texel instead (z' = NaN unless index > 0, confidence >
-                          tapThreshold and z > 0, sign bit = lastTime == tick), the filtered depth in this column-major plane -- only for a clean pass enqueued
-                          with it, with the same tick and threshold */, float tapThreshold = 0.f,
-                          bool maskFree = false /* with depthT: every byte of `mask` is maskID (a frame without a mask, for the background) -- the taps are
-                          written, the planes depthT / maskT and the statistics are not touched: clean_test's mask rule cannot apply ("maskFreeClean") */);
-void launch_fuse_data(const uint8_t* rgb, const float* depthRaw, const float* depthF, const uint8_t* mask,
-                      int maskID, const FrameDev* frame, const PoseDev* pose, float weightMultiplier, float maxDepth,
-                      int W, int H, Intr k, const int* index, const float4* vc, const float4* nr, uint8_t* cand_op,
-                      float4* cand_rec, int* upd_first, int* cand_best, hipStream_t s, int bboxLimit = 1,
-                      int lanes = 4 /* lanes per candidate: 1 or 4 (a quad shares the 3 x 3 window, one column per lane) */);
-// update.vert IN PLACE: one thread per candidate, the winning candidate of a surfel (upd_first) merges into it where it stands
-void launch_fuse_update(Surfels s, const FrameDev* frame, int* upd_first, const uint8_t* cand_op, const int* cand_best, const float4* cand_rec,
-                        int W, int H, hipStream_t st);
-// the same as a copy src -> dst over the whole buffer; keys_or_null != nullptr: the index-map scatter of the pass that feeds clean rides on it
-// (the form for small maps)
-void launch_fuse_update_copy(Surfels src, Surfels dst, const FrameDev* frame, int* upd_first, const float4* cand_rec, const PoseDev* pose,
-                             int W, int H, Intr k, float maxDepth, int timeDelta, unsigned long long* keys_or_null, bool transposed,
-                             hipStream_t s, int blocks = kSurfelGridBlocks);
-// Model::clean (copy_unstable.vert:53-157, Model.cpp:649-772).  What every form is given: the shader's uniforms and textures + the frame's
-// candidates (new-surfel records of the association pass) + the two-launch form's intermediates
-struct CleanIn {
-    FrameDev* frame; const PoseDev* pose; int W, H; Intr k; int timeDelta; float confThreshold, outlierCoeff; int maskID;
-    const int* index; const float4* vc; const float4* ct;    // the index map as separate images, or
-    const float4* packed; const uint8_t* maskT;              // ... the packed column-major map with the mask beside it
-    const float* depthT = nullptr;                           // with tap16: the plane of the filtered depth (launch_index_resolve), unless maskFree
-    bool tap16 = false;                                      // `packed` holds 16-byte taps
-    int tapGroup = 1;                                        // 16-byte taps requested together: 1, 3 (a window column) or 9 ("cleanTapGroup")
-    bool maskFree = false;                                   // with tap16: launch_index_resolve's maskFree -- depthT and maskT were not written
-    const float* depthF; const uint8_t* mask;
-    const uint8_t* cand_op; const float4* cand_rec;
-    uint8_t* flags; float* newconf; int* block_counts;       // [elements], [elements], [kCompactBlocks]
-    int* host_count;                                         // pinned mirror of the surfel count
-    unsigned long long* host_append; unsigned seq;           // in place: pinned mirror of where the buffer ends after THIS pass, tagged with the pass's
-                                                             // sequence number (append_mirror() below); nullptr: none
-    bool transposed;                                         // layout of index / vc / ct / packed: column-major
-    bool literalWindow;                                      // the window walked with the shader's own fp32 trip count
+// The index-map resolve's outputs.  Two consumers, two shapes: index + vertConf + normRad (+ colorTime) as row-major images for the pass that feeds
+// fuse, ONE packed record per texel, column-major, for the pass that feeds clean (mf_surfel.hip: "Two consumers, two output shapes").
+// Frame planes that travel with the packed map (copy_unstable.vert:139-156 looks the filtered depth and the mask up at the surfel's own texel: in the
+// packed, column-major order these are neighbours of its window taps; in the row-major images every lane pulled a sector of its own):
+// depthF -> the packed record's spare word (32-byte record) or depthT (16-byte tap: column-major floats), mask -> maskT (column-major bytes)
+struct ResolveOut {
+    int* index; float4* vc; float4* nr; float4* ct; float4* packed; const float* depthF; const uint8_t* mask; uint8_t* maskT;
+    float* depthT; float tapThreshold;    // tap16: the 16-byte tap (one float4 per texel), live against this confidence threshold; depthT: its depth plane
+    const FrameDev* frame;    // the buffer's frame state (`first`)
+    // with `packed`, optional: what Model::clean's mask-disagreement rule (copy_unstable.vert:139-156) can meet in this frame, for the run culling of
+    // the in-place clean (k_cull_clean): order-preserving ints -- {min, max} filtered depth over the texels of the LEFT column, the RIGHT column, the
+    // TOP row, the BOTTOM row whose mask is foreign to the model (neither its id nor >= 255), then the min over ALL foreign texels (kDecayStats
+    // ints); armed (empty) between frames
+    int* decay_stats; int maskID;
+    // packed: one float4 per texel (tap16_encode) instead of the 32-byte record.  The frame planes travel in depthT / maskT -- unless both are
+    // nullptr: a frame without a mask, for the background ("maskFreeClean": clean_test<.., kMaskFree = true> reads neither)
+    int tap16;
 };
+// the row-major maps; want_ct: the colorTime image too (only the clean pass of a freshly spawned model and the model API read it from there)
+__host__ __device__ inline ResolveOut resolve_out_maps(const PassModel& m, bool want_ct) {
+    ResolveOut o{};
+    o.index = m.scr.index; o.vc = m.scr.ivc; o.nr = m.scr.inr; o.ct = want_ct ? m.scr.ict : nullptr; o.frame = m.frame;
+    return o;
+}
+// the packed map: the 32-byte record with the filtered depth in its spare word, or (f.depthT) the 16-byte tap {x, y, z', initTime} (z' = NaN unless
+// index > 0, confidence > the model's threshold and z > 0, sign bit = lastTime == tick) -- only for a clean pass enqueued with it, with the same
+// tick and threshold.  maskFree (16-byte taps only): every byte of the mask is the model's id (a frame without a mask, for the background) -- no
+// plane is carried and no texel is foreign: depthT / maskT and the statistics are not touched ("maskFreeClean").
+// decay_stats (optional): kDecayStats ints for launch_cull_clean (armed by launch_arm_decay_stats / k_cull_clean)
+__host__ __device__ inline ResolveOut resolve_out_packed(const PassFrame& f, const PassModel& m, bool maskFree = false, int* decay_stats = nullptr) {
+    ResolveOut o{};
+    const bool planes = !(f.depthT && maskFree);
+    o.packed = m.scr.iclean; o.depthF = f.depthF; o.mask = f.mask; o.maskT = planes ? f.maskT : nullptr; o.depthT = planes ? f.depthT : nullptr;
+    o.tapThreshold = m.confThreshold; o.frame = m.frame; o.decay_stats = planes ? decay_stats : nullptr; o.maskID = m.maskID; o.tap16 = f.depthT ? 1 : 0;
+    return o;
+}
+void launch_index_resolve_maps(Surfels src, const PassFrame& f, const PassModel& m, bool want_ct, hipStream_t s);
+void launch_index_resolve_packed(Surfels src, const PassFrame& f, const PassModel& m, hipStream_t s, bool maskFree = false, int* decay_stats = nullptr);
+
+struct FuseDataArgs {
+    const uint8_t* rgb; const float* depthRaw; const float* depthF; const uint8_t* mask; int maskID;
+    const FrameDev* frame; const PoseDev* pose; float weightMultiplier; float maxDepth;
+    int bboxLimit;                 // 1: object models limit their fusion depth by lastBoundingBox (upstream with its GUI; "objectBoundingBoxLimit")
+    int W, H; Intr k;
+    const int* index; const float4* vc; const float4* nr;
+    uint8_t* cand_op; float4* cand_rec; int* upd_first;
+    int* cand_best;                // surfel a merge candidate was associated with (read by the update pass; untouched for the others)
+};
+__host__ __device__ inline FuseDataArgs fuse_data_args(const PassFrame& f, const PassModel& m) {
+    FuseDataArgs a;
+    a.rgb = f.rgb; a.depthRaw = f.depthRaw; a.depthF = f.depthF; a.mask = f.mask; a.maskID = m.maskID; a.frame = m.frame; a.pose = m.pose;
+    a.weightMultiplier = m.weightMultiplier; a.maxDepth = m.fuseMaxDepth; a.bboxLimit = f.bboxLimit; a.W = f.W; a.H = f.H; a.k = f.k;
+    a.index = m.scr.index; a.vc = m.scr.ivc; a.nr = m.scr.inr;
+    a.cand_op = m.scr.cand_op; a.cand_rec = m.scr.cand_rec; a.upd_first = m.scr.upd_first; a.cand_best = m.scr.cand_best;
+    return a;
+}
+void launch_fuse_data(const FuseDataArgs& a, int lanes /* per candidate: 1 or 4 (a quad shares the 3 x 3 window, one column per lane) */, hipStream_t s);
+// update.vert IN PLACE: one thread per candidate, the winning candidate of a surfel (upd_first) merges into it where it stands
+void launch_fuse_update(Surfels s, const PassFrame& f, const PassModel& m, hipStream_t st);
+// the same as a copy src -> dst over the whole buffer; scatter: the index-map scatter of the pass that feeds clean rides on it (the form for small maps)
+struct IndexScatterArgs { const PoseDev* pose; int W, H; Intr k; float maxDepth; int timeDelta; unsigned long long* keys; int transposed; };
+__host__ __device__ inline IndexScatterArgs index_scatter_args(const PassFrame& f, const PassModel& m, bool scatter, int transposed) {
+    IndexScatterArgs ix;
+    ix.pose = m.pose; ix.W = f.W; ix.H = f.H; ix.k = f.k; ix.maxDepth = f.maxDepthProcessed; ix.timeDelta = f.timeDelta;
+    ix.keys = scatter ? m.scr.keys : nullptr; ix.transposed = transposed;
+    return ix;
+}
+void launch_fuse_update_copy(Surfels src, Surfels dst, const PassFrame& f, const PassModel& m, bool scatter, hipStream_t s, int blocks = kSurfelGridBlocks);
 // seq (20 bits) | runs of the table (18 bits) | first slot behind the last run (26 bits): one 64-bit store the host can read at any time --
 // its bounds on what the device has appended then start from a recent exact value instead of the last compaction (mf_frame.inl: prepare_in_place)
 constexpr int kAppendSeqBits = 20, kAppendRunBits = 18, kAppendPhysBits = 26;
@@ -335,19 +414,57 @@ __host__ __device__ inline unsigned long long append_mirror(unsigned seq, int ru
     return ((unsigned long long)(seq & ((1u << kAppendSeqBits) - 1u)) << (kAppendRunBits + kAppendPhysBits)) | ((unsigned long long)(unsigned)runs << kAppendPhysBits) |
            (unsigned long long)(unsigned)phys;
 }
-// two launches (flags + ordered copy), src -> dst: dst is a DENSE buffer without a run table.  src must be dense.
+// Model::clean (copy_unstable.vert:53-157, Model.cpp:649-772).  What every form of the pass is given: the shader's uniforms and textures + the frame's candidates (new-surfel records of the association pass)
+// + the two-launch form's intermediates.  Element i < count is an old surfel, element count + c is candidate c (only op == 2 live).
+struct CleanArgs {
+    Surfels src, dst; FrameDev* frame; const PoseDev* pose; int W, H; Intr k;
+    int timeDelta; float confThreshold; float outlierCoeff; int maskID; int transposed;
+    int literal;   // 1: the window is walked with copy_unstable.vert's own fp32 induction variable (4 or 5 steps per axis), 0: 4 x 4
+    const int* index; const float4* vc; const float4* ct;   // separate images (only when the packed map is absent)
+    const float4* packed;                                    // {vertConf | initTime, lastTime, index, 0} per texel
+    const float* depthF; const uint8_t* mask;
+    const uint8_t* maskT;                                    // the mask in the packed map's order (only with `packed`)
+    const float* depthT;                                     // the filtered depth in the same order (only with the 16-byte tap, unless maskFree)
+    const uint8_t* cand_op; const float4* cand_rec;
+    uint8_t* flags; float* newconf;    // keep flag / new confidence per element: pass 1 -> pass 2 of the two-launch form
+    int* block_counts;                 // [kCompactBlocks] survivors per workgroup (two-launch form)
+    int* host_count;
+    unsigned long long* host_append; unsigned seq;   // append: PassModel::host_append / clean_seq
+    int append;                        // two-launch form, 1: the buffer's own surfels have been cleaned where they stand (k_clean_runs) -- the two passes
+                                       // handle the frame's candidates only and append the survivors at frame->phys (dst = src)
+    const int* run_list; const int* run_count;   // k_clean_runs: the runs to visit (k_cull_clean); nullptr: every run of the table
+    int* ctl;                          // k_clean_runs: kCleanCtlInts ints, zero between launches
+    int tap16;                         // `packed` holds 16-byte taps (clean_test<true>)
+    int tapGroup;                      // 16-byte taps requested together: 1 (one by one), 3 (a window column) or 9 (the window) -- "cleanTapGroup"
+    int maskFree;                      // 1: the frame has no mask and the model is id 0: no mask / depth planes travel with the taps -- "maskFreeClean"
+};
+// The pass that reads the packed column-major map a resolve pass of the SAME enqueue wrote (resolve_out_packed: the same f, m and maskFree), every run.
+// maskFree: an object model's mask is never its own id everywhere -- only the background's launches pass it.
+__host__ __device__ inline CleanArgs clean_args(const PassFrame& f, const PassModel& m, Surfels src, Surfels dst, int append, bool maskFree = false) {
+    CleanArgs a;
+    a.src = src; a.dst = dst; a.frame = m.frame; a.pose = m.pose; a.W = f.W; a.H = f.H; a.k = f.k; a.timeDelta = f.timeDelta;
+    a.confThreshold = m.confThreshold; a.outlierCoeff = f.outlierCoeff; a.maskID = m.maskID; a.transposed = 1; a.literal = f.cleanLiteral;
+    a.index = m.scr.index; a.vc = m.scr.ivc; a.ct = m.scr.ict; a.packed = m.scr.iclean;
+    a.depthF = f.depthF; a.mask = f.mask; a.maskT = f.maskT; a.depthT = maskFree ? nullptr : f.depthT;
+    a.cand_op = m.scr.cand_op; a.cand_rec = m.scr.cand_rec; a.flags = m.scr.flags; a.newconf = m.scr.newconf; a.block_counts = m.scr.block_counts;
+    a.host_count = m.host_count; a.host_append = m.host_append; a.seq = m.clean_seq;
+    a.append = append; a.run_list = nullptr; a.run_count = nullptr; a.ctl = m.scr.clean_ctl;
+    a.tap16 = f.depthT ? 1 : 0; a.tapGroup = f.cleanTapGroup; a.maskFree = maskFree ? 1 : 0;
+    return a;
+}
+// two launches (flags + ordered copy), a.src -> a.dst: dst is a DENSE buffer without a run table.  src must be dense.
 int compact_blocks_for(long elements);   // workgroups of an ordered-compaction launch for that many elements (<= kCompactBlocks)
-void launch_clean_small(const CleanIn& in, Surfels src, Surfels dst, hipStream_t s, int blocks = kCompactBlocks);
-// IN PLACE (mf_surfel.hip "clean, in place"; buf has a run table): launch_clean_runs tests the surfels of the listed runs (nullptr: of every run)
-// and compacts each run where it stands; launch_clean_append tests the frame's candidates and appends the survivors behind the last run.
-// ctl: kCleanCtlInts ints, zero between launches; blocks: clean_runs_grid(elements expected)
+void launch_clean_small(const CleanArgs& a, hipStream_t s, int blocks = kCompactBlocks);
+// IN PLACE (mf_surfel.hip "clean, in place"; a.src = a.dst has a run table): launch_clean_runs tests the surfels of the listed runs (nullptr: of
+// every run) and compacts each run where it stands; launch_clean_append tests the frame's candidates and appends the survivors behind the last run.
+// blocks: clean_runs_grid(elements expected)
 constexpr int kCleanGridMax = 2048;
 constexpr int kCleanCtlInts = 8;
 int clean_runs_grid(long elements);
-void launch_clean_runs(const CleanIn& in, Surfels buf, const VisList* runs, int* ctl, int blocks, hipStream_t s);
-void launch_clean_append(const CleanIn& in, Surfels buf, hipStream_t s);
+void launch_clean_runs(CleanArgs a, const VisList* runs, int blocks, hipStream_t s);
+void launch_clean_append(CleanArgs a, hipStream_t s);
 // the runs launch_clean_runs has to visit for the BACKGROUND-style culling of a model: those in which one of the pass's rules can apply at all
-// (decay_stats: launch_index_resolve's, re-armed here; list / count / ctl as launch_cull)
+// (decay_stats: launch_index_resolve_packed's, re-armed here; list / count / ctl as launch_cull)
 constexpr int kDecayStats = 9;     // ResolveOut::decay_stats (mf_surfel.hip): {min, max} x {left, right, top, bottom border} + min over all foreign texels
 void launch_arm_decay_stats(int* stats /*[kDecayStats]*/, hipStream_t st);   // once, when the statistics block is allocated
 void launch_cull_clean(Surfels s, const FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, int timeDelta, float confThreshold, int* decay_stats,
@@ -391,37 +508,7 @@ int launch_splat_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W,
                        SplatTuning tune = SplatTuning(), const VisList* vis = nullptr, const SplatFilterJob* filter = nullptr,
                        const SplatPyramidJob* pyramid = nullptr);
 bool splat_tiled_applies(int W, int H, SplatTuning tune);   // launch_splat_tiled would not return -1 for this image
-// ---- the surfel passes of ALL object models of a frame, one launch per pass (grid.z = model) ----
-// An object model holds a few thousand surfels: each of its ~11 per-frame launches is pure launch latency (~85 us per object and frame in
-// round 2's profile).  The batched kernels are the single-model kernels' bodies called with one model's arguments, picked from a device
-// array by blockIdx.z; every model brings its own scratch (index maps, key image, candidate records, ...), which the single-model path shares.
-struct ObjPassArgs {
-    Surfels a, b;                      // live buffer when the frame's fusion starts / the other one (small models: fuse a -> b, clean b -> a; from
-                                       // inPlaceElements on: fuse in place in a, clean a -> b, then b is live; big ones: everything in place in a)
-    FrameDev* frame; PoseDev* pose;
-    int maskID; float confThreshold, fuseMaxDepth, weightMultiplier;
-    unsigned long long* keys; int* index; float4* ivc; float4* inr; float4* iclean;
-    uint8_t* cand_op; float4* cand_rec; int* upd_first; int* cand_best; int* clean_ctl; int* host_count;
-    unsigned long long* host_append; unsigned clean_seq;   // CleanIn::host_append / seq
-    uint8_t* flags; float* newconf; int* block_counts;   // the two-launch clean form's intermediates
-    float4* predV; float4* predN; uchar4* predImage; uint16_t* predTime; uint8_t* predGray;
-    FrameDev* host_frame; float* log_slot;
-    unsigned global_payload;           // GlobalProjection: order << 8 | id
-};
-struct ObjBatch {
-    const ObjPassArgs* m; int n;
-    int W, H; Intr k; float maxDepthProcessed, globalMaxDepth; int timeDelta; float outlierCoeff; int cleanLiteral, bboxLimit;
-    int denseSprites;                  // 1: a model of the batch is above inPlaceElements -- the sprite passes (prediction, GlobalProjection) run one thread
-                                       // per surfel: such a map holds sub-pixel sprites, and four lanes per surfel repeat its set-up four times
-    int updateCopy;                    // 1: every model of the batch is below inPlaceElements -- update.vert as a copy a -> b, clean b -> a
-    int cleanSmall;                    // 1: the two-launch clean form src -> dst; 0: every model of the batch has a run table -- clean in place
-    const uint8_t* rgb; const float* depthRaw; const float* depthF; const uint8_t* mask; const PoseDev* bg_pose;
-    uint8_t* maskT;                    // the mask in column-major order, beside the packed maps (every model's resolve writes the same bytes)
-    float* depthT;                     // != nullptr: the packed maps hold 16-byte taps, and this plane the filtered depth in column-major order (as maskT)
-    int fuseLanes;                     // lanes per candidate of the association pass: 1 or 4
-    int cleanTapGroup;                 // 16-byte taps requested together: 1, 3 or 9 (CleanIn::tapGroup)
-    unsigned long long* global_keys;
-};
+// ---- the surfel passes of ALL object models of a frame, one launch per pass (struct ObjBatch above) ----
 void launch_obj_global_scatter(const ObjBatch& b, int blocks, hipStream_t s);          // GlobalProjection of every object model (mf_segment.hip)
 void launch_obj_fuse_clean(const ObjBatch& b, int blocks, int clean_blocks, hipStream_t s, int compact_blocks = kCompactBlocks);   // predictIndices -> fuse -> predictIndices -> clean
 void launch_obj_predict_advance(const ObjBatch& b, int blocks, hipStream_t s);         // combinedPredict (scatter form) + the end-of-frame bookkeeping

@@ -22,6 +22,14 @@ static void set_model_tick(mf_ctx* c, ModelState& m, int tick) {
 }
 static long staged_frame(const mf_ctx* c) { return c->frame_no - 1; }   // index of the frame staged / processed last
 static const uint8_t* current_mask(const mf_ctx* c) { return c->cfg.enable_multiple_models ? c->d_mask_tex : c->d_zero_mask; }
+// What the surfel passes of the staged frame share (mf_frame.inl: pass_frame) in a Model-level call.  No 16-byte taps: tick and threshold may
+// change between mf_model_predict_indices and mf_model_clean.  max_depth / time_delta: the call's own.  (+ 3: with no frame staged yet the index is -1;
+// the index passes read no frame plane, but the slot must exist)
+static PassFrame api_frame(const mf_ctx* c, float max_depth, int time_delta) {
+    PassFrame f = pass_frame(c, c->cur_rgb, c->cur_depth, c->d_depthF[(staged_frame(c) + 3) % 3], current_mask(c), false, c->stream);
+    f.maxDepthProcessed = max_depth; f.timeDelta = time_delta;
+    return f;
+}
 
 // upload + MaskFusion::filterDepth (:217) + Model::generateCUDATextures (Model.cpp:350-389) + intensity pyramid: everything of
 // processFrame that does not touch a model.  mask: model id per pixel = what textureMask holds for fuse / clean (NULL: left as it is)
@@ -62,9 +70,9 @@ extern "C" int mf_model_initialise(mf_ctx* c, int32_t model) {
     ModelState* m = model_at(c, model);
     if (!m || c->frame_no == 0) return MF_EINVAL;
     const long k = staged_frame(c);
-    launch_init_surfels(c->cur_rgb, c->cur_depth, c->d_depthF[k % 3], c->W, c->H, c->K, c->cfg.max_depth_processed, m->d_frame, c->d_cand_rec,
-                        c->d_flags, c->stream);
-    launch_compact_records(c->d_cand_rec, c->d_flags, c->P, m->surf[m->cur], m->d_frame, c->d_block_counts, m->h_count, c->stream);
+    launch_init_surfels(c->cur_rgb, c->cur_depth, c->d_depthF[k % 3], c->W, c->H, c->K, c->cfg.max_depth_processed, m->d_frame, c->scr.cand_rec,
+                        c->scr.flags, c->stream);
+    launch_compact_records(c->scr.cand_rec, c->scr.flags, c->P, m->surf[m->cur], m->d_frame, c->scr.block_counts, m->h_count, c->stream);
     launch_run_table(m->surf[m->cur], m->d_frame, c->stream);
     m->fresh_table(m->cur, (long)c->P);
     c->vis_tag.model = nullptr;
@@ -165,12 +173,13 @@ extern "C" int mf_model_predict_indices(mf_ctx* c, int32_t model, int32_t time, 
     if (!m) return MF_EINVAL;
     hipStream_t s = c->stream;
     set_model_tick(c, *m, time);
-    launch_index_scatter(m->surf[m->cur], m->d_frame, m->d_pose, c->W, c->H, c->K, max_depth, time_delta, c->d_keys, true, s);
-    launch_index_resolve(m->surf[m->cur], m->d_frame, m->d_pose, c->d_keys, c->W, c->H, c->d_index, c->d_ivc, c->d_inr, c->d_ict, nullptr, nullptr, nullptr, nullptr, true, s);
+    const PassFrame f = api_frame(c, max_depth, time_delta);
+    const PassModel pm = pass_model(c, *m, c->scr, 1.0f, c->cfg.depth_cutoff);
+    launch_index_scatter(pm.a, f, pm, s);
+    launch_index_resolve_maps(pm.a, f, pm, true, s);
     if (c->sw.model_api_packed) {   // the layout mf_process_frame feeds clean() with: packed records, column-major
-        launch_index_scatter(m->surf[m->cur], m->d_frame, m->d_pose, c->W, c->H, c->K, max_depth, time_delta, c->d_keys, true, s);
-        launch_index_resolve(m->surf[m->cur], m->d_frame, m->d_pose, c->d_keys, c->W, c->H, nullptr, nullptr, nullptr, nullptr, c->d_iclean, c->d_depthF[staged_frame(c) % 3],
-                             current_mask(c), c->d_maskT, true, s);
+        launch_index_scatter(pm.a, f, pm, s);
+        launch_index_resolve_packed(pm.a, f, pm, s);
         c->iclean_is_tap16 = false;   // (the 32-byte record: tick and threshold may change before mf_model_clean)
     }
     return check_launch(c);
@@ -184,12 +193,11 @@ extern "C" int mf_model_fuse(mf_ctx* c, int32_t model, int32_t time, float depth
     ModelState* m = model_at(c, model);
     if (!m || c->frame_no == 0) return MF_EINVAL;
     hipStream_t s = c->stream;
-    const long k = staged_frame(c);
     set_model_tick(c, *m, time);
-    launch_fuse_data(c->cur_rgb, c->cur_depth, c->d_depthF[k % 3], current_mask(c), m->id, m->d_frame, m->d_pose, weight_multiplier,
-                     fminf(depth_cutoff, m->maxDepth), c->W, c->H, c->K, c->d_index, c->d_ivc, c->d_inr, c->d_cand_op, c->d_cand_rec,
-                     c->d_upd_first, c->d_cand_best, s, c->sw.bbox_limit ? 1 : 0, c->sw.fuse_lanes);
-    launch_fuse_update(m->surf[m->cur], m->d_frame, c->d_upd_first, c->d_cand_op, c->d_cand_best, c->d_cand_rec, c->W, c->H, s);   // in place
+    const PassFrame f = api_frame(c, c->cfg.max_depth_processed, c->cfg.time_delta);
+    const PassModel pm = pass_model(c, *m, c->scr, weight_multiplier, depth_cutoff);
+    launch_fuse_data(fuse_data_args(f, pm), f.fuseLanes, s);
+    launch_fuse_update(pm.a, f, pm, s);   // in place
     // merged surfels moved and were seen now: the boxes and time stamps of their runs are refreshed (inside mf_process_frame the clean pass that
     // follows rewrites the entries of every run it visits -- and it visits every run a merge can have touched)
     if (m->table_valid) launch_run_table(m->surf[m->cur], m->d_frame, s, true);
@@ -204,15 +212,16 @@ extern "C" int mf_model_clean(mf_ctx* c, int32_t model, int32_t time, int32_t ti
     ModelState* m = model_at(c, model);
     (void)depth_cutoff;   // the maxDepth uniform of copy_unstable.vert is never read (:53-157)
     if (!m || c->frame_no == 0) return MF_EINVAL;
-    const long k = staged_frame(c);
     set_model_tick(c, *m, time);
-    const bool packed = c->sw.model_api_packed != 0;
     CleanForm form;
     int rc = prepare_clean(c, &m, 1, !clean_small(c, *m), form);
     if (rc != MF_OK) return rc;
-    CleanIn in = clean_in(c, *m, time_delta, packed, c->d_depthF[k % 3], current_mask(c));
-    if (form.in_place) enqueue_clean_in_place(c, *m, in, false);   // (no decay statistics outside a frame: every run is visited)
-    else launch_clean_small(in, m->surf[m->cur], m->surf[1 - m->cur], c->stream);
+    const PassFrame f = api_frame(c, c->cfg.max_depth_processed, time_delta);
+    const PassModel pm = pass_model(c, *m, c->scr, 1.0f, c->cfg.depth_cutoff);
+    CleanArgs a = clean_args(f, pm, pm.a, form.in_place ? pm.a : pm.b, 0);
+    if (!c->sw.model_api_packed) a = unpacked(a);
+    if (form.in_place) enqueue_clean_in_place(c, *m, a, false);   // (no decay statistics outside a frame: every run is visited)
+    else launch_clean_small(a, c->stream);
     after_clean(c, *m, form.in_place, 1 - m->cur);
     return check_launch(c);
 }
@@ -385,16 +394,16 @@ extern "C" int mf_export_projection_keys_dev(mf_ctx* c, const int32_t* orders, i
         if (orders[i] < 0) continue;   // a stand-in (e.g. the background on a rank that only holds objects): not drawn
         enqueue_global_projection(c, m, orders[i]);
     }
-    MF_HIP(c, hipMemcpyAsync(d_keys_out, c->d_keys, (size_t)c->P * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
-    launch_fill_keys(c->d_keys, c->P, s);
+    MF_HIP(c, hipMemcpyAsync(d_keys_out, c->scr.keys, (size_t)c->P * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    launch_fill_keys(c->scr.keys, c->P, s);
     return check_launch(c);
 }
 // GlobalProjection::downloadDirect (:109-114) of a key image merged over all contexts (per-pixel minimum)
 extern "C" int mf_import_projection_keys_dev(mf_ctx* c, const uint64_t* d_keys) {
     settle(c);
     if (!c || !d_keys) return MF_EINVAL;
-    MF_HIP(c, hipMemcpyAsync(c->d_keys, d_keys, (size_t)c->P * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
-    launch_global_resolve(c->d_keys, c->d_proj_ids, c->P, c->stream);   // leaves the key image empty again
+    MF_HIP(c, hipMemcpyAsync(c->scr.keys, d_keys, (size_t)c->P * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
+    launch_global_resolve(c->scr.keys, c->d_proj_ids, c->P, c->stream);   // leaves the key image empty again
     return check_launch(c);
 }
 // MaskFusion::performSegmentation (Core/MaskFusion.h:59; MfSegmentation::performSegmentation, MfSegmentation.cpp:83-538) on the

@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void k_global_scatter(Surfels src, const Frame
 }
 // every object model of the list in one launch (grid.z = model; ObjBatch, mf_internal.h): all of them z-test into the one key image
 __global__ __launch_bounds__(256) void k_obj_global_scatter(const ObjBatch b) {
-    const ObjPassArgs& m = b.m[blockIdx.z];
+    const PassModel& m = b.m[blockIdx.z];
     if (b.denseSprites) global_scatter_body<1>(m.a, m.frame, m.pose, b.W, b.H, b.k, b.globalMaxDepth, 12.0f, b.timeDelta, m.global_payload, b.global_keys, true);
     else global_scatter_body<4>(m.a, m.frame, m.pose, b.W, b.H, b.k, b.globalMaxDepth, 12.0f, b.timeDelta, m.global_payload, b.global_keys, true);
 }

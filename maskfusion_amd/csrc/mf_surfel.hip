@@ -230,10 +230,9 @@ __global__ __launch_bounds__(256) void k_index_scatter(Surfels src, const FrameD
     index_scatter_body(src, frame, pose, W, H, k, maxDepth, timeDelta, keys, transposed, vis_list, vis_count);
 }
 
-void launch_index_scatter(Surfels src, const FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth,
-                          int timeDelta, unsigned long long* keys, bool transposed, hipStream_t s, int blocks, const VisList* vis) {
-    hipLaunchKernelGGL(k_index_scatter, dim3(blocks), dim3(256), 0, s, src, frame, pose, W, H, k, maxDepth, timeDelta, keys,
-                       transposed ? 1 : 0, vis ? vis->list : nullptr, vis ? vis->count : nullptr);
+void launch_index_scatter(Surfels src, const PassFrame& f, const PassModel& m, hipStream_t s, int blocks, const VisList* vis) {
+    hipLaunchKernelGGL(k_index_scatter, dim3(blocks), dim3(256), 0, s, src, m.frame, m.pose, f.W, f.H, f.k, f.maxDepthProcessed, f.timeDelta, m.scr.keys,
+                       1, vis ? vis->list : nullptr, vis ? vis->count : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -433,22 +432,6 @@ __device__ __forceinline__ ResolvedTexel resolve_texel(const Surfels& src, const
     }
     return r;
 }
-// frame planes that travel with the packed map (copy_unstable.vert:139-156 looks the filtered depth and the mask up at the surfel's own texel: in the
-// packed, column-major order these are neighbours of its window taps; in the row-major images every lane pulled a sector of its own):
-// depthF -> the packed record's spare word (32-byte record) or depthT (16-byte tap: column-major floats), mask -> maskT (column-major bytes)
-struct ResolveOut {
-    int* index; float4* vc; float4* nr; float4* ct; float4* packed; const float* depthF; const uint8_t* mask; uint8_t* maskT;
-    float* depthT; float tapThreshold;    // tap16: the 16-byte tap (one float4 per texel), live against this confidence threshold; depthT: its depth plane
-    const FrameDev* frame;    // the buffer's frame state (`first`)
-    // with `packed`, optional: what Model::clean's mask-disagreement rule (copy_unstable.vert:139-156) can meet in this frame, for the run culling of
-    // the in-place clean (k_cull_clean): order-preserving ints -- {min, max} filtered depth over the texels of the LEFT column, the RIGHT column, the
-    // TOP row, the BOTTOM row whose mask is foreign to the model (neither its id nor >= 255), then the min over ALL foreign texels (kDecayStats
-    // ints); armed (empty) between frames
-    int* decay_stats; int maskID;
-    // packed: one float4 per texel (tap16_encode) instead of the 32-byte record.  The frame planes travel in depthT / maskT -- unless both are
-    // nullptr: a frame without a mask, for the background ("maskFreeClean": clean_test<.., kMaskFree = true> reads neither)
-    int tap16;
-};
 // a workgroup's texels -> the decay statistics (one atomic per statistic and wavefront that saw such a texel)
 __device__ __forceinline__ void decay_stats_add(const ResolveOut& o, bool in_image, int x, int y, int W, int H, float depth, int maskValue) {
     if (!o.decay_stats) return;
@@ -555,9 +538,8 @@ __device__ __forceinline__ void index_resolve_packed_body(Surfels src, const Pos
         if (planes) o.maskT[tp] = s_mk[g][f];
     }
 }
-__global__ __launch_bounds__(256) void k_index_resolve(Surfels src, const PoseDev* __restrict__ pose, unsigned long long* __restrict__ keys, int P, ResolveOut o) {
-    index_resolve_same_body<false>(src, pose, keys, P, o);
-}
+// (the model-by-model launches scatter column-major: the maps go through the transposing tile kernel, the packed map through k_index_resolve_packed;
+// index_resolve_same_body and index_resolve_transposing_body<true> serve the object batch's row-major keys)
 __global__ __launch_bounds__(256) void k_index_resolve_packed(Surfels src, const PoseDev* __restrict__ pose, unsigned long long* __restrict__ keys, int W, int H,
                                                               ResolveOut o) {
     index_resolve_packed_body(src, pose, keys, W, H, o, (int)blockIdx.x);
@@ -569,42 +551,19 @@ __global__ __launch_bounds__(256) void k_index_resolve_transposing(Surfels src, 
 }
 int resolve_tiles(int W, int H) { return ((W + kResolveTile - 1) / kResolveTile) * ((H + kResolveTile - 1) / kResolveTile); }
 
-// packed != nullptr: the packed column-major map (index / vc / nr / ct unused) with the frame's filtered depth in its spare word and the mask
-// transposed into maskT -- or, with depthT, the 16-byte tap with the filtered depth transposed into depthT; else the row-major maps.
-// keys_transposed: the order the scatter used.
-void launch_index_resolve(Surfels src, const FrameDev* frame, const PoseDev* pose, unsigned long long* keys, int W, int H, int* index, float4* vc,
-                          float4* nr, float4* ct, float4* packed, const float* depthF, const uint8_t* mask, uint8_t* maskT, bool keys_transposed,
-                          hipStream_t s, int* decay_stats, int maskID, float* depthT, float tapThreshold, bool maskFree) {
-    const int P = W * H;
-    const bool tap16 = packed && depthT;
-    // maskFree (16-byte taps only): every mask byte is the model's id -- no plane is carried, and no texel is foreign: the statistics stay armed
-    const bool planes = !(tap16 && maskFree);
-    const ResolveOut o{index, vc, nr, ct, packed, depthF, mask, planes ? maskT : nullptr, tap16 && planes ? depthT : nullptr, tapThreshold, frame,
-                       packed && planes ? decay_stats : nullptr, maskID, tap16 ? 1 : 0};
-    const dim3 flat((P + 255) / 256), tiles(resolve_tiles(W, H));
-    if (packed) {
-        if (keys_transposed) hipLaunchKernelGGL(k_index_resolve_packed, tiles, dim3(256), 0, s, src, pose, keys, W, H, o);
-        else hipLaunchKernelGGL(k_index_resolve_transposing<true>, tiles, dim3(256), 0, s, src, pose, keys, W, H, o);
-    } else {
-        if (keys_transposed) hipLaunchKernelGGL(k_index_resolve_transposing<false>, tiles, dim3(256), 0, s, src, pose, keys, W, H, o);
-        else hipLaunchKernelGGL(k_index_resolve, flat, dim3(256), 0, s, src, pose, keys, P, o);
-    }
+void launch_index_resolve_maps(Surfels src, const PassFrame& f, const PassModel& m, bool want_ct, hipStream_t s) {
+    hipLaunchKernelGGL(k_index_resolve_transposing<false>, dim3(resolve_tiles(f.W, f.H)), dim3(256), 0, s, src, m.pose, m.scr.keys, f.W, f.H,
+                       resolve_out_maps(m, want_ct));
+}
+void launch_index_resolve_packed(Surfels src, const PassFrame& f, const PassModel& m, hipStream_t s, bool maskFree, int* decay_stats) {
+    hipLaunchKernelGGL(k_index_resolve_packed, dim3(resolve_tiles(f.W, f.H)), dim3(256), 0, s, src, m.pose, m.scr.keys, f.W, f.H,
+                       resolve_out_packed(f, m, maskFree, decay_stats));
 }
 
 // ------------------------------------------------------------------------------------------------
 // data association (data.vert).  Threads walk candidates row-major (coalesced image reads); the candidate's
 // column-major index c = xi * nyc + yi is only its slot / its priority in the first-writer-wins merge.
 // ------------------------------------------------------------------------------------------------
-struct FuseDataArgs {
-    const uint8_t* rgb; const float* depthRaw; const float* depthF; const uint8_t* mask; int maskID;
-    const FrameDev* frame; const PoseDev* pose; float weightMultiplier; float maxDepth;
-    int bboxLimit;                 // 1: object models limit their fusion depth by lastBoundingBox (upstream with its GUI; "objectBoundingBoxLimit")
-    int W, H; Intr k;
-    const int* index; const float4* vc; const float4* nr;
-    uint8_t* cand_op; float4* cand_rec; int* upd_first;
-    int* cand_best;                // surfel a merge candidate was associated with (read by the update pass; untouched for the others)
-};
-
 // kLanes == 1: one thread per candidate walks the nine taps.  kLanes == 4: a quad of neighbouring lanes per candidate (16 candidates per wavefront);
 // lanes 0, 1, 2 own the window columns da = -1, 0, +1 -- taps q = 3 lane .. 3 lane + 2 of the serial order -- and the three partial results are merged in
 // lane order with the same strict <: the first arg-min over the gated taps in the order q = 0..8, which is what the serial loop computes.  Every
@@ -756,14 +715,9 @@ __device__ __forceinline__ void fuse_data_body(const FuseDataArgs& a) {
 template <int kLanes>
 __global__ __launch_bounds__(256) void k_fuse_data(const FuseDataArgs a) { fuse_data_body<kLanes>(a); }
 
-void launch_fuse_data(const uint8_t* rgb, const float* depthRaw, const float* depthF, const uint8_t* mask, int maskID,
-                      const FrameDev* frame, const PoseDev* pose, float weightMultiplier, float maxDepth, int W, int H, Intr k,
-                      const int* index, const float4* vc, const float4* nr, uint8_t* cand_op, float4* cand_rec, int* upd_first,
-                      int* cand_best, hipStream_t s, int bboxLimit, int lanes) {
-    FuseDataArgs a{rgb, depthRaw, depthF, mask, maskID, frame, pose, weightMultiplier, maxDepth, bboxLimit, W, H, k,
-                   index, vc, nr, cand_op, cand_rec, upd_first, cand_best};
+void launch_fuse_data(const FuseDataArgs& a, int lanes, hipStream_t s) {
     const int per_wave = lanes == 4 ? 16 : 64;
-    dim3 grid(((W + 1) / 2 + per_wave - 1) / per_wave, ((H + 1) / 2 + 3) / 4);
+    dim3 grid(((a.W + 1) / 2 + per_wave - 1) / per_wave, ((a.H + 1) / 2 + 3) / 4);
     if (lanes == 4) hipLaunchKernelGGL(k_fuse_data<4>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_fuse_data<1>, grid, dim3(256), 0, s, a);
 }
@@ -813,7 +767,6 @@ __device__ __forceinline__ void fuse_update_body(Surfels s, const FrameDev* __re
 // The same as a COPY src -> dst over the whole buffer with the second index scatter (predictIndices after fuse, MaskFusion.cpp:556) riding on
 // the values just written (rounds 1-4): the form for SMALL maps, where one 12 us pass beats an in-place update + a scatter launch of its own
 // (8 + 10 us at VGA) and the whole frame is a chain of such launches; on a 26.9 M-surfel map the copy is 100 B per surfel, 0.56 ms.
-struct IndexScatterArgs { const PoseDev* pose; int W, H; Intr k; float maxDepth; int timeDelta; unsigned long long* keys; int transposed; };
 __device__ __forceinline__ void fuse_update_copy_body(Surfels src, Surfels dst, const FrameDev* __restrict__ frame, int* __restrict__ upd_first,
                                                       const float4* __restrict__ cand_rec, const IndexScatterArgs& ix) {
     const int n = frame->count;
@@ -850,11 +803,8 @@ __global__ __launch_bounds__(256) void k_fuse_update_copy(Surfels src, Surfels d
                                                           const float4* __restrict__ cand_rec, const IndexScatterArgs ix) {
     fuse_update_copy_body(src, dst, frame, upd_first, cand_rec, ix);
 }
-void launch_fuse_update_copy(Surfels src, Surfels dst, const FrameDev* frame, int* upd_first, const float4* cand_rec, const PoseDev* pose,
-                             int W, int H, Intr k, float maxDepth, int timeDelta, unsigned long long* keys_or_null, bool transposed,
-                             hipStream_t s, int blocks) {
-    IndexScatterArgs ix{pose, W, H, k, maxDepth, timeDelta, keys_or_null, transposed ? 1 : 0};
-    hipLaunchKernelGGL(k_fuse_update_copy, dim3(blocks), dim3(256), 0, s, src, dst, frame, upd_first, cand_rec, ix);
+void launch_fuse_update_copy(Surfels src, Surfels dst, const PassFrame& f, const PassModel& m, bool scatter, hipStream_t s, int blocks) {
+    hipLaunchKernelGGL(k_fuse_update_copy, dim3(blocks), dim3(256), 0, s, src, dst, m.frame, m.scr.upd_first, m.scr.cand_rec, index_scatter_args(f, m, scatter, 1));
 }
 
 __global__ __launch_bounds__(256) void k_fuse_update(Surfels s, const FrameDev* __restrict__ frame, int* __restrict__ upd_first,
@@ -865,38 +815,15 @@ __global__ __launch_bounds__(256) void k_fuse_update(Surfels s, const FrameDev* 
 
 static inline int cand_blocks(int W, int H) { return (((W + 1) / 2) * ((H + 1) / 2) + 255) / 256; }
 
-void launch_fuse_update(Surfels s, const FrameDev* frame, int* upd_first, const uint8_t* cand_op, const int* cand_best, const float4* cand_rec,
-                        int W, int H, hipStream_t st) {
-    hipLaunchKernelGGL(k_fuse_update, dim3(cand_blocks(W, H)), dim3(256), 0, st, s, frame, upd_first, cand_op, cand_best, cand_rec, W, H);
+void launch_fuse_update(Surfels s, const PassFrame& f, const PassModel& m, hipStream_t st) {
+    hipLaunchKernelGGL(k_fuse_update, dim3(cand_blocks(f.W, f.H)), dim3(256), 0, st, s, m.frame, m.scr.upd_first, m.scr.cand_op, m.scr.cand_best, m.scr.cand_rec,
+                       f.W, f.H);
 }
 
 // ------------------------------------------------------------------------------------------------
 // clean (copy_unstable.vert:53-157): pass 1 = per-element test + new confidence + per-workgroup counts;
 // pass 2 = ordered copy.  Element i < count is an old surfel, element count + c is candidate c (only op == 2 live).
 // ------------------------------------------------------------------------------------------------
-struct CleanArgs {
-    Surfels src, dst; FrameDev* frame; const PoseDev* pose; int W, H; Intr k;
-    int timeDelta; float confThreshold; float outlierCoeff; int maskID; int transposed;
-    int literal;   // 1: the window is walked with copy_unstable.vert's own fp32 induction variable (4 or 5 steps per axis), 0: 4 x 4
-    const int* index; const float4* vc; const float4* ct;   // separate images (only when the packed map is absent)
-    const float4* packed;                                    // {vertConf | initTime, lastTime, index, 0} per texel
-    const float* depthF; const uint8_t* mask;
-    const uint8_t* maskT;                                    // the mask in the packed map's order (only with `packed`)
-    const float* depthT;                                     // the filtered depth in the same order (only with the 16-byte tap, unless maskFree)
-    const uint8_t* cand_op; const float4* cand_rec;
-    uint8_t* flags; float* newconf;    // keep flag / new confidence per element: pass 1 -> pass 2 of the two-launch form
-    int* block_counts;                 // [kCompactBlocks] survivors per workgroup (two-launch form)
-    int* host_count;
-    unsigned long long* host_append; unsigned seq;   // append: CleanIn::host_append / seq
-    int append;                        // two-launch form, 1: the buffer's own surfels have been cleaned where they stand (k_clean_runs) -- the two passes
-                                       // handle the frame's candidates only and append the survivors at frame->phys (dst = src)
-    const int* run_list; const int* run_count;   // k_clean_runs: the runs to visit (k_cull_clean); nullptr: every run of the table
-    int* ctl;                          // k_clean_runs: kCleanCtlInts ints, zero between launches
-    int tap16;                         // `packed` holds 16-byte taps (clean_test<true>)
-    int tapGroup;                      // 16-byte taps requested together: 1 (one by one), 3 (a window column) or 9 (the window) -- "cleanTapGroup"
-    int maskFree;                      // 1: the frame has no mask and the model is id 0: no mask / depth planes travel with the taps -- "maskFreeClean"
-};
-
 // The window of copy_unstable.vert:85-86 along one axis, exactly as the shader text walks it: `for (i = c - 2s; i < c + 2s; i += s)` on an
 // fp32 induction variable makes 4 steps in exact arithmetic and 4 OR 5 in fp32, depending on the rounding of the centre c (27 % of
 // the x positions at 640 columns make 5); every step is a tap that COUNTS towards `count > 8` / `zCount > 4`.  A tap's texel is the
@@ -1045,7 +972,7 @@ __device__ __forceinline__ bool clean_test(const CleanArgs& a, float4 pc, float4
     const int fx_ = isnan(x) ? 0 : clampi((int)fminf(fmaxf(floorf(x), -1.f), (float)W), 0, W - 1);
     const int fy_ = isnan(y) ? 0 : clampi((int)fminf(fmaxf(floorf(y), -1.f), (float)H), 0, H - 1);
     // (with the packed map: the filtered depth rides in its spare word -- 16-byte tap: in the column-major plane depthT --, the mask in the
-    // column-major plane beside it -- launch_index_resolve)
+    // column-major plane beside it -- launch_index_resolve_packed)
     const float wDepth = kTap16 ? a.depthT[fx_ * H + fy_] : a.packed ? a.packed[2 * (fx_ * H + fy_) + 1].w : a.depthF[fy_ * W + fx_];
     const int maskValue = a.packed ? a.maskT[fx_ * H + fy_] : a.mask[fy_ * W + fx_];
     if (maskValue != a.maskID && maskValue < 255 && (wDepth > lp.z - 0.05f && wDepth < lp.z + 0.05f)) {
@@ -1693,20 +1620,6 @@ void launch_pose_log(const PoseDev* pose, const PoseDev* bg_pose, float* slot, h
     hipLaunchKernelGGL(k_pose_log, dim3(1), dim3(64), 0, s, pose, bg_pose, slot);
 }
 
-static CleanArgs clean_args(const CleanIn& in, Surfels src, Surfels dst) {
-    CleanArgs a;
-    a.transposed = in.transposed ? 1 : 0;
-    a.literal = in.literalWindow ? 1 : 0;
-    a.src = src; a.dst = dst; a.frame = in.frame; a.pose = in.pose; a.W = in.W; a.H = in.H; a.k = in.k; a.timeDelta = in.timeDelta;
-    a.confThreshold = in.confThreshold; a.outlierCoeff = in.outlierCoeff; a.maskID = in.maskID; a.index = in.index; a.vc = in.vc; a.ct = in.ct;
-    a.packed = in.packed; a.tap16 = in.packed && in.tap16 ? 1 : 0; a.depthT = a.tap16 ? in.depthT : nullptr;
-    a.tapGroup = in.tapGroup; a.maskFree = a.tap16 && in.maskFree ? 1 : 0;
-    a.depthF = in.depthF; a.mask = in.mask; a.maskT = in.maskT; a.cand_op = in.cand_op; a.cand_rec = in.cand_rec;
-    a.flags = in.flags; a.newconf = in.newconf; a.block_counts = in.block_counts; a.host_count = in.host_count;
-    a.host_append = in.host_append; a.seq = in.seq;
-    a.append = 0; a.run_list = nullptr; a.run_count = nullptr; a.ctl = nullptr;
-    return a;
-}
 // Workgroups of the two ordered-compaction launches for `elements` elements (the host's last known count: any grid is correct).  A VGA map
 // (0.75 M elements) is fastest on 2 048 (303.6 against 309-313 us per frame on 1 024 and 305.0 on 4 096); from ~1.5 M elements on, 1 024 workgroups
 // with longer slices win: 1280 x 960 on its natural map 847 -> 835 us, the four 3.7 M-element object maps of configs[4] 4.16 -> 4.07-4.12 ms
@@ -1727,18 +1640,15 @@ static CleanArgs clean_args(const CleanIn& in, Surfels src, Surfels dst) {
         else MF_LAUNCH_CLEAN_GROUP(K, false, group, grid, s, arg);                                                          \
     } while (0)
 int compact_blocks_for(long elements) { return elements >= 1500000L ? kCompactBlocks / 2 : kCompactBlocks; }
-void launch_clean_small(const CleanIn& in, Surfels src, Surfels dst, hipStream_t s, int blocks) {
-    const CleanArgs a = clean_args(in, src, dst);
+void launch_clean_small(const CleanArgs& a, hipStream_t s, int blocks) {
     MF_LAUNCH_CLEAN(k_clean_small_flags, true, a.tap16, a.tapGroup, a.maskFree, dim3(blocks), s, a);
     hipLaunchKernelGGL(k_clean_small_compact, dim3(blocks), dim3(256), 0, s, a);
 }
-void launch_clean_runs(const CleanIn& in, Surfels buf, const VisList* runs, int* ctl, int blocks, hipStream_t s) {
-    CleanArgs a = clean_args(in, buf, buf);
-    a.run_list = runs ? runs->list : nullptr; a.run_count = runs ? runs->count : nullptr; a.ctl = ctl;
+void launch_clean_runs(CleanArgs a, const VisList* runs, int blocks, hipStream_t s) {
+    a.run_list = runs ? runs->list : nullptr; a.run_count = runs ? runs->count : nullptr;
     MF_LAUNCH_CLEAN(k_clean_runs, true, a.tap16, a.tapGroup, a.maskFree, dim3(blocks), s, a);
 }
-void launch_clean_append(const CleanIn& in, Surfels buf, hipStream_t s) {
-    CleanArgs a = clean_args(in, buf, buf);
+void launch_clean_append(CleanArgs a, hipStream_t s) {
     a.append = 1;
     // (the candidates are <= P / 4 elements: a grid of one 256-element slice per workgroup, at most kCompactBlocks of them)
     MF_LAUNCH_CLEAN(k_clean_small_flags, true, a.tap16, a.tapGroup, a.maskFree, dim3(kCompactBlocks), s, a);
@@ -1746,57 +1656,42 @@ void launch_clean_append(const CleanIn& in, Surfels buf, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// The surfel passes of every OBJECT model of a frame, one launch per pass (grid.z = model; mf_internal.h: ObjBatch).  Same bodies, same
-// arguments as the model-by-model launches of enqueue_fuse_clean / enqueue_predict (mf_context.hip) -- the results are bit-identical
-// (tests/test_gpu_multimodel.py::test_object_model_launch_switches_change_nothing) -- but a frame with M objects costs 9 launches
-// instead of 9 M.  Core/MaskFusion.cpp:539-569 runs the models one after the other; nothing couples them.
+// The surfel passes of every OBJECT model of a frame, one launch per pass (grid.z = model; mf_internal.h: ObjBatch = the frame's PassFrame + a
+// device array of PassModel + the launch's form).  Same bodies as the model-by-model launches of enqueue_fuse_clean / enqueue_predict
+// (mf_frame.inl), whose kernel arguments come from the same builders (mf_internal.h: resolve_out_maps / _packed, fuse_data_args,
+// index_scatter_args, clean_args) over the same two structs -- the results are bit-identical
+// (tests/test_gpu_multimodel.py::test_object_model_launch_switches_change_nothing, ::test_batched_object_passes_agree_in_every_form) -- but a
+// frame with M objects costs 9 launches instead of 9 M.  Core/MaskFusion.cpp:539-569 runs the models one after the other; nothing couples them.
+// (The object models' keys are row-major in both index passes: index_scatter_one.)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_obj_index_scatter(const ObjBatch b) {
-    const ObjPassArgs& m = b.m[blockIdx.z];
-    index_scatter_body(m.a, m.frame, m.pose, b.W, b.H, b.k, b.maxDepthProcessed, b.timeDelta, m.keys, 0, nullptr, nullptr, true);
+    const PassModel& m = b.m[blockIdx.z];
+    index_scatter_body(m.a, m.frame, m.pose, b.W, b.H, b.k, b.maxDepthProcessed, b.timeDelta, m.scr.keys, 0, nullptr, nullptr, true);
 }
-__global__ __launch_bounds__(256) void k_obj_index_resolve(const ObjBatch b) {   // (the object models' keys are row-major in both passes)
-    const ObjPassArgs& m = b.m[blockIdx.z];
-    index_resolve_same_body<false>(m.a, m.pose, m.keys, b.W * b.H, ResolveOut{m.index, m.ivc, m.inr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, m.frame, nullptr, 0, 0});
+__global__ __launch_bounds__(256) void k_obj_index_resolve(const ObjBatch b) {
+    const PassModel& m = b.m[blockIdx.z];
+    index_resolve_same_body<false>(m.a, m.pose, m.scr.keys, b.W * b.H, resolve_out_maps(m, false));
 }
 __global__ __launch_bounds__(256) void k_obj_index_resolve_packed(const ObjBatch b) {   // the pass that feeds clean(): grid.x = 16 x 16-pixel tiles
-    const ObjPassArgs& m = b.m[blockIdx.z];
-    index_resolve_transposing_body<true>(b.updateCopy ? m.b : m.a, m.pose, m.keys, b.W, b.H,
-                                         ResolveOut{nullptr, nullptr, nullptr, nullptr, m.iclean, b.depthF, b.mask, b.maskT, b.depthT, m.confThreshold, m.frame, nullptr, 0, b.depthT ? 1 : 0},
-                                         (int)blockIdx.x);
+    const PassModel& m = b.m[blockIdx.z];
+    index_resolve_transposing_body<true>(b.updateCopy ? m.b : m.a, m.pose, m.scr.keys, b.W, b.H, resolve_out_packed(b, m), (int)blockIdx.x);
 }
 template <int kLanes>
-__global__ __launch_bounds__(256) void k_obj_fuse_data(const ObjBatch b) {
-    const ObjPassArgs& m = b.m[blockIdx.z];
-    const FuseDataArgs a{b.rgb, b.depthRaw, b.depthF, b.mask, m.maskID, m.frame, m.pose, m.weightMultiplier, m.fuseMaxDepth, b.bboxLimit, b.W, b.H, b.k,
-                         m.index, m.ivc, m.inr, m.cand_op, m.cand_rec, m.upd_first, m.cand_best};
-    fuse_data_body<kLanes>(a);
-}
+__global__ __launch_bounds__(256) void k_obj_fuse_data(const ObjBatch b) { fuse_data_body<kLanes>(fuse_data_args(b, b.m[blockIdx.z])); }
 __global__ __launch_bounds__(256) void k_obj_fuse_update(const ObjBatch b) {
-    const ObjPassArgs& m = b.m[blockIdx.z];
-    fuse_update_body(m.a, m.frame, m.upd_first, m.cand_op, m.cand_best, m.cand_rec, b.W, b.H);
+    const PassModel& m = b.m[blockIdx.z];
+    fuse_update_body(m.a, m.frame, m.scr.upd_first, m.scr.cand_op, m.scr.cand_best, m.scr.cand_rec, b.W, b.H);
 }
 __global__ __launch_bounds__(256) void k_obj_fuse_update_copy(const ObjBatch b) {   // small models: a -> b with the second index scatter riding
-    const ObjPassArgs& m = b.m[blockIdx.z];
-    const IndexScatterArgs ix{m.pose, b.W, b.H, b.k, b.maxDepthProcessed, b.timeDelta, m.keys, 0};
-    fuse_update_copy_body(m.a, m.b, m.frame, m.upd_first, m.cand_rec, ix);
+    const PassModel& m = b.m[blockIdx.z];
+    fuse_update_copy_body(m.a, m.b, m.frame, m.scr.upd_first, m.scr.cand_rec, index_scatter_args(b, m, true, 0));
 }
-__device__ __forceinline__ CleanArgs obj_clean_args(const ObjBatch& b, const ObjPassArgs& m, int append) {
-    CleanArgs a;
-    // copy-update: fuse copied a -> b, clean goes b -> a (the live buffer stays); in-place update + two-launch clean: clean goes a -> b;
-    // in-place clean (cleanSmall == 0): everything happens in a
-    a.src = b.updateCopy ? m.b : m.a; a.dst = b.updateCopy ? m.a : (b.cleanSmall ? m.b : m.a);
-    a.frame = m.frame; a.pose = m.pose; a.W = b.W; a.H = b.H; a.k = b.k; a.timeDelta = b.timeDelta;
-    a.confThreshold = m.confThreshold; a.outlierCoeff = b.outlierCoeff; a.maskID = m.maskID; a.transposed = 1; a.literal = b.cleanLiteral;
-    a.index = m.index; a.vc = m.ivc; a.ct = nullptr; a.packed = m.iclean; a.depthT = b.depthT; a.depthF = b.depthF; a.mask = b.mask; a.maskT = b.maskT;
-    a.tap16 = b.depthT ? 1 : 0; a.tapGroup = b.cleanTapGroup; a.maskFree = 0;    // (an object model's mask is never its own id everywhere)
-    a.cand_op = m.cand_op; a.cand_rec = m.cand_rec; a.flags = m.flags; a.newconf = m.newconf;
-    a.block_counts = m.block_counts; a.host_count = m.host_count;
-    a.host_append = m.host_append; a.seq = m.clean_seq;
-    a.append = append; a.run_list = nullptr; a.run_count = nullptr; a.ctl = m.clean_ctl;
-    return a;
+// copy-update: fuse copied a -> b, clean goes b -> a (the live buffer stays); in-place update + two-launch clean: clean goes a -> b;
+// in-place clean (cleanSmall == 0): everything happens in a, the two-launch form appends
+__device__ __forceinline__ CleanArgs obj_clean_args(const ObjBatch& b, const PassModel& m, int append) {
+    return clean_args(b, m, b.updateCopy ? m.b : m.a, b.updateCopy ? m.a : (b.cleanSmall ? m.b : m.a), append);
 }
-template <bool kTap16, int kGroup, bool kMaskFree>   // (kMaskFree: always false, as obj_clean_args says)
+template <bool kTap16, int kGroup, bool kMaskFree>   // (kMaskFree: always false, as clean_args says)
 __global__ __launch_bounds__(256) void k_obj_clean_runs(const ObjBatch b) { clean_runs_body<kTap16, kGroup, kMaskFree>(obj_clean_args(b, b.m[blockIdx.z], 0)); }
 template <bool kTap16, int kGroup, bool kMaskFree>
 __global__ __launch_bounds__(256) void k_obj_clean_small_flags(const ObjBatch b) {
@@ -1804,17 +1699,17 @@ __global__ __launch_bounds__(256) void k_obj_clean_small_flags(const ObjBatch b)
 }
 __global__ __launch_bounds__(256) void k_obj_clean_small_compact(const ObjBatch b) { clean_small_compact_body(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1)); }
 __global__ __launch_bounds__(256) void k_obj_splat_scatter(const ObjBatch b) {
-    const ObjPassArgs& m = b.m[blockIdx.z];
+    const PassModel& m = b.m[blockIdx.z];
     // (both forms write the same keys: the z-test is a minimum)
-    if (b.denseSprites) splat_scatter_body<1>(m.a, m.frame, m.pose, b.W, b.H, b.k, b.maxDepthProcessed, m.confThreshold, b.timeDelta, m.keys, true);
-    else splat_scatter_body<4>(m.a, m.frame, m.pose, b.W, b.H, b.k, b.maxDepthProcessed, m.confThreshold, b.timeDelta, m.keys, true);
+    if (b.denseSprites) splat_scatter_body<1>(m.a, m.frame, m.pose, b.W, b.H, b.k, b.maxDepthProcessed, m.confThreshold, b.timeDelta, m.scr.keys, true);
+    else splat_scatter_body<4>(m.a, m.frame, m.pose, b.W, b.H, b.k, b.maxDepthProcessed, m.confThreshold, b.timeDelta, m.scr.keys, true);
 }
 __global__ __launch_bounds__(256) void k_obj_splat_resolve(const ObjBatch b) {
-    const ObjPassArgs& m = b.m[blockIdx.z];
-    splat_resolve_body(m.a, m.pose, m.keys, b.W, b.H, b.k, m.predV, m.predN, m.predImage, m.predTime, m.frame, b.rgb, m.predGray, nullptr, 0);
+    const PassModel& m = b.m[blockIdx.z];
+    splat_resolve_body(m.a, m.pose, m.scr.keys, b.W, b.H, b.k, m.predV, m.predN, m.predImage, m.predTime, m.frame, b.rgb, m.predGray, nullptr, 0);
 }
 __global__ void k_obj_frame_advance(const ObjBatch b) {
-    const ObjPassArgs& m = b.m[blockIdx.z];
+    const PassModel& m = b.m[blockIdx.z];
     frame_advance_body(m.frame, b.W, b.H, m.host_frame, m.pose, b.bg_pose, m.log_slot);
 }
 

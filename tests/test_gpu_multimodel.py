@@ -320,6 +320,24 @@ def test_object_model_launch_switches_change_nothing(hip):
     assert same(tracked_one, run(track_all=True, objectStream=0, fusedPreprocessLaunch=0, batchSolveInPixelPass=0))
 
 
+def test_batched_object_passes_agree_in_every_form(hip):
+    """The batched object launches (k_obj_*, grid.z = model) and the model-by-model launches build their kernel arguments from the same two structs
+    with the same builders (mf_internal.h: PassFrame / PassModel, clean_args, resolve_out_*, fuse_data_args): in each of the three forms a launch
+    takes -- the copying update + two-launch clean of small maps (the defaults at this size), the in-place update + two-launch clean
+    (`inPlaceElements` = 0), everything in place on runs (`bigMapElements` = 0 as well) -- and with the packed map as 16-byte taps (`cleanTap16` = 1)
+    or 32-byte records (0), `batchObjectPasses` 0 and 1 give the same ids, poses, counts, clouds, predictions and label images, bit for bit."""
+    forms = (dict(), dict(inPlaceElements=0), dict(inPlaceElements=0, bigMapElements=0))
+    for form in forms:
+        for tap16 in (1, 0):
+            p = dict(form, cleanTap16=tap16, objectStream=0)
+            one_by_one = _small_scene_run(batchObjectPasses=0, **p)
+            assert len(one_by_one["ids"]) >= 3, "the scenario must hold two object models (the batched passes need two)"
+            assert _same(one_by_one, _small_scene_run(batchObjectPasses=1, **p)), p
+    # ... and with the objects tracked (spawns, drops by the jump rule, re-spawns into buffers an in-place life left)
+    p = dict(forms[2], objectStream=0)
+    assert _same(_small_scene_run(track_all=True, batchObjectPasses=0, **p), _small_scene_run(track_all=True, batchObjectPasses=1, **p))
+
+
 def test_pooled_model_reused_after_an_in_place_life(hip):
     """A model that goes back to the pool and out again starts from an empty buffer whatever shape its last life left: with `bigMapElements` =
     `inPlaceElements` = 0 every model's clean is in place from its first one (a sparse buffer with a device-maintained run table, bounds and
