@@ -1,5 +1,5 @@
 // mf_bilateral_device.h -- the 13x13 bilateral depth filter's workgroup body (depth_bilateral_metric.frag:30-76), shared by k_bilateral
-// (mf_preproc.hip), the launch that runs it beside the model-side pyramid of the same frame (mf_odometry.hip: k_bilateral_model_pyramid) and the one
+// (mf_preproc.hip), the launch that runs it beside the model-side pyramid of the same frame (mf_model_pyramid.hip: k_bilateral_model_pyramid) and the one
 // that runs it beside the previous frame's sprite binning (mf_splat.hip: k_bin_bilateral).
 // Every float operation of the body is rounded on its own (the pragma inside the function: the including file may allow contraction).
 #pragma once
@@ -55,7 +55,7 @@ __device__ __forceinline__ void bilateral_body(const float* __restrict__ depth, 
     float res = 0.f;
     if (!(value <= 0.03f)) {   // the shader's gate as written (`if (value <= 0.03f) 0 else filter`, :34): a NaN centre is filtered, to NaN
         // {sum of tap * weight, sum of weights} as ONE two-lane value: the two additions of a tap are a single v_pk_add_f32 -- two independent IEEE
-        // additions, the same bits -- whether or not the including file lets the SLP vectoriser find the pair (mf_odometry.hip does not)
+        // additions, the same bits -- whether or not the including file lets the SLP vectoriser find the pair (mf_model_pyramid.hip does not)
         typedef float pair_t __attribute__((vector_size(8)));
         pair_t acc = {0.f, 0.f};
 #pragma unroll

@@ -65,6 +65,37 @@ static float rgb_min_scale(int level) {
 // rgb = rgbOnly || icpWeight < 100 (RGBDOdometry.cpp:238)
 static bool photometric_on(const mf_ctx* c) { return c->cfg.rgb_only != 0 || c->cfg.icp_weight < 100.f; }
 
+// The schedule of a tracking step, for the model-by-model loop and the batched one: iterations per pyramid level (level 2 runs first;
+// RGBDOdometry.cpp:327-329), the two gates (RGBDOdometry.h:35-36), every level's size and intrinsics.  iters[0] >= 3 whatever the configuration:
+// a loop never has zero iterations, and neither host carries code for a finalize step without a last iteration to finish.
+struct GnSchedule { int iters[3]; float distThres, angleThres; int W[3], H[3]; Intr k[3]; };
+static GnSchedule gn_schedule(const mf_ctx* c) {
+    const mf_config& g = c->cfg;
+    GnSchedule sch{{g.fast_odom ? 3 : 10, g.pyramid ? 5 : 0, g.pyramid ? 4 : 0}, 0.10f, sinf(20.f * 3.14159254f / 180.f), {}, {}, {}};
+    for (int lvl = 0; lvl < 3; ++lvl) {
+        const float div = (float)(1 << lvl);
+        sch.W[lvl] = c->W >> lvl; sch.H[lvl] = c->H >> lvl; sch.k[lvl] = Intr{g.fx / div, g.fy / div, g.cx / div, g.cy / div};
+    }
+    return sch;
+}
+// The SO(3) pre-alignment of frame_k against its predecessor (RGBDOdometry.cpp:264-324; the previous frame's intensity pyramid is
+// RGBDOdometry::lastNextImage, identical for every tracked model).  nullptr: none ran -- no seed, the loop starts from the identity as with the switch off
+static const So3Result* enqueue_so3_seed(mf_ctx* c, long frame_k) {
+    const mf_config& g = c->cfg;
+    const int set = (int)(frame_k & 1);
+    if (g.so3 == 0 || c->gray_frame[set ^ 1] != frame_k - 1 || c->gray_frame[set] != frame_k) return nullptr;
+    return launch_so3_prealign(c->d_gray[set ^ 1][2], c->d_gray[set][2], c->W >> 2, c->H >> 2, Intr{g.fx / 4, g.fy / 4, g.cx / 4, g.cy / 4}, c->d_so3,
+                               c->d_so3_scratch, c->stream) == 0 ? c->d_so3 : nullptr;
+}
+// "timings": the event pair around the Gauss-Newton launches of the background's step (first: the first model the step tracks); true: it is timed
+static bool icp_marks_begin(mf_ctx* c, const ModelState* first, hipStream_t s) {
+    if (!c->sw.timings_on || first != c->models[0].get()) return false;
+    (void)hipEventRecord(c->ev_icp[0], s);
+    c->tracked_once = true; c->icp_mid_recorded = false;
+    return true;
+}
+static void icp_marks_end(mf_ctx* c, bool timed, hipStream_t s) { if (timed) (void)hipEventRecord(c->ev_icp[1], s); }
+
 // Model::performTracking (Core/Model/Model.cpp:427-447): initICP (model pyramid + fill-in, RGB pyramids), the optional
 // SO(3) pre-alignment, then the Gauss-Newton loop (ICP only: one launch per iteration; with the photometric term: two).
 // pyr_built: the model-side pyramid of this step was built beside the frame's depth filter (enqueue_preprocess, "fusedPreprocessLaunch")
@@ -80,12 +111,7 @@ static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, floa
         launch_model_pyramid(m.d_predV, m.d_predN, m.allowFillIn ? fillDepth : nullptr, m.d_frame, m.d_pose, nullptr, m.d_vmap_g, m.d_nmap_g, W, H, c->K, s);
     const bool rgb = photometric_on(c);
     const bool icp = !g.rgb_only && g.icp_weight > 0.f;
-    // the previous frame's intensity pyramid is RGBDOdometry::lastNextImage (identical for every tracked model)
-    bool so3 = g.so3 != 0 && c->gray_frame[set ^ 1] == frame_k - 1 && c->gray_frame[set] == frame_k;
-    if (so3)   // (a pre-alignment that did not run leaves no seed: the loop then starts from the identity, as with the switch off)
-        so3 = launch_so3_prealign(c->d_gray[set ^ 1][2], c->d_gray[set][2], W >> 2, H >> 2, Intr{g.fx / 4, g.fy / 4, g.cx / 4, g.cy / 4},
-                                  c->d_so3, c->d_so3_scratch, s) == 0;
-    const So3Result* so3_seed = so3 ? c->d_so3 : nullptr;
+    const So3Result* so3_seed = enqueue_so3_seed(c, frame_k);   // (once per model this function tracks)
     if (rgb) {
         // initRGBModel + initRGB (Model.cpp:395-406; Q1: both depth pyramids come from the vertex map initICPModel was given)
         launch_rgbd_last_l0(m.d_predV, m.allowFillIn ? fillDepth : nullptr, m.d_predGray, m.d_fillGray, m.d_frame, c->d_lastDepth[0],
@@ -98,31 +124,22 @@ static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, floa
             launch_small_jobs(jobs, s);
         }
     }
-    const int iters[3] = {g.fast_odom ? 3 : 10, g.pyramid ? 5 : 0, g.pyramid ? 4 : 0};  // RGBDOdometry.cpp:327-329
-    const float sobelScale = 1.0f / 8.0f;                                                // 1 / 2^sobelSize, :31-32
-    const bool timed = c->sw.timings_on && &m == c->models[0].get();
-    if (timed) { (void)hipEventRecord(c->ev_icp[0], s); c->tracked_once = true; c->icp_mid_recorded = false; }
+    const GnSchedule sch = gn_schedule(c);
+    const float sobelScale = 1.0f / 8.0f;                                                // 1 / 2^sobelSize, RGBDOdometry.cpp:31-32
+    const bool timed = icp_marks_begin(c, &m, s);
     int k = 0, nb_prev = 0, prev_level = -1;
-    // every launch of the loop and its finalize
-    auto issue_loop = [&](bool with_marks) {
     for (int lvl = 2; lvl >= 0; --lvl) {
-        const float div = (float)(1 << lvl);
-        if (lvl == 0 && with_marks && timed) { (void)hipEventRecord(c->ev_icp_mid, s); c->icp_mid_recorded = true; }   // coarse levels | level 0 (bench.py: roofline.levels)
-        for (int j = 0; j < iters[lvl]; ++j) {
-            IcpLaunch l;
-            l.vmap_curr = cur_vmap[lvl]; l.nmap_curr = cur_nmap[lvl];
-            l.vmap_prev = m.d_vmap_g[lvl]; l.nmap_prev = m.d_nmap_g[lvl];
-            l.W = W >> lvl; l.H = H >> lvl; l.k = Intr{g.fx / div, g.fy / div, g.cx / div, g.cy / div};
-            l.distThres = 0.10f; l.angleThres = sinf(20.f * 3.14159254f / 180.f);  // RGBDOdometry.h:35-36
-            l.partials_in = nb_prev ? m.d_partials[(k + 1) & 1] : nullptr;
-            l.nblocks_in = nb_prev;
-            l.partials_out = m.d_partials[k & 1];
+        if (lvl == 0 && timed) { (void)hipEventRecord(c->ev_icp_mid, s); c->icp_mid_recorded = true; }   // coarse levels | level 0 (bench.py: roofline.levels)
+        for (int j = 0; j < sch.iters[lvl]; ++j) {
+            IcpLaunch l;   // launch k of the step reads what launch k - 1 left (k = 0: nothing -- it seeds the state)
+            l.vmap_curr = cur_vmap[lvl]; l.nmap_curr = cur_nmap[lvl]; l.vmap_prev = m.d_vmap_g[lvl]; l.nmap_prev = m.d_nmap_g[lvl];
+            l.W = sch.W[lvl]; l.H = sch.H[lvl]; l.k = sch.k[lvl]; l.distThres = sch.distThres; l.angleThres = sch.angleThres;
+            l.partials_in = nb_prev ? m.d_partials[(k + 1) & 1] : nullptr; l.nblocks_in = nb_prev; l.partials_out = m.d_partials[k & 1];
             l.state_in = &m.d_gn[k & 1]; l.state_out = &m.d_gn[(k + 1) & 1];
             l.log_out = (k > 0) ? m.d_icp_log + 32 * (k - 1) : nullptr;
             l.trace = rgb ? nullptr : m.d_gn_trace; l.it = k;
             l.prof_out = (c->sw.icp_prof_on && m.id == 0 && !rgb) ? c->d_icp_prof + 16 * k : nullptr;
-            l.pose_in = (k == 0) ? m.d_pose : nullptr;
-            l.so3_in = (k == 0) ? so3_seed : nullptr;
+            l.pose_in = (k == 0) ? m.d_pose : nullptr; l.so3_in = (k == 0) ? so3_seed : nullptr;
             if (!rgb) {
                 launch_icp_iteration(l, s);
             } else {
@@ -131,15 +148,10 @@ static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, floa
                 r.L.dIdx = c->d_dIdx[lvl]; r.L.dIdy = c->d_dIdy[lvl];
                 r.L.lastDepth = c->d_lastDepth[lvl]; r.L.nextDepth = c->d_lastDepth[lvl];
                 r.L.lastImage = c->d_lastImage[lvl]; r.L.nextImage = c->d_gray[set][lvl];
-                r.L.W = l.W; r.L.H = l.H;
-                r.L.minScale = rgb_min_scale(lvl);
-                r.L.gate = c->d_rgb_gate[lvl];
-                r.L.maxDepthDelta = 0.07f;                                          // maxDepthDeltaRGB, :33
-                r.corres = c->d_corres;
-                r.rgb_partials_in = nb_prev ? c->d_rgb_partials[(k + 1) & 1] : nullptr;
-                r.rgb_partials_out = c->d_rgb_partials[k & 1];
-                r.cnt_in = nb_prev ? c->d_cnt[(k + 1) & 1] : nullptr;
-                r.cnt_out = c->d_cnt[k & 1];
+                r.L.W = l.W; r.L.H = l.H; r.L.minScale = rgb_min_scale(lvl); r.L.gate = c->d_rgb_gate[lvl];
+                r.L.maxDepthDelta = 0.07f; r.corres = c->d_corres;                  // maxDepthDeltaRGB, RGBDOdometry.cpp:33
+                r.rgb_partials_in = nb_prev ? c->d_rgb_partials[(k + 1) & 1] : nullptr; r.rgb_partials_out = c->d_rgb_partials[k & 1];
+                r.cnt_in = nb_prev ? c->d_cnt[(k + 1) & 1] : nullptr; r.cnt_out = c->d_cnt[k & 1];
                 r.icpWeight = g.icp_weight; r.icpOn = icp ? 1 : 0; r.rgbOnly = g.rgb_only ? 1 : 0; r.sobelScale = sobelScale;
                 r.level = lvl; r.prev_level = (prev_level < 0) ? lvl : prev_level;
                 r.so3_in = l.so3_in;
@@ -150,17 +162,11 @@ static void enqueue_track(mf_ctx* c, ModelState& m, const float* fillDepth, floa
             ++k;
         }
     }
-    if (with_marks && timed) (void)hipEventRecord(c->ev_icp[1], s);
-    float* log_out = (k > 0) ? m.d_icp_log + 32 * (k - 1) : nullptr;
-    if (!rgb)
-        launch_icp_finalize(nb_prev ? m.d_partials[(k + 1) & 1] : nullptr, nb_prev, &m.d_gn[k & 1], m.d_pose, m.h_pose, log_out,
-                            jump_limit, so3_seed, s, m.d_gn_trace, k);
-    else
-        launch_rgbd_finalize(nb_prev ? m.d_partials[(k + 1) & 1] : nullptr, nb_prev ? c->d_rgb_partials[(k + 1) & 1] : nullptr,
-                             nb_prev ? c->d_cnt[(k + 1) & 1] : nullptr, nb_prev, g.icp_weight, icp ? 1 : 0, g.rgb_only ? 1 : 0, 1,
-                             prev_level, &m.d_gn[k & 1], so3_seed, m.d_pose, m.h_pose, log_out, jump_limit, s);
-    };
-    issue_loop(true);
+    icp_marks_end(c, timed, s);
+    const GnLast last{m.d_partials[(k + 1) & 1], nb_prev, &m.d_gn[k & 1], c->d_rgb_partials[(k + 1) & 1], c->d_cnt[(k + 1) & 1], prev_level};
+    const GnFinalize f{m.d_pose, m.h_pose, m.d_icp_log + 32 * (k - 1), jump_limit, so3_seed, rgb ? nullptr : m.d_gn_trace, k};
+    if (!rgb) launch_icp_finalize(last, f, s);
+    else launch_rgbd_finalize(last, g.icp_weight, icp ? 1 : 0, g.rgb_only ? 1 : 0, f, s);
 }
 
 // The same for several models at once (geometric term only; MaskFusion.cpp:247-276 tracks the models one after the other, their
@@ -174,38 +180,31 @@ static TrackBatch track_batch_of(const std::vector<ModelState*>& ms) {
     return b;
 }
 static void enqueue_track_batch(mf_ctx* c, const std::vector<ModelState*>& ms, const float* fillDepth, long frame_k, bool pyr_built) {
-    const mf_config& g = c->cfg;
     const int set = (int)(frame_k & 1);
     const int W = c->W, H = c->H;
     hipStream_t s = c->stream;
     const TrackBatch b = track_batch_of(ms);
     if (!pyr_built) launch_model_pyramid_batch(b, fillDepth, W, H, c->K, s);
-    bool so3 = g.so3 != 0 && c->gray_frame[set ^ 1] == frame_k - 1 && c->gray_frame[set] == frame_k;
-    if (so3)   // one pre-alignment serves every model: it only looks at the two frames (RGBDOdometry.cpp:264-324); one that did not run leaves no seed
-        so3 = launch_so3_prealign(c->d_gray[set ^ 1][2], c->d_gray[set][2], W >> 2, H >> 2, Intr{g.fx / 4, g.fy / 4, g.cx / 4, g.cy / 4},
-                                  c->d_so3, c->d_so3_scratch, s) == 0;
-    const So3Result* so3_seed = so3 ? c->d_so3 : nullptr;
-    const int iters[3] = {g.fast_odom ? 3 : 10, g.pyramid ? 5 : 0, g.pyramid ? 4 : 0};
-    const bool timed = c->sw.timings_on && ms[0] == c->models[0].get();
-    if (timed) { (void)hipEventRecord(c->ev_icp[0], s); c->tracked_once = true; c->icp_mid_recorded = false; }
+    const So3Result* so3_seed = enqueue_so3_seed(c, frame_k);   // one pre-alignment serves every model: it only looks at the two frames
+    const GnSchedule sch = gn_schedule(c);
+    const bool timed = icp_marks_begin(c, ms[0], s);
     // slab culling of the pixel pass (mf_odometry.hip: k_icp_batch_pixels): the depth range of every row of the frame's vertex maps, once per frame
     if (c->sw.slab_culling) launch_row_zrange(c->d_vmap[set], W, H, c->d_row_z, s);
     const int row_base[3] = {0, H, H + (H >> 1)};
     int it = 0, nb_prev = 0;
     for (int lvl = 2; lvl >= 0; --lvl) {
-        const float div = (float)(1 << lvl);
-        for (int j = 0; j < iters[lvl]; ++j) {
+        const IcpBatchLevel L{lvl, c->d_vmap[set][lvl], c->d_nmap[set][lvl], sch.W[lvl], sch.H[lvl], sch.k[lvl], sch.distThres, sch.angleThres,
+                              c->sw.slab_culling ? c->d_row_z + row_base[lvl] : nullptr};
+        for (int j = 0; j < sch.iters[lvl]; ++j) {
             // one launch per iteration ("batchSolveInPixelPass", default): the pixel pass finishes the previous iteration in its prologue; else two
-            if (!c->sw.batch_solve_fused) launch_icp_batch_solve(b, it, nb_prev, it == 0 ? so3_seed : nullptr, s);
-            launch_icp_batch_pixels(b, it, lvl, c->d_vmap[set][lvl], c->d_nmap[set][lvl], W >> lvl, H >> lvl,
-                                    Intr{g.fx / div, g.fy / div, g.cx / div, g.cy / div}, 0.10f, sinf(20.f * 3.14159254f / 180.f), s,
-                                    c->sw.slab_culling ? c->d_row_z + row_base[lvl] : nullptr, c->sw.batch_solve_fused, nb_prev, it == 0 ? so3_seed : nullptr);
-            nb_prev = icp_batch_blocks(W >> lvl, H >> lvl, b.n);
+            const So3Result* seed = it == 0 ? so3_seed : nullptr;
+            if (!c->sw.batch_solve_fused) launch_icp_batch_solve(b, it, nb_prev, seed, s);
+            launch_icp_batch_pixels(b, it, L, c->sw.batch_solve_fused, nb_prev, seed, s);
+            nb_prev = icp_batch_blocks(L.W, L.H, b.n);
             ++it;
         }
     }
-    if (timed) (void)hipEventRecord(c->ev_icp[1], s);
-    if (it == 0) launch_icp_batch_solve(b, 0, 0, so3_seed, s);   // no iterations at all: the states still have to exist
+    icp_marks_end(c, timed, s);
     launch_icp_batch_finalize(b, it, nb_prev, so3_seed, s);
 }
 

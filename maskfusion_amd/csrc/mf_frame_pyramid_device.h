@@ -1,7 +1,7 @@
 // mf_frame_pyramid_device.h -- Model::generateCUDATextures' workgroup body (pyrDownGaussF x2 + createVMap / createNMap x3 of the frame's filtered
-// depth), shared by k_frame_pyramid (mf_preproc.hip) and the launch that runs it beside the model-side pyramid (mf_odometry.hip:
+// depth), shared by k_frame_pyramid (mf_preproc.hip) and the launch that runs it beside the model-side pyramid (mf_model_pyramid.hip:
 // k_frame_model_pyramid).  Every float operation of these functions is rounded on its own -- the pragma sits inside each body, and the helpers
-// they call carry it too: the including file may allow contraction (mf_odometry.hip does), and the preprocessing feeds normals, which amplify a
+// they call carry it too: the including file may allow contraction (mf_model_pyramid.hip does), and the preprocessing feeds normals, which amplify a
 // 1-ulp depth difference ~1000x.
 #pragma once
 #include "mf_device.h"

@@ -125,7 +125,7 @@ struct TrackModelDev {
     float* vm[3]; float* nm[3];                   // model-side vertex / normal pyramid (global frame)
     float* partials[2]; GNState* st;              // ping-pong per-workgroup partial sums [nb][32]; st[0], st[1]
     float* log;                                   // [19][32] reduced systems (background model) or nullptr
-    double* trace;                                // [20][kGnTraceRow] Gauss-Newton trace (mf_odometry.hip: gn_trace_write) or nullptr
+    double* trace;                                // [20][kGnTraceRow] Gauss-Newton trace (mf_gn_device.h: gn_trace_write) or nullptr
     float jump_limit;                             // object models: 0.2 m rule of MaskFusion.cpp:268-272; background: 0
     int allow_fill;                               // Model::allowsFillIn (background only)
     int* rect;                                    // {x0, y0, x1, y1}: the pixels of nm[0] that hold a normal (an object's prediction is NaN outside the object,
@@ -140,7 +140,7 @@ struct TrackBatch { const TrackModelDev* m[kMaxTrackBatch]; int n; };   // by va
 // ---------------- preprocessing ----------------
 void launch_bilateral_model_pyramid(const float* depth, float* depthF, const float4* predV, const float4* predN, const float* fillDepth,
                                     const FrameDev* frame, const PoseDev* pose, float* const vmaps[3], float* const nmaps[3], int W, int H, Intr k,
-                                    hipStream_t s);   // the filter + launch_model_pyramid's work in one launch (mf_odometry.hip)
+                                    hipStream_t s);   // the filter + launch_model_pyramid's work in one launch (mf_model_pyramid.hip)
 void launch_bilateral(const float* depth, float* out, int W, int H, hipStream_t s);
 void launch_pyrdown_f(const float* src, float* dst, int sw, int sh, hipStream_t s);
 void launch_vmap_nmap(const float* depth, float* vmap, float* nmap, int W, int H, Intr k, float cutoff, hipStream_t s);
@@ -148,18 +148,19 @@ void launch_vmap_nmap(const float* depth, float* vmap, float* nmap, int W, int H
 void launch_frame_pyramid(const float* depth, float* const vmap[3], float* const nmap[3], int W, int H, Intr k, float cutoff,
                           hipStream_t s);
 
-// launch_frame_pyramid's and launch_model_pyramid's work (device pose) in one launch (mf_odometry.hip: k_frame_model_pyramid)
+// launch_frame_pyramid's and launch_model_pyramid's work (device pose) in one launch (mf_model_pyramid.hip: k_frame_model_pyramid)
 void launch_frame_model_pyramid(const float* depthF, float* const fvmap[3], float* const fnmap[3], float cutoff, const float4* predV, const float4* predN,
                                 const float* fillDepth, const FrameDev* frame, const PoseDev* pose, float* const vmaps[3], float* const nmaps[3], int W, int H,
                                 Intr k, hipStream_t s, int* fixup = nullptr);   // fixup: as launch_model_pyramid's
 
-// ---------------- odometry ----------------
-// Fused RGBDOdometry::initICPModel.  pose: device PoseDev (R,t used).  fill-in inputs may be null (no fill-in).
+// Fused RGBDOdometry::initICPModel (mf_model_pyramid.hip).  pose: device PoseDev (R,t used).  fill-in inputs may be null (no fill-in).
 void launch_model_pyramid(const float4* predV, const float4* predN, const float* fillDepth, const FrameDev* frame,
                           const PoseDev* pose, const float* R9t3_host_or_null, float* const vmaps[3],
                           float* const nmaps[3], int W, int H, Intr k, hipStream_t s, int* fixup = nullptr);
 // fixup ("tilePyramid"): the tile pass has already written the pyramid without fill-in -- the launch runs only if frame->useFillIn is set, and then
 // counts the frame in *fixup
+
+// ---------------- odometry (mf_odometry.hip; the parts of a Gauss-Newton step: mf_gn_device.h) ----------------
 // One Gauss-Newton iteration: [reduce+solve of the previous launch] -> normal equations of this level.
 struct IcpLaunch {
     const float* vmap_curr; const float* nmap_curr; const float* vmap_prev; const float* nmap_prev;
@@ -187,25 +188,29 @@ void launch_icp_iteration(const IcpLaunch& a, hipStream_t s);
 // because the redundant per-workgroup prologue of k_icp_iter would be paid once per model and per round.
 int icp_batch_max_blocks(int W, int H);                       // upper bound of workgroups per model of launch_icp_batch_pixels
 int icp_batch_blocks(int W, int H, int n_models);             // workgroups per model it will use for this image size
-void launch_model_pyramid_batch(const TrackBatch& b, const float* fillDepth, int W, int H, Intr k, hipStream_t s);
+void launch_model_pyramid_batch(const TrackBatch& b, const float* fillDepth, int W, int H, Intr k, hipStream_t s);   // (mf_model_pyramid.hip, as the next)
 void launch_bilateral_model_pyramid_batch(const float* depth, float* depthF, const TrackBatch& b, const float* fillDepth, int W, int H, Intr k,
                                           hipStream_t s);   // the depth filter + launch_model_pyramid_batch's work in one launch
 // it = 0 seeds the states from the model poses (+ SO(3) rotation); it >= 1 finishes iteration it-1 whose pixel pass used nb_in blocks
 void launch_icp_batch_solve(const TrackBatch& b, int it, int nb_in, const So3Result* so3_or_null, hipStream_t s);
-// row_z: launch_row_zrange's output for this level (nullptr: no culling -- every workgroup walks its pixels)
-void launch_icp_batch_pixels(const TrackBatch& b, int it, int level, const float* vmap_curr, const float* nmap_curr, int W, int H, Intr k,
-                             float distThres, float angleThres, hipStream_t s, const float2* row_z = nullptr, bool fused = false, int nb_in = 0,
-                             const So3Result* so3_or_null = nullptr);   // fused: launch_icp_batch_solve(b, it, nb_in, so3) is this launch's prologue
+// The pyramid level a pixel pass works on.  row_z: launch_row_zrange's output for this level (nullptr: no culling -- every workgroup walks its pixels)
+struct IcpBatchLevel { int level; const float* vmap_curr; const float* nmap_curr; int W, H; Intr k; float distThres, angleThres; const float2* row_z; };
+// fused: launch_icp_batch_solve(b, it, nb_in, so3) is this launch's prologue
+void launch_icp_batch_pixels(const TrackBatch& b, int it, const IcpBatchLevel& l, bool fused, int nb_in, const So3Result* so3_or_null, hipStream_t s);
 // depth range of every row of the frame's three vertex maps: out[0 .. H) level 0, [H .. H + H/2) level 1, [.. + H/4) level 2: {min z, max z} over the
 // row's valid vertices ({+inf, -inf}: none)
 void launch_row_zrange(const float* const vmap[3], int W, int H, float2* out, hipStream_t s);
 // last solve (iteration n_it - 1) + Model pose / lastPose / statistics / jump rule
 void launch_icp_batch_finalize(const TrackBatch& b, int n_it, int nb_in, const So3Result* so3_or_null, hipStream_t s);
+// What the end of a tracking step writes, for the three finalize kernels (the batched one fills it per model from the TrackModelDev): the pose block
+// and its pinned mirror (or nullptr), optionally the last reduced system ([32] floats), the pre-alignment that seeded the step (its statistics go to
+// the pose), optionally the trace and the iterations that ran.  jump_limit > 0: object-model rule of MaskFusion.cpp:268-272 (|increment| > limit => alive = 0)
+struct GnFinalize { PoseDev* pose; PoseDev* host_mirror; float* log; float jump_limit; const So3Result* so3; double* trace; int n_it; };
+// What the last iteration of a step left for the finalize step to finish: its per-workgroup partial sums and the state it started from; with the
+// photometric term also the RGB partials, the correspondence counts and its pyramid level (else unused)
+struct GnLast { const float* partials; int nblocks; const GNState* state; const float* rgb_partials; const int2* cnt; int level; };
 // Last reduce+solve, then pose / lastPose / inverse / fusion weight update and host mirror.
-// jump_limit > 0: object-model rule of MaskFusion.cpp:268-272 (|increment translation| > limit => pose->alive = 0)
-void launch_icp_finalize(const float* partials_in, int nblocks_in, const GNState* state_in, PoseDev* pose,
-                         PoseDev* host_mirror, float* log_out, float jump_limit, const So3Result* so3, hipStream_t s,
-                         double* trace = nullptr, int n_it = 0);
+void launch_icp_finalize(const GnLast& last, const GnFinalize& f, hipStream_t s);
 // Stand-alone icpStep (parity tests): host-provided poses, output 32 floats.
 void launch_icp_step_standalone(const float* Rcurr, const float* tcurr, const float* vc, const float* nc,
                                 const float* Rpi, const float* tprev, Intr k, const float* vp, const float* np,
@@ -261,9 +266,7 @@ struct RgbdLaunch {
     const So3Result* so3_in;
 };
 void launch_rgbd_iteration(const RgbdLaunch& l, hipStream_t s);
-void launch_rgbd_finalize(const float* icp_partials, const float* rgb_partials, const int2* cnt, int nb, float icpWeight, int icpOn,
-                          int rgbOnly, int rgbOn, int prev_level, const GNState* st_in, const So3Result* so3, PoseDev* pose,
-                          PoseDev* host_mirror, float* log_out, float jump_limit, hipStream_t s);
+void launch_rgbd_finalize(const GnLast& last, float icpWeight, int icpOn, int rgbOnly, const GnFinalize& f, hipStream_t s);
 
 // ---------------- surfels ----------------
 void launch_init_surfels(const uint8_t* rgb, const float* depthRaw, const float* depthF, int W, int H, Intr k,

@@ -1,7 +1,7 @@
 // mf_model_pyramid_device.h -- the arithmetic of the model-side pyramid (copyMaps + resize x2 + transform x3), shared by model_pyramid_body
-// (mf_odometry.hip: k_model_pyramid, k_bilateral_model_pyramid, k_frame_model_pyramid) and the epilogue of the tile pass that builds the same three
+// (mf_model_pyramid.hip: k_model_pyramid, k_bilateral_model_pyramid, k_frame_model_pyramid) and the epilogue of the tile pass that builds the same three
 // levels from the prediction it has just drawn (mf_splat.hip: k_splat_tile, "tilePyramid").  Every float operation of these functions is pinned: the
-// pragma sits inside each body and the fused multiply-adds are written out, in the form mf_odometry.hip -- which allows contraction -- compiled
+// pragma sits inside each body and the fused multiply-adds are written out, in the form mf_model_pyramid.hip -- which allows contraction -- compiled
 // them to before they moved here (read off the gfx950 ISA of the three kernels: R a as fma(R2, az, fma(R0, ax, R1 * ay)), the squared length of an
 // averaged normal as fma(z, z, fma(x, x, y * y))).  mf_splat.hip has contraction off; written out, both files run the same instructions.
 #pragma once

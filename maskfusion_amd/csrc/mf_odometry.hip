@@ -1,8 +1,6 @@
 // mf_odometry.hip -- frame-to-model projective ICP with the whole Gauss-Newton loop resident on the device.
 //
-// Replaces (reference, relative to /root/reference):
-//   RGBDOdometry::initICPModel            Core/Utils/RGBDOdometry.cpp:153-185  (copyMaps, resizeVMap/NMap, tranformMaps;
-//                                         Core/Cuda/cudafuncs.cu:207-331,366-445) + FillIn (Core/Shaders/fill_*.frag)
+// Replaces (paths in the reference's tree; initICPModel, the model-side pyramid, is mf_model_pyramid.hip):
 //   icpStep / ICPReduction / reduceSum    Core/Cuda/reduce.cu:92-187,259-525
 //   the host side of getIncrementalTransformation (LDLT, SE(3) update)  RGBDOdometry.cpp:327-497,
 //                                         Core/Utils/OdometryProvider.h:32-90
@@ -16,14 +14,14 @@
 // bit-reproducible run to run.  With the photometric term an iteration is two launches (k_rgbd_iter, k_rgb_step).
 // A launch per iteration is the cheapest device-wide synchronisation this GPU offers: the same loop inside one persistent
 // launch (device-wide barriers) was measured 5.8x slower in round 3 and removed.
+// This file holds the solve (ldlt6_solve ... gn_finish_wg, gn_step_wg: the test builds cut it out of this file's text), the kernels of the three
+// loops, their argument structs and launch forms; the reductions, the per-pixel arithmetic and the other parts the loops share are mf_gn_device.h.
 #include <string.h>
 
 #include "mf_internal.h"
 #include "mf_device.h"
 #include "mf_rgbd_device.h"
-#include "mf_bilateral_device.h"
-#include "mf_frame_pyramid_device.h"
-#include "mf_model_pyramid_device.h"
+#include "mf_gn_device.h"
 
 namespace mf {
 
@@ -206,10 +204,11 @@ __device__ __forceinline__ void gn_solve_update_serial(const double* sys, const 
 // s_st is updated in place: resultRt, Rcurr, tcurr, trR, trt, lastICPError / Count, valid, ill; everything else keeps its value.  s_pose
 // receives Rcurr[9] tcurr[3] (slots 0..11; slots 12..23 = Rprev_inv, tprev are pose-independent and written by the caller once).
 // The caller places a barrier between this call and any other wavefront's use of s_st / s_pose.
-struct GnStamps { unsigned long long t[6]; };   // shader-clock stamps inside the solve (profiling; thread 0 of workgroup 0)
-__device__ __forceinline__ void gn_finish_wg(const double* s_sys, GNState* s_st, float* s_pose, float* s_T /*[16], unused since round 4*/, bool stamps,
-                                             GnStamps& st) {
-    (void)s_T;
+// Shader-clock stamps inside the solve ("icpProfile").  `on` is set in the one thread that keeps them (thread 0 of workgroup 0): a flag beside the
+// stamps, not a null pointer in the other threads, so that the struct stays in registers
+struct GnStamps { unsigned long long t[6]; bool on; };
+__device__ __forceinline__ void gn_finish_wg(const double* s_sys, GNState* s_st, float* s_pose /*[24]*/, GnStamps* stamps = nullptr) {
+    const bool stamped = stamps != nullptr && stamps->on;
     if (threadIdx.x == 64) {   // wavefront 1 has nothing to do until the caller's barrier: the iteration's statistics (an IEEE square root and a
                                // division, ~150 cycles) leave wavefront 0's chain
         const float res = (float)s_sys[27], inl = (float)s_sys[28];
@@ -239,10 +238,10 @@ __device__ __forceinline__ void gn_finish_wg(const double* s_sys, GNState* s_st,
                 if (j == 6) b[i] = value;
                 else { A[i][j] = value; A[j][i] = value; }
             }
-        if (stamps) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st.t[0] = __builtin_amdgcn_s_memtime(); }
+        if (stamped) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); stamps->t[0] = __builtin_amdgcn_s_memtime(); }
         ldlt6_solve(A, b, x, &ratio);
         ill = (s_sys[28] < 6.0 || !(ratio >= 1e-8)) ? 1 : 0;   // outside the stated domain of this solver (finding F4): counted, see GNState::ill
-        if (stamps) st.t[1] = __builtin_amdgcn_s_memtime() + (unsigned long long)(x[0] == 1.2345e300);   // (the stamp waits for the solve)
+        if (stamped) stamps->t[1] = __builtin_amdgcn_s_memtime() + (unsigned long long)(x[0] == 1.2345e300);   // (the stamp waits for the solve)
         double Rw[3][3];
         rodrigues_d(x[3], x[4], x[5], Rw);
         const double w0 = r == 0 ? Rw[0][0] : (r == 1 ? Rw[1][0] : Rw[2][0]);
@@ -251,7 +250,7 @@ __device__ __forceinline__ void gn_finish_wg(const double* s_sys, GNState* s_st,
         const double xr = r == 0 ? x[0] : (r == 1 ? x[1] : x[2]);
         const double* Rt = s_st->resultRt;
         nr = w0 * Rt[0 * 4 + c] + w1 * Rt[1 * 4 + c] + w2 * Rt[2 * 4 + c] + xr * Rt[3 * 4 + c];   // resultRt <- [exp(w) | t] * resultRt
-        if (stamps) st.t[2] = __builtin_amdgcn_s_memtime() + (unsigned long long)(nr == 1.2345e300);
+        if (stamped) stamps->t[2] = __builtin_amdgcn_s_memtime() + (unsigned long long)(nr == 1.2345e300);
     }
     // Isometry3f transform T = float(resultRt[0..2][0..3]) lives in lanes r * 4 + c; currentT = [Rprev|tprev] * transform.inverse():
     // iR = trR^T, it = -iR trt, Rcurr = Rprev iR, tcurr = Rprev it + tprev.  The twelve entries are broadcast with v_readlane (a scalar
@@ -289,188 +288,17 @@ __device__ __forceinline__ void gn_finish_wg(const double* s_sys, GNState* s_st,
     else if (isT) { s_st->tcurr[q] = tcur; s_pose[9 + q] = tcur; }
     if (l == 0) {
         s_st->ill += ill;
-        if (stamps) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st.t[3] = __builtin_amdgcn_s_memtime(); st.t[4] = st.t[3]; st.t[5] = st.t[3]; }
-    }
-}
-__device__ __forceinline__ void gn_finish_wg(const double* s_sys, GNState* s_st, float* s_pose, float* s_T /*[16]*/) {
-    GnStamps unused;
-    gn_finish_wg(s_sys, s_st, s_pose, s_T, false, unused);
-}
-
-// value of lane (lane ^ kXor) for a 32-bit pattern, kXor = 1 or 2: quad permutes on the DPP path (no LDS crossbar)
-template <int kXor>
-__device__ __forceinline__ float lane_xor_bits(int bits, int /*lane*/) {
-    static_assert(kXor == 1 || kXor == 2, "quad permutes only");
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, bits, kXor == 1 ? 0xB1 : 0x4E, 0xf, 0xf, false));
-}
-
-// Fixed-order reduction of `nb` per-workgroup partials ([nb][32] floats) by a 256-thread workgroup -> sys[32] doubles
-// in LDS.  The array is read as float4s with up to 10 independent 16 B loads in flight per lane (a one-load-at-a-time
-// loop cost ~70 cycles per partial: 10 us at 300 workgroups; the partials live in other XCDs' L2s, so every batch is
-// a fabric round trip).  Thread t < 256 owns components 4*(t%8)..+3 of workgroups t/8, t/8 + 32, ...
-// Round 4 (in-kernel stamps, profiles/r04c_icp_prof.txt: this phase was 3.1 k of a launch's 13.6 k ticks, of which the memory round trip
-// is ~0.9 k): a thread's own <= 10 values per component are added in fp32 -- they ARE fp32 sums of up to 1 536 products each, the extra
-// rounding is below theirs -- instead of 40 conversions + 40 fp64 additions + 80 selects per thread on a quarter-rate pipe; the 32 row sums
-// per component are then added in fp64 by FOUR lanes per component (8 rows each, in row order) and a quad butterfly on the DPP path
-// instead of one lane walking 32 dependent additions.  The order is fixed, so every workgroup (and every run) gets bit-identical sums.
-__device__ __forceinline__ double quad_sum_d(double v) {   // v + its three quad neighbours, same bits in all four lanes
-    const int lane = threadIdx.x & 63;
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    double o = __hiloint2double(__float_as_int(lane_xor_bits<1>(hi, lane)), __float_as_int(lane_xor_bits<1>(lo, lane)));
-    v = (lane & 1) ? o + v : v + o;            // both lanes of a pair add (even lane's value) + (odd lane's value)
-    lo = __double2loint(v); hi = __double2hiint(v);
-    o = __hiloint2double(__float_as_int(lane_xor_bits<2>(hi, lane)), __float_as_int(lane_xor_bits<2>(lo, lane)));
-    return (lane & 2) ? o + v : v + o;
-}
-__device__ __forceinline__ void reduce_rows(const double* s_seg /*[32][32]*/, double* s_sys /*[32]*/, int t /* 0..127 */) {
-    const int comp = t >> 2, part = t & 3;
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += s_seg[(part * 8 + k) * 32 + comp];
-    s = quad_sum_d(s);
-    if (part == 0) s_sys[comp] = s;
-}
-__device__ __forceinline__ void partial_sums_f32(const float4* __restrict__ p4, int n4, int t, float (&a)[4]) {
-    a[0] = a[1] = a[2] = a[3] = 0.f;
-    for (int f = t; f < n4; f += 2560) {  // 10 independent 16 B loads in flight per lane
-        float4 v[10];
-#pragma unroll
-        for (int u = 0; u < 10; ++u) v[u] = p4[min(f + 256 * u, n4 - 1)];  // unconditional: all ten issue back to back
-#pragma unroll
-        for (int u = 0; u < 10; ++u) {
-            const bool in = f + 256 * u < n4;
-            a[0] += in ? v[u].x : 0.f; a[1] += in ? v[u].y : 0.f;
-            a[2] += in ? v[u].z : 0.f; a[3] += in ? v[u].w : 0.f;
-        }
-    }
-}
-__device__ __forceinline__ void reduce_partials(const float* __restrict__ partials, int nb, double* s_seg /*[32][32]*/,
-                                                double* s_sys /*[32]*/) {
-    // The first 256 threads of the workgroup load; any workgroup size that is a multiple of 256 may call this.
-    if (threadIdx.x < 256) {
-        float a[4];
-        partial_sums_f32(reinterpret_cast<const float4*>(partials), nb * (kIcpSlots / 4), threadIdx.x, a);
-        const int row = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;
-        s_seg[row * 32 + c4 + 0] = (double)a[0]; s_seg[row * 32 + c4 + 1] = (double)a[1];
-        s_seg[row * 32 + c4 + 2] = (double)a[2]; s_seg[row * 32 + c4 + 3] = (double)a[3];
-    }
-    __syncthreads();
-    if (threadIdx.x < 128) reduce_rows(s_seg, s_sys, threadIdx.x);
-    __syncthreads();
-}
-
-// Two partial arrays (ICP and photometric) and the correspondence counts in ONE memory latency: threads 0..255 reduce the
-// first array, threads 256..511 the second, wavefront 0 issues the count loads ahead of its partial loads.  Needs a
-// workgroup of >= 512 threads (the kernels here have exactly that); bit-identical sums to two reduce_partials calls.
-__device__ __forceinline__ void reduce_partials_pair(const float* __restrict__ pa, const float* __restrict__ pb, const int2* __restrict__ cnt,
-                                                     int nb, double* s_segA, double* s_segB, double* s_sysA, double* s_sysB, int* s_cnt) {
-    const int half = threadIdx.x >> 8, t = threadIdx.x & 255;
-    unsigned c = 0, g = 0;
-    if (threadIdx.x < 64)
-        for (int i = threadIdx.x; i < nb; i += 64) { const int2 v = cnt[i]; c += (unsigned)v.x; g += (unsigned)v.y; }
-    if (half < 2) {
-        float a[4];
-        partial_sums_f32(reinterpret_cast<const float4*>(half ? pb : pa), nb * (kIcpSlots / 4), t, a);
-        double* s_seg = half ? s_segB : s_segA;
-        const int row = t >> 3, c4 = (t & 7) * 4;
-        s_seg[row * 32 + c4 + 0] = (double)a[0]; s_seg[row * 32 + c4 + 1] = (double)a[1];
-        s_seg[row * 32 + c4 + 2] = (double)a[2]; s_seg[row * 32 + c4 + 3] = (double)a[3];
-    }
-    if (threadIdx.x < 64) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { c += (unsigned)__shfl_xor((int)c, o, 64); g += (unsigned)__shfl_xor((int)g, o, 64); }
-        if (threadIdx.x == 0) { s_cnt[0] = (int)c; s_cnt[1] = (int)g; }
-    }
-    __syncthreads();
-    if (t < 128 && half < 2) reduce_rows(half ? s_segB : s_segA, half ? s_sysB : s_sysA, t);
-    __syncthreads();
-}
-
-// Sum of 29 (padded to 32) accumulators over the 64 lanes of a wavefront by recursive halving: at step s each lane
-// keeps the half of its remaining values selected by bit s of its lane id and hands the other half to lane ^ (1 << s),
-// so 16 + 8 + 4 + 2 + 1 + 1 = 32 cross-lane moves do what 29 x 6 = 174 full-width reductions did (measured: the
-// 174-DPP form cost ~2.2k cycles per wavefront and dominated the launch at 4 wavefronts per SIMD).
-// On return lane l holds the wave total of component bitrev5(l & 31) in v[0] (components >= 29 are zero padding).
-__device__ __forceinline__ int icp_component_of_lane(int lane) {
-    const int l = lane & 31;
-    return ((l & 1) << 4) | ((l & 2) << 2) | (l & 4) | ((l & 8) >> 2) | ((l & 16) >> 4);
-}
-// bitwise select (one v_bfi_b32): written on the bit patterns so that the compiler cannot turn "cond ? v[a] : v[b]" into
-// a dynamically indexed register array (which it lowers to a 32-deep compare/select chain per access).
-__device__ __forceinline__ float bitsel(unsigned mask, float a, float b) {
-    return __uint_as_float((__float_as_uint(a) & mask) | (__float_as_uint(b) & ~mask));
-}
-// Cross-lane fetch "value of lane (lane ^ kXor)".  xor 1 / 2 are quad permutes, xor 8 a 16-lane row rotation, xor 4 two row
-// rotations and a select -- all DPP modifiers on VALU instructions (no LDS crossbar traffic); only xor 16 / 32 cross a DPP row
-// and go through ds_bpermute.  30 of the 32 exchanges of the halving tree are xor 1..8: with every exchange on the
-// bpermute path the tree cost ~5 k cycles per launch at 16 wavefronts per CU (the crossbar serialises them).
-template <int kXor>
-__device__ __forceinline__ float lane_xor(float v, int lane) {
-    const int iv = __float_as_int(v);
-    if constexpr (kXor == 1) return __int_as_float(__builtin_amdgcn_update_dpp(0, iv, 0xB1, 0xf, 0xf, false));   // quad_perm:[1,0,3,2]
-    else if constexpr (kXor == 2) return __int_as_float(__builtin_amdgcn_update_dpp(0, iv, 0x4E, 0xf, 0xf, false));   // quad_perm:[2,3,0,1]
-    else if constexpr (kXor == 4) {
-        const int dn = __builtin_amdgcn_update_dpp(0, iv, 0x124, 0xf, 0xf, false);   // row_ror:4  -> lane i reads i - 4 (mod 16)
-        const int up = __builtin_amdgcn_update_dpp(0, iv, 0x12C, 0xf, 0xf, false);   // row_ror:12 -> lane i reads i + 4 (mod 16)
-        return __int_as_float((lane & 4) ? dn : up);
-    } else if constexpr (kXor == 8) return __int_as_float(__builtin_amdgcn_update_dpp(0, iv, 0x128, 0xf, 0xf, false));   // row_ror:8
-    else return __shfl_xor(v, kXor, 64);
-}
-
-template <int kStep>
-__device__ __forceinline__ void halving_step(float (&v)[32], int lane) {
-    constexpr int half = 16 >> kStep;
-    const unsigned up = ((lane >> kStep) & 1) ? 0xFFFFFFFFu : 0u;
-#pragma unroll
-    for (int k = 0; k < half; ++k) {
-        const float send = bitsel(up, v[k], v[k + half]);
-        const float keep = bitsel(up, v[k + half], v[k]);
-        v[k] = keep + lane_xor<(1 << kStep)>(send, lane);
+        if (stamped) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); stamps->t[3] = __builtin_amdgcn_s_memtime(); stamps->t[4] = stamps->t[3]; stamps->t[5] = stamps->t[3]; }
     }
 }
 
-__device__ __forceinline__ float wave_sum32_halving(float (&v)[32]) {
-    const int lane = threadIdx.x & 63;
-    halving_step<0>(v, lane);
-    halving_step<1>(v, lane);
-    halving_step<2>(v, lane);
-    halving_step<3>(v, lane);
-    halving_step<4>(v, lane);
-    return v[0] + __shfl_xor(v[0], 32, 64);
-}
-
-// Sum of the 29 accumulators over ALL kT threads of a workgroup through LDS, in a fixed order: lane pairs first (one DPP add per
-// accumulator), even lanes store column-wise [component][kT / 2] (consecutive lanes -> consecutive banks), then component c is
-// summed by G = kT / 32 neighbouring threads (16 values each, read as four conflict-free float4 rows) and a G-lane DPP butterfly.
-// ~85 instructions per wavefront and 60 KB of LDS traffic per 512-thread workgroup against ~300 instructions per wavefront for
-// the register halving tree above (which stays for the RGB-D kernels): the tree was 2.4 k of the 15 k cycles of a level-0 launch.
-// out: the workgroup's 32-float partial (components >= 29 are written as zeros).
-template <int kT>
-__device__ __forceinline__ void block_sum29_lds(const float (&acc)[32], float* s_red /*[29][kT / 2]*/, float* __restrict__ out) {
-    constexpr int kHalf = kT / 2, G = kT / 32;
-    static_assert(G == 8 || G == 16, "kT must be 256 or 512");
-    const int tid = threadIdx.x, lane = tid & 63;
-#pragma unroll
-    for (int c = 0; c < 29; ++c) {
-        const float v = acc[c] + lane_xor<1>(acc[c], lane);
-        if ((lane & 1) == 0) s_red[c * kHalf + (tid >> 1)] = v;
-    }
-    __syncthreads();
-    const int c = tid / G, g = tid % G;
-    float s = 0.f;
-    if (c < 29) {
-        const float4* __restrict__ row = reinterpret_cast<const float4*>(s_red + c * kHalf);
-        float4 v[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) v[m] = row[m * G + g];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) s += (v[m].x + v[m].y) + (v[m].z + v[m].w);
-    }
-    s += lane_xor<1>(s, lane);
-    s += lane_xor<2>(s, lane);
-    s += lane_xor<4>(s, lane);
-    if (G == 16) s += lane_xor<8>(s, lane);
-    if (g == 0) out[c] = s;
+// Finishing the previous iteration, identically in every workgroup that calls it: its state -> LDS, its per-workgroup partial sums -> s_sys in a
+// fixed order, solve + pose update in place (Rcurr / tcurr also to s_pose[0..11]).  The caller places a barrier behind it.
+__device__ __forceinline__ void gn_step_wg(const GNState* st_in, const float* __restrict__ partials, int nb, double* s_seg, double* s_sys, GNState* s_st,
+                                           float* s_pose) {
+    gn_stage(s_st, st_in);
+    reduce_partials(partials, nb, s_seg, s_sys);   // (its barriers also publish s_st)
+    gn_finish_wg(s_sys, s_st, s_pose);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -488,17 +316,6 @@ static void icp_gates(float distThres, float angleThres, float& dist2Max, float&
     dist2Max = d2; sine2Min = s2;
 }
 
-// Gauss-Newton trace of a tracking step (debug tap "gn_trace", tests/test_gpu_parity_long.py): row r = [0..31] the reduced system of iteration r
-// as the device summed it (fp64: 27 packed products, sum r^2, inliers), [32..47] resultRt, [48..56] Rcurr, [57..59] tcurr as iteration r USED
-// them; row n_iterations holds the state after the last update.  Written by lanes u = 0..59 of whoever finishes an iteration.
-__device__ __forceinline__ void gn_trace_write(double* __restrict__ trace, int it, bool have_sys, const double* s_sys, const GNState* s_st, int u) {
-    if (!trace || u < 0) return;
-    if (u < 32) { if (have_sys) trace[kGnTraceRow * (it - 1) + u] = s_sys[u]; }
-    else if (u < 48) trace[kGnTraceRow * it + u] = s_st->resultRt[u - 32];
-    else if (u < 57) trace[kGnTraceRow * it + u] = (double)s_st->Rcurr[u - 48];
-    else if (u < 60) trace[kGnTraceRow * it + u] = (double)s_st->tcurr[u - 57];
-}
-
 struct IcpKArgs {
     const float* vc; const float* nc; const float* vp; const float* np;
     int W, H; Intr k;
@@ -512,87 +329,6 @@ struct IcpKArgs {
     const PoseDev* pose_in;        // first launch of a tracking step: seed the state from the model pose
     const So3Result* so3_in;       // ... and resultRt's rotation from the SO(3) pre-alignment (RGBDOdometry.cpp:338-344)
 };
-
-// Correspondence search for one pixel, split in two so that the gathers of all four pixels of a thread are in flight
-// together (a per-pixel search-then-accumulate serialises four dependent L2 round trips: ~2 us per launch).
-struct IcpCorr { float3 vcurr_g, vcurr_cp, ncurr_g; int j; bool ok; };
-
-// Per-pixel arithmetic of the ICP kernels, every operation rounded on its own and in the order of the CPU restatement the
-// parity tests check against (its m33_mul / f3_dot / f3_cross: a plain reading of Core/Cuda/reduce.cu:292-415), contraction off.  Two reasons:
-//  * everything that DECIDES something -- the rounded projection (ux, uy), the 0.10 m distance gate, the sin 20 degrees gate, the
-//    NaN tests -- is then bit-identical to the oracle, so the inlier set (not just its size) matches by construction, and the
-//    seven row entries of every inlier do too; only the accumulation of the 28 products differs (fp32 block sums here, double there);
-//  * k_icp_iter<512>, k_icp_iter<256>, k_icp_batch_pixels and k_rgbd_iter are separate functions, and left to itself the compiler
-//    contracts a * b + c differently in each.  The 1e-7 relative spread that causes is invisible for a room-sized model, but a freshly
-//    spawned object (2 000 pixels on two box faces: a 6x6 system with condition ~1e5) turns it into millimetres of pose: the batched
-//    loop and the model-by-model loop must agree pixel for pixel (tests/test_gpu_multimodel.py::test_batched_tracking_...).
-// Cost: ~20 instructions per pixel (3 mul + 2 add instead of 1 mul + 2 fma per matrix row).
-__device__ __forceinline__ float3 icp_mul33(const float* R, float3 v) {
-#pragma clang fp contract(off)
-    return f3(R[0] * v.x + R[1] * v.y + R[2] * v.z, R[3] * v.x + R[4] * v.y + R[5] * v.z, R[6] * v.x + R[7] * v.y + R[8] * v.z);
-}
-__device__ __forceinline__ float icp_dot3(float3 a, float3 b) {
-#pragma clang fp contract(off)
-    return a.x * b.x + a.y * b.y + a.z * b.z;
-}
-__device__ __forceinline__ float3 icp_cross3(float3 a, float3 b) {
-#pragma clang fp contract(off)
-    return f3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-}
-
-template <class Args>
-__device__ __forceinline__ IcpCorr icp_project(float vx, float vy, float vz, float nx, float ny, float nz, const float* Rc,
-                                               float3 tc, const float* Rpi, float3 tp, const Args& a) {
-#pragma clang fp contract(off)
-    // search(), first half: Core/Cuda/reduce.cu:292-314
-    IcpCorr c;
-    const float3 g = icp_mul33(Rc, f3(vx, vy, vz));
-    c.vcurr_g = f3(g.x + tc.x, g.y + tc.y, g.z + tc.z);
-    c.vcurr_cp = icp_mul33(Rpi, f3(c.vcurr_g.x - tp.x, c.vcurr_g.y - tp.y, c.vcurr_g.z - tp.z));
-    const int ux = __float2int_rn((c.vcurr_cp.x * a.k.fx) / c.vcurr_cp.z + a.k.cx);
-    const int uy = __float2int_rn((c.vcurr_cp.y * a.k.fy) / c.vcurr_cp.z + a.k.cy);
-    c.ok = !(ux < 0 || uy < 0 || ux >= a.W || uy >= a.H || c.vcurr_cp.z < 0) && !isnan(nx);
-    c.j = c.ok ? uy * a.W + ux : 0;
-    c.ncurr_g = icp_mul33(Rc, f3(nx, ny, nz));
-    return c;
-}
-
-template <class Args>
-__device__ __forceinline__ void icp_accumulate(const IcpCorr& c, float3 vprev_g, float3 nprev_g, const float* Rpi, float3 tp,
-                                               const Args& a, float* acc) {
-#pragma clang fp contract(off)
-    // search(), second half + getProducts(): Core/Cuda/reduce.cu:326-415
-    // dist = |vprev_g - vcurr_g| <= distThres and sine = |ncurr_g x nprev_g| < angleThres, decided on the squares: sqrtf is monotonic and
-    // correctly rounded, so sqrtf(x) <= T  <=>  x <= max{y : sqrtf(y) <= T}, and sqrtf(x) < T  <=>  x < min{y : sqrtf(y) >= T}; the host finds
-    // the two boundary floats once (icp_gates) and the kernel saves two IEEE square roots (~30 instructions) per pixel -- same inlier set, bit for bit.
-    const float3 dv = f3(vprev_g.x - c.vcurr_g.x, vprev_g.y - c.vcurr_g.y, vprev_g.z - c.vcurr_g.z);
-    const float dist2 = icp_dot3(dv, dv);
-    const float3 cr = icp_cross3(c.ncurr_g, nprev_g);
-    const float sine2 = icp_dot3(cr, cr);
-    const bool found = c.ok && sine2 < a.sine2Min && dist2 <= a.dist2Max && !isnan(nprev_g.x);
-    if (!found) return;
-    const float3 s_cp = c.vcurr_cp;
-    const float3 d_cp = icp_mul33(Rpi, f3(vprev_g.x - tp.x, vprev_g.y - tp.y, vprev_g.z - tp.z));
-    const float3 n_cp = icp_mul33(Rpi, nprev_g);
-    const float3 sxn = icp_cross3(s_cp, n_cp);
-    const float row[7] = {n_cp.x, n_cp.y, n_cp.z, sxn.x, sxn.y, sxn.z,
-                          icp_dot3(n_cp, f3(s_cp.x - d_cp.x, s_cp.y - d_cp.y, s_cp.z - d_cp.z))};
-    int k = 0;
-#pragma unroll
-    for (int r = 0; r < 7; ++r)
-#pragma unroll
-        for (int cc = r; cc < 7; ++cc) { acc[k] = fmaf(row[r], row[cc], acc[k]); ++k; }
-    acc[28] += 1.0f;
-}
-
-__device__ __forceinline__ void seed_state(const PoseDev& pose, GNState& s) {
-    for (int k = 0; k < 16; ++k) s.resultRt[k] = (k % 5 == 0) ? 1.0 : 0.0;
-    for (int k = 0; k < 9; ++k) { s.Rprev[k] = pose.R[k]; s.Rcurr[k] = pose.R[k]; s.trR[k] = (k % 4 == 0) ? 1.f : 0.f; }
-    for (int k = 0; k < 3; ++k) { s.tprev[k] = pose.t[k]; s.tcurr[k] = pose.t[k]; s.trt[k] = 0.f; }
-    m33_inverse_f(s.Rprev, s.Rprev_inv);  // RGBDOdometry.cpp:332
-    s.lastICPError = 0.f; s.lastICPCount = 0.f; s.valid = 0;
-    s.levelDone = -1; s.lastRGBError = 3.4028234664e38f; s.lastRGBCount = 0.f; s.ill = 0;
-}
 
 // Workgroup shape.  Per launch a CU spends its time in three VALU-throughput-bound stretches (one VALU instruction per 4
 // cycles per SIMD, 4 SIMDs): the per-pixel chain (project -> gather -> gate -> 29 products, ~250 instructions per 64
@@ -625,22 +361,14 @@ __global__ __launch_bounds__(kT) void k_icp_iter(const IcpKArgs a) {
     __shared__ float s_pose[24];  // Rcurr[9] tcurr[3] Rprev_inv[9] tprev[3]
     __shared__ float s_red[29 * (kT / 2)];
     __shared__ GNState s_st;      // the Gauss-Newton state: loaded (or seeded), updated in place by gn_finish_wg, stored by workgroup 0
-    __shared__ float s_T[16];
 
     const int tid = threadIdx.x;
-    // stage the Gauss-Newton state through LDS with one coalesced load (thread 0 would otherwise chase ~80 dependent
-    // scalar loads after the solve)
-    if (a.pose_in == nullptr) {
-        if (tid < (int)(sizeof(GNState) / 4)) reinterpret_cast<uint32_t*>(&s_st)[tid] = reinterpret_cast<const uint32_t*>(a.st_in)[tid];
-    } else if (tid == 0) {
-        seed_state(*a.pose_in, s_st);   // RGBDOdometry.cpp:239-243,332-336: Rprev = Rcurr = pose, resultRt = I
-        if (a.so3_in)
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) s_st.resultRt[r * 4 + c] = a.so3_in->R[r * 3 + c];
-    }
+    if (a.pose_in == nullptr) gn_stage(&s_st, a.st_in);
+    else if (tid == 0) gn_seed(*a.pose_in, a.so3_in, s_st);
     const bool prof = a.prof_out != nullptr && blockIdx.x == 0 && tid == 0;
     unsigned long long stamp[8];
     GnStamps gst;
+    gst.on = prof;
     if (prof) stamp[0] = __builtin_amdgcn_s_memtime();
     const int P = a.W * a.H;
     // A workgroup owns a contiguous chunk of <= kPx * kT pixels (icp_grid_blocks keeps the grid <= one workgroup
@@ -651,7 +379,7 @@ __global__ __launch_bounds__(kT) void k_icp_iter(const IcpKArgs a) {
 
     // (1) issue the pose-independent streamed loads first so their latency overlaps the solve below
     int idx[kPx]; bool act[kPx], won[kPx];
-    float vx[kPx], vy[kPx], vz[kPx], nx[kPx], ny[kPx], nz[kPx];
+    IcpPx px[kPx];
 #pragma unroll
     for (int q = 0; q < kPx; ++q) {
         // lanes past the end of the chunk re-read its last pixel and are masked out of the sums below: no divergent control flow
@@ -662,20 +390,20 @@ __global__ __launch_bounds__(kT) void k_icp_iter(const IcpKArgs a) {
         // (only where whole wavefronts are known to idle: a scalar branch is a scheduling fence for the loads around it, and at level 0 --
         // every wavefront carries at least two full slots -- the fenced form measured 0.2 us SLOWER per launch, profiles/r04b_*)
         won[q] = kSkipIdleSlots ? (__builtin_amdgcn_readfirstlane(beg + q * kT + (tid & ~63)) < end) : true;
-        vx[q] = vy[q] = vz[q] = nx[q] = ny[q] = nz[q] = 0.f;
+        px[q] = IcpPx{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (won[q]) {
             const int i = min(idx[q], P - 1);
-            vx[q] = a.vc[i]; vy[q] = a.vc[P + i]; vz[q] = a.vc[2 * P + i];
-            nx[q] = a.nc[i]; ny[q] = a.nc[P + i]; nz[q] = a.nc[2 * P + i];
+            px[q] = IcpPx{a.vc[i], a.vc[P + i], a.vc[2 * P + i], a.nc[i], a.nc[P + i], a.nc[2 * P + i]};
         }
     }
 
-    // (2) prologue: finish the previous iteration (reduce -> solve -> pose), identically in every workgroup
+    // (2) prologue: finish the previous iteration (reduce -> solve -> pose), identically in every workgroup -- gn_step_wg's three calls, with the
+    // streamed loads issued in front of them and the stamps between them
     if (prof) stamp[1] = __builtin_amdgcn_s_memtime();
     if (a.nb_in > 0) {
         reduce_partials(a.partials_in, a.nb_in, s_seg, s_sys);   // (its barriers also publish s_st)
         if (prof) stamp[2] = __builtin_amdgcn_s_memtime();
-        gn_finish_wg(s_sys, &s_st, s_pose, s_T, prof, gst);     // solve, exp, pose composition: state in place, Rcurr / tcurr -> s_pose[0..11]
+        gn_finish_wg(s_sys, &s_st, s_pose, &gst);   // solve, exp, pose composition: state in place, Rcurr / tcurr -> s_pose[0..11]
     } else {
         __syncthreads();
     }
@@ -686,15 +414,7 @@ __global__ __launch_bounds__(kT) void k_icp_iter(const IcpKArgs a) {
     if (prof) { if (a.nb_in == 0) stamp[2] = stamp[1]; stamp[3] = __builtin_amdgcn_s_memtime(); }
     __syncthreads();
     if (prof) stamp[4] = __builtin_amdgcn_s_memtime();
-    if (blockIdx.x == 0) {
-        // workgroup 0 publishes the state (84 words) and the iteration log (32 floats): one store instruction each, after the barrier
-        constexpr int kWords = (int)(sizeof(GNState) / 4);
-        static_assert(kWords + 32 <= kT, "state + log lanes");
-        if (tid < kWords) reinterpret_cast<uint32_t*>(a.st_out)[tid] = reinterpret_cast<const uint32_t*>(&s_st)[tid];
-        else if (tid < kWords + 32 && a.log_out && a.nb_in > 0) a.log_out[tid - kWords] = (float)s_sys[tid - kWords];
-        static_assert(kWords + 32 + 60 <= kT, "trace lanes");
-        gn_trace_write(a.trace, a.it, a.nb_in > 0, s_sys, &s_st, tid - (kWords + 32));
-    }
+    if (blockIdx.x == 0) gn_publish(a.st_out, a.log_out, a.trace, a.it, a.nb_in > 0, s_sys, &s_st);
 
     float Rc[9], Rpi[9];
 #pragma unroll
@@ -706,26 +426,7 @@ __global__ __launch_bounds__(kT) void k_icp_iter(const IcpKArgs a) {
     float acc[32];
 #pragma unroll
     for (int k = 0; k < 32; ++k) acc[k] = 0.f;
-    // all projections, then all gathers (independent loads in flight together), then the products
-    IcpCorr cor[kPx];
-    float3 pv[kPx], pn[kPx];
-#pragma unroll
-    for (int q = 0; q < kPx; ++q) {
-        if (!won[q]) continue;
-        cor[q] = icp_project(vx[q], vy[q], vz[q], nx[q], ny[q], nz[q], Rc, tc, Rpi, tp, a);
-        cor[q].ok = cor[q].ok && act[q];
-        cor[q].j = cor[q].ok ? cor[q].j : 0;
-    }
-#pragma unroll
-    for (int q = 0; q < kPx; ++q) {
-        if (!won[q]) continue;
-        const int j = cor[q].j;
-        pv[q] = f3(a.vp[j], a.vp[P + j], a.vp[2 * P + j]);
-        pn[q] = f3(a.np[j], a.np[P + j], a.np[2 * P + j]);
-    }
-#pragma unroll
-    for (int q = 0; q < kPx; ++q)
-        if (won[q]) icp_accumulate(cor[q], pv[q], pn[q], Rpi, tp, a, acc);
+    icp_slots<kPx>(px, act, won, a.vp, a.np, P, Rc, tc, Rpi, tp, a, acc);
 
     // (4) wavefront reduction (halving tree), one LDS stage across the wavefronts, one 128 B partial per workgroup
     if (prof) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp[5] = __builtin_amdgcn_s_memtime(); }
@@ -811,54 +512,45 @@ void launch_icp_iteration(const IcpLaunch& l, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // last reduce + solve of a tracking step, then Model::pose / lastPose / statistics (RGBDOdometry.cpp:476-496, Model.cpp:437-446)
 // and the object-model jump rule.  Called by all 256 threads of a workgroup.
-// s_st: LDS copy of the state (st_in may already point at it); s_scr: 40 floats of LDS.
-__device__ __forceinline__ void icp_finalize_body(const float* __restrict__ partials_in, int nb_in, const GNState* st_in,
-                                                  PoseDev* __restrict__ pose, PoseDev* __restrict__ host_mirror, float* __restrict__ log_out,
-                                                  float jump_limit, const So3Result* __restrict__ so3, double* s_seg, double* s_sys,
-                                                  GNState* s_st, float* s_scr, double* __restrict__ trace = nullptr, int n_it = 0) {
-    if (st_in != s_st && threadIdx.x < (int)(sizeof(GNState) / 4))
-        reinterpret_cast<uint32_t*>(s_st)[threadIdx.x] = reinterpret_cast<const uint32_t*>(st_in)[threadIdx.x];
-    if (nb_in > 0) {
-        reduce_partials(partials_in, nb_in, s_seg, s_sys);     // (its barriers also publish s_st)
-        gn_finish_wg(s_sys, s_st, s_scr, s_scr + 24);
-        if (log_out && threadIdx.x >= 64 && threadIdx.x < 96) log_out[threadIdx.x - 64] = (float)s_sys[threadIdx.x - 64];
-    }
-    __syncthreads();
-    gn_trace_write(trace, n_it, nb_in > 0, s_sys, s_st, (int)threadIdx.x - 128);   // the last system and the state it led to
-    if (threadIdx.x == 0) {
-        const GNState& st = *s_st;
-        PoseDev p = *pose;
-        for (int k = 0; k < 9; ++k) { p.lastR[k] = st.Rprev[k]; p.R[k] = st.Rcurr[k]; }
-        for (int k = 0; k < 3; ++k) { p.lastT[k] = st.tprev[k]; p.t[k] = st.tcurr[k]; }
-        p.lastICPError = st.lastICPError;
-        p.lastICPCount = st.lastICPCount;
-        p.rejected = 0; p.lastRGBError = 0.f; p.lastRGBCount = 0.f;
-        if (so3) { p.lastSO3Error = so3->error; p.lastSO3Count = so3->count; p.so3Iterations = so3->iterations; }
-        else { p.lastSO3Error = 0.f; p.lastSO3Count = 0.f; p.so3Iterations = 0; }
-        for (int k = 0; k < 3; ++k) p.incT[k] = st.trt[k];
-        p.illIterations = st.ill;
-        if (jump_limit > 0.f && norm3(f3(st.trt[0], st.trt[1], st.trt[2])) >= jump_limit) p.alive = 0;   // `float d > 0.2` is a DOUBLE comparison upstream (MaskFusion.cpp:268): true from 0.2f on
-        pose_derive(p);
-        *pose = p;
-        if (host_mirror) *host_mirror = p;
-    }
+// one thread: the model's pose block and its pinned mirror from the final state (the fields a tracking step does not own keep their values)
+// (the two blocks as restrict PARAMETERS: the compiler then carries the untouched fields from *pose to both stores in registers)
+__device__ __forceinline__ void write_pose(PoseDev* __restrict__ pose, PoseDev* __restrict__ host_mirror, const GNState& st, const GnFinalize& f,
+                                           bool photometric) {
+    PoseDev p = *pose;
+    pose_from_state(st, f.so3, f.jump_limit, photometric, p);
+    *pose = p;
+    if (host_mirror) *host_mirror = p;
 }
 
-__global__ __launch_bounds__(256) void k_icp_finalize(const float* __restrict__ partials_in, int nb_in,
-                                                       const GNState* __restrict__ st_in, PoseDev* __restrict__ pose,
-                                                       PoseDev* __restrict__ host_mirror, float* __restrict__ log_out,
+// f.log: where the last reduced system goes (or nullptr).  s_st: the workgroup's LDS copy of the state.
+__device__ __forceinline__ void icp_finalize_body(const float* __restrict__ partials_in, int nb_in, const GNState* st_in, const GnFinalize& f,
+                                                  double* s_seg, double* s_sys, GNState* s_st, float* s_pose) {
+    if (nb_in > 0) {
+        gn_step_wg(st_in, partials_in, nb_in, s_seg, s_sys, s_st, s_pose);
+        if (f.log && threadIdx.x >= 64 && threadIdx.x < 96) f.log[threadIdx.x - 64] = (float)s_sys[threadIdx.x - 64];
+    } else {
+        gn_stage(s_st, st_in);
+    }
+    __syncthreads();
+    gn_trace_write(f.trace, f.n_it, nb_in > 0, s_sys, s_st, (int)threadIdx.x - 128);   // the last system and the state it led to
+    if (threadIdx.x == 0) write_pose(f.pose, f.host_mirror, *s_st, f, false);
+}
+
+// (GnFinalize's fields arrive as restrict parameters of their own: inside a by-value struct they are not, and the kernel took 130 registers for 126)
+__global__ __launch_bounds__(256) void k_icp_finalize(const float* __restrict__ partials_in, int nb_in, const GNState* __restrict__ st_in,
+                                                       PoseDev* __restrict__ pose, PoseDev* __restrict__ host_mirror, float* __restrict__ log_out,
                                                        float jump_limit, const So3Result* __restrict__ so3, double* __restrict__ trace, int n_it) {
+    const GnFinalize f{pose, host_mirror, log_out, jump_limit, so3, trace, n_it};
     __shared__ double s_seg[32 * 32];
     __shared__ double s_sys[32];
     __shared__ GNState s_st;
-    __shared__ float s_scr[40];
-    icp_finalize_body(partials_in, nb_in, st_in, pose, host_mirror, log_out, jump_limit, so3, s_seg, s_sys, &s_st, s_scr, trace, n_it);
+    __shared__ float s_pose[24];
+    icp_finalize_body(partials_in, nb_in, st_in, f, s_seg, s_sys, &s_st, s_pose);
 }
 
-void launch_icp_finalize(const float* partials_in, int nblocks_in, const GNState* state_in, PoseDev* pose,
-                         PoseDev* host_mirror, float* log_out, float jump_limit, const So3Result* so3, hipStream_t s, double* trace, int n_it) {
-    hipLaunchKernelGGL(k_icp_finalize, dim3(1), dim3(256), 0, s, partials_in, nblocks_in, state_in, pose, host_mirror,
-                       log_out, jump_limit, so3, trace, n_it);
+void launch_icp_finalize(const GnLast& last, const GnFinalize& f, hipStream_t s) {
+    hipLaunchKernelGGL(k_icp_finalize, dim3(1), dim3(256), 0, s, last.partials, last.nblocks, last.state, f.pose, f.host_mirror, f.log, f.jump_limit, f.so3,
+                       f.trace, f.n_it);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -866,37 +558,28 @@ void launch_icp_finalize(const float* partials_in, int nblocks_in, const GNState
 // ------------------------------------------------------------------------------------------------
 struct IcpSolveArgs { TrackBatch b; int it; int nb_in; const So3Result* so3; };
 
+// One model's step between two pixel passes of the batched loop, by all threads of a workgroup: it == 0 seeds the state, it > 0 finishes iteration
+// it - 1 (the functions k_icp_iter's prologue calls, on the same data in the same order: the same bits).  publish: this workgroup also leaves state,
+// log and trace in the model's block.  s_st is ready for every thread on return.
+__device__ __forceinline__ void batch_step(const TrackModelDev& md, int it, int nb_in, const So3Result* so3, bool publish, double* s_seg, double* s_sys,
+                                           GNState* s_st, float* s_pose) {
+    if (it == 0) {
+        if (threadIdx.x == 0) gn_seed(*md.pose, so3, *s_st);
+    } else {
+        const int prev = (it - 1) & 1;
+        gn_step_wg(md.st + prev, md.partials[prev], nb_in, s_seg, s_sys, s_st, s_pose);
+    }
+    __syncthreads();
+    // (it == 0: no system was reduced -- s_sys holds nothing, and have_sys = false keeps gn_publish from reading it)
+    if (publish) gn_publish(md.st + (it & 1), (md.log && it > 0) ? md.log + 32 * (it - 1) : nullptr, md.trace, it, it > 0, s_sys, s_st);
+}
+
 __global__ __launch_bounds__(256) void k_icp_batch_solve(const IcpSolveArgs a) {
     __shared__ double s_seg[32 * 32];
     __shared__ double s_sys[32];
     __shared__ GNState s_st;
-    __shared__ float s_scr[40];
-    const TrackModelDev* __restrict__ md = a.b.m[blockIdx.x];
-    const int tid = threadIdx.x;
-    if (a.it == 0) {   // RGBDOdometry.cpp:239-243,332-344: Rprev = Rcurr = pose, resultRt = I (or the SO(3) rotation)
-        if (tid == 0) {
-            GNState s;
-            seed_state(*md->pose, s);
-            if (a.so3)
-                for (int r = 0; r < 3; ++r)
-                    for (int c = 0; c < 3; ++c) s.resultRt[r * 4 + c] = a.so3->R[r * 3 + c];
-            md->st[0] = s;
-            if (md->trace) {
-                for (int u = 32; u < 60; ++u) gn_trace_write(md->trace, 0, false, nullptr, &s, u);
-            }
-        }
-        return;
-    }
-    const int prev = (a.it - 1) & 1;
-    if (tid < (int)(sizeof(GNState) / 4)) reinterpret_cast<uint32_t*>(&s_st)[tid] = reinterpret_cast<const uint32_t*>(md->st + prev)[tid];
-    reduce_partials(md->partials[prev], a.nb_in, s_seg, s_sys);   // (its barriers also publish s_st)
-    gn_finish_wg(s_sys, &s_st, s_scr, s_scr + 24);                 // the same function as k_icp_iter: bit-identical states
-    __syncthreads();
-    // state (84 words) and log (32 floats) leave through one store instruction each instead of ~115 scalar stores of thread 0
-    constexpr int kWords = (int)(sizeof(GNState) / 4);
-    if (tid < kWords) reinterpret_cast<uint32_t*>(md->st + (a.it & 1))[tid] = reinterpret_cast<const uint32_t*>(&s_st)[tid];
-    else if (tid < kWords + 32 && md->log) md->log[32 * (a.it - 1) + tid - kWords] = (float)s_sys[tid - kWords];
-    gn_trace_write(md->trace, a.it, true, s_sys, &s_st, tid - (kWords + 32));
+    __shared__ float s_pose[24];
+    batch_step(*a.b.m[blockIdx.x], a.it, a.nb_in, a.so3, true, s_seg, s_sys, &s_st, s_pose);
 }
 
 struct IcpPxArgs {
@@ -938,44 +621,17 @@ __global__ __launch_bounds__(kBatchThreads) void k_icp_batch_pixels(const IcpPxA
     __shared__ double s_seg[32 * 32];
     __shared__ double s_sys[32];
     __shared__ GNState s_st;
-    __shared__ float s_scr[40];
+    __shared__ float s_pose[24];
     const TrackModelDev* __restrict__ md = a.b.m[blockIdx.y];
     const float* __restrict__ vp = md->vm[a.level];
     const float* __restrict__ np = md->nm[a.level];
     const int tid = threadIdx.x;
-    constexpr int kWords = (int)(sizeof(GNState) / 4);
-    static_assert(kWords + 32 + 60 <= kBatchThreads, "state + log + trace lanes");
     if (a.fused) {
-        // k_icp_batch_solve's work as this launch's prologue (the same functions on the same data in the same order: the same bits), in every workgroup
-        // of the model; workgroup 0 of the model publishes state, log and trace for the next launch and the finalize step.  One launch per iteration
-        // instead of two: a dependent launch is 3.4 us before it does anything
-        if (a.it == 0) {
-            if (tid == 0) {
-                seed_state(*md->pose, s_st);
-                if (a.so3)
-                    for (int r = 0; r < 3; ++r)
-                        for (int c = 0; c < 3; ++c) s_st.resultRt[r * 4 + c] = a.so3->R[r * 3 + c];
-            }
-            __syncthreads();
-            if (blockIdx.x == 0) {
-                if (tid < kWords) reinterpret_cast<uint32_t*>(md->st)[tid] = reinterpret_cast<const uint32_t*>(&s_st)[tid];
-                if (tid == 0 && md->trace)
-                    for (int u = 32; u < 60; ++u) gn_trace_write(md->trace, 0, false, nullptr, &s_st, u);
-            }
-        } else {
-            const int prev = (a.it - 1) & 1;
-            if (tid < kWords) reinterpret_cast<uint32_t*>(&s_st)[tid] = reinterpret_cast<const uint32_t*>(md->st + prev)[tid];
-            reduce_partials(md->partials[prev], a.nb_in, s_seg, s_sys);   // (its barriers also publish s_st)
-            gn_finish_wg(s_sys, &s_st, s_scr, s_scr + 24);
-            __syncthreads();
-            if (blockIdx.x == 0) {
-                if (tid < kWords) reinterpret_cast<uint32_t*>(md->st + (a.it & 1))[tid] = reinterpret_cast<const uint32_t*>(&s_st)[tid];
-                else if (tid < kWords + 32 && md->log) md->log[32 * (a.it - 1) + tid - kWords] = (float)s_sys[tid - kWords];
-                gn_trace_write(md->trace, a.it, true, s_sys, &s_st, tid - (kWords + 32));
-            }
-        }
+        // k_icp_batch_solve's work as this launch's prologue, in every workgroup of the model; workgroup 0 of the model publishes state, log and trace
+        // for the next launch and the finalize step.  One launch per iteration instead of two: a dependent launch is 3.4 us before it does anything
+        batch_step(*md, a.it, a.nb_in, a.so3, blockIdx.x == 0, s_seg, s_sys, &s_st, s_pose);
     } else {
-        if (tid < kWords) reinterpret_cast<uint32_t*>(&s_st)[tid] = reinterpret_cast<const uint32_t*>(md->st + a.parity)[tid];
+        gn_stage(&s_st, md->st + a.parity);
         __syncthreads();
     }
     const GNState* st = &s_st;
@@ -1038,33 +694,19 @@ __global__ __launch_bounds__(kBatchThreads) void k_icp_batch_pixels(const IcpPxA
     float acc[32];
 #pragma unroll
     for (int k = 0; k < 32; ++k) acc[k] = 0.f;
+    static_assert(kBatchPx == 3, "kAllSlots names every slot");
+    const bool kAllSlots[kBatchPx] = {true, true, true};   // (no wavefront of a round idles: the chunk is a multiple of the round)
     for (int base = beg; base < end; base += kBatchPx * kBatchThreads) {
         bool act[kBatchPx];
-        float vx[kBatchPx], vy[kBatchPx], vz[kBatchPx], nx[kBatchPx], ny[kBatchPx], nz[kBatchPx];
+        IcpPx px[kBatchPx];
 #pragma unroll
         for (int q = 0; q < kBatchPx; ++q) {
             const int i0 = base + q * kBatchThreads + tid;
             act[q] = i0 < end;
             const int i = min(i0, P - 1);      // masked slots re-read a valid pixel: no divergent control flow (see k_icp_iter)
-            vx[q] = a.vc[i]; vy[q] = a.vc[P + i]; vz[q] = a.vc[2 * P + i];
-            nx[q] = a.nc[i]; ny[q] = a.nc[P + i]; nz[q] = a.nc[2 * P + i];
+            px[q] = IcpPx{a.vc[i], a.vc[P + i], a.vc[2 * P + i], a.nc[i], a.nc[P + i], a.nc[2 * P + i]};
         }
-        IcpCorr cor[kBatchPx];
-        float3 pv[kBatchPx], pn[kBatchPx];
-#pragma unroll
-        for (int q = 0; q < kBatchPx; ++q) {
-            cor[q] = icp_project(vx[q], vy[q], vz[q], nx[q], ny[q], nz[q], Rc, tc, Rpi, tp, a);
-            cor[q].ok = cor[q].ok && act[q];
-            cor[q].j = cor[q].ok ? cor[q].j : 0;
-        }
-#pragma unroll
-        for (int q = 0; q < kBatchPx; ++q) {
-            const int j = cor[q].j;
-            pv[q] = f3(vp[j], vp[P + j], vp[2 * P + j]);
-            pn[q] = f3(np[j], np[P + j], np[2 * P + j]);
-        }
-#pragma unroll
-        for (int q = 0; q < kBatchPx; ++q) icp_accumulate(cor[q], pv[q], pn[q], Rpi, tp, a, acc);
+        icp_slots<kBatchPx>(px, act, kAllSlots, vp, np, P, Rc, tc, Rpi, tp, a, acc);
     }
     block_sum29_lds<kBatchThreads>(acc, s_red, md->partials[a.parity] + blockIdx.x * kIcpSlots);
 }
@@ -1074,11 +716,11 @@ __global__ __launch_bounds__(256) void k_icp_batch_finalize(const IcpFinArgs a) 
     __shared__ double s_seg[32 * 32];
     __shared__ double s_sys[32];
     __shared__ GNState s_st;
-    __shared__ float s_scr[40];
+    __shared__ float s_pose[24];
     const TrackModelDev* __restrict__ md = a.b.m[blockIdx.x];
     const int last = (a.n_it - 1) & 1;
-    icp_finalize_body(a.n_it > 0 ? md->partials[last] : nullptr, a.n_it > 0 ? a.nb_in : 0, md->st + (a.n_it > 0 ? last : 0), md->pose, md->pose_host,
-                      (md->log && a.n_it > 0) ? md->log + 32 * (a.n_it - 1) : nullptr, md->jump_limit, a.so3, s_seg, s_sys, &s_st, s_scr, md->trace, a.n_it);
+    const GnFinalize f{md->pose, md->pose_host, (md->log && a.n_it > 0) ? md->log + 32 * (a.n_it - 1) : nullptr, md->jump_limit, a.so3, md->trace, a.n_it};
+    icp_finalize_body(a.n_it > 0 ? md->partials[last] : nullptr, a.n_it > 0 ? a.nb_in : 0, md->st + (a.n_it > 0 ? last : 0), f, s_seg, s_sys, &s_st, s_pose);
     if (threadIdx.x < 4) md->rect[threadIdx.x] = (threadIdx.x & 2) ? (int)0x80000000 : 0x7FFFFFFF;   // armed for the next frame's model pyramid
 }
 
@@ -1100,14 +742,13 @@ void launch_icp_batch_solve(const TrackBatch& b, int it, int nb_in, const So3Res
     IcpSolveArgs a{b, it, nb_in, so3};
     hipLaunchKernelGGL(k_icp_batch_solve, dim3(b.n), dim3(256), 0, s, a);
 }
-void launch_icp_batch_pixels(const TrackBatch& b, int it, int level, const float* vmap_curr, const float* nmap_curr, int W, int H, Intr k,
-                             float distThres, float angleThres, hipStream_t s, const float2* row_z, bool fused, int nb_in, const So3Result* so3) {
+void launch_icp_batch_pixels(const TrackBatch& b, int it, const IcpBatchLevel& l, bool fused, int nb_in, const So3Result* so3, hipStream_t s) {
     IcpPxArgs a;
-    a.row_z = row_z;
+    a.row_z = l.row_z;
     a.fused = fused ? 1 : 0; a.it = it; a.nb_in = nb_in; a.so3 = so3;
-    a.b = b; a.vc = vmap_curr; a.nc = nmap_curr; a.W = W; a.H = H; a.k = k; icp_gates(distThres, angleThres, a.dist2Max, a.sine2Min);
-    a.level = level; a.parity = it & 1; a.chunk = icp_batch_chunk(W * H, b.n);
-    hipLaunchKernelGGL(k_icp_batch_pixels, dim3(icp_batch_blocks(W, H, b.n), b.n), dim3(kBatchThreads), 0, s, a);
+    a.b = b; a.vc = l.vmap_curr; a.nc = l.nmap_curr; a.W = l.W; a.H = l.H; a.k = l.k; icp_gates(l.distThres, l.angleThres, a.dist2Max, a.sine2Min);
+    a.level = l.level; a.parity = it & 1; a.chunk = icp_batch_chunk(l.W * l.H, b.n);
+    hipLaunchKernelGGL(k_icp_batch_pixels, dim3(icp_batch_blocks(l.W, l.H, b.n), b.n), dim3(kBatchThreads), 0, s, a);
 }
 void launch_icp_batch_finalize(const TrackBatch& b, int n_it, int nb_in, const So3Result* so3, hipStream_t s) {
     IcpFinArgs a{b, n_it, nb_in, so3};
@@ -1122,22 +763,20 @@ __global__ __launch_bounds__(128) void k_gn_solve_test(const double* __restrict_
     __shared__ double s_sys[32];
     __shared__ GNState s_st;
     __shared__ float s_pose[24];
-    __shared__ float s_T[16];
     if (threadIdx.x < 32) s_sys[threadIdx.x] = threadIdx.x < 29 ? sys29[threadIdx.x] : 0.0;
-    if (threadIdx.x == 0) {
-        GNState& in = s_st;
-        for (int k = 0; k < 16; ++k) in.resultRt[k] = resultRt[k];
-        for (int k = 0; k < 9; ++k) { in.Rprev[k] = Rprev[k]; in.Rcurr[k] = Rprev[k]; in.trR[k] = 0.f; }
-        for (int k = 0; k < 3; ++k) { in.tprev[k] = tprev[k]; in.tcurr[k] = tprev[k]; in.trt[k] = 0.f; }
-        m33_inverse_f(in.Rprev, in.Rprev_inv);
-        in.lastICPError = in.lastICPCount = 0.f; in.valid = 0; in.levelDone = -1; in.lastRGBError = 0.f; in.lastRGBCount = 0.f; in.ill = 0;
+    if (threadIdx.x == 0) {   // a seed from the pose [Rprev | tprev], but for the given resultRt
+        PoseDev p;
+        for (int k = 0; k < 9; ++k) p.R[k] = Rprev[k];
+        for (int k = 0; k < 3; ++k) p.t[k] = tprev[k];
+        gn_seed(p, nullptr, s_st);
+        for (int k = 0; k < 16; ++k) s_st.resultRt[k] = resultRt[k];
     }
     __syncthreads();
     double xw[6];
     solve6_wave(s_sys, xw);
     // what k_icp_iter / k_icp_batch_solve / k_icp_finalize call: twelve lanes, state in LDS (the serial form -- gn_solve_update_serial --
     // stays as the executable specification: tests/test_devmath_host.py compiles it for the host)
-    gn_finish_wg(s_sys, &s_st, s_pose, s_T);
+    gn_finish_wg(s_sys, &s_st, s_pose);
     __syncthreads();
     if (threadIdx.x != 0) return;
     double A[6][6], b[6], x[6];
@@ -1192,11 +831,13 @@ __global__ __launch_bounds__(256) void k_icp_reduce_only(const float* __restrict
 
 __global__ void k_state_from_args(GNState* st, const float* Rc, const float* tc, const float* Rpi, const float* tp) {
     if (threadIdx.x != 0) return;
-    GNState s;
-    for (int k = 0; k < 16; ++k) s.resultRt[k] = (k % 5 == 0) ? 1.0 : 0.0;
-    for (int k = 0; k < 9; ++k) { s.Rcurr[k] = Rc[k]; s.Rprev_inv[k] = Rpi[k]; s.Rprev[k] = 0.f; s.trR[k] = 0.f; }
-    for (int k = 0; k < 3; ++k) { s.tcurr[k] = tc[k]; s.tprev[k] = tp[k]; s.trt[k] = 0.f; }
-    s.lastICPError = s.lastICPCount = 0.f; s.valid = 0; s.levelDone = -1; s.lastRGBError = 3.4028234664e38f; s.lastRGBCount = 0.f; s.ill = 0;
+    GNState s;   // a seed from the pose [Rc | tc], but for the given previous pose's inverse rotation and translation
+    PoseDev p;
+    for (int k = 0; k < 9; ++k) p.R[k] = Rc[k];
+    for (int k = 0; k < 3; ++k) p.t[k] = tc[k];
+    gn_seed(p, nullptr, s);
+    for (int k = 0; k < 9; ++k) s.Rprev_inv[k] = Rpi[k];
+    for (int k = 0; k < 3; ++k) s.tprev[k] = tp[k];
     *st = s;
 }
 
@@ -1233,19 +874,6 @@ struct RgbdKArgs {
     int level, prev_level;
     const So3Result* so3_in;      // first launch: rotation seed of resultRt (nullptr: identity)
 };
-
-// Sum of nb int2 records by the first wavefront; result broadcast through LDS (s_cnt[2]).  int32 wrap-around like the
-// reference's int2 sums (reduce.cu:716-772).
-__device__ __forceinline__ void reduce_counts(const int2* __restrict__ cnt, int nb, int* s_cnt) {
-    if (threadIdx.x < 64) {
-        unsigned c = 0, g = 0;
-        for (int i = threadIdx.x; i < nb; i += 64) { const int2 v = cnt[i]; c += (unsigned)v.x; g += (unsigned)v.y; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { c += (unsigned)__shfl_xor((int)c, o, 64); g += (unsigned)__shfl_xor((int)g, o, 64); }
-        if (threadIdx.x == 0) { s_cnt[0] = (int)c; s_cnt[1] = (int)g; }
-    }
-    __syncthreads();
-}
 
 __device__ __forceinline__ float rgb_tmp_error(int count, int sigma) {  // RGBDOdometry.cpp:389
     return (float)(sqrt((double)sigma) / (double)count);
@@ -1301,14 +929,8 @@ __global__ __launch_bounds__(kIcpThreads) void k_rgbd_iter(const RgbdKArgs a) {
 
     const int tid = threadIdx.x;
     const IcpKArgs& ia = a.icp;
-    if (ia.pose_in == nullptr) {
-        if (tid < (int)(sizeof(GNState) / 4)) reinterpret_cast<uint32_t*>(&s_st)[tid] = reinterpret_cast<const uint32_t*>(ia.st_in)[tid];
-    } else if (tid == 0) {
-        seed_state(*ia.pose_in, s_st);
-        if (a.so3_in)  // RGBDOdometry.cpp:338-344
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) s_st.resultRt[r * 4 + c] = a.so3_in->R[r * 3 + c];
-    }
+    if (ia.pose_in == nullptr) gn_stage(&s_st, ia.st_in);
+    else if (tid == 0) gn_seed(*ia.pose_in, a.so3_in, s_st);
     __syncthreads();
     const int P = ia.W * ia.H;
     const int chunk = icp_chunk(P, gridDim.x);
@@ -1381,14 +1003,7 @@ __global__ __launch_bounds__(kIcpThreads) void k_rgbd_iter(const RgbdKArgs a) {
     for (int o = 32; o > 0; o >>= 1) { cnt += (unsigned)__shfl_xor((int)cnt, o, 64); sig += (unsigned)__shfl_xor((int)sig, o, 64); }
     if (lane == 0) { s_icnt[wave * 2] = (int)cnt; s_icnt[wave * 2 + 1] = (int)sig; }
     __syncthreads();
-    if (tid < kIcpSlots) {
-        float sv = 0.f;
-        if (tid < 29) {
-#pragma unroll
-            for (int w = 0; w < kIcpThreads / 64; ++w) sv += s_part[w * kIcpSlots + tid];
-        }
-        ia.partials_out[blockIdx.x * kIcpSlots + tid] = sv;
-    }
+    store_block_partial<kIcpThreads>(s_part, ia.partials_out);
     if (tid == 0) {
         unsigned c = 0, g = 0;
         for (int w = 0; w < kIcpThreads / 64; ++w) { c += (unsigned)s_icnt[w * 2]; g += (unsigned)s_icnt[w * 2 + 1]; }
@@ -1431,58 +1046,34 @@ __global__ __launch_bounds__(kIcpThreads) void k_rgb_step(const RgbStepKArgs a) 
     const float wsum = wave_sum32_halving(acc);
     if (lane < 32) s_part[wave * kIcpSlots + icp_component_of_lane(lane)] = wsum;
     __syncthreads();
-    if (tid < kIcpSlots) {
-        float sv = 0.f;
-        if (tid < 29) {
-#pragma unroll
-            for (int w = 0; w < kIcpThreads / 64; ++w) sv += s_part[w * kIcpSlots + tid];
-        }
-        a.partials_out[blockIdx.x * kIcpSlots + tid] = sv;
-    }
+    store_block_partial<kIcpThreads>(s_part, a.partials_out);
 }
 
-__global__ __launch_bounds__(256) void k_rgbd_finalize(const float* __restrict__ icp_partials, const float* __restrict__ rgb_partials,
-                                                        const int2* __restrict__ cnt, int nb, float icpWeight, int icpOn, int rgbOnly,
-                                                        int rgbOn, int prev_level, const GNState* __restrict__ st_in,
-                                                        const So3Result* __restrict__ so3, PoseDev* __restrict__ pose,
-                                                        PoseDev* __restrict__ host_mirror, float* __restrict__ log_out, float jump_limit) {
+struct RgbdFinKArgs {
+    const float* icp_partials; const float* rgb_partials; const int2* cnt; int nb;   // of the last iteration (nb = 0: none ran)
+    float icpWeight; int icpOn, rgbOnly, prev_level;
+    const GNState* st_in;
+    GnFinalize f;
+};
+
+__global__ __launch_bounds__(256) void k_rgbd_finalize(const RgbdFinKArgs a) {
     __shared__ double s_seg[32 * 32];
     __shared__ double s_sys[32];
     __shared__ double s_sys2[32];
     __shared__ int s_cnt[2];
     __shared__ GNState s_st;
-    if (threadIdx.x < (int)(sizeof(GNState) / 4)) reinterpret_cast<uint32_t*>(&s_st)[threadIdx.x] = reinterpret_cast<const uint32_t*>(st_in)[threadIdx.x];
+    gn_stage(&s_st, a.st_in);
     __syncthreads();
     GNState st;
     bool mine;
-    if (nb > 0) {
-        mine = finish_rgbd_iteration(icp_partials, rgb_partials, cnt, nb, icpWeight, icpOn, rgbOnly, prev_level, s_st, st, s_seg, s_seg,
-                                     s_sys, s_sys2, s_cnt, log_out);
+    if (a.nb > 0) {
+        mine = finish_rgbd_iteration(a.icp_partials, a.rgb_partials, a.cnt, a.nb, a.icpWeight, a.icpOn, a.rgbOnly, a.prev_level, s_st, st, s_seg, s_seg,
+                                     s_sys, s_sys2, s_cnt, a.f.log);
     } else {
         mine = threadIdx.x == 0;
         if (mine) st = s_st;
     }
-    if (!mine) return;
-    PoseDev p = *pose;
-    p.rejected = 0;
-    const float dx = st.tcurr[0] - st.tprev[0], dy = st.tcurr[1] - st.tprev[1], dz = st.tcurr[2] - st.tprev[2];
-    if (rgbOn && (double)sqrtf(dx * dx + dy * dy + dz * dz) > 0.3) {   // RGBDOdometry.cpp:477-481
-        for (int k = 0; k < 9; ++k) st.Rcurr[k] = st.Rprev[k];
-        for (int k = 0; k < 3; ++k) { st.tcurr[k] = st.tprev[k]; st.trt[k] = 0.f; }
-        p.rejected = 1;
-    }
-    for (int k = 0; k < 9; ++k) { p.lastR[k] = st.Rprev[k]; p.R[k] = st.Rcurr[k]; }
-    for (int k = 0; k < 3; ++k) { p.lastT[k] = st.tprev[k]; p.t[k] = st.tcurr[k]; }
-    p.lastICPError = st.lastICPError; p.lastICPCount = st.lastICPCount;
-    p.lastRGBError = st.lastRGBError; p.lastRGBCount = st.lastRGBCount;
-    if (so3) { p.lastSO3Error = so3->error; p.lastSO3Count = so3->count; p.so3Iterations = so3->iterations; }
-    else { p.lastSO3Error = 0.f; p.lastSO3Count = 0.f; p.so3Iterations = 0; }
-    for (int k = 0; k < 3; ++k) p.incT[k] = st.trt[k];
-    p.illIterations = st.ill;   // (the photometric loop does not count: its combined system goes through the wave Gauss-Jordan)
-    if (jump_limit > 0.f && norm3(f3(st.trt[0], st.trt[1], st.trt[2])) >= jump_limit) p.alive = 0;   // `float d > 0.2` is a DOUBLE comparison upstream (MaskFusion.cpp:268): true from 0.2f on
-    pose_derive(p);
-    *pose = p;
-    if (host_mirror) *host_mirror = p;
+    if (mine) write_pose(a.f.pose, a.f.host_mirror, st, a.f, true);
 }
 
 void launch_rgbd_iteration(const RgbdLaunch& l, hipStream_t s) {
@@ -1502,245 +1093,9 @@ void launch_rgbd_iteration(const RgbdLaunch& l, hipStream_t s) {
     hipLaunchKernelGGL(k_rgb_step, dim3(nb), dim3(kIcpThreads), 0, s, b);
 }
 
-void launch_rgbd_finalize(const float* icp_partials, const float* rgb_partials, const int2* cnt, int nb, float icpWeight, int icpOn,
-                          int rgbOnly, int rgbOn, int prev_level, const GNState* st_in, const So3Result* so3, PoseDev* pose,
-                          PoseDev* host_mirror, float* log_out, float jump_limit, hipStream_t s) {
-    hipLaunchKernelGGL(k_rgbd_finalize, dim3(1), dim3(256), 0, s, icp_partials, rgb_partials, cnt, nb, icpWeight, icpOn, rgbOnly, rgbOn,
-                       prev_level, st_in, so3, pose, host_mirror, log_out, jump_limit);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Model-side pyramid: copyMaps + resize x2 + transform x3 (+ fill-in) in ONE pass.  One thread owns a 4x4 block of
-// level-0 pixels = 2x2 of level 1 = 1 pixel of level 2, so the averages follow the reference's operation order
-// ((x00 + x01 + x10 + x11) / 4, level 2 from level-1 values) and nothing is re-read from HBM.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ MapPx load_model_px(const float4* __restrict__ predV, const float4* __restrict__ predN,
-                                               const float* __restrict__ fillDepth, bool useFill, int x, int y, int W,
-                                               int H, Intr k) {
-    const int p = y * W + x;
-    float4 v4 = predV[p], n4 = predN[p];
-    if (useFill) {
-        if (v4.z == 0) {  // fill_vertex.frag:37-53
-            const float z = fillDepth[p];
-            v4 = make_float4(((float)x - k.cx) * z * (1.0f / k.fx), ((float)y - k.cy) * z * (1.0f / k.fy), z, 1.f);
-        }
-        if (n4.z == 0) {  // fill_normal.frag:34-50
-            const float3 vp = get_vertex(fillDepth, W, H, x, y, (float)x, (float)y, k);
-            const float3 n = get_normal_forward(fillDepth, W, H, x, y, vp, k);
-            n4 = make_float4(n.x, n.y, n.z, 1.f);
-        }
-    }
-    return copy_maps_px(v4, n4);   // copyMapsKernel, cudafuncs.cu:286-305
-}
-
-// (mul33_fixed, store_tx, the quad broadcasts and the two smaller levels' arithmetic: mf_model_pyramid_device.h, shared with the tile pass's epilogue)
-struct PyrArgs {
-    const float4* predV; const float4* predN; const float* fillDepth; const FrameDev* frame; const PoseDev* pose;
-    float R[9]; float t[3]; int hostPose;
-    float* vm[3]; float* nm[3];
-    int W, H; Intr k;
-    TrackBatch b;   // b.n > 0: grid.z = model, everything but fillDepth / W / H / k comes from the model's block
-    int* fixup;     // non-null ("tilePyramid"): the tile pass has written the no-fill pyramid -- run only if frame->useFillIn, and count such frames here
-};
-
-// One thread per LEVEL-1 pixel (2x2 level-0 pixels); the four lanes of a DPP quad hold the 2x2 level-1 block of one level-2
-// pixel and exchange their values with quad broadcasts, so the averages keep the reference's operation order
-// ((x00 + x01 + x10 + x11) / 4, level 2 from level-1 values).  (A thread per level-2 pixel -- 19 200 threads walking 16
-// pixels each -- left three quarters of the CUs idle: 15 us.)
-__device__ __forceinline__ void model_pyramid_body(const PyrArgs& a0, const int blk_x, const int blk_y, const int blk_z) {
-    PyrArgs a = a0;
-    if (a0.b.n > 0) {
-        const TrackModelDev* __restrict__ md = a0.b.m[blk_z];
-        a.predV = md->predV; a.predN = md->predN; a.frame = md->frame; a.pose = md->pose; a.hostPose = 0;
-        a.fillDepth = md->allow_fill ? a0.fillDepth : nullptr;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { a.vm[i] = md->vm[i]; a.nm[i] = md->nm[i]; }
-    }
-    const int W2 = a.W >> 2, H2 = a.H >> 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = lane & 3, bx = b & 1, by = b >> 1;
-    const int x2 = blk_x * 16 + (lane >> 2);
-    const int y2 = blk_y * 4 + wave;
-    const bool inside = x2 < W2 && y2 < H2;   // whole quads are in or out: the DPP exchanges below stay well defined
-    float R[9]; float3 t;
-    if (a.hostPose) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] = a.R[k];
-        t = f3(a.t[0], a.t[1], a.t[2]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] = a.pose->R[k];
-        t = f3(a.pose->t[0], a.pose->t[1], a.pose->t[2]);
-    }
-    const bool useFill = a.fillDepth != nullptr && a.frame != nullptr && a.frame->useFillIn != 0;
-    const int W = a.W, H = a.H, W1 = W >> 1, H1 = H >> 1;
-    const int P0 = W * H, P1 = W1 * H1, P2 = W2 * H2;
-
-    bool n0any = false;                       // (batched tracker) this thread's level-0 pixels that hold a normal: their box
-    int n0x0 = 0, n0y0 = 0, n0x1 = 0, n0y1 = 0;
-    MapPx px[4];
-    if (inside) {
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                const int x = 4 * x2 + 2 * bx + dx, y = 4 * y2 + 2 * by + dy;
-                px[dy * 2 + dx] = load_model_px(a.predV, a.predN, a.fillDepth, useFill, x, y, W, H, a.k);
-                store_tx(a.vm[0], a.nm[0], P0, y * W + x, px[dy * 2 + dx].v, px[dy * 2 + dx].vok, px[dy * 2 + dx].n,
-                         px[dy * 2 + dx].nok, R, t);
-                if (px[dy * 2 + dx].nok) {
-                    n0x0 = n0any ? min(n0x0, x) : x; n0y0 = n0any ? min(n0y0, y) : y; n0x1 = n0any ? max(n0x1, x) : x; n0y1 = n0any ? max(n0y1, y) : y;
-                    n0any = true;
-                }
-            }
-    }
-    // levels 1 and 2 (mf_model_pyramid_device.h; executed by every lane: its quad broadcasts need them active)
-    model_pyramid_down(px, inside, b, R, t, a.vm[1], a.nm[1], P1, (2 * y2 + by) * W1 + 2 * x2 + bx, a.vm[2], a.nm[2], P2, y2 * W2 + x2);
-    if (a0.b.n > 0 && !a0.b.m[blk_z]->allow_fill) {
-        // batched tracker, object models: the rectangle of level-0 pixels that hold a normal (TrackModelDev::rect) -- a superset of the pixels store_tx
-        // wrote a normal to (it writes NaN wherever the flag is off), which is all the pixel pass of the Gauss-Newton loop can pair a frame pixel
-        // with.  A level-1 / level-2 normal needs all four normals below it (resizeMapKernel), so the rectangle shifted right by the level bounds
-        // those levels too.  An object covers ~1 % of the image: nearly every wavefront sees no normal at all and leaves after one ballot.
-        if (__ballot(inside && n0any) != 0ull) {
-            int* __restrict__ rect = a0.b.m[blk_z]->rect;
-            const bool on = inside && n0any;
-            const int x0 = wave_min_i(on ? n0x0 : 0x7FFFFFFF), y0 = wave_min_i(on ? n0y0 : 0x7FFFFFFF);
-            const int x1 = wave_max_i(on ? n0x1 : (int)0x80000000), y1 = wave_max_i(on ? n0y1 : (int)0x80000000);
-            if (lane == 0) { atomicMin(&rect[0], x0); atomicMin(&rect[1], y0); atomicMax(&rect[2], x1); atomicMax(&rect[3], y1); }
-        }
-    }
-}
-
-// "tilePyramid": the tile pass of the fused head has already written the three levels without fill-in (mf_splat.hip: k_splat_tile's epilogue), and its
-// last workgroup has decided frame->useFillIn behind them -- the kernel boundary orders that write.  A launch with a.fixup set only repairs the
-// frames whose decision came out "fill": every workgroup leaves at once otherwise; else the launch runs as ever and overwrites all three levels, and
-// its first workgroup counts the frame ("pyramidFixupFrames").  true: this workgroup has nothing to do.
-__device__ __forceinline__ bool pyramid_fixup_skips(const PyrArgs& a, const bool first) {
-    if (a.fixup == nullptr) return false;
-    if (a.frame->useFillIn == 0) return true;
-    if (first && threadIdx.x == 0) *a.fixup += 1;
-    return false;
-}
-
-__global__ __launch_bounds__(256) void k_model_pyramid(const PyrArgs a) {
-    if (pyramid_fixup_skips(a, blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)) return;
-    model_pyramid_body(a, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
-}
-
-// The depth filter of the frame and the model-side pyramid of the same frame's tracking step in ONE launch ("fusedPreprocessLaunch"): the two are
-// independent -- the filter reads the new depth image, the pyramid the previous frame's prediction -- and complement each other (the filter is
-// VALU-bound on 1 208 workgroups at VGA, the pyramid a 20 MB stream on 300), but on one stream two launches run one after the other.  Workgroups
-// below nbil run bilateral_body (mf_bilateral_device.h), the others model_pyramid_body with their index as the 2-D block of k_model_pyramid:
-// the same instructions on the same data as the two kernels, hence the same bits.
-// (six wavefronts per SIMD = six workgroups per compute unit: at VGA all 1 508 workgroups are resident at once; the pyramid half would take 83 registers)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_bilateral_model_pyramid(const float* __restrict__ depth, float* __restrict__ out, int W, int H, int nbil,
-                                                                 int interleave, const PyrArgs a) {
-    __shared__ float tile[kBLdsH * kBLdsW];
-    // Which half a workgroup belongs to.  Workgroups are dispatched in index order: with the filter's first and the pyramids' behind them, a launch
-    // that does not fit the GPU at once (1280 x 960: 4 808 + 1 200 per tracked model) ran the two halves one after the other.  The pyramids' workgroups
-    // are therefore spread evenly among the filter's (a Bresenham walk: workgroup b is a pyramid workgroup when floor((b + 1) npyr / total) steps),
-    // so that the VALU-bound half and the bandwidth-bound half are in flight together from the first round on.
-    const int gx = ((W >> 2) + 15) / 16, gy = ((H >> 2) + 3) / 4, per = gx * gy;
-    // (a launch that IS resident at once -- VGA, one tracked model: 1 508 workgroups -- keeps the filter's workgroups first: their index is what
-    // places a tile on the XCD that holds its neighbours' halo rows, worth 1 us there)
-    const int total = (int)gridDim.x, npyr = total - nbil, b = (int)blockIdx.x;
-    int before, after;
-    if (interleave) { before = (int)(((long long)b * npyr) / total); after = (int)(((long long)(b + 1) * npyr) / total); }
-    else { before = b < nbil ? 0 : b - nbil; after = b < nbil ? 0 : b - nbil + 1; }
-    if (after == before) { bilateral_body(depth, out, W, H, tile, b - before, (int)threadIdx.x, true); return; }
-    // (a.b.n > 0: the batched tracker's pyramids, model by model -- k_model_pyramid's grid.z unrolled)
-    const int j = before;
-    model_pyramid_body(a, (j % per) % gx, (j % per) / gx, j / per);
-}
-
-void launch_model_pyramid(const float4* predV, const float4* predN, const float* fillDepth, const FrameDev* frame,
-                          const PoseDev* pose, const float* R9t3_host_or_null, float* const vmaps[3], float* const nmaps[3],
-                          int W, int H, Intr k, hipStream_t s, int* fixup) {
-    PyrArgs a;
-    a.predV = predV; a.predN = predN; a.fillDepth = fillDepth; a.frame = frame; a.pose = pose;
-    a.fixup = fixup;
-    a.hostPose = R9t3_host_or_null != nullptr;
-    for (int i = 0; i < 9; ++i) a.R[i] = a.hostPose ? R9t3_host_or_null[i] : 0.f;
-    for (int i = 0; i < 3; ++i) a.t[i] = a.hostPose ? R9t3_host_or_null[9 + i] : 0.f;
-    for (int i = 0; i < 3; ++i) { a.vm[i] = vmaps[i]; a.nm[i] = nmaps[i]; }
-    a.W = W; a.H = H; a.k = k;
-    a.b.n = 0;
-    dim3 grid(((W >> 2) + 15) / 16, ((H >> 2) + 3) / 4);
-    hipLaunchKernelGGL(k_model_pyramid, grid, dim3(256), 0, s, a);
-}
-
-void launch_bilateral_model_pyramid(const float* depth, float* depthF, const float4* predV, const float4* predN, const float* fillDepth,
-                                    const FrameDev* frame, const PoseDev* pose, float* const vmaps[3], float* const nmaps[3], int W, int H, Intr k,
-                                    hipStream_t s) {
-    PyrArgs a;
-    a.predV = predV; a.predN = predN; a.fillDepth = fillDepth; a.frame = frame; a.pose = pose;
-    a.fixup = nullptr;
-    a.hostPose = 0;
-    for (int i = 0; i < 9; ++i) a.R[i] = 0.f;
-    for (int i = 0; i < 3; ++i) a.t[i] = 0.f;
-    for (int i = 0; i < 3; ++i) { a.vm[i] = vmaps[i]; a.nm[i] = nmaps[i]; }
-    a.W = W; a.H = H; a.k = k;
-    a.b.n = 0;
-    const int nbil = bilateral_grid(W, H), npyr = (((W >> 2) + 15) / 16) * (((H >> 2) + 3) / 4);
-    hipLaunchKernelGGL(k_bilateral_model_pyramid, dim3(nbil + npyr), dim3(256), 0, s, depth, depthF, W, H, nbil, (nbil + npyr > 1536) ? 1 : 0, a);
-}
-
-// ... and for the batched tracker: the filter beside launch_model_pyramid_batch's work
-void launch_bilateral_model_pyramid_batch(const float* depth, float* depthF, const TrackBatch& b, const float* fillDepth, int W, int H, Intr k,
-                                          hipStream_t s) {
-    PyrArgs a;
-    memset(&a, 0, sizeof(a));
-    a.fillDepth = fillDepth; a.W = W; a.H = H; a.k = k; a.b = b;
-    const int nbil = bilateral_grid(W, H), npyr = (((W >> 2) + 15) / 16) * (((H >> 2) + 3) / 4) * b.n;
-    hipLaunchKernelGGL(k_bilateral_model_pyramid, dim3(nbil + npyr), dim3(256), 0, s, depth, depthF, W, H, nbil, (nbil + npyr > 1536) ? 1 : 0, a);
-}
-
-// The frame's pyramid and the model-side pyramid of the same tracking step in ONE launch ("fusedFramePyramids"), for a frame whose prediction was
-// deferred into its successor's head (mf_frame.inl: enqueue_fused_head): there the model-side pyramid can no longer ride beside the depth filter --
-// the prediction it reads is drawn behind the filter --, and both pyramids are streams that wait for nothing but the tile pass.  The first nfp
-// workgroups run frame_pyramid_body (mf_frame_pyramid_device.h: every operation rounded on its own), the others model_pyramid_body with their index
-// as k_model_pyramid's 2-D block: the same instructions on the same data as the two kernels, hence the same bits.  Both counts are multiples of 8
-// and a launch that is not resident at once interleaves the halves in groups of 8 workgroups, so that a frame tile's index keeps the XCD that holds
-// its neighbours (xcd_contiguous_tile) either way.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_frame_model_pyramid(const FramePyrArgs f, int nfp, int interleave, const PyrArgs a) {
-    __shared__ float lds[kFpLdsFloats];
-    const int groups = (int)gridDim.x >> 3, gpyr = groups - (nfp >> 3), g = (int)blockIdx.x >> 3, lane = (int)blockIdx.x & 7;
-    int before, after;   // pyramid groups in front of group g / of group g + 1 (a Bresenham walk, as k_bilateral_model_pyramid's)
-    if (interleave) { before = (int)(((long long)g * gpyr) / groups); after = (int)(((long long)(g + 1) * gpyr) / groups); }
-    else { before = g < (nfp >> 3) ? 0 : g - (nfp >> 3); after = g < (nfp >> 3) ? 0 : before + 1; }
-    if (after == before) { frame_pyramid_body(f, lds, ((g - before) << 3) + lane); return; }
-    const int gx = ((a.W >> 2) + 15) / 16, gy = ((a.H >> 2) + 3) / 4, j = (before << 3) + lane;
-    if (j >= gx * gy) return;   // (padding of the pyramid half to a multiple of 8)
-    if (pyramid_fixup_skips(a, j == 0)) return;
-    model_pyramid_body(a, j % gx, j / gx, 0);
-}
-
-void launch_frame_model_pyramid(const float* depthF, float* const fvmap[3], float* const fnmap[3], float cutoff, const float4* predV, const float4* predN,
-                                const float* fillDepth, const FrameDev* frame, const PoseDev* pose, float* const vmaps[3], float* const nmaps[3], int W, int H,
-                                Intr k, hipStream_t s, int* fixup) {
-    FramePyrArgs f;
-    f.depth = depthF; f.W = W; f.H = H; f.k = k; f.cutoff = cutoff;
-    for (int i = 0; i < 3; ++i) { f.vmap[i] = fvmap[i]; f.nmap[i] = fnmap[i]; }
-    PyrArgs a;
-    a.predV = predV; a.predN = predN; a.fillDepth = fillDepth; a.frame = frame; a.pose = pose;
-    a.fixup = fixup;
-    a.hostPose = 0;
-    for (int i = 0; i < 9; ++i) a.R[i] = 0.f;
-    for (int i = 0; i < 3; ++i) a.t[i] = 0.f;
-    for (int i = 0; i < 3; ++i) { a.vm[i] = vmaps[i]; a.nm[i] = nmaps[i]; }
-    a.W = W; a.H = H; a.k = k;
-    a.b.n = 0;
-    const int nfp = xcd_padded_grid(frame_pyramid_tiles(W, H)), npyr = xcd_padded_grid((((W >> 2) + 15) / 16) * (((H >> 2) + 3) / 4));
-    // (six 256-thread workgroups per compute unit: 1 536 are resident at once, as for k_bilateral_model_pyramid)
-    hipLaunchKernelGGL(k_frame_model_pyramid, dim3(nfp + npyr), dim3(256), 0, s, f, nfp, (nfp + npyr > 1536) ? 1 : 0, a);
-}
-
-void launch_model_pyramid_batch(const TrackBatch& b, const float* fillDepth, int W, int H, Intr k, hipStream_t s) {
-    PyrArgs a;
-    memset(&a, 0, sizeof(a));
-    a.fillDepth = fillDepth; a.W = W; a.H = H; a.k = k; a.b = b;
-    dim3 grid(((W >> 2) + 15) / 16, ((H >> 2) + 3) / 4, b.n);
-    hipLaunchKernelGGL(k_model_pyramid, grid, dim3(256), 0, s, a);
+void launch_rgbd_finalize(const GnLast& last, float icpWeight, int icpOn, int rgbOnly, const GnFinalize& f, hipStream_t s) {
+    const RgbdFinKArgs a{last.partials, last.rgb_partials, last.cnt, last.nblocks, icpWeight, icpOn, rgbOnly, last.level, last.state, f};
+    hipLaunchKernelGGL(k_rgbd_finalize, dim3(1), dim3(256), 0, s, a);
 }
 
 }  // namespace mf

@@ -90,7 +90,7 @@ void launch_vmap_nmap(const float* depth, float* vmap, float* nmap, int W, int H
 }
 
 // Model::generateCUDATextures in ONE launch: the body lives in mf_frame_pyramid_device.h (shared with the launch that runs it beside the
-// model-side pyramid, mf_odometry.hip: k_frame_model_pyramid)
+// model-side pyramid, mf_model_pyramid.hip: k_frame_model_pyramid)
 __global__ __launch_bounds__(256) void k_frame_pyramid(const FramePyrArgs a) {
     __shared__ float lds[kFpLdsFloats];
     frame_pyramid_body(a, lds, (int)blockIdx.x);

@@ -316,7 +316,7 @@ __device__ __forceinline__ void tile_ztest(int tile, int tilesX, int tileH, Intr
 // (combo_splat.frag) of every pixel of the tile.
 //
 // "tilePyramid" (a.vm set): the workgroup then also writes the three levels of the model-side pyramid for its tile -- what model_pyramid_body
-// (mf_odometry.hip) computes WITHOUT fill-in from the prediction maps this workgroup has just written.  Every output of that pyramid depends on one
+// (mf_model_pyramid.hip) computes WITHOUT fill-in from the prediction maps this workgroup has just written.  Every output of that pyramid depends on one
 // aligned 4 x 4 block of level-0 texels, and a tile is a whole number of such blocks: level 0 goes out from the registers that hold the pixel, the
 // pixel's copyMaps value is staged in the z-test's LDS (free by now: rays in s_ray, keys in s_key -- a thread overwrites only the slot it has read),
 // and behind the barrier the workgroup takes anyway one thread per level-1 texel, a DPP quad per level-2 texel, runs model_pyramid_down

@@ -1,5 +1,5 @@
 // devmath_host.cpp -- the product's own device-side scalar math (maskfusion_amd/csrc/mf_device.h and a few functions cut out of
-// mf_odometry.hip / mf_surfel.hip by tests/devmath.py), compiled for the HOST with g++ so that `-m "not gpu"` tests can hold it to the
+// mf_odometry.hip / mf_gn_device.h / mf_surfel.hip by tests/devmath.py), compiled for the HOST with g++ so that `-m "not gpu"` tests can hold it to the
 // oracle, numpy and SciPy without a GPU.  Nothing here is shipped: it is a second compilation of product source for testing.
 //
 // Stand-ins for what only exists on the device: bit casts, rsqrtf, the v_rcp_f64 / v_rsq_f64 seeds of rcp_d / sqrt_d (here the exact
@@ -97,6 +97,25 @@ void dm_pose_derive(const float* R9, const float* t3, const float* lastR9, const
     for (int k = 0; k < 9; ++k) Ri9[k] = p.Ri[k];
     for (int k = 0; k < 3; ++k) ti3[k] = p.ti[k];
     *fusionWeight = p.fusionWeight;
+}
+// pose_from_state: the end of a tracking step.  in: the final state's Rprev9 / tprev3 / Rcurr9 / tcurr3 / trt3 and its RGB statistics rgb2 =
+// {lastRGBError, lastRGBCount}; the pose block starts alive, not rejected.  out: R9, t3, incT3, rgb_out2 = {lastRGBError, lastRGBCount},
+// flags2 = {rejected, alive}
+void dm_pose_from_state(const float* Rprev9, const float* tprev3, const float* Rcurr9, const float* tcurr3, const float* trt3, const float* rgb2,
+                        float jump_limit, int photometric, float* R9, float* t3, float* incT3, float* rgb_out2, int* flags2) {
+    mf::GNState st;
+    memset(&st, 0, sizeof(st));
+    for (int k = 0; k < 9; ++k) { st.Rprev[k] = Rprev9[k]; st.Rcurr[k] = Rcurr9[k]; }
+    for (int k = 0; k < 3; ++k) { st.tprev[k] = tprev3[k]; st.tcurr[k] = tcurr3[k]; st.trt[k] = trt3[k]; }
+    st.lastRGBError = rgb2[0]; st.lastRGBCount = rgb2[1];
+    mf::PoseDev p;
+    memset(&p, 0, sizeof(p));
+    p.alive = 1; p.rejected = -1; p.lastRGBError = p.lastRGBCount = -1.f;
+    mf::pose_from_state(st, nullptr, jump_limit, photometric != 0, p);
+    for (int k = 0; k < 9; ++k) R9[k] = p.R[k];
+    for (int k = 0; k < 3; ++k) { t3[k] = p.t[k]; incT3[k] = p.incT[k]; }
+    rgb_out2[0] = p.lastRGBError; rgb_out2[1] = p.lastRGBCount;
+    flags2[0] = p.rejected; flags2[1] = p.alive;
 }
 
 }  // extern "C"

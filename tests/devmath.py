@@ -16,7 +16,7 @@ CSRC = os.path.join(ROOT, "maskfusion_amd", "csrc")
 OUT = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT, "libdevmath.so")
 SLICES = [("mf_odometry.hip", "ldlt6_solve"), ("mf_odometry.hip", "gn_update_from_x"), ("mf_odometry.hip", "gn_solve_update_serial"),
-          ("mf_surfel.hip", "window_slots_literal")]
+          ("mf_gn_device.h", "pose_from_state"), ("mf_surfel.hip", "window_slots_literal")]
 
 f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
@@ -47,7 +47,7 @@ def translation_unit() -> str:
 
 
 def build() -> str:
-    deps = [os.path.join(CSRC, f) for f in ("mf_device.h", "mf_internal.h", "mf_labels.h", "mf_odometry.hip", "mf_surfel.hip")]
+    deps = [os.path.join(CSRC, f) for f in ("mf_device.h", "mf_internal.h", "mf_labels.h", "mf_odometry.hip", "mf_gn_device.h", "mf_surfel.hip")]
     deps += [os.path.join(HERE, "cpp", "devmath_host.cpp"), os.path.abspath(__file__)]
     if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
         return LIB
@@ -77,5 +77,6 @@ def lib():
         L.dm_window_slots_literal.argtypes = [C.c_float, C.c_int, i32p, i32p]
         L.dm_gn_solve_update.argtypes = [f64p, f64p, f32p, f32p, f64p, f64p, f32p, f32p, f32p, f32p, f32p]
         L.dm_pose_derive.argtypes = [f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int]
+        L.dm_pose_from_state.argtypes = [f32p, f32p, f32p, f32p, f32p, f32p, C.c_float, C.c_int, f32p, f32p, f32p, f32p, i32p]
         _lib = L
     return _lib

@@ -1,4 +1,4 @@
-"""The device's own scalar math -- maskfusion_amd/csrc/mf_device.h and the solve / update / window-walk functions of mf_odometry.hip and
+"""The device's own scalar math -- maskfusion_amd/csrc/mf_device.h and the solve / update / window-walk functions of mf_odometry.hip / mf_gn_device.h and
 mf_surfel.hip -- compiled for the host (tests/devmath.py) and held to the oracle, numpy and SciPy WITHOUT a GPU.  SURVEY.md rows a11
 (LDL^T, rodrigues, computeUpdateSE3, pose composition), a15 (computeFusionWeight), a13-a16 shader helpers (exp, acos, radius,
 confidence, colour code), a16 (the clean window walk), a22 (quaternion of the pose log).  The same source runs on the device; what the
@@ -225,6 +225,62 @@ def test_pose_inverse_and_fusion_weight(dm):
         dm.dm_pose_derive(R1.reshape(9), t1, R0.reshape(9), t0, Ri, ti, wl, 1)
         wol = mfo.fusion_weight(T1f, T0f, 1.0)                   # the oracle's default IS the literal mode
         assert float(wl[0]) == wol, (k, float(wl[0]), wol)
+
+
+def _pose_from_state(dm, tcurr, trt, photometric, jump_limit=0.2):
+    """pose_from_state on a state with previous pose [A | tprev], current pose [B | tcurr] and increment translation trt"""
+    A = np.ascontiguousarray(Rot.from_rotvec([0.1, -0.2, 0.3]).as_matrix(), np.float32).reshape(9)
+    B = np.ascontiguousarray(Rot.from_rotvec([-0.3, 0.1, 0.2]).as_matrix(), np.float32).reshape(9)
+    tprev = np.array([0.0, 2.0, -1.0], np.float32)
+    R, t, incT, rgb = np.zeros(9, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(2, np.float32)
+    flags = np.zeros(2, np.int32)
+    dm.dm_pose_from_state(A, tprev, B, np.asarray(tcurr, np.float32), np.asarray(trt, np.float32), np.array([0.5, 1234.0], np.float32),
+                          np.float32(jump_limit), int(photometric), R, t, incT, rgb, flags)
+    return dict(R=R, t=t, incT=incT, rgb=rgb, rejected=int(flags[0]), alive=int(flags[1]), A=A, B=B, tprev=tprev)
+
+
+def test_pose_from_state_rejection_and_jump_edges(dm):
+    """pose_from_state, the one writer of the pose block behind both finalize kernels.  The 0.3 m rejection of RGBDOdometry.cpp:477-481 compares
+    (double)sqrtf(.) > 0.3 and the 0.2 m jump rule of MaskFusion.cpp:268 norm3(trt) >= limit: both are true FROM the float 0.3f / 0.2f on (0.3f as
+    a double exceeds 0.3) and false for the next float below.  No tolerance: the edges follow from the comparisons as written.  The states
+    move along one axis, so that |tcurr - tprev| and |trt| are those floats exactly (sqrtf(x * x) == x)."""
+    f03, f02 = np.float32(0.3), np.float32(0.2)
+    below03, below02 = np.nextafter(f03, np.float32(0)), np.nextafter(f02, np.float32(0))
+    assert float(f03) > 0.3 > float(below03) and float(f02) > 0.2 > float(below02)
+    small = [0.01, 0.0, 0.0]                                    # an increment the jump rule lets pass
+    for sign in (1.0, -1.0):
+        def at(d):
+            return np.array([np.float32(sign) * d, 2.0, -1.0], np.float32)       # tprev = (0, 2, -1): the difference is (+-d, 0, 0) exactly
+        # photometric: |tcurr - tprev| == 0.3f is rejected ...
+        r = _pose_from_state(dm, at(f03), small, True)
+        assert r["rejected"] == 1 and r["alive"] == 1
+        assert np.array_equal(r["R"], r["A"]) and np.array_equal(r["t"], r["tprev"]) and np.array_equal(r["incT"], np.zeros(3, np.float32))
+        assert np.array_equal(r["rgb"], np.array([0.5, 1234.0], np.float32))
+        # ... the next float below is kept
+        r = _pose_from_state(dm, at(below03), small, True)
+        assert r["rejected"] == 0 and r["alive"] == 1
+        assert np.array_equal(r["R"], r["B"]) and np.array_equal(r["t"], at(below03)) and np.array_equal(r["incT"], np.asarray(small, np.float32))
+        assert np.array_equal(r["rgb"], np.array([0.5, 1234.0], np.float32))
+        # without the photometric term the same states are kept and the RGB statistics read 0
+        for d in (f03, below03, np.float32(5.0)):
+            r = _pose_from_state(dm, at(d), small, False)
+            assert r["rejected"] == 0 and r["alive"] == 1
+            assert np.array_equal(r["R"], r["B"]) and np.array_equal(r["t"], at(d)) and np.array_equal(r["incT"], np.asarray(small, np.float32))
+            assert np.array_equal(r["rgb"], np.zeros(2, np.float32))
+    # the jump rule: |trt| == 0.2f clears alive, the next float below does not -- with and without the photometric term
+    for photometric in (False, True):
+        for k in range(3):
+            trt = np.zeros(3, np.float32); trt[k] = -f02
+            r = _pose_from_state(dm, [0.0, 2.0, -1.0], trt, photometric)
+            assert r["alive"] == 0 and r["rejected"] == 0 and np.array_equal(r["incT"], trt)
+            trt[k] = below02
+            r = _pose_from_state(dm, [0.0, 2.0, -1.0], trt, photometric)
+            assert r["alive"] == 1 and r["rejected"] == 0 and np.array_equal(r["incT"], trt)
+        r = _pose_from_state(dm, [0.0, 2.0, -1.0], [f02, 0.0, 0.0], photometric, jump_limit=0.0)     # the background: no limit
+        assert r["alive"] == 1
+    # a rejected step has no increment: its incT is 0, which no limit takes for a jump
+    r = _pose_from_state(dm, [f03, 2.0, -1.0], [f02, 0.0, 0.0], True)
+    assert r["rejected"] == 1 and r["alive"] == 1 and np.array_equal(r["incT"], np.zeros(3, np.float32))
 
 
 def test_mask_id_and_m33_inverse(dm):

@@ -203,6 +203,42 @@ def test_iteration_schedules(hip, oracle, name, fast, pyr, icp, so3):
     print(name, "max pose difference", worst)
 
 
+def test_icp_profile_stamps_and_changes_nothing(hip):
+    """`icpProfile`: workgroup 0 / thread 0 of every k_icp_iter launch of the background's tracking step leaves 16 shader-clock stamps -- eight of
+    the launch and, behind them, those gn_finish_wg takes inside the solve (a launch that finishes no iteration, the first of a step, leaves zeros
+    there).  Four frames of a 328 x 248 stream (the smallest size of test_gpu_launch_forms.ICP_SIZES), single model, geometric term, with the
+    switch off and on: poses and surfel counts the same bytes; on, every launch that finished an iteration holds eight non-decreasing launch
+    stamps and solve stamps in order between launch stamps 2 (system reduced) and 3 (back from the solve); off, the buffer stays as allocated."""
+    from maskfusion_amd import MaskFusion, synth
+    W, H = 328, 248
+    f = 528.0 * W / 640.0
+    st = synth.Stream(W=W, H=H, fx=f, fy=f, cx=W / 2.0, cy=H / 2.0, noise=True)
+    frames = [st.frame(k) for k in range(4)]
+
+    def run(prof):
+        mf = MaskFusion(W, H, f, f, W / 2.0, H / 2.0, icpThresh=100.0, so3=False, enableMultipleModels=False, numGSurfels=1 << 18)
+        mf.setParam("icpProfile", prof)
+        poses, counts = [], []
+        for k, (rgb, d, _) in enumerate(frames):
+            mf.processFrame(rgb, d, timestamp=k)
+            poses.append(mf.getCurrPose().copy())
+            counts.append(mf.getBackgroundModel().lastCount())
+        stamps = mf.debugRead("icp_prof").copy()
+        mf.close()
+        return poses, counts, stamps
+
+    (pa, ca, sa), (pb, cb, sb) = run(0), run(1)
+    assert ca == cb and all(x.tobytes() == y.tobytes() for x, y in zip(pa, pb))
+    assert sa.shape == (19, 16) and not sa.any()
+    s = sb.astype(np.int64)                                  # launches 0..18 of the last frame's step: 10 + 5 + 4 iterations
+    launch, solve = s[:, :8], s[:, 8:12]
+    print("icpProfile: ticks per launch", (launch[:, 7] - launch[:, 0]).tolist(), "-- inside the solve", (solve[1:, 3] - solve[1:, 0]).tolist())
+    assert (launch > 0).all() and (np.diff(launch[1:], axis=1) >= 0).all()
+    assert not s[0, 8:14].any()                              # the first launch seeds the state: no solve
+    assert (solve[1:] > 0).all() and (np.diff(solve[1:], axis=1) >= 0).all()
+    assert (launch[1:, 2] <= solve[1:, 0]).all() and (solve[1:, 3] <= launch[1:, 3]).all()
+
+
 def test_device_resident_masks_equal_host_pointer_run(hip):
     """mf_process_frame_dev + mf_set_mask_class_ids (frames and masks already in HBM: what bench.py --config 2s times) against
     mf_process_frame with host pointers and FrameData::classIDs: the same multi-model run bit for bit (tracked objects, spawns, drops)."""

@@ -12,7 +12,6 @@ __global__ void k_chain(const double* sys29, unsigned long long* out, double* si
     __shared__ double s_sys[32];
     __shared__ GNState s_st;
     __shared__ float s_pose[24];
-    __shared__ float s_T[16];
     if (threadIdx.x < 32) s_sys[threadIdx.x] = threadIdx.x < 29 ? sys29[threadIdx.x] : 0.0;
     if (threadIdx.x == 0) {
         for (int k = 0; k < 16; ++k) s_st.resultRt[k] = (k % 5 == 0) ? 1.0 : 0.0;
@@ -38,7 +37,7 @@ __global__ void k_chain(const double* sys29, unsigned long long* out, double* si
     sink[64 + threadIdx.x] = Rw[0][0] + Rw[0][1] + Rw[0][2] + Rw[1][0] + Rw[1][1] + Rw[1][2] + Rw[2][0] + Rw[2][1] + Rw[2][2];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     t[3] = __builtin_amdgcn_s_memtime();                       // exp
-    gn_finish_wg(s_sys, &s_st, s_pose, s_T);
+    gn_finish_wg(s_sys, &s_st, s_pose);
     __syncthreads();
     t[4] = __builtin_amdgcn_s_memtime();                       // the whole production function (solve + exp + composition + barriers)
     if (threadIdx.x == 0) for (int k = 0; k < 5; ++k) out[k] = t[k];
