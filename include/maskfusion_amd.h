@@ -828,6 +828,18 @@ int mf_k_segmentation_labels(int32_t W, int32_t H, const uint8_t* binary, const 
                            const int32_t* model_class_ids, int32_t n_models, int32_t next_model_id, int32_t allow_new,
                            const float* params11, uint8_t* ignore_map, uint8_t* full_segmentation, int32_t* has_new_label,
                            int32_t* new_class_id);
+/* The device stage with its intermediates readable (what mf_k_segmentation_labels calls with the extra arguments null).
+ * alive: nullable, one flag per model, 0 = dropped by the 0.2 m jump rule in this frame (entry 0, the background, is ignored).
+ * Outputs, each nullable, HOST pointers: lab_cc [W*H] component labels in cv::connectedComponentsWithStats numbering; lab_swept
+ * [W*H] the labels the votes read (after the removeEdges sweeps); stats5 [min(n_comp, stats_cap) x 5] left, top, width, height,
+ * area per component (row 0, the background, is not written); n_comp: components including the background.  They are written
+ * even where the call returns MF_ESTATE because the vote tables would not fit. */
+int mf_k_label_stage(int32_t W, int32_t H, const uint8_t* binary, const float* depth, const uint8_t* mask,
+                     const int32_t* class_ids, int32_t n_masks, const uint8_t* projected_ids, const int32_t* model_ids,
+                     const int32_t* model_class_ids, int32_t n_models, int32_t next_model_id, int32_t allow_new,
+                     const float* params11, uint8_t* ignore_map, uint8_t* full_segmentation, int32_t* has_new_label,
+                     int32_t* new_class_id, const int32_t* alive, int32_t* lab_cc, int32_t* lab_swept, int32_t* stats5,
+                     int32_t* n_comp, int32_t stats_cap);
 /* imageBGRToIntensity (Core/Cuda/cudafuncs.cu:626-654); channels = 3 or 4, the first three are used as stored */
 int mf_k_intensity(const uint8_t* d_img, int32_t channels, uint8_t* d_out, int32_t n, void* stream);
 /* pyrDownUcharGauss (Core/Cuda/cudafuncs.cu:534-588) */

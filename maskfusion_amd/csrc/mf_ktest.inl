@@ -155,14 +155,18 @@ extern "C" int mf_segmentation_labels(int32_t W, int32_t H, const uint8_t* binar
 }
 
 // Device twin of mf_segmentation_labels (same arguments, HOST pointers; the images are staged to the device, the stage runs
-// in mf_labels_gpu.hip, the outputs come back) -- the parity tests run both against the oracle.
-static __global__ void k_alive_pose(PoseDev* p) { if (threadIdx.x == 0 && blockIdx.x == 0) p->alive = 1; }
-extern "C" int mf_k_segmentation_labels(int32_t W, int32_t H, const uint8_t* binary, const float* depth, const uint8_t* mask,
-                                        const int32_t* class_ids, int32_t n_masks, const uint8_t* projected_ids, const int32_t* model_ids,
-                                        const int32_t* model_class_ids, int32_t n_models, int32_t next_model_id, int32_t allow_new,
-                                        const float* p, uint8_t* ignore_map, uint8_t* full, int32_t* has_new, int32_t* new_class) {
+// in mf_labels_gpu.hip, the outputs come back) -- the parity tests run both against the oracle.  mf_k_label_stage is the same
+// call with the stage's intermediates readable and the jump rule's `alive` flags settable: one body serves both.
+static __global__ void k_set_alive(PoseDev* p, int n) { if (blockIdx.x == 0 && (int)threadIdx.x < n) p[threadIdx.x].alive = threadIdx.x; }
+extern "C" int mf_k_label_stage(int32_t W, int32_t H, const uint8_t* binary, const float* depth, const uint8_t* mask,
+                                const int32_t* class_ids, int32_t n_masks, const uint8_t* projected_ids, const int32_t* model_ids,
+                                const int32_t* model_class_ids, int32_t n_models, int32_t next_model_id, int32_t allow_new,
+                                const float* p, uint8_t* ignore_map, uint8_t* full, int32_t* has_new, int32_t* new_class,
+                                const int32_t* alive, int32_t* lab_cc, int32_t* lab_swept, int32_t* stats5, int32_t* n_comp,
+                                int32_t stats_cap) {
     if (!binary || !depth || !projected_ids || !model_ids || !model_class_ids || n_models < 1 || n_models > 64 || !p || !ignore_map ||
-        !full || !has_new || !new_class || W <= 2 || H <= 2 || (n_masks > 0 && (!mask || !class_ids)) || n_masks > 256)
+        !full || !has_new || !new_class || W <= 2 || H <= 2 || (n_masks > 0 && (!mask || !class_ids)) || n_masks > 256 ||
+        (stats5 && stats_cap < 0))
         return MF_EINVAL;
     SegParams prm;
     prm.threshold = p[0]; prm.weightDistance = p[1]; prm.weightConvexity = p[2];
@@ -173,7 +177,7 @@ extern "C" int mf_k_segmentation_labels(int32_t W, int32_t H, const uint8_t* bin
     if (!sc.init((int)P)) return MF_ENOMEM;
     uint8_t *d_bin = nullptr, *d_mask = nullptr, *d_proj = nullptr, *d_full = nullptr; float* d_depth = nullptr; PoseDev* d_pose = nullptr;
     if (!sc.dalloc(&d_bin, P) || !sc.dalloc(&d_mask, P) || !sc.dalloc(&d_proj, P) || !sc.dalloc(&d_full, P) || !sc.dalloc(&d_depth, P) ||
-        !sc.dalloc(&d_pose, 1))
+        !sc.dalloc(&d_pose, 2))
         return MF_ENOMEM;
     hipStream_t s = nullptr;
     hipError_t e = hipMemcpy(d_bin, binary, P, hipMemcpyHostToDevice);
@@ -182,21 +186,49 @@ extern "C" int mf_k_segmentation_labels(int32_t W, int32_t H, const uint8_t* bin
     if (e == hipSuccess && n_masks > 0) e = hipMemcpy(d_mask, mask, P, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(sc.ignoreMap, ignore_map, P, hipMemcpyHostToDevice);
     if (e != hipSuccess) return MF_EHIP;
-    hipLaunchKernelGGL(k_alive_pose, dim3(1), dim3(64), 0, s, d_pose);
+    hipLaunchKernelGGL(k_set_alive, dim3(1), dim3(64), 0, s, d_pose, 2);   // one pose per distinct flag value: [0] dropped, [1] alive
     std::vector<SegModelInfo> infos;
     std::vector<const PoseDev*> poses;
-    for (int i = 0; i < n_models; ++i) { infos.push_back(SegModelInfo{model_ids[i], model_class_ids[i]}); poses.push_back(d_pose); }
+    for (int i = 0; i < n_models; ++i) {
+        infos.push_back(SegModelInfo{model_ids[i], model_class_ids[i]});
+        poses.push_back(d_pose + ((alive && i > 0 && alive[i] == 0) ? 0 : 1));
+    }
     static const int32_t kNoClass[1] = {0};
     int rc = sc.enqueue(prm, W, H, d_bin, d_depth, n_masks > 0 ? d_mask : nullptr, n_masks > 0 ? class_ids : kNoClass, n_masks, d_proj, infos,
                         poses, next_model_id, allow_new != 0, d_full, s);
     if (rc != MF_OK) return rc;
     if (hipDeviceSynchronize() != hipSuccess) return MF_EHIP;
+    // the component half ran before the vote tables were sized: readable whether or not they fit
+    const int nc = sc.h_result[3];
+    if (n_comp) *n_comp = nc;
+    if (lab_cc && hipMemcpy(lab_cc, sc.lab[0], P * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return MF_EHIP;
+    if (lab_swept && hipMemcpy(lab_swept, sc.lab[prm.removeEdges ? 1 : 0], P * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return MF_EHIP;
+    if (stats5) {   // cv::connectedComponentsWithStats order: left, top, width, height, area; row 0 (the background, never read by the stage) is not written
+        const int rows = std::min(nc, (int)stats_cap);
+        std::vector<int32_t> h_area((size_t)std::max(rows, 1));
+        std::vector<int4> h_box((size_t)std::max(rows, 1));
+        if (rows > 0 && (hipMemcpy(h_area.data(), sc.area, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(h_box.data(), sc.bbox, (size_t)rows * sizeof(int4), hipMemcpyDeviceToHost) != hipSuccess))
+            return MF_EHIP;
+        for (int c = 1; c < rows; ++c) {
+            const int4 b = h_box[c];
+            stats5[c * 5 + 0] = b.x; stats5[c * 5 + 1] = b.y; stats5[c * 5 + 2] = b.z - b.x + 1; stats5[c * 5 + 3] = b.w - b.y + 1;
+            stats5[c * 5 + 4] = h_area[c];
+        }
+    }
     if (sc.h_result[2]) return MF_ESTATE;
     if (hipMemcpy(full, d_full, P, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(ignore_map, sc.ignoreMap, P, hipMemcpyDeviceToHost) != hipSuccess)
         return MF_EHIP;
     *has_new = sc.h_result[0];
     *new_class = sc.h_result[1];
     return MF_OK;
+}
+extern "C" int mf_k_segmentation_labels(int32_t W, int32_t H, const uint8_t* binary, const float* depth, const uint8_t* mask,
+                                        const int32_t* class_ids, int32_t n_masks, const uint8_t* projected_ids, const int32_t* model_ids,
+                                        const int32_t* model_class_ids, int32_t n_models, int32_t next_model_id, int32_t allow_new,
+                                        const float* p, uint8_t* ignore_map, uint8_t* full, int32_t* has_new, int32_t* new_class) {
+    return mf_k_label_stage(W, H, binary, depth, mask, class_ids, n_masks, projected_ids, model_ids, model_class_ids, n_models, next_model_id,
+                            allow_new, p, ignore_map, full, has_new, new_class, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
 extern "C" int mf_k_gn_solve(const double* sys29, const double* result_rt16, const float* Rprev9, const float* tprev3, double* x6_serial,

@@ -2174,6 +2174,34 @@ void mfo_morph_close_ellipse(uint8_t* img, int W, int H, int radius, int iterati
  * which is undefined for such inputs; the product and this restatement define it the same way */
 static inline int mask_id(int value, int nMasks) { return value < nMasks ? value : 0; }
 
+/* removeEdges, MfSegmentation.cpp:243-291: 5 Jacobi sweeps (neighbours are read from the previous sweep's labels); labels in place,
+ * stats as mfo_connected_components4 wrote them (the areas stay those of the components before the sweeps) */
+void mfo_remove_edges(int32_t* labels, const int32_t* stats, const float* depth, int W, int H) {
+    const int total = W * H;
+    int32_t* r = (int32_t*)malloc(sizeof(int32_t) * total);
+    static const int ox[8] = {-1, 0, 1, -1, 1, -1, 0, 1};
+    static const int oy[8] = {-1, -1, -1, 0, 0, 1, 1, 1};
+    for (int it = 0; it < 5; ++it) {
+        memcpy(r, labels, sizeof(int32_t) * total);
+        for (int y = 1; y < H - 1; ++y)
+            for (int x = 1; x < W - 1; ++x) {
+                const int c = r[y * W + x];
+                const float d = depth[y * W + x];
+                if (c == 0 || stats[c * 5 + 4] < 50) {
+                    for (int k = 0; k < 8; ++k) {
+                        const int n = labels[(y + oy[k]) * W + (x + ox[k])];
+                        if (n != 0 && fabsf(depth[(y + oy[k]) * W + (x + ox[k])] - d) < 0.008 && stats[n * 5 + 4] > 50) {
+                            r[y * W + x] = n;
+                            break;
+                        }
+                    }
+                }
+            }
+        memcpy(labels, r, sizeof(int32_t) * total);
+    }
+    free(r);
+}
+
 void mfo_mf_segmentation_cpu(const mfo_seg_params* prm, int W, int H, const uint8_t* binaryIn, const float* depth,
                              const uint8_t* mask, const int32_t* classIDs, int nMasks, const uint8_t* projectedIDs,
                              const int32_t* modelIDs, const int32_t* modelClassIDs, int nModels, int nextModelID,
@@ -2199,31 +2227,7 @@ void mfo_mf_segmentation_cpu(const mfo_seg_params* prm, int W, int H, const uint
     int32_t* labels = (int32_t*)malloc(sizeof(int32_t) * total);
     int32_t* stats = (int32_t*)malloc(sizeof(int32_t) * 5 * (size_t)maxComp);
     const int nComponents = mfo_connected_components4(binary, labels, stats, maxComp, W, H);
-    /* removeEdges, :243-291: 5 Jacobi sweeps (neighbours are read from the previous sweep's labels) */
-    if (prm->removeEdges) {
-        int32_t* r = (int32_t*)malloc(sizeof(int32_t) * total);
-        static const int ox[8] = {-1, 0, 1, -1, 1, -1, 0, 1};
-        static const int oy[8] = {-1, -1, -1, 0, 0, 1, 1, 1};
-        for (int it = 0; it < 5; ++it) {
-            memcpy(r, labels, sizeof(int32_t) * total);
-            for (int y = 1; y < H - 1; ++y)
-                for (int x = 1; x < W - 1; ++x) {
-                    const int c = r[y * W + x];
-                    const float d = depth[y * W + x];
-                    if (c == 0 || stats[c * 5 + 4] < 50) {
-                        for (int k = 0; k < 8; ++k) {
-                            const int n = labels[(y + oy[k]) * W + (x + ox[k])];
-                            if (n != 0 && fabsf(depth[(y + oy[k]) * W + (x + ox[k])] - d) < 0.008 && stats[n * 5 + 4] > 50) {
-                                r[y * W + x] = n;
-                                break;
-                            }
-                        }
-                    }
-                }
-            memcpy(labels, r, sizeof(int32_t) * total);
-        }
-        free(r);
-    }
+    if (prm->removeEdges) mfo_remove_edges(labels, stats, depth, W, H);
     /* overlaps, :299-318 */
     int* mapComponentToMask = (int*)calloc(nComponents, sizeof(int));
     int* maskComponentPixels = (int*)calloc(nMasks > 0 ? nMasks : 1, sizeof(int));

@@ -303,6 +303,8 @@ void mfo_global_projection(const mfo_cam* cam, const mfo_model_view* models, int
  * component's first pixel, 0 = background (stand-in for cv::connectedComponentsWithStats(..., 4),
  * MfSegmentation.cpp:239).  stats: n_components x 5 ints {left, top, width, height, area}.  Returns n (incl. bg). */
 int mfo_connected_components4(const uint8_t* bin, int32_t* labels, int32_t* stats, int max_comp, int W, int H);
+/* the five removeEdges sweeps of MfSegmentation.cpp:243-291 on the labels / stats of mfo_connected_components4, in place */
+void mfo_remove_edges(int32_t* labels, const int32_t* stats, const float* depth, int W, int H);
 
 typedef struct {
     float threshold, weightDistance, weightConvexity;   /* 0.1 / 1 / 1   (MfSegmentation.h:48-50) */

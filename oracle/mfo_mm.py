@@ -42,6 +42,8 @@ def mm_lib():
                                         C.c_float, u8p]
     L.mfo_connected_components4.argtypes = [u8p, i32p, i32p, C.c_int, C.c_int, C.c_int]
     L.mfo_connected_components4.restype = C.c_int
+    L.mfo_remove_edges.argtypes = [i32p, i32p, f32p, C.c_int, C.c_int]
+    L.mfo_remove_edges.restype = None
     L.mfo_default_seg_params.argtypes = [C.POINTER(SegParams)]
     L.mfo_mf_segmentation_cpu.argtypes = [C.POINTER(SegParams), C.c_int, C.c_int, u8p, f32p, u8p, i32p, C.c_int, u8p,
                                           i32p, i32p, C.c_int, C.c_int, C.c_int, u8p, u8p, C.POINTER(C.c_int),
@@ -126,6 +128,14 @@ def connected_components4(binary):
     stats = np.zeros((maxc, 5), np.int32)
     n = mm_lib().mfo_connected_components4(np.ascontiguousarray(binary, np.uint8), labels, stats.reshape(-1), maxc, W, H)
     return n, labels, stats[:n]
+
+
+def remove_edges(labels, stats, depth):
+    """the five removeEdges sweeps (MfSegmentation.cpp:243-291) on connected_components4's labels / stats; returns the swept labels"""
+    H, W = labels.shape
+    out = np.ascontiguousarray(labels, np.int32).copy()
+    mm_lib().mfo_remove_edges(out, np.ascontiguousarray(stats, np.int32).reshape(-1), np.ascontiguousarray(depth, np.float32), W, H)
+    return out
 
 
 def global_projection(camera: Cam, models, time, time_delta, depth_cutoff):
