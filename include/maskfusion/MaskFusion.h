@@ -338,6 +338,21 @@ public:
     void savePly() { check(mf_save_ply(ctx_, exportDir_.c_str())); }          // MaskFusion.h:282
     void exportPoses() { check(mf_export_poses(ctx_, exportDir_.c_str())); }  // MaskFusion.h:284
 
+    // Sessions (no upstream twin; maskfusion_amd.h "Sessions"): the running context as a file, and a new object that continues it bit for bit.
+    // Non-virtual and inline, like the render calls.  Frames still waiting in the frame queue are not part of a session: saveSession refuses
+    // while there are any.  The loaded object has an empty export directory, no listeners and no frame queue: set what you need.
+    void saveSession(const std::string& path) {
+        if (!frameQueue_.empty()) throw std::logic_error("maskfusion_amd: saveSession with frames waiting in the frame queue");
+        check(mf_session_save(ctx_, path.c_str(), nullptr, 0));
+    }
+    static std::unique_ptr<MaskFusion> loadSession(const std::string& path) {
+        mf_session_info_t info;
+        mf_ctx* ctx = nullptr;
+        if (mf_session_info(path.c_str(), &info, nullptr, 0, nullptr) != MF_OK || mf_session_load(path.c_str(), -1, &ctx) != MF_OK)
+            throw std::runtime_error(std::string("maskfusion_amd: ") + mf_last_error(nullptr));
+        return std::unique_ptr<MaskFusion>(new MaskFusion(ctx, info.width, info.height));
+    }
+
     // Headless rendering of the maps (no upstream twin: what Model::renderPointCloud draws for MainController::drawScene, mf_render_view in
     // maskfusion_amd.h).  Non-virtual and inline: a program that never renders needs no render symbol of the library.
     mf_render_view_t defaultRenderView(int width, int height, bool icl = false) {
@@ -434,6 +449,9 @@ public:
     mf_ctx* handle() { return ctx_; }
 
 private:
+    MaskFusion(mf_ctx* loaded, int width, int height) : ctx_(loaded), width_(width), height_(height), exportSegmentation_(false), queueLength_(0) {
+        refreshModels();   // loadSession: the saved model list
+    }
     void set(const char* k, double v) { check(mf_set_param(ctx_, k, v)); }
     void check(int rc) {
         if (rc != MF_OK) throw std::runtime_error(std::string("maskfusion_amd: ") + mf_last_error(ctx_));

@@ -882,6 +882,89 @@ int mf_k_icp_step(const float* Rcurr9, const float* tcurr3, const float* d_vmap_
  * pixel}.  Read from the functions the launch itself calls, so that a test can name the form its image sizes select. */
 int mf_k_icp_launch_form(int32_t W, int32_t H, int32_t out[5]);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sessions: a running context saved to a file and resumed bit for bit (no upstream twin; DESIGN.md "Sessions").
+ * A run that is saved, destroyed, loaded and continued leaves the same bits as a run that never stopped.
+ * A session is read by the build of the library that wrote it: the file records sizeof(PoseDev), sizeof(FrameDev), sizeof(mf_config)
+ * and the run length of the surfel tables, and a build in which one of them differs refuses the file.  Nothing more is promised across
+ * versions of the library.
+ *
+ * THE FILE (little-endian; every offset from the start of the file):
+ *   header, 64 bytes
+ *      0  char[8]   magic "MFSESSN1"
+ *      8  uint32    format version (MF_SESSION_VERSION)
+ *     12  uint32    sizeof(PoseDev)      16  uint32  sizeof(FrameDev)      20  uint32  run length of the surfel tables (kRun)
+ *     24  int32     image width          28  int32   image height
+ *     32  int32     models in the list (the background included)
+ *     36  int32     tick (mf_get_tick)
+ *     40  uint64    bytes of the user blob
+ *     48  uint32    sections             52  uint32  sizeof(mf_config)
+ *     56  int64     frames the context has processed or staged
+ *   section table at offset 64, 64 bytes per section
+ *      0  char[32]  name, NUL-padded     32  int32   owner: index in the model list, or -1 (the context)
+ *     36  uint32    0                    40  uint64  offset of the payload (a multiple of 256, behind the table)
+ *     48  uint64    bytes of the payload 56  uint64  digest of the payload
+ *   payloads, each at its offset; the bytes between them are zero.
+ * The user blob is the section "user" (owner -1); its size is also in the header.
+ * DIGEST of a block of bytes: with the bytes taken as little-endian 32-bit words w_0 .. w_{n-1}, the last one zero-padded,
+ *      D = sum_i (uint64(w_i) + 1) * (2 i + 1)   mod 2^64          (numpy: ((w.astype(uint64) + 1) * (2 * arange(n, dtype=uint64) + 1)).sum())
+ * The digest of no bytes is 0.  A section whose digest does not match its bytes makes mf_session_load refuse the file.
+ * SECTIONS.  In device memory: the MF_STATE_CONTEXT_SECTIONS sections of the context and the MF_STATE_MODEL_SECTIONS sections of every model
+ * that mf_state_section_name names ("surfels": the live surfels in mf_download_map's order and layout, whatever shape the buffer has; "pose" /
+ * "frame": the device blocks PoseDev / FrameDev; "pose_log": the used entries of the ring, 8 floats each {t xyz, q xyzw, 0}; "vmap_g<level>" / "nmap_g<level>": the model-side
+ * pyramid of the last tracking step -- the next step rebuilds it, but an object that only follows the background keeps what it has, and
+ * a spawned object inherits the planes of the pool member it is made from, so the pool's planes are sections too, owner = models + position
+ * in the pool; "frame_rgb" /
+ * "frame_depth" / "frame_mask": the last staged frame, present when it lies in the context's own memory, i.e. not for mf_process_frame_dev /
+ * mf_stage_frame_dev, whose buffers belong to the caller).  In host memory: "config" (mf_config), "params" (every read-write key of
+ * mf_set_param with its value), "context", "ignore_map_host", "retired" (pose logs of dropped models), "model" (one per model) and "user".
+ * NOT in a session (DESIGN.md lists every member): scratch of the surfel passes, tile and visibility lists, the frame's vertex / normal
+ * pyramid and derivative images and the models' Gauss-Newton state (rebuilt by the next frame), timings, profiles, host clocks.
+ * ------------------------------------------------------------------------------------------------ */
+#define MF_SESSION_VERSION 1
+#define MF_STATE_CONTEXT_SECTIONS 14
+#define MF_STATE_MODEL_SECTIONS 16
+typedef struct mf_session_info_t {
+    uint32_t version;
+    int32_t width, height;
+    int32_t n_models;          /* models in the list */
+    int32_t tick;
+    uint32_t n_sections;
+    int64_t frames;
+    uint64_t user_bytes;
+    uint64_t file_bytes;
+    uint32_t pose_bytes, frame_bytes, run, config_bytes;   /* what the writing build was compiled with */
+    int32_t reserved[4];
+} mf_session_info_t;
+/* Writes the context's session to `path` (through path + ".tmp" and a rename: a failed save leaves no file at `path`, and the context stays
+ * usable).  Settles a pending prediction and waits for the context's streams first, as every call does; beyond that it only READS the context:
+ * no buffer is compacted, no table rebuilt ("densifyCount", "backgroundRuns" and every later result are what they would have been).
+ * user: an opaque blob stored verbatim (may be NULL with user_bytes 0).  MF_EINVAL with the reason in mf_last_error(ctx) when the file cannot
+ * be written. */
+int mf_session_save(mf_ctx* ctx, const char* path, const void* user, uint64_t user_bytes);
+/* Creates a context from a session: mf_create with the saved configuration (on `device` if it is >= 0, else on the saved one), every
+ * read-write parameter, the model list in order with its ids and classes, the pool of preallocated models at its saved size, then the
+ * sections.  Live surfel buffers come back dense in download order (the first live surfel stays first), with a fresh run table where the
+ * saved buffer had a table.  MF_EINVAL with the reason in mf_last_error(NULL) for a short file, a wrong magic or version, a struct size or
+ * run length that differs from this build's, or a section whose digest does not match its bytes (the reason names the section); a HIP or
+ * allocation failure destroys the half-built context.  *out is NULL unless the call returns MF_OK. */
+int mf_session_load(const char* path, int32_t device, mf_ctx** out);
+/* The header of a session file and its user blob, without a GPU: checks the magic, the version, the sizes, that the section table and every
+ * payload lie inside the file, and the user blob's digest.  user (may be NULL): receives min(user_capacity, blob size) bytes; *user_bytes
+ * (may be NULL): the blob's size.  Errors as mf_session_load. */
+int mf_session_info(const char* path, mf_session_info_t* out, void* user, uint64_t user_capacity, uint64_t* user_bytes);
+/* The digests of the context's device-resident sections, computed on the device without a download: out[0 .. MF_STATE_CONTEXT_SECTIONS) for
+ * the context, then MF_STATE_MODEL_SECTIONS words per model in list order; *n = the number of words (MF_EINVAL if capacity is smaller).  Two
+ * contexts in the same state give the same words; a dense and a run-structured buffer holding the same surfels give the same "surfels" word. */
+int mf_state_digest(mf_ctx* ctx, uint64_t* out, int32_t capacity, int32_t* n);
+/* name of section kind i: i < MF_STATE_CONTEXT_SECTIONS a context section, then the MF_STATE_MODEL_SECTIONS per-model kinds; NULL beyond.
+ * Word j >= MF_STATE_CONTEXT_SECTIONS of mf_state_digest belongs to model (j - MF_STATE_CONTEXT_SECTIONS) / MF_STATE_MODEL_SECTIONS and has
+ * kind MF_STATE_CONTEXT_SECTIONS + (j - MF_STATE_CONTEXT_SECTIONS) % MF_STATE_MODEL_SECTIONS. */
+const char* mf_state_section_name(int32_t i);
+/* Tooling (tools/session_timing.py): GPU milliseconds between HIP events of ms2[0] k_session_pack over the whole live buffer of `model`, chunk by
+ * chunk into the staging block without the copies, and ms2[1] k_state_digest over the same surfels; *surfels: the live count.  Read-only. */
+int mf_k_session_timing(mf_ctx* ctx, int32_t model, float* ms2, uint32_t* surfels);
+
 #ifdef __cplusplus
 }
 #endif

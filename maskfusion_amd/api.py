@@ -9,7 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import numpy as np
 
-from .lib import load, MFError, Config, ModelInfo, RenderView, MF_N_TIMINGS, TIMING_LABELS, MF_N_PASSES, PASS_LABELS
+from .lib import (load, MFError, Config, ModelInfo, RenderView, SessionInfo, MF_N_TIMINGS, TIMING_LABELS, MF_N_PASSES, PASS_LABELS,
+                  MF_STATE_CONTEXT_SECTIONS, MF_STATE_MODEL_SECTIONS)
 
 
 class Model:
@@ -159,6 +160,76 @@ class MaskFusion:
         if rc != 0:
             msg = self._L.mf_last_error(self._h)
             raise MFError(f"code {rc}: {msg.decode() if msg else ''}")
+
+    # -- sessions (include/maskfusion_amd.h "Sessions"): a running context as a file, resumed bit for bit -------------------------
+    def saveSession(self, path: str, user: bytes = b""):
+        """Writes the context's state to `path` (read-only: nothing of the context changes); `user` is an opaque blob stored verbatim"""
+        user = bytes(user)
+        self._chk(self._L.mf_session_save(self._h, str(path).encode(), user if user else None, len(user)))
+
+    @classmethod
+    def loadSession(cls, path: str, device: int | None = None) -> "MaskFusion":
+        """A new context that continues the saved one (on `device`; None: the device it was saved on)"""
+        L = load()
+        h = C.c_void_p()
+        rc = L.mf_session_load(str(path).encode(), -1 if device is None else int(device), C.byref(h))
+        if rc != 0:
+            msg = L.mf_last_error(None)
+            raise MFError(f"code {rc}: {msg.decode() if msg else ''}")
+        self = cls.__new__(cls)
+        self._L, self._h = L, h
+        self.cfg = cls._sessionConfig(path)
+        if device is not None:
+            self.cfg.device = int(device)
+        self.width, self.height = int(self.cfg.width), int(self.cfg.height)
+        return self
+
+    @staticmethod
+    def _sessionConfig(path: str) -> Config:
+        """the mf_config a session was saved with: its section "config", found through the section table (maskfusion_amd.h "Sessions")"""
+        import struct
+        with open(path, "rb") as f:
+            head = f.read(64)
+            table = f.read(64 * struct.unpack_from("<I", head, 48)[0])
+            for i in range(len(table) // 64):
+                name, owner, _, off, size, _ = struct.unpack_from("<32siIQQQ", table, 64 * i)
+                if name.rstrip(b"\0") == b"config" and owner == -1 and size == C.sizeof(Config):
+                    f.seek(off)
+                    return Config.from_buffer_copy(f.read(size))
+        raise MFError(f"{path}: no section config")
+
+    @staticmethod
+    def sessionInfo(path: str) -> dict:
+        """Header and user blob of a session file; needs no GPU and creates no context"""
+        L = load()
+        out, n = SessionInfo(), C.c_uint64(0)
+        rc = L.mf_session_info(str(path).encode(), C.byref(out), None, 0, C.byref(n))
+        blob = C.create_string_buffer(max(int(n.value), 1))
+        if rc == 0 and n.value:
+            rc = L.mf_session_info(str(path).encode(), C.byref(out), blob, n.value, C.byref(n))
+        if rc != 0:
+            msg = L.mf_last_error(None)
+            raise MFError(f"code {rc}: {msg.decode() if msg else ''}")
+        d = {k: int(getattr(out, k)) for k in ("version", "width", "height", "n_models", "tick", "n_sections", "frames", "user_bytes", "file_bytes")}
+        d["user"] = blob.raw[:int(n.value)]
+        return d
+
+    def stateDigest(self) -> dict:
+        """One 64-bit word per device-resident section, computed on the device (mf_state_digest): context sections by name, a model's as
+        "<name>[<index in the model list>]".  Equal states give equal words."""
+        n = C.c_int32(0)
+        cap = MF_STATE_CONTEXT_SECTIONS + 256 * MF_STATE_MODEL_SECTIONS
+        out = np.zeros(cap, np.uint64)
+        self._chk(self._L.mf_state_digest(self._h, out.ctypes.data, cap, C.byref(n)))
+        names = [self._L.mf_state_section_name(i).decode() for i in range(MF_STATE_CONTEXT_SECTIONS + MF_STATE_MODEL_SECTIONS)]
+        d = {}
+        for j in range(n.value):
+            if j < MF_STATE_CONTEXT_SECTIONS:
+                d[names[j]] = int(out[j])
+            else:
+                m, k = divmod(j - MF_STATE_CONTEXT_SECTIONS, MF_STATE_MODEL_SECTIONS)
+                d[f"{names[MF_STATE_CONTEXT_SECTIONS + k]}[{m}]"] = int(out[j])
+        return d
 
     # -- MaskFusion::processFrame ---------------------------------------------------------------
     def processFrame(self, rgb: np.ndarray, depth: np.ndarray, mask: np.ndarray | None = None, timestamp: int = 0,

@@ -20,6 +20,10 @@ sensor's own view (MaskFusion.sensorRenderView) compared with the frame on the G
 PSNR, SSIM, per model and for the whole image) -- and writes the result to <exportdir>views.json at the end.
 Another: -emesh <voxel> writes, beside -em's cloud-<id>.ply, a triangle mesh mesh-<id>.ply of every model's map (MaskFusion.saveMesh: GPU
 surface nets at that voxel size in metres, maskfusion_amd.mesh).
+Two more: -savestate FILE writes the context's session (MaskFusion.saveSession, DESIGN.md "Sessions") behind the last processed frame, i.e. at -e
+or at the end of the log; its user blob is JSON: the number of frames consumed from the reader and the argument list.  -loadstate FILE builds the
+context from such a file instead of from the flags, passes over the frames the saved run consumed, and goes on: the -ep poses, -em clouds and -es
+images of the two halves are those of one uninterrupted run.  (The core parameters are the saved ones; -gpu still chooses the device.)
 """
 from __future__ import annotations
 
@@ -32,7 +36,7 @@ import numpy as np
 _VALUE_FLAGS = {"-l", "-dir", "-depthdir", "-maskdir", "-colorprefix", "-depthprefix", "-maskprefix", "-indexW", "-cal", "-basedir",
                 "-exportdir", "-d", "-i", "-or", "-confG", "-confO", "-s", "-e", "-nm", "-offset", "-t", "-ie", "-cv", "-pt", "-ft",
                 "-ic", "-a", "-frameQ", "-method", "-p", "-segMinNew", "-segMaxNew", "-thNew", "-gpu", "-name", "-k", "-crfRGB", "-crfDepth",
-                "-crfPos", "-crfAppearance", "-crfSmooth", "-emesh"}
+                "-crfPos", "-crfAppearance", "-crfSmooth", "-emesh", "-savestate", "-loadstate"}
 _BOOL_FLAGS = {"-static", "-run", "-q", "-ep", "-em", "-es", "-ev", "-el", "-en", "-fo", "-nso", "-f", "-tum3", "-v2", "-icl", "-rl",
                "-fs", "-r", "-ftf", "-sc", "-keep", "-o", "-v1", "-rgbonly", "-evalviews"}
 
@@ -145,15 +149,9 @@ def export_renders(mf, flags, export_dir):
         Image.fromarray(np.ascontiguousarray(rgba[:, :, :3]), "RGB").save(os.path.join(export_dir, f"{name}{tick}.png"))
 
 
-def main(argv=None):
-    flags = parse(sys.argv[1:] if argv is None else argv)
-    st = settings(flags)
-    reader = open_reader(flags, st)
+def make_context(st):
+    """the context the flags describe"""
     from .api import MaskFusion
-    views = None
-    if "-evalviews" in flags:
-        from .eval import ViewScorer
-        views = ViewScorer()            # before the context: the scorer opens torch's side of the GPU, which has to come first
     mf = MaskFusion(st["W"], st["H"], st["fx"], st["fy"], st["cx"], st["cy"], timeDelta=st["timeDelta"],
                     initConfidenceGlobal=st["confGlobal"], initConfidenceObject=st["confObject"], depthCut=st["depthCutoff"],
                     icpThresh=st["icpWeight"], fastOdom=st["fastOdom"], so3=st["so3"], device=st["device"],
@@ -168,6 +166,28 @@ def main(argv=None):
         mf.setTrackableClassIds(ids)
     if st["preallocate"]:
         mf.preallocateModels(st["preallocate"])
+    return mf
+
+
+def main(argv=None):
+    flags = parse(sys.argv[1:] if argv is None else argv)
+    st = settings(flags)
+    reader = open_reader(flags, st)
+    from .api import MaskFusion
+    views = None
+    if "-evalviews" in flags:
+        from .eval import ViewScorer
+        views = ViewScorer()            # before the context: the scorer opens torch's side of the GPU, which has to come first
+    consumed = 0
+    if "-loadstate" in flags:
+        import json
+        info = MaskFusion.sessionInfo(flags["-loadstate"])
+        if (info["width"], info["height"]) != (st["W"], st["H"]):
+            raise SystemExit(f"-loadstate: the session is {info['width']} x {info['height']}, the input {st['W']} x {st['H']}")
+        consumed = int(json.loads(info["user"].decode())["frames"])
+        mf = MaskFusion.loadSession(flags["-loadstate"], device=st["device"] if "-gpu" in flags else None)
+    else:
+        mf = make_context(st)
     export_dir = flags.get("-exportdir", "")
     if export_dir and not export_dir.endswith(os.sep):
         export_dir += os.sep
@@ -175,6 +195,9 @@ def main(argv=None):
         os.makedirs(export_dir, exist_ok=True)
     n, t0 = 0, time.time()
     for frame in reader:
+        if n < consumed:          # -loadstate: the saved run has been here
+            n += 1
+            continue
         if mf.getTick() >= st["end"]:
             break
         if n + 1 < st["start"]:   # -s: skip ahead like fastForward(start)
@@ -190,8 +213,11 @@ def main(argv=None):
         n += 1
     dt = time.time() - t0
     models = mf.getModels()
-    print(f"processed {n} frames in {dt:.2f} s ({n / max(dt, 1e-9):.1f} fps incl. decoding); models: "
+    print(f"processed {n - consumed} frames in {dt:.2f} s ({n / max(dt, 1e-9):.1f} fps incl. decoding); models: "
           + ", ".join(f"id {m.getID()}: {m.lastCount()} surfels" for m in models))
+    if "-savestate" in flags:
+        import json
+        mf.saveSession(flags["-savestate"], json.dumps({"frames": n, "argv": list(sys.argv[1:] if argv is None else argv)}).encode())
     if "-ep" in flags:
         mf.exportPoses(export_dir)
     if "-em" in flags:

@@ -157,6 +157,8 @@ struct RenderScratch;                          // mf_render.inl: the headless re
 static void render_free(RenderScratch* r);
 struct EvalScratch;                            // mf_eval.inl: the model nearest-neighbour query's scratch, allocated on its first call
 static void eval_free(EvalScratch* e);
+struct SessionScratch;                         // mf_session.inl: staging of mf_session_save / _load / mf_state_digest, allocated on their first call
+static void session_free(SessionScratch* s);
 
 // Every implementation switch and tuning knob of a context, in the order of their table (mf_params.inl: key, legal values, side effects of setting
 // one).  The defaults are the product; the other positions exist for A/B measurements and as executable specifications.  A flag is a bool, a
@@ -351,6 +353,7 @@ struct mf_ctx {
     std::vector<void*> host_allocs;
     RenderScratch* render = nullptr;
     EvalScratch* eval = nullptr;
+    SessionScratch* session = nullptr;
 };
 
 #define MF_HIP(ctx, call)                                                                         \
@@ -681,6 +684,7 @@ extern "C" void mf_destroy(mf_ctx* c) {
     c->models.clear();
     if (c->render) render_free(c->render);
     if (c->eval) eval_free(c->eval);
+    if (c->session) session_free(c->session);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->d_splat_prof) (void)hipFree(c->d_splat_prof);
     for (void* p : c->host_allocs) (void)hipHostFree(p);
@@ -1165,3 +1169,4 @@ extern "C" int mf_debug_read_model(mf_ctx* c, int32_t model, const char* what, v
 #include "mf_ktest.inl"      // kernel-level entry points of the parity tests
 #include "mf_render.inl"     // headless rendering of the maps
 #include "mf_eval.inl"       // nearest-neighbour queries against a live map
+#include "mf_session.inl"    // a context's state as a file: save, load, digests

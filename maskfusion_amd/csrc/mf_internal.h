@@ -575,6 +575,21 @@ int nn_run(const float* d_target, int target_stride, int64_t n_target, const flo
 // a model's live surfels in download order (offs: launch_run_offsets): their positions -> out[n], NaN for confidence <= thr
 void launch_nn_gather(Surfels s, const FrameDev* frame, const int* offs, float thr, float4* out, int n, int max_runs, hipStream_t st);
 
+// ---------------- sessions (mf_session.hip) ----------------
+// the live surfels with ordinals [first, first + n) of download order -> out[0, 3 n): 48-byte records, mf_download_map's layout (offs:
+// launch_run_offsets; first + n at most its total).  Reads s, its table and frame->runs; writes out only
+void launch_session_pack(Surfels s, const FrameDev* frame, const int* offs, int first, int n, float4* out, hipStream_t st);
+// the inverse into a DENSE buffer: rec[0, 3 n) -> slots [first, first + n) of dst's three streams
+void launch_session_unpack(const float4* rec, int n, Surfels dst, int first, hipStream_t st);
+// *word += sum_i (uint64(w_i) + 1) (2 (first_word + i) + 1) mod 2^64 over the little-endian 32-bit words of data[0, bytes) (tail zero-padded;
+// data 16-byte aligned, device memory).  The digest of a block is what this leaves in a zeroed word; blocks of one section add up
+void launch_state_digest(const void* data, uint64_t bytes, uint64_t first_word, unsigned long long* word, hipStream_t st);
+// ... of the records launch_session_pack would write for the whole buffer (*total live surfels, device memory: launch_run_offsets' total;
+// expected: a host-side guess that sizes the grid)
+void launch_state_digest_surfels(Surfels s, const FrameDev* frame, const int* offs, const int* total, int expected, unsigned long long* word,
+                                 hipStream_t st);
+uint64_t state_digest_host(const void* data, uint64_t bytes, uint64_t first_word = 0);   // the same word for host memory
+
 // end-of-frame bookkeeping: tick++, cover -> useFillIn decision for the next frame
 // ... and the pose-log entry of this frame (MaskFusion.cpp:580-596) when log != nullptr
 void launch_pose_log(const PoseDev* pose, const PoseDev* bg_pose /*nullptr: the background itself*/, float* slot, hipStream_t s);

@@ -44,6 +44,18 @@ class Config(C.Structure):
                 ("pose_log_capacity", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class SessionInfo(C.Structure):
+    """mf_session_info_t (include/maskfusion_amd.h)"""
+    _fields_ = [("version", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("n_models", C.c_int32), ("tick", C.c_int32),
+                ("n_sections", C.c_uint32), ("frames", C.c_int64), ("user_bytes", C.c_uint64), ("file_bytes", C.c_uint64),
+                ("pose_bytes", C.c_uint32), ("frame_bytes", C.c_uint32), ("run", C.c_uint32), ("config_bytes", C.c_uint32),
+                ("reserved", C.c_int32 * 4)]
+
+
+MF_STATE_CONTEXT_SECTIONS = 14
+MF_STATE_MODEL_SECTIONS = 16
+
+
 class RenderView(C.Structure):
     """mf_render_view_t (include/maskfusion_amd.h)"""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
@@ -209,6 +221,12 @@ SYMBOLS = {
                                 C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
                                 C.c_int32, C.c_void_p, C.c_void_p]),
     "mf_k_icp_launch_form": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
+    "mf_session_save": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]),
+    "mf_session_load": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mf_session_info": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mf_state_digest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "mf_state_section_name": (C.c_char_p, [C.c_int32]),
+    "mf_k_session_timing": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_uint32)]),
 }
 
 _lib = None
