@@ -434,7 +434,14 @@ public:
     void setNewModelMaxRelativeSize(const float& v) { set("newModelMaxRelativeSize", v); }
     void setEnableMultipleModels(bool v) { set("enableMultipleModels", v); }
     void setTrackAllModels(bool v) { set("trackAllModels", v); }
-    void setEnableSmartModelDelete(bool) {}  // MaskFusion.h:263: read by no code path upstream
+    // MaskFusion.h:263.  Upstream reads it on line 702 of MaskFusion.cpp only; here it is live with mf_set_param("keepInactiveModels", 1): which
+    // dropped models' maps are archived.  Recognition of a returning object is driven from Python for now (maskfusion_amd.redetect)
+    void setEnableSmartModelDelete(bool v) { set("enableSmartModelDelete", v); }
+    int getInactiveModelCount() {
+        int32_t n = 0;
+        check(mf_inactive_count(ctx_, &n));
+        return (int)n;
+    }
 
     // Listeners, MaskFusion.h:303-306.  Called from processFrame (the caller's thread) after the frame that spawned / dropped the
     // model, in model-list order; the inactive model's getID() / getClassID() stay readable, its other calls throw.

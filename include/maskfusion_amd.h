@@ -277,6 +277,42 @@ int mf_cloud_fpfh_dev(const float* d_points, int32_t stride, int32_t normal_offs
  * rows or a null pointer.  Enqueued on `stream`, which the call synchronises before it returns. */
 int mf_feature_match_dev(const float* d_target, int64_t n_target, const float* d_query, int64_t n_query, int32_t dim, int32_t* d_idx,
                          float* d_d2, void* stream);
+/* The hypothesis search of a registration without a start, on the GPU (kernels: mf_register.hip; DESIGN.md "Inactive models and re-detection";
+ * the Python side: maskfusion_amd.eval.ransac_correspondences(device=True)).  src[k] <-> dst[k], k = 0 .. m - 1, are correspondences: x y z
+ * at d_src + k * stride and d_dst + k * stride floats, DEVICE fp32, stride >= 3; the pose sought maps src onto dst.  d_triples holds h
+ * triples (i0, i1, i2) of correspondence indices, DEVICE int32.  Everything below is computed in fp64 from the fp32 values, every operation
+ * rounded on its own (no contraction), in the order written; s0 s1 s2 are the triple's points in src, d0 d1 d2 in dst.
+ * STATUS of a triple, the first that applies:
+ *   1  an index is outside [0, m), or two indices are equal;
+ *   3  one of the six points has a coordinate that is not finite;
+ *   2  the edge test fails.  For the pairs (0,1), (0,2), (1,2) in that order, with (dx, dy, dz) the difference of the pair's points:
+ *      ls = sqrt((dx*dx + dy*dy) + dz*dz) in src, ld likewise in dst; the pair passes when min(ls, ld) > 0 and
+ *      min(ls, ld) >= (1.0 - edge_tolerance) * max(ls, ld), the factor formed once on the host (a rigid motion keeps lengths: the rule of
+ *      maskfusion_amd.eval.ransac_correspondences);
+ *   3  degenerate: with a = s1 - s0, b = s2 - s0, w = a x b = (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx) and
+ *      |w| = sqrt((wx*wx + wy*wy) + wz*wz): |w| == 0 in src or in dst;
+ *   0  tested.
+ * FIT of a tested triple.  Closed form from the triple's two frames -- NOT Horn's least-squares rule (no SVD: a device SVD could not be
+ * restated bit for bit); it maps s0, s1, s2 onto d0, d1, d2 exactly only when the triangles are congruent, which the edge test asks for up to
+ * its tolerance.  In src: e1 = a / |a| (|a| as ls above, per component), e3 = w / |w|, e2 = e3 x e1 (the cross product as above); in dst f1, f2,
+ * f3 likewise.  R[r][c] = (f1[r]*e1[c] + f2[r]*e2[c]) + f3[r]*e3[c].  cs = ((s0 + s1) + s2) / 3.0 per component, cd likewise.
+ * t[r] = cd[r] - ((R[r][0]*cs.x + R[r][1]*cs.y) + R[r][2]*cs.z).
+ * SCORE.  For every k: q[r] = ((R[r][0]*x + R[r][1]*y) + R[r][2]*z) + t[r] of src[k], (dx, dy, dz) = q - dst[k], e2 = (dx*dx + dy*dy) + dz*dz;
+ * k is an INLIER iff e2 <= inlier_distance * inlier_distance, the product formed once on the host in fp64.  A correspondence with a NaN
+ * fails the comparison: it is never an inlier.
+ * OUTPUT, all DEVICE.  d_status[j]: the status.  d_counts[j]: the number of inliers of a tested triple, 0 for the others.  d_best = {j*, count}:
+ * the tested triple with the largest count, ties to the smallest index, or {-1, 0} when no triple is tested.  d_inlier[k] (may be NULL): 1 for
+ * the inliers under j*'s pose, all 0 when j* = -1.  d_pose (may be NULL): j*'s 12 doubles R[0][0] R[0][1] R[0][2] t[0], R[1][0] ..., untouched
+ * when j* = -1.  Every decision is an integer count or an index: the result is a function of the inputs alone and the same for every call.
+ * The re-fit on the winner's inliers (Horn's rule) is the caller's, on the host.
+ * MF_EINVAL, with nothing enqueued and nothing written: a null d_src, d_dst, d_triples, d_counts, d_status or d_best when m > 0 and h > 0;
+ * stride < 3; m or h negative or above 2^24; inlier_distance not finite or <= 0; edge_tolerance outside [0, 1).  m < 3 or h == 0 is MF_OK
+ * with d_best = {-1, 0}.  Needs no context and no workspace.  Enqueued on `stream` (a memset and up to three launches); the call does NOT
+ * wait: synchronise the stream before reading the outputs. */
+int mf_pose_ransac_dev(const float* d_src, const float* d_dst, int32_t stride, int32_t m, const int32_t* d_triples /* [h][3] */, int32_t h,
+                       double inlier_distance, double edge_tolerance, uint32_t* d_counts /* [h] */, uint8_t* d_status /* [h] */,
+                       int32_t* d_best /* [2]: index or -1, count */, uint8_t* d_inlier /* [m] or NULL */, double* d_pose /* [12] or NULL */,
+                       void* stream);
 /* A triangle mesh of a cloud of oriented points (surfels), on the GPU (kernels: mf_mesh.hip; DESIGN.md "Surfel meshing"; the Python side:
  * maskfusion_amd.mesh): naive surface nets over a moving-least-squares signed distance to the points' tangent planes.  No table of cases.
  * INPUT.  n records of `stride` floats at d_points: x y z at offset 0, a normal at normal_offset (>= 3) and, with color_offset >= 3, three
@@ -516,6 +552,11 @@ int mf_get_last_fillin(mf_ctx* ctx, int32_t* used);
  *   "fastOdom", "so3" (int)
  *   "rgbOnly" (int; setRgbOnly: photometric term only)
  *   "pyramid", "timeDelta", "enableMultipleModels", "trackAllModels", "modelSpawnOffset" (int)
+ *   "keepInactiveModels" (flag, 0): a dropped object model's map is archived on the inactive list (mf_inactive_count ...) when the rule of
+ *     MaskFusion::inactivateModel (Core/MaskFusion.cpp:702) keeps it; 0: the map is deleted, and a drop costs no synchronisation
+ *   "enableSmartModelDelete" (flag, 1), "modelKeepMinSurfels" (int, 4000), "modelKeepConfThreshold" (float, 0.3): upstream's members of those
+ *     names (MaskFusion.h:398-399,414-415).  A model is kept iff !enableSmartModelDelete || (surfels >= modelKeepMinSurfels &&
+ *     confidence threshold > modelKeepConfThreshold).  They matter only with "keepInactiveModels"
  *
  * Segmentation parameters:
  *   "newModelMinRelativeSize", "newModelMaxRelativeSize" (float; SegmentationPerformer.h:36-37)
@@ -786,6 +827,42 @@ int mf_import_segmentation_dev(mf_ctx* ctx, const uint8_t* d_in);
 int mf_spawn_object_model(mf_ctx* ctx, int32_t id, int32_t class_id);
 /* MaskFusion::inactivateModel (Core/MaskFusion.cpp:686-713) */
 int mf_drop_model(mf_ctx* ctx, int32_t model);
+/* Inactive models (MaskFusion::inactiveModels, MaskFusion.h:398; DESIGN.md "Inactive models and re-detection").  With
+ * mf_set_param("keepInactiveModels", 1) a model that mf_drop_model or the jump rule of mf_process_frame retires is first ARCHIVED when line 702
+ * keeps it (the rule: the parameter list above): its map's records exactly as mf_download_map would return them at that moment -- compacted,
+ * in the live order, also for a map kept as runs -- in a device buffer of exactly that size, and the info below.  Keeping synchronises the
+ * context's streams and allocates; with the key at 0 (the default) nothing of this happens and a drop is what it was.  The list is in the
+ * order of the drops; k indexes it, and every call returns MF_EINVAL for a k outside it.  Upstream declares the way back
+ * (MaskFusion::redetectModels, Model::detectInRegion) and ships it empty; here recognition is maskfusion_amd.redetect, driven from Python. */
+typedef struct mf_inactive_info_t {
+    int32_t id, class_id;           /* Model::getID(), getClassID() */
+    uint32_t surfels;               /* records in the archive */
+    uint32_t age;                   /* Model::age at the drop */
+    float confidence_threshold;     /* Model::getConfidenceThreshold() at the drop */
+    int32_t tick;                   /* mf_get_tick at the drop */
+    float pose[16];                 /* the model's last pose, column-major as mf_get_pose */
+} mf_inactive_info_t;
+int mf_inactive_count(mf_ctx* ctx, int32_t* n);
+int mf_inactive_info(mf_ctx* ctx, int32_t k, mf_inactive_info_t* out);
+/* the archive in DEVICE memory: *n records of 12 floats (NULL for an empty map); valid until the list changes (a kept drop, a discard, a
+ * reactivation, mf_destroy) */
+int mf_inactive_map_dev(mf_ctx* ctx, int32_t k, const float** d_records, uint32_t* n);
+/* as mf_download_map: min(*count, max_count) records into host memory */
+int mf_inactive_download_map(mf_ctx* ctx, int32_t k, float* out, uint32_t max_count, uint32_t* count);
+/* frees entry k; the later entries move up */
+int mf_inactive_discard(mf_ctx* ctx, int32_t k);
+/* No upstream twin: sets an object model's age and confidence threshold (what processFrame's ramp, Core/MaskFusion.cpp:369-374, derives from
+ * the age every frame).  MF_EINVAL for the background or a threshold that is negative or NaN. */
+int mf_model_set_age(mf_ctx* ctx, int32_t model, uint32_t age, float confidence_threshold);
+/* Brings entry k back into the model list.  DEFINED as this sequence of public calls, whose bits it leaves:
+ *   1. mf_spawn_object_model(archived id, archived class) -- MF_EINVAL, "model id in use", when a live model has the id; the entry then stays;
+ *   2. mf_model_upload_map of the archive;
+ *   3. mf_model_override_pose(pose16, or the archived pose when pose16 is NULL; column-major);
+ *   4. mf_make_nonstatic;
+ *   5. mf_model_set_age(archived age, archived confidence threshold).
+ * The entry then leaves the list and the later entries move up.  The model's pose log starts anew; mf_export_poses writes the retired
+ * segment(s) of an id and then the live one into the one poses-<id>.txt, which is time order. */
+int mf_reactivate_model(mf_ctx* ctx, int32_t k, const float* pose16);
 /* Model::updateStaticPose(globalPose) (Core/Model/Model.h:263) with this context's background pose */
 int mf_model_update_static_pose(mf_ctx* ctx, int32_t model);
 /* Model::setMaxDepth + the object confidence ramp of processFrame (Core/MaskFusion.cpp:335-339,369-374) for the local objects */
@@ -917,7 +994,9 @@ int mf_k_icp_launch_form(int32_t W, int32_t H, int32_t out[5]);
  * in the pool; "frame_rgb" /
  * "frame_depth" / "frame_mask": the last staged frame, present when it lies in the context's own memory, i.e. not for mf_process_frame_dev /
  * mf_stage_frame_dev, whose buffers belong to the caller).  In host memory: "config" (mf_config), "params" (every read-write key of
- * mf_set_param with its value), "context", "ignore_map_host", "retired" (pose logs of dropped models), "model" (one per model) and "user".
+ * mf_set_param with its value), "context", "ignore_map_host", "retired" (pose logs of dropped models), "model" (one per model), "user" and,
+ * only when the inactive list is not empty, "inactive" (uint32 count, then per entry mf_inactive_info_t and the archive's records; a file
+ * without it loads with an empty list).
  * NOT in a session (DESIGN.md lists every member): scratch of the surfel passes, tile and visibility lists, the frame's vertex / normal
  * pyramid and derivative images and the models' Gauss-Newton state (rebuilt by the next frame), timings, profiles, host clocks.
  * ------------------------------------------------------------------------------------------------ */

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import numpy as np
 
-from .lib import (load, MFError, Config, ModelInfo, RenderView, SessionInfo, MF_N_TIMINGS, TIMING_LABELS, MF_N_PASSES, PASS_LABELS,
+from .lib import (load, MFError, Config, ModelInfo, InactiveInfo, RenderView, SessionInfo, MF_N_TIMINGS, TIMING_LABELS, MF_N_PASSES, PASS_LABELS,
                   MF_STATE_CONTEXT_SECTIONS, MF_STATE_MODEL_SECTIONS)
 
 
@@ -249,6 +249,8 @@ class MaskFusion:
                                            cid.ctypes.data if cid is not None else None, len(classIDs), timestamp,
                                            pose.ctypes.data if pose is not None else None, weightMultiplier,
                                            int(bootstrap)))
+        if getattr(self, "_redetect", False):
+            self.redetectModels()
         return False  # the reference always returns false (MaskFusion.cpp:606)
 
     def processFrameDevice(self, d_rgb: int, d_depth: int, d_mask: int = 0, timestamp: int = 0,
@@ -316,6 +318,87 @@ class MaskFusion:
 
     def preallocateModels(self, count: int):
         self._chk(self._L.mf_preallocate_models(self._h, count))
+
+    # -- inactive models and their re-detection (MaskFusion.h:311,398-399: inactiveModels, redetectModels; shipped empty upstream) --------
+    REDETECT_MIN_AGE = 25                  # frames: the age at which the object confidence ramp min(4.5, age / 25) reaches 1 (MaskFusion.cpp:369-374)
+
+    def setEnableRedetection(self, on: bool):
+        """MaskFusion::enableRedetection (default off): processFrame calls redetectModels() after every frame.  The maps to recognise come
+        from setParam("keepInactiveModels", 1), which this does not set."""
+        self._redetect = bool(on)
+
+    def inactiveModels(self) -> list:
+        """the kept maps of dropped models, in the order of the drops: one InactiveInfo (id, class_id, surfels, age, confidence_threshold,
+        tick, pose: 16 floats column-major) each"""
+        n = C.c_int32(0)
+        self._chk(self._L.mf_inactive_count(self._h, C.byref(n)))
+        out = []
+        for k in range(n.value):
+            info = InactiveInfo()
+            self._chk(self._L.mf_inactive_info(self._h, k, C.byref(info)))
+            out.append(info)
+        return out
+
+    def inactiveMap(self, k: int) -> np.ndarray:
+        """the archive of inactive model k as Model.downloadMap lays a map out: (surfels, 12) float32"""
+        cnt = C.c_uint32(0)
+        self._chk(self._L.mf_inactive_download_map(self._h, k, None, 0, C.byref(cnt)))
+        out = np.zeros((max(cnt.value, 1), 12), np.float32)
+        self._chk(self._L.mf_inactive_download_map(self._h, k, out.ctypes.data, cnt.value, C.byref(cnt)))
+        return out[:cnt.value]
+
+    def reactivateModel(self, k: int, pose=None):
+        """mf_reactivate_model: inactive model k returns to the end of the model list under its old id, with its archived map, non-static, at
+        `pose` (4 x 4, Model.overridePose's argument) or at its archived pose"""
+        p = None if pose is None else np.ascontiguousarray(np.asarray(pose, np.float32).T.reshape(16))
+        self._chk(self._L.mf_reactivate_model(self._h, k, p.ctypes.data if p is not None else None))
+
+    def discardInactive(self, k: int):
+        self._chk(self._L.mf_inactive_discard(self._h, k))
+
+    def redetectModels(self, min_age: int | None = None, **match) -> list:
+        """MaskFusion::redetectModels.  For every object model whose age is exactly `min_age` (REDETECT_MIN_AGE by default: a new model is
+        looked at once, when its map has had that many frames to grow) and every inactive model of the same class, in list order,
+        maskfusion_amd.redetect.match_model(new map, archived map, **match).  On the first acceptance the archived model is reactivated in the
+        new one's place and the new one is dropped without being kept.  Returns the merged pairs [(new id, old id), ...].
+
+        The pose.  A model's pose P (Model.getPose / overridePose) takes camera coordinates to the model's: a surfel n of the map is seen at
+        P^-1 n.  match_model's T takes the new map onto the old one, o = T n.  The returning object must stay where the camera sees the new
+        one, P_old^-1 o = P_new^-1 n for every n, so P_old^-1 T = P_new^-1:  P_old = T P_new.  (With poses written the other way round, model to
+        camera, Q = P^-1, the same statement reads Q_old = Q_new T^-1.)"""
+        from . import redetect
+        min_age = self.REDETECT_MIN_AGE if min_age is None else int(min_age)
+        merged = []
+        if not self.inactiveModels():       # (host state: a run without archived models pays no synchronisation for the question)
+            return merged
+        i = 1
+        while i < len(self.modelIDs()):
+            m = Model(self, i)
+            info = m.info()
+            done = False
+            if info.age == min_age and all(info.id != old_id for _, old_id in merged):      # (not a model this call brought back)
+                new_map = None
+                for k, old in enumerate(self.inactiveModels()):
+                    if old.class_id != info.class_id:
+                        continue
+                    new_map = m.downloadMap() if new_map is None else new_map
+                    r = redetect.match_model(new_map, self.inactiveMap(k), **match)
+                    if not r["accepted"]:
+                        continue
+                    pose = r["T"] @ m.getPose()
+                    keep = self.getParam("keepInactiveModels")
+                    self.setParam("keepInactiveModels", 0)          # the new model is dropped for good
+                    try:
+                        self._chk(self._L.mf_drop_model(self._h, i))
+                    finally:
+                        self.setParam("keepInactiveModels", keep)
+                    self.reactivateModel(k, pose)
+                    merged.append((int(info.id), int(old.id)))
+                    done = True
+                    break
+            if not done:
+                i += 1
+        return merged
 
     # -- exports (Core/MaskFusion.h:282-284) --------------------------------------------------------
     def savePly(self, exportDir: str):

@@ -24,6 +24,9 @@ Two more: -savestate FILE writes the context's session (MaskFusion.saveSession, 
 or at the end of the log; its user blob is JSON: the number of frames consumed from the reader and the argument list.  -loadstate FILE builds the
 context from such a file instead of from the flags, passes over the frames the saved run consumed, and goes on: the -ep poses, -em clouds and -es
 images of the two halves are those of one uninterrupted run.  (The core parameters are the saved ones; -gpu still chooses the device.)
+And -redetect: dropped object models are kept ("keepInactiveModels") and every new object model is compared, once, with the kept ones of its class
+(MaskFusion.setEnableRedetection, maskfusion_amd.redetect; upstream's enableRedetection, whose matching the release ships empty): a returning
+object gets its id and its map back, so -em writes one cloud-<id>.ply for it and -ep its pose log under that id, both segments.
 """
 from __future__ import annotations
 
@@ -38,7 +41,7 @@ _VALUE_FLAGS = {"-l", "-dir", "-depthdir", "-maskdir", "-colorprefix", "-depthpr
                 "-ic", "-a", "-frameQ", "-method", "-p", "-segMinNew", "-segMaxNew", "-thNew", "-gpu", "-name", "-k", "-crfRGB", "-crfDepth",
                 "-crfPos", "-crfAppearance", "-crfSmooth", "-emesh", "-savestate", "-loadstate"}
 _BOOL_FLAGS = {"-static", "-run", "-q", "-ep", "-em", "-es", "-ev", "-el", "-en", "-fo", "-nso", "-f", "-tum3", "-v2", "-icl", "-rl",
-               "-fs", "-r", "-ftf", "-sc", "-keep", "-o", "-v1", "-rgbonly", "-evalviews"}
+               "-fs", "-r", "-ftf", "-sc", "-keep", "-o", "-v1", "-rgbonly", "-evalviews", "-redetect"}
 
 
 def parse(argv):
@@ -188,6 +191,9 @@ def main(argv=None):
         mf = MaskFusion.loadSession(flags["-loadstate"], device=st["device"] if "-gpu" in flags else None)
     else:
         mf = make_context(st)
+    if "-redetect" in flags:      # dropped object models are kept, and a new model that turns out to be one of them gets its id and map back
+        mf.setParam("keepInactiveModels", 1)
+        mf.setEnableRedetection(True)
     export_dir = flags.get("-exportdir", "")
     if export_dir and not export_dir.endswith(os.sep):
         export_dir += os.sep

@@ -229,6 +229,11 @@ struct Switches {
                                                        // launch of its own (~18 us per million surfels + ~10 us); below, the copying update with the scatter
                                                        // riding on it (~30 us per million).  Only with the two-launch clean (<= big_map_elements)
     SplatTuning splat_tune;                            // "tileHeight" / "tileThreads" / "spriteLanes" of THIS context: launch shape of the tile passes (mf_splat.hip)
+    // ---- the model lifecycle (MaskFusion::inactivateModel, Core/MaskFusion.cpp:699-713) ----
+    bool keep_inactive = false;                        // "keepInactiveModels": a dropped object model's map is archived (mf_ctx::inactive) when line 702 says so; 0: deleted
+    bool smart_delete = true;                          // "enableSmartModelDelete": MaskFusion::enableSmartModelDelete -- 1: only models that pass the two thresholds are kept
+    int keep_min_surfels = 4000;                       // "modelKeepMinSurfels": MaskFusion::modelKeepMinSurfels
+    float keep_conf = 0.3f;                            // "modelKeepConfThreshold": MaskFusion::modelKeepConfThreshold
     // ---- test knobs ----
     int densify_every = 0;                             // "densifyEvery": > 0 = a model's sparse buffer is compacted every so many frames whatever its bounds say (tests)
     bool timings_on = false, pass_timings_on = false;  // "timings" / "passTimings": HIP events around the stages (mf_get_timings) / the surfel passes (mf_get_pass_timings)
@@ -313,6 +318,10 @@ struct mf_ctx {
     struct RetiredLog { int id; std::vector<int64_t> ts; std::vector<float> p; size_t arena_off = 0, n = 0; bool in_arena = false; };
     std::vector<RetiredLog> retired;
     float* d_retired = nullptr; size_t retired_cap = 0, retired_used = 0;   // [retired_cap][8] floats
+    // the maps of dropped models that were kept (MaskFusion::inactiveModels; "keepInactiveModels"): n = info.surfels records of 48 bytes in
+    // mf_download_map's order and layout, in a device buffer of exactly that size (none for an empty map)
+    struct Inactive { mf_inactive_info_t info; float4* d_rec = nullptr; };
+    std::vector<Inactive> inactive;
     std::vector<std::unique_ptr<ModelState>> pool;   // MaskFusion::preallocatedModels (buffers allocated ahead of the spawn)
     SurfelScratch scr = {};                // the shared scratch of the surfel passes (mf_internal.h); scr.keys is also GlobalProjection's key image
     uint8_t* d_maskT = nullptr;            // the frame's mask in the packed map's column-major order (launch_index_resolve_packed writes it, clean reads it)
@@ -682,6 +691,7 @@ extern "C" void mf_destroy(mf_ctx* c) {
     if (!c) return;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->models.clear();
+    for (auto& a : c->inactive) if (a.d_rec) (void)hipFree(a.d_rec);
     if (c->render) render_free(c->render);
     if (c->eval) eval_free(c->eval);
     if (c->session) session_free(c->session);
@@ -875,20 +885,35 @@ extern "C" int mf_export_poses(mf_ctx* c, const char* export_dir) {
     settle(c);
     if (!c || !export_dir) return MF_EINVAL;
     const std::string dir(export_dir);
+    {
+        int rc = materialise_retired(c);
+        if (rc != MF_OK) return rc;
+    }
+    // one file per id: the retired segments in the order of their retirement, then the live model's log (a reactivated model -- mf_reactivate_model
+    // -- has both under one id, and its live log starts at the reactivation: time order)
+    auto write_id = [&](int id, const std::vector<int64_t>* live_t, const std::vector<float>* live_p) {
+        std::vector<int64_t> t; std::vector<float> p;
+        for (auto& r : c->retired)
+            if (r.id == id) { t.insert(t.end(), r.ts.begin(), r.ts.end()); p.insert(p.end(), r.p.begin(), r.p.end()); }
+        if (live_t) { t.insert(t.end(), live_t->begin(), live_t->end()); p.insert(p.end(), live_p->begin(), live_p->end()); }
+        return write_pose_file(c, dir, id, t, p);
+    };
+    std::vector<int> live_ids;
     for (auto& m : c->models) {
         std::vector<int64_t> t; std::vector<float> p;
         int rc = download_pose_log(c, *m, t, p);
         if (rc != MF_OK) return rc;
         if (!m->d_poselog) continue;
-        rc = write_pose_file(c, dir, m->id, t, p);
+        live_ids.push_back(m->id);
+        rc = write_id(m->id, &t, &p);
         if (rc != MF_OK) return rc;
     }
-    {
-        int rc = materialise_retired(c);
-        if (rc != MF_OK) return rc;
-    }
-    for (auto& r : c->retired) {
-        int rc = write_pose_file(c, dir, r.id, r.ts, r.p);
+    for (size_t k = 0; k < c->retired.size(); ++k) {
+        const int id = c->retired[k].id;
+        bool done = std::find(live_ids.begin(), live_ids.end(), id) != live_ids.end();
+        for (size_t q = 0; q < k && !done; ++q) done = c->retired[q].id == id;
+        if (done) continue;
+        int rc = write_id(id, nullptr, nullptr);
         if (rc != MF_OK) return rc;
     }
     return MF_OK;

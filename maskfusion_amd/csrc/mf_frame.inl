@@ -847,8 +847,42 @@ static int enqueue_predict_loop(mf_ctx* c, size_t first, bool may_batch, int64_t
 // waits for the GPU: round 3 freed ~30 allocations here and allocated them again (plus a drained stream and a 2 MB read-back for the log) at
 // the next spawn -- 1.5 of the 2.4 ms of a frame of bench.py --config 2s, whose scene drops and re-spawns a tracked box every other frame.
 static int materialise_retired(mf_ctx* c);
+// "keepInactiveModels": the map of a model that is about to be retired goes onto mf_ctx::inactive when line 702 keeps it --
+//   !enableSmartModelDelete || (count >= modelKeepMinSurfels && confThreshold > modelKeepConfThreshold)
+// -- as a right-sized device buffer of the records mf_download_map would return now (a map kept as runs is compacted first, as there), beside the
+// model's identity, age, threshold, the context's tick and the pose.  Synchronises the context's streams (the exact count and the pose are the
+// host mirrors') and allocates: the price of keeping; with the key at 0 retire_model does not come here.
+static int keep_retiring_model(mf_ctx* c, ModelState& m) {
+    require_dense(c, m);
+    MF_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->stream_obj) MF_HIP(c, hipStreamSynchronize(c->stream_obj));
+    const int n = *m.h_count;
+    if (c->sw.smart_delete && !(n >= c->sw.keep_min_surfels && m.confThr > c->sw.keep_conf)) return MF_OK;
+    mf_ctx::Inactive a;
+    memset(&a.info, 0, sizeof(a.info));
+    a.info.id = m.id; a.info.class_id = m.classID; a.info.surfels = (uint32_t)n; a.info.age = m.age; a.info.confidence_threshold = m.confThr;
+    a.info.tick = c->host_tick;
+    const PoseDev& p = *m.h_pose;          // column-major, as mf_get_pose
+    for (int r = 0; r < 3; ++r) {
+        for (int col = 0; col < 3; ++col) a.info.pose[col * 4 + r] = p.R[r * 3 + col];
+        a.info.pose[12 + r] = p.t[r];
+    }
+    a.info.pose[15] = 1.f;
+    if (n > 0) {
+        if (hipMalloc(&a.d_rec, (size_t)n * 48) != hipSuccess) { (void)hipGetLastError(); c->err = "keepInactiveModels: no device memory for the archive"; return MF_ENOMEM; }
+        launch_run_offsets(m.surf[m.cur], m.d_frame, c->d_run_offs, nullptr, c->stream);
+        launch_session_pack(m.surf[m.cur], m.d_frame, c->d_run_offs, 0, n, a.d_rec, c->stream);
+        if (hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipFree(a.d_rec); c->err = "keepInactiveModels: copying the map failed"; return MF_EHIP; }
+    }
+    c->inactive.push_back(a);
+    return MF_OK;
+}
 static int retire_model(mf_ctx* c, size_t i) {
     ModelState* m = c->models[i].get();   // (everything that can fail happens before the model leaves the list)
+    if (c->sw.keep_inactive) {
+        int rc = keep_retiring_model(c, *m);
+        if (rc != MF_OK) return rc;
+    }
     const size_t cap = (size_t)c->cfg.pose_log_capacity, n_all = m->log_ts.size(), n = n_all < cap ? n_all : cap;
     if (m->d_poselog && n > 0) {
         mf_ctx::RetiredLog r;

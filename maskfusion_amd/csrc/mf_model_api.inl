@@ -538,3 +538,69 @@ extern "C" int mf_update_object_params(mf_ctx* c) {
     }
     return MF_OK;
 }
+
+// ---- inactive models (MaskFusion::inactiveModels; "keepInactiveModels"; DESIGN.md "Inactive models and re-detection") ----
+static mf_ctx::Inactive* inactive_at(mf_ctx* c, int32_t k) {
+    if (!c || k < 0 || (size_t)k >= c->inactive.size()) { if (c) c->err = "no such inactive model"; return nullptr; }
+    return &c->inactive[(size_t)k];
+}
+extern "C" int mf_inactive_count(mf_ctx* c, int32_t* n) {
+    if (!c || !n) return MF_EINVAL;
+    *n = (int32_t)c->inactive.size();
+    return MF_OK;
+}
+extern "C" int mf_inactive_info(mf_ctx* c, int32_t k, mf_inactive_info_t* out) {
+    mf_ctx::Inactive* a = inactive_at(c, k);
+    if (!a || !out) return MF_EINVAL;
+    *out = a->info;
+    return MF_OK;
+}
+extern "C" int mf_inactive_map_dev(mf_ctx* c, int32_t k, const float** d_records, uint32_t* n) {
+    mf_ctx::Inactive* a = inactive_at(c, k);
+    if (!a || !d_records || !n) return MF_EINVAL;
+    *d_records = reinterpret_cast<const float*>(a->d_rec);
+    *n = a->info.surfels;
+    return MF_OK;
+}
+extern "C" int mf_inactive_download_map(mf_ctx* c, int32_t k, float* out, uint32_t max_count, uint32_t* count) {
+    mf_ctx::Inactive* a = inactive_at(c, k);
+    if (!a || !count || (!out && max_count)) return MF_EINVAL;
+    *count = a->info.surfels;
+    const uint32_t m = a->info.surfels < max_count ? a->info.surfels : max_count;
+    if (m) MF_HIP(c, hipMemcpy(out, a->d_rec, (size_t)m * 48, hipMemcpyDeviceToHost));   // (the archive was complete when the keep returned)
+    return MF_OK;
+}
+extern "C" int mf_inactive_discard(mf_ctx* c, int32_t k) {
+    mf_ctx::Inactive* a = inactive_at(c, k);
+    if (!a) return MF_EINVAL;
+    if (a->d_rec) MF_HIP(c, hipFree(a->d_rec));
+    c->inactive.erase(c->inactive.begin() + k);
+    return MF_OK;
+}
+// no upstream twin (Model::age and the confidence ramp are processFrame's, Core/MaskFusion.cpp:369-374): what a caller that brings a model
+// back by hand restores last
+extern "C" int mf_model_set_age(mf_ctx* c, int32_t model, uint32_t age, float confidence_threshold) {
+    settle(c);
+    ModelState* m = model_at(c, model);
+    if (!m || model == 0 || !(confidence_threshold >= 0.f)) return MF_EINVAL;
+    m->age = age; m->confThr = confidence_threshold;
+    return MF_OK;
+}
+// DEFINED as the public calls below, in this order (include/maskfusion_amd.h): the bits it leaves are theirs
+extern "C" int mf_reactivate_model(mf_ctx* c, int32_t k, const float* pose16) {
+    settle(c);
+    mf_ctx::Inactive* a = inactive_at(c, k);
+    if (!a) return MF_EINVAL;
+    const mf_inactive_info_t info = a->info;
+    std::vector<float> rec((size_t)info.surfels * 12);
+    if (info.surfels) MF_HIP(c, hipMemcpy(rec.data(), a->d_rec, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
+    int rc = mf_spawn_object_model(c, info.id, info.class_id);          // "model id in use": the entry stays
+    if (rc != MF_OK) return rc;
+    const int32_t model = (int32_t)c->models.size() - 1;
+    rc = mf_model_upload_map(c, model, rec.data(), info.surfels);
+    if (rc == MF_OK) rc = mf_model_override_pose(c, model, pose16 ? pose16 : info.pose);
+    if (rc == MF_OK) rc = mf_make_nonstatic(c, model);
+    if (rc == MF_OK) rc = mf_model_set_age(c, model, info.age, info.confidence_threshold);
+    if (rc != MF_OK) return rc;
+    return mf_inactive_discard(c, k);
+}

@@ -115,6 +115,10 @@ static const ParamRow kParamTable[] = {
     {"enableMultipleModels", kInCfg, offsetof(mf_config, enable_multiple_models), kInt},
     {"trackAllModels", kInCfg, offsetof(mf_config, track_all_models), kInt},
     {"modelSpawnOffset", kInCfg, offsetof(mf_config, model_spawn_offset), kInt},
+    {"keepInactiveModels", kInSw, offsetof(Switches, keep_inactive), kFlag},
+    {"enableSmartModelDelete", kInSw, offsetof(Switches, smart_delete), kFlag},
+    {"modelKeepMinSurfels", kInSw, offsetof(Switches, keep_min_surfels), kInt},
+    {"modelKeepConfThreshold", kInSw, offsetof(Switches, keep_conf), kFloat},
     // ---- segmentation parameters ----
     {"newModelMinRelativeSize", kInSeg, offsetof(SegParams, minRelSizeNew), kFloat},
     {"newModelMaxRelativeSize", kInSeg, offsetof(SegParams, maxRelSizeNew), kFloat},

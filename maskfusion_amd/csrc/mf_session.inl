@@ -310,6 +310,17 @@ static void session_host_sections(mf_ctx* c, const void* user, uint64_t user_byt
         add("model", (int)i, w);
     }
     { SessWriter w; if (user_bytes) w.bytes(user, (size_t)user_bytes); add("user", -1, w); }
+    if (!c->inactive.empty()) {   // the kept maps of dropped models, last: a file of a context without any has the sections it always had
+        SessWriter w;
+        w.put<uint32_t>((uint32_t)c->inactive.size());
+        for (const mf_ctx::Inactive& a : c->inactive) {
+            w.put<uint32_t>((uint32_t)sizeof(mf_inactive_info_t)); w.put(a.info);
+            std::vector<float> rec((size_t)a.info.surfels * 12);
+            if (!rec.empty()) (void)hipMemcpy(rec.data(), a.d_rec, rec.size() * sizeof(float), hipMemcpyDeviceToHost);
+            w.vec(rec);
+        }
+        add("inactive", -1, w);
+    }
 }
 
 extern "C" int mf_session_save(mf_ctx* c, const char* path, const void* user, uint64_t user_bytes) {
@@ -573,6 +584,26 @@ extern "C" int mf_session_load(const char* path, int32_t device, mf_ctx** out) {
             c->retired.push_back(std::move(q));
         }
         if (!r.ok) return fail(session_refuse("section retired is malformed"));
+    }
+    if (session_find(table, "inactive", -1)) {   // (optional: written only for a list that is not empty)
+        std::vector<uint8_t> b_inactive;
+        if ((rc = session_read_host(f, table, "inactive", -1, b_inactive)) != MF_OK) return fail(rc);
+        SessReader r(b_inactive);
+        const uint32_t n = r.get<uint32_t>();
+        for (uint32_t i = 0; i < n && r.ok; ++i) {
+            mf_ctx::Inactive a;
+            if (r.get<uint32_t>() != sizeof(mf_inactive_info_t)) { r.ok = false; break; }
+            a.info = r.get<mf_inactive_info_t>();
+            std::vector<float> rec;
+            r.vec(rec);
+            if (!r.ok || rec.size() != (size_t)a.info.surfels * 12) { r.ok = false; break; }
+            if (!rec.empty()) {
+                LOAD_HIP((hipMalloc(&a.d_rec, rec.size() * sizeof(float))));
+                c->inactive.push_back(a);   // (owned by the context from here on: a failure below frees it with the context)
+                LOAD_HIP((hipMemcpy(a.d_rec, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice)));
+            } else c->inactive.push_back(a);
+        }
+        if (!r.ok) return fail(session_refuse("section inactive is malformed"));
     }
     // the model list in order, with the saved ids and classes
     const int cap_obj = surfel_capacity(c->cfg.num_osurfels);

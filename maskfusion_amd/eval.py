@@ -813,8 +813,32 @@ def _horn_batch(src, dst):
     return R, md - np.einsum("kab,kb->ka", R, ms)
 
 
+def _pose_ransac_device(src, dst, tri, inlier_distance: float, edge_tolerance: float):
+    """mf_pose_ransac_dev on (m, 3) float32 correspondences and (h, 3) int32 triples.  Returns numpy (status uint8 (h,), counts uint32 (h,),
+    best int32 (2,): index or -1 and count, inlier mask bool (m,), pose fp64 3 x 4 [R | t] or None without a tested triple)."""
+    import torch
+    from .lib import load
+    L = load()
+    s, d = _device_points(src), _device_points(dst)
+    m, h = int(s.shape[0]), int(len(tri))
+    dev = s.device
+    t = torch.as_tensor(np.ascontiguousarray(tri, np.int32)).to(dev)
+    counts = torch.zeros(max(h, 1), dtype=torch.int32, device=dev)
+    status = torch.zeros(max(h, 1), dtype=torch.uint8, device=dev)
+    best = torch.zeros(2, dtype=torch.int32, device=dev)
+    mask = torch.zeros(max(m, 1), dtype=torch.uint8, device=dev)
+    pose = torch.zeros(12, dtype=torch.float64, device=dev)
+    rc = L.mf_pose_ransac_dev(s.data_ptr() if m else None, d.data_ptr() if m else None, int(s.shape[1]), m, t.data_ptr() if h else None, h,
+                              float(inlier_distance), float(edge_tolerance), counts.data_ptr(), status.data_ptr(), best.data_ptr(),
+                              mask.data_ptr(), pose.data_ptr(), _stream_of(dev))
+    _check(rc, "mf_pose_ransac_dev", "inlier_distance must be finite and > 0, edge_tolerance in [0, 1), at most 2^24 correspondences and triples")
+    b = best.cpu().numpy()               # (the copy waits for the stream)
+    return (status[:h].cpu().numpy(), counts[:h].cpu().numpy().view(np.uint32), b, mask[:m].cpu().numpy().astype(bool),
+            pose.cpu().numpy().reshape(3, 4) if b[0] >= 0 else None)
+
+
 def ransac_correspondences(src, dst, inlier_distance: float, hypotheses: int = 20000, seed: int = 0, edge_tolerance: float = 0.1,
-                           chunk: int = 512) -> dict:
+                           chunk: int = 512, device: bool = False) -> dict:
     """The hypothesis search of register_global over correspondences src[k] <-> dst[k] ((m, 3) each; the T sought maps src onto dst).
     `hypotheses` triples of three different correspondences are drawn at once from numpy.random.default_rng(seed); a triple is dropped
     when one of its three edges has lengths in src and dst that disagree by more than edge_tolerance (the shorter below 1 - edge_tolerance
@@ -822,7 +846,11 @@ def ransac_correspondences(src, dst, inlier_distance: float, hypotheses: int = 2
     number of correspondences with |T src - dst| <= inlier_distance, in fp64.  The largest count wins, ties go to the hypothesis drawn
     earlier; T is then fitted again to the winner's inliers (align_horn).  Returns {"T" 4 x 4, "inliers": the winner's count, "inlier_mask"
     bool (m,): under the winning triple's pose, "hypotheses": drawn, "tested": solved and scored}; without a testable triple T is None and
-    inliers 0.  The same input and seed give the same result."""
+    inliers 0.  The same input and seed give the same result.
+    device=True: the same draw of triples, checked, fitted and scored on the GPU (mf_pose_ransac_dev, on the fp32 values of src and dst).
+    The edge rule is the same; a triple's pose is the closed form of the header, not align_horn's, so counts and winner may differ from the
+    host's.  T is align_horn on the device's inlier mask when that has at least three members, the device's pose otherwise; "tested" counts
+    the triples of status 0."""
     src, dst = np.asarray(src, np.float64).reshape(-1, 3), np.asarray(dst, np.float64).reshape(-1, 3)
     m = len(src)
     out = {"T": None, "inliers": 0, "inlier_mask": np.zeros(m, bool), "hypotheses": int(hypotheses), "tested": 0}
@@ -830,6 +858,17 @@ def ransac_correspondences(src, dst, inlier_distance: float, hypotheses: int = 2
         return out
     rng = np.random.default_rng(seed)
     tri = rng.integers(0, m, (int(hypotheses), 3))
+    if device:
+        status, _, best, mask, pose = _pose_ransac_device(src.astype(np.float32), dst.astype(np.float32), tri, inlier_distance, edge_tolerance)
+        out["tested"] = int((status == 0).sum())
+        if best[0] < 0:
+            return out
+        T = np.eye(4)
+        T[:3] = pose
+        if mask.sum() >= 3:
+            T = align_horn(src[mask], dst[mask])
+        out.update({"T": T, "inliers": int(best[1]), "inlier_mask": mask})
+        return out
     keep = (tri[:, 0] != tri[:, 1]) & (tri[:, 0] != tri[:, 2]) & (tri[:, 1] != tri[:, 2])
     for a, b in ((0, 1), (0, 2), (1, 2)):
         ls = np.linalg.norm(src[tri[:, a]] - src[tri[:, b]], axis=1)
@@ -870,7 +909,7 @@ def _towards_centroid(points, normals):
 
 def register_global(est, ref, voxel: float, est_normals=None, ref_normals=None, seed: int = 0, hypotheses: int = 20000,
                     inlier_distance=None, refine: bool = True, min_mutual: int = MIN_MUTUAL, max_iterations: int = 50, method: str = "plane",
-                    schedule=None) -> dict:
+                    schedule=None, ransac: str = "host") -> dict:
     """Rigid registration of `est` onto `ref` (numpy (n, 3) float32) WITHOUT a start: a coarse pose from matched FPFH descriptors, then
     register().
       1. both clouds are subsampled to one point per voxel (voxel_subsample);
@@ -880,7 +919,8 @@ def register_global(est, ref, voxel: float, est_normals=None, ref_normals=None, 
       3. FPFH of the key points at radius 5 voxel (fpfh);
       4. descriptors are matched both ways (match_features); the mutual matches are the correspondences, or, with fewer than min_mutual
          of them, every est -> ref match;
-      5. ransac_correspondences(seed, hypotheses, inlier_distance -- default 1.5 voxel);
+      5. ransac_correspondences(seed, hypotheses, inlier_distance -- default 1.5 voxel); ransac="device" runs its search on the GPU
+         (device=True: mf_pose_ransac_dev), "host" in numpy;
       6. refine: register() on the FULL clouds from that pose, radii halving from inlier_distance down to voxel / 2, or `schedule`
          (point-to-plane on ref_normals, given or estimated; method "point": point-to-point).
     Returns register()'s dictionary -- with refine=False: T = the coarse pose, iterations 0, converged False, reason "not refined" --
@@ -893,6 +933,8 @@ def register_global(est, ref, voxel: float, est_normals=None, ref_normals=None, 
     inlier_distance = 1.5 * voxel if inlier_distance is None else float(inlier_distance)
     if not (math.isfinite(inlier_distance) and inlier_distance > 0):
         raise ValueError("inlier_distance must be finite and > 0")
+    if ransac not in ("host", "device"):
+        raise ValueError('ransac must be "host" or "device"')
     clouds = []
     for pts, nrm in ((est, est_normals), (ref, ref_normals)):
         pts = np.ascontiguousarray(np.asarray(pts, np.float32)[:, :3])
@@ -911,7 +953,7 @@ def register_global(est, ref, voxel: float, est_normals=None, ref_normals=None, 
     hit = np.flatnonzero(e2r >= 0)
     mutual = hit[r2e[e2r[hit]] == hit]
     use = mutual if len(mutual) >= min_mutual else hit
-    rs = ransac_correspondences(ke[use], kr[e2r[use]], inlier_distance, hypotheses, seed)
+    rs = ransac_correspondences(ke[use], kr[e2r[use]], inlier_distance, hypotheses, seed, device=ransac == "device")
     coarse = {"T": rs["T"], "correspondences": int(len(use)), "mutual": int(len(mutual)), "inliers": rs["inliers"], "hypotheses": rs["hypotheses"],
               "tested": rs["tested"], "key_points": [int(len(ke)), int(len(kr))]}
     if rs["T"] is None:

@@ -32,6 +32,12 @@ class ModelInfo(C.Structure):
                 ("is_static", C.c_int32), ("age", C.c_uint32)]
 
 
+class InactiveInfo(C.Structure):
+    """mf_inactive_info_t"""
+    _fields_ = [("id", C.c_int32), ("class_id", C.c_int32), ("surfels", C.c_uint32), ("age", C.c_uint32), ("confidence_threshold", C.c_float),
+                ("tick", C.c_int32), ("pose", C.c_float * 16)]
+
+
 class Config(C.Structure):
     """mf_config (include/maskfusion_amd.h)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
@@ -161,6 +167,13 @@ SYMBOLS = {
     "mf_import_segmentation_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mf_spawn_object_model": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "mf_drop_model": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mf_inactive_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mf_inactive_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mf_inactive_map_dev": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]),
+    "mf_inactive_download_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "mf_inactive_discard": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mf_model_set_age": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_float]),
+    "mf_reactivate_model": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "mf_model_update_static_pose": (C.c_int, [C.c_void_p, C.c_int32]),
     "mf_update_object_params": (C.c_int, [C.c_void_p]),
     "mf_make_nonstatic": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -193,6 +206,8 @@ SYMBOLS = {
     "mf_cloud_fpfh_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                     C.c_void_p]),
     "mf_feature_match_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mf_pose_ransac_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_cloud_mesh_build_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_float,
                                           C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]),
     "mf_cloud_mesh_emit_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

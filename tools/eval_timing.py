@@ -13,12 +13,16 @@ sampled from it and jittered by N(0, 5 mm) per axis, radius 5 cm.
   global       mf_cloud_fpfh_dev on --keys points of the map with the map's normals at --fpfh-radius, and mf_feature_match_dev of those
                descriptors against the descriptors of as many other points of the map (33 values each): the two device calls of
                eval.register_global at 50 k x 50 k key points, each as the median of 5 calls after 1 warm-up
+  ransac       mf_pose_ransac_dev on --triples triples x --correspondences correspondences (40 % under one rigid motion with 1 mm of noise, the
+               others uniform in a 2 m cube; inlier distance 1 cm, edge tolerance 0.1): the median of 5 calls after 1 warm-up, next to the wall
+               time of eval.ransac_correspondences on the host (numpy) for the same input and seed; --ransac-only runs this line alone
 
 Device times are medians of 10 calls after 2 warm-up calls, between HIP events on the call's stream.  One CPU line for contrast:
 scipy.spatial.cKDTree with 16 workers on the same clouds (tree build + query), if scipy is present.
 
     python tools/eval_timing.py [--targets 26.9e6] [--queries 5e6] [--radius 0.05] [--no-cpu] [--no-live] [--no-icp] [--no-normals]
-                                [--no-global] [--keys 50000] [--fpfh-radius 0.25]
+                                [--no-global] [--keys 50000] [--fpfh-radius 0.25] [--no-ransac] [--ransac-only] [--triples 20000]
+                                [--correspondences 50000]
 """
 from __future__ import annotations
 
@@ -48,6 +52,44 @@ def _median_ms(fn, stream, reps=10, warm=2):
     return float(np.median(out)), float(min(out)), float(max(out))
 
 
+def _ransac_line(a, L):
+    import torch
+    from maskfusion_amd import eval as ev
+    from maskfusion_amd import synth
+    m, h = int(a.correspondences), int(a.triples)
+    rng = np.random.default_rng(0)
+    T = synth.make_pose(synth.rot_xyz(*np.deg2rad([40.0, -70.0, 110.0])), [2.0, -1.0, 2.0])
+    src = rng.uniform(-1, 1, (m, 3))
+    dst = rng.uniform(-1, 1, (m, 3))
+    planted = rng.permutation(m)[:int(0.4 * m)]
+    dst[planted] = src[planted] @ T[:3, :3].T + T[:3, 3] + rng.normal(scale=1e-3, size=(len(planted), 3))
+    src, dst = src.astype(np.float32), dst.astype(np.float32)
+    tri = np.random.default_rng(0).integers(0, m, (h, 3)).astype(np.int32)          # the draw of ransac_correspondences(seed=0)
+    s = torch.cuda.current_stream()
+    ds, dd, dtri = torch.from_numpy(src).cuda(), torch.from_numpy(dst).cuda(), torch.from_numpy(tri).cuda()
+    counts = torch.empty(h, dtype=torch.int32, device="cuda")
+    status = torch.empty(h, dtype=torch.uint8, device="cuda")
+    best = torch.empty(2, dtype=torch.int32, device="cuda")
+    mask = torch.empty(m, dtype=torch.uint8, device="cuda")
+    pose = torch.empty(12, dtype=torch.float64, device="cuda")
+
+    def call():
+        rc = L.mf_pose_ransac_dev(ds.data_ptr(), dd.data_ptr(), 3, m, dtri.data_ptr(), h, 0.01, 0.1, counts.data_ptr(), status.data_ptr(), best.data_ptr(),
+                                  mask.data_ptr(), pose.data_ptr(), s.cuda_stream)
+        assert rc == 0, rc
+    td = _median_ms(call, s, reps=5, warm=1)
+    tested = int((status == 0).sum().item())
+    t0 = time.perf_counter()
+    dev = ev.ransac_correspondences(src, dst, 0.01, hypotheses=h, seed=0, device=True)
+    t_dev = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    host = ev.ransac_correspondences(src, dst, 0.01, hypotheses=h, seed=0)
+    t_host = time.perf_counter() - t0
+    print(f"ransac     : median {td[0]:.2f} ms (min {td[1]:.2f}, max {td[2]:.2f}) for {h} triples x {m} correspondences, {tested} tested: "
+          f"{tested * m / td[0] / 1e6:.1f} G scores/s; winner {best.cpu().tolist()}; eval.ransac_correspondences device {1e3 * t_dev:.0f} ms wall "
+          f"({dev['inliers']} inliers), host {1e3 * t_host:.0f} ms wall ({host['inliers']} inliers, {host['tested']} tested)")
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--targets", type=float, default=26.9e6)
@@ -60,11 +102,18 @@ def main(argv=None) -> int:
     ap.add_argument("--no-global", action="store_true")
     ap.add_argument("--keys", type=float, default=50e3)
     ap.add_argument("--fpfh-radius", type=float, default=0.25)
+    ap.add_argument("--no-ransac", action="store_true")
+    ap.add_argument("--ransac-only", action="store_true")
+    ap.add_argument("--triples", type=float, default=20e3)
+    ap.add_argument("--correspondences", type=float, default=50e3)
     a = ap.parse_args(argv)
     import torch
     from maskfusion_amd import stress, synth
     from maskfusion_amd.lib import load
     L = load()
+    if a.ransac_only:
+        _ransac_line(a, L)
+        return 0
     t0 = time.perf_counter()
     st = stress.stream()
     room = synth.dense_room_map(st.scene, int(a.targets), last_time=1.0, furniture_above=st.masked_objects)
@@ -185,6 +234,8 @@ def main(argv=None) -> int:
         print(f"match      : median {tm[0]:.2f} ms (min {tm[1]:.2f}, max {tm[2]:.2f}) for {nk} x {nk} descriptors of 33 values: "
               f"{nk * nk * 33 / tm[0] / 1e6:.1f} G terms/s; {int((midx >= 0).sum().item())} queries matched")
         del ws_f, desc, cnts
+    if not a.no_ransac:
+        _ransac_line(a, L)
     if not a.no_live:
         mf = stress.make_context()
         rgb, depth, mask = st.frame(0)
