@@ -202,6 +202,13 @@ public:
         chk(mf_download_map(ctx_, idx(), m.data->data(), m.numPoints, &n));
         return m;
     }
+    // No upstream twin (mf_model_merge_map): merges `count` records of downloadMap's layout, given in the frame that sourceToModel (column-major
+    // 4 x 4, or nullptr) maps into the model's, into this model's map.  Returns {averaged, confidence only, appended, dropped}
+    std::array<uint64_t, 4> mergeMap(const float* source12, uint32_t count, const float* sourceToModel, float radius, float minCos) {
+        std::array<uint64_t, 4> stats{};
+        chk(mf_model_merge_map(ctx_, idx(), source12, count, sourceToModel, radius, minCos, stats.data()));
+        return stats;
+    }
     std::vector<PoseLogItem> getPoseLog() const {  // Model.h:262
         uint32_t n = 0;
         chk(mf_get_pose_log(ctx_, idx(), nullptr, nullptr, 0, &n));

@@ -313,6 +313,47 @@ int mf_pose_ransac_dev(const float* d_src, const float* d_dst, int32_t stride, i
                        double inlier_distance, double edge_tolerance, uint32_t* d_counts /* [h] */, uint8_t* d_status /* [h] */,
                        int32_t* d_best /* [2]: index or -1, count */, uint8_t* d_inlier /* [m] or NULL */, double* d_pose /* [12] or NULL */,
                        void* stream);
+/* Map-to-map fusion, on the GPU (kernels: mf_merge.hip; DESIGN.md "Map merging"; the Python side: maskfusion_amd.merge): the surfels of a
+ * source map, moved by a rigid transform, are merged into a target map by the weighted rule of the frame fusion (Core/Shaders/update.vert:64-93)
+ * or appended to it.  No upstream twin: the reference fuses depth frames only.  d_target, d_source, d_out: DEVICE, 16-byte aligned, records of 12
+ * floats in mf_download_map's layout {x y z conf | colour, unused, initTime, lastTime | nx ny nz radius}; d_out overlaps neither input.  All
+ * arithmetic is fp32, rounded operation by operation in the order written (no contraction).
+ * 1. TRANSFORM.  source_to_target16 (HOST, column-major 4 x 4, or NULL: nothing is applied) maps a source's position as mf_cloud_nn_dev maps a
+ *    query, x' = ((T00 x + T01 y) + T02 z) + T03, and its normal by the same rows without the translation, n'x = (T00 nx + T01 ny) + T02 nz; the
+ *    normal is not renormalised.  Confidence, colour, the unused word, both stamps and the radius pass through.
+ * 2. ELIGIBILITY.  A source is DROPPED when a component of x' or n' is not finite, or when its confidence or its radius is not finite or is
+ *    <= 0: d_match = -2, counted, nowhere in the output.  A target with a position or a normal that is not finite is never a partner; it is
+ *    copied through unchanged.  Every other target is ELIGIBLE.
+ * 3. PARTNER.  With d = x' - p and d2 = dx*dx + dy*dy + dz*dz (mf_cloud_nn_dev's expression and order), the candidates of a source are the
+ *    eligible targets with d2 <= fl(radius * radius) AND (n'x qx + n'y qy) + n'z qz >= min_cos, q the target's normal.  The partner is the
+ *    candidate with the smallest d2, ties to the smallest target index: the nearest target that passes the normal test, not the nearest target
+ *    tested afterwards (a wall seen from both sides finds its own side).  d_match = its index, or -1 without a candidate.  Every source chooses
+ *    against the INPUT targets, as a frame's association is made against the index map before update.vert runs.
+ * 4. MERGE.  A target q receives the sources that chose it in ascending source index, each merged into the record the merge before it left.
+ *    With c = q.conf and a = s.conf:  if s.radius < 1.5f * q.radius:  position ((c * v_k) + (a * v_g)) / (c + a) per component;  colour
+ *    encode(((c * k) + (a * g)) / (c + a) per channel) of the two decoded colours (color_encoding.glsl: decode (float)(((int)colour >> 16, 8, 0)
+ *    & 255) / 255.0f, encode (float)(((int)roundf(r * 255.0f) << 8) + (int)roundf(g * 255.0f) << 8) + (int)roundf(b * 255.0f)), roundf half away
+ *    from zero; colours are expected in [0, 2^24));  {normal, radius} ((c * nr_k) + (a * nr_g)) / (c + a) per component, the normal then
+ *    multiplied by 1.0f / sqrtf((x*x + y*y) + z*z).  In both branches conf = c + a and lastTime = s.lastTime > q.lastTime ? s.lastTime :
+ *    q.lastTime; initTime and the unused word stay the target's.  (Which bit pattern a NaN has that this arithmetic PRODUCES, e.g. from an
+ *    infinite confidence, is the hardware's; a NaN that is only carried keeps its bits.)
+ * 5. OUTPUT.  d_out[0, n_target): the targets in their order, merged.  Behind them the unmatched eligible sources in ascending source index,
+ *    as transformed.  *n_out (HOST) = n_target + appended.  stats4 (HOST) = {merges that averaged, merges that added the confidence only,
+ *    appended, dropped}: the four add up to n_source.  d_match (DEVICE, [n_source], or NULL).  out_capacity < n_target + appended: MF_ENOMEM, *n_out
+ *    the count needed, d_out untouched.
+ * 6. MF_EINVAL as for mf_cloud_nn_dev -- a null pointer (n_out and stats4 included), more than 2^30 targets or sources, a radius <= 0 or not
+ *    finite, a transform that is not finite, a workspace smaller than mf_cloud_merge_workspace says or not 16-byte aligned, a finite coordinate
+ *    (eligible target, or eligible source after the transform) with |x / radius| >= 2^30 -- and for a min_cos that is not finite or outside
+ *    [-1, 1], records that are not 16-byte aligned and a negative out_capacity; d_out is untouched then.  n_source == 0 (the targets are
+ *    copied) and n_target == 0 (the eligible sources are appended) are valid.
+ * Targets are found over mf_cloud_nn_dev's grid with cell edge `radius`.  A target's sources are put in order by an insertion sort, so the
+ * time is quadratic in the length of ONE list -- the number of source surfels on one target surfel, a handful when two maps of similar
+ * density meet; any length is correct.  Only integer atomics are used and nothing in the output depends on their order: the same inputs give
+ * the same bytes on every call.  Enqueued on `stream`, which the call synchronises (once before d_out is written, once before it returns). */
+int mf_cloud_merge_workspace(int64_t n_target, int64_t n_source, uint64_t* bytes);
+int mf_cloud_merge_dev(const float* d_target /* [n_target][12] */, int64_t n_target, const float* d_source /* [n_source][12] */, int64_t n_source,
+                       const float* source_to_target16, float radius, float min_cos, float* d_out /* [out_capacity][12] */, int64_t out_capacity,
+                       int64_t* n_out, int32_t* d_match, uint64_t stats4[4], void* d_workspace, uint64_t workspace_bytes, void* stream);
 /* A triangle mesh of a cloud of oriented points (surfels), on the GPU (kernels: mf_mesh.hip; DESIGN.md "Surfel meshing"; the Python side:
  * maskfusion_amd.mesh): naive surface nets over a moving-least-squares signed distance to the points' tangent planes.  No table of cases.
  * INPUT.  n records of `stride` floats at d_points: x y z at offset 0, a normal at normal_offset (>= 3) and, with color_offset >= 3, three
@@ -863,6 +904,17 @@ int mf_model_set_age(mf_ctx* ctx, int32_t model, uint32_t age, float confidence_
  * The entry then leaves the list and the later entries move up.  The model's pose log starts anew; mf_export_poses writes the retired
  * segment(s) of an id and then the live one into the one poses-<id>.txt, which is time order. */
 int mf_reactivate_model(mf_ctx* ctx, int32_t k, const float* pose16);
+/* Merges `count` records (HOST, mf_download_map's layout) into the live map of `model`.  DEFINED as this sequence of public calls, whose bits
+ * it leaves:
+ *   1. mf_download_map of the model: the targets;
+ *   2. mf_cloud_merge_dev(targets, source12, source_to_model16 (HOST, column-major, or NULL), radius, min_cos) on mf_get_stream(ctx), into a
+ *      buffer of n_target + count records;
+ *   3. mf_model_upload_map of the merged records.
+ * The model keeps its pose, age, id, class and static flag.  stats4 as mf_cloud_merge_dev's (may be NULL).  A merged map larger than the
+ * model's surfel buffer fails as mf_model_upload_map fails (MF_EINVAL) and leaves the model as it was; stats4 is filled all the same.  The map
+ * makes a round trip through host memory: a tool's call, not a frame's. */
+int mf_model_merge_map(mf_ctx* ctx, int32_t model, const float* source12, uint32_t count, const float* source_to_model16, float radius,
+                       float min_cos, uint64_t stats4[4]);
 /* Model::updateStaticPose(globalPose) (Core/Model/Model.h:263) with this context's background pose */
 int mf_model_update_static_pose(mf_ctx* ctx, int32_t model);
 /* Model::setMaxDepth + the object confidence ramp of processFrame (Core/MaskFusion.cpp:335-339,369-374) for the local objects */

@@ -96,6 +96,21 @@ class Model:
         s = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12)
         self._o._chk(self._o._L.mf_model_upload_map(self._o._h, self._i, s.ctypes.data, len(s)))
 
+    def mergeMap(self, source, T=None, radius=None, min_cos=None) -> list:
+        """mf_model_merge_map: merges `source` ((n, 12) float32, downloadMap's layout) into this model's map on the GPU (DESIGN.md "Map
+        merging").  T: 4 x 4, source frame -> the model's; radius: the partner search's (None: maskfusion_amd.merge.default_radius of the
+        model's map); min_cos: the normal gate (None: merge.COS_HALF_RAD).  The model keeps its pose, age, id, class and static flag.
+        Returns [averaged, confidence only, appended, dropped]; a merged map beyond the model's buffer raises and leaves the model as it was."""
+        from . import merge as _merge
+        s = np.ascontiguousarray(source, np.float32).reshape(-1, 12)
+        radius = _merge.default_radius(self.downloadMap()) if radius is None else radius
+        T16 = None if T is None else np.ascontiguousarray(np.asarray(T, np.float32).T.reshape(16))
+        stats = (C.c_uint64 * 4)()
+        self._o._chk(self._o._L.mf_model_merge_map(self._o._h, self._i, s.ctypes.data if len(s) else None, len(s),
+                                                   T16.ctypes.data if T16 is not None else None, float(radius),
+                                                   float(_merge.COS_HALF_RAD if min_cos is None else min_cos), stats))
+        return [int(v) for v in stats]
+
     def makeNonStatic(self):
         self._o._chk(self._o._L.mf_make_nonstatic(self._o._h, self._i))
 
@@ -250,7 +265,7 @@ class MaskFusion:
                                            pose.ctypes.data if pose is not None else None, weightMultiplier,
                                            int(bootstrap)))
         if getattr(self, "_redetect", False):
-            self.redetectModels()
+            self.redetectModels(merge=getattr(self, "_redetect_merge", False))
         return False  # the reference always returns false (MaskFusion.cpp:606)
 
     def processFrameDevice(self, d_rgb: int, d_depth: int, d_mask: int = 0, timestamp: int = 0,
@@ -322,10 +337,11 @@ class MaskFusion:
     # -- inactive models and their re-detection (MaskFusion.h:311,398-399: inactiveModels, redetectModels; shipped empty upstream) --------
     REDETECT_MIN_AGE = 25                  # frames: the age at which the object confidence ramp min(4.5, age / 25) reaches 1 (MaskFusion.cpp:369-374)
 
-    def setEnableRedetection(self, on: bool):
-        """MaskFusion::enableRedetection (default off): processFrame calls redetectModels() after every frame.  The maps to recognise come
-        from setParam("keepInactiveModels", 1), which this does not set."""
+    def setEnableRedetection(self, on: bool, merge: bool = False):
+        """MaskFusion::enableRedetection (default off): processFrame calls redetectModels(merge=merge) after every frame.  The maps to
+        recognise come from setParam("keepInactiveModels", 1), which this does not set."""
         self._redetect = bool(on)
+        self._redetect_merge = bool(merge)
 
     def inactiveModels(self) -> list:
         """the kept maps of dropped models, in the order of the drops: one InactiveInfo (id, class_id, surfels, age, confidence_threshold,
@@ -356,11 +372,14 @@ class MaskFusion:
     def discardInactive(self, k: int):
         self._chk(self._L.mf_inactive_discard(self._h, k))
 
-    def redetectModels(self, min_age: int | None = None, **match) -> list:
+    def redetectModels(self, min_age: int | None = None, merge: bool = False, **match) -> list:
         """MaskFusion::redetectModels.  For every object model whose age is exactly `min_age` (REDETECT_MIN_AGE by default: a new model is
         looked at once, when its map has had that many frames to grow) and every inactive model of the same class, in list order,
         maskfusion_amd.redetect.match_model(new map, archived map, **match).  On the first acceptance the archived model is reactivated in the
         new one's place and the new one is dropped without being kept.  Returns the merged pairs [(new id, old id), ...].
+        merge=True: the new model's map is not lost with it but merged into the reactivated map (Model.mergeMap with match_model's T, new ->
+        old, radius voxel / 2 -- the acceptance test's -- and the default normal gate): what the camera saw of the object during its second
+        visit stays.  The default drops it.
 
         The pose.  A model's pose P (Model.getPose / overridePose) takes camera coordinates to the model's: a surfel n of the map is seen at
         P^-1 n.  match_model's T takes the new map onto the old one, o = T n.  The returning object must stay where the camera sees the new
@@ -393,6 +412,8 @@ class MaskFusion:
                     finally:
                         self.setParam("keepInactiveModels", keep)
                     self.reactivateModel(k, pose)
+                    if merge:                                       # (the reactivated model stands at the end of the list)
+                        Model(self, len(self.modelIDs()) - 1).mergeMap(new_map, T=r["T"], radius=r["voxel"] / 2.0)
                     merged.append((int(info.id), int(old.id)))
                     done = True
                     break

@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmaskfusion_amd.so")
-SOURCES = ["mf_preproc.hip", "mf_odometry.hip", "mf_model_pyramid.hip", "mf_rgbd.hip", "mf_surfel.hip", "mf_splat.hip", "mf_segment.hip", "mf_labels.hip", "mf_labels_gpu.hip", "mf_render.hip", "mf_eval.hip", "mf_eval_image.hip", "mf_eval_visibility.hip", "mf_mesh.hip", "mf_eval_trimesh.hip", "mf_trimesh_ray.hip", "mf_register.hip", "mf_session.hip", "mf_context.hip"]
+SOURCES = ["mf_preproc.hip", "mf_odometry.hip", "mf_model_pyramid.hip", "mf_rgbd.hip", "mf_surfel.hip", "mf_splat.hip", "mf_segment.hip", "mf_labels.hip", "mf_labels_gpu.hip", "mf_render.hip", "mf_eval.hip", "mf_eval_image.hip", "mf_eval_visibility.hip", "mf_mesh.hip", "mf_eval_trimesh.hip", "mf_trimesh_ray.hip", "mf_register.hip", "mf_merge.hip", "mf_session.hip", "mf_context.hip"]
 HEADERS = ["mf_internal.h", "mf_device.h", "mf_labels.h", os.path.join("..", "..", "include", "maskfusion_amd.h"), "mf_rgbd_device.h", "mf_walk.h", "mf_cloud_grid.h", "mf_trimesh.h",
            "mf_bilateral_device.h", "mf_frame_pyramid_device.h", "mf_model_pyramid_device.h", "mf_gn_device.h",
            "mf_frame.inl", "mf_model_api.inl", "mf_params.inl", "mf_ktest.inl", "mf_render.inl", "mf_eval.inl", "mf_session.inl"]   # (the .inl files are parts of mf_context.hip)
@@ -24,10 +24,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", 
 # mf_eval_trimesh: the header's operation-by-operation fp64 point-to-triangle distance, which the tests compare bit for bit
 # mf_trimesh_ray: the header's operation-by-operation fp64 ray-triangle test, compared bit for bit as well
 # mf_register: the header's operation-by-operation fp64 fit and score of a triple, compared bit for bit too
+# mf_merge: the header's operation-by-operation fp32 merge rule and the grid's rounding argument, compared bit for bit as well
 # mf_session: self-contained like them (integer digests and copies: no floating-point arithmetic to contract)
 FILE_FLAGS = {"mf_odometry.hip": ["-fno-slp-vectorize"], "mf_model_pyramid.hip": ["-fno-slp-vectorize"], "mf_eval.hip": ["-ffp-contract=off"], "mf_eval_image.hip": ["-ffp-contract=off"],
               "mf_eval_visibility.hip": ["-ffp-contract=off"], "mf_mesh.hip": ["-ffp-contract=off"], "mf_eval_trimesh.hip": ["-ffp-contract=off"],
-              "mf_trimesh_ray.hip": ["-ffp-contract=off"], "mf_register.hip": ["-ffp-contract=off"], "mf_session.hip": ["-ffp-contract=off"]}
+              "mf_trimesh_ray.hip": ["-ffp-contract=off"], "mf_register.hip": ["-ffp-contract=off"], "mf_merge.hip": ["-ffp-contract=off"],
+              "mf_session.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -27,6 +27,8 @@ images of the two halves are those of one uninterrupted run.  (The core paramete
 And -redetect: dropped object models are kept ("keepInactiveModels") and every new object model is compared, once, with the kept ones of its class
 (MaskFusion.setEnableRedetection, maskfusion_amd.redetect; upstream's enableRedetection, whose matching the release ships empty): a returning
 object gets its id and its map back, so -em writes one cloud-<id>.ply for it and -ep its pose log under that id, both segments.
+-redetectmerge implies -redetect and merges the new model's map into the reactivated one on the GPU (maskfusion_amd.merge) instead of dropping
+it: what the camera saw during the object's second visit is kept.
 """
 from __future__ import annotations
 
@@ -41,7 +43,7 @@ _VALUE_FLAGS = {"-l", "-dir", "-depthdir", "-maskdir", "-colorprefix", "-depthpr
                 "-ic", "-a", "-frameQ", "-method", "-p", "-segMinNew", "-segMaxNew", "-thNew", "-gpu", "-name", "-k", "-crfRGB", "-crfDepth",
                 "-crfPos", "-crfAppearance", "-crfSmooth", "-emesh", "-savestate", "-loadstate"}
 _BOOL_FLAGS = {"-static", "-run", "-q", "-ep", "-em", "-es", "-ev", "-el", "-en", "-fo", "-nso", "-f", "-tum3", "-v2", "-icl", "-rl",
-               "-fs", "-r", "-ftf", "-sc", "-keep", "-o", "-v1", "-rgbonly", "-evalviews", "-redetect"}
+               "-fs", "-r", "-ftf", "-sc", "-keep", "-o", "-v1", "-rgbonly", "-evalviews", "-redetect", "-redetectmerge"}
 
 
 def parse(argv):
@@ -191,9 +193,9 @@ def main(argv=None):
         mf = MaskFusion.loadSession(flags["-loadstate"], device=st["device"] if "-gpu" in flags else None)
     else:
         mf = make_context(st)
-    if "-redetect" in flags:      # dropped object models are kept, and a new model that turns out to be one of them gets its id and map back
+    if "-redetect" in flags or "-redetectmerge" in flags:      # dropped object models are kept, and a new model that turns out to be one of them gets its id and map back
         mf.setParam("keepInactiveModels", 1)
-        mf.setEnableRedetection(True)
+        mf.setEnableRedetection(True, merge="-redetectmerge" in flags)
     export_dir = flags.get("-exportdir", "")
     if export_dir and not export_dir.endswith(os.sep):
         export_dir += os.sep

@@ -604,3 +604,44 @@ extern "C" int mf_reactivate_model(mf_ctx* c, int32_t k, const float* pose16) {
     if (rc != MF_OK) return rc;
     return mf_inactive_discard(c, k);
 }
+// DEFINED as the three public calls below, in this order (include/maskfusion_amd.h): the bits it leaves are theirs
+extern "C" int mf_model_merge_map(mf_ctx* c, int32_t model, const float* source12, uint32_t count, const float* source_to_model16, float radius,
+                                  float min_cos, uint64_t stats4[4]) {
+    settle(c);
+    ModelState* m = model_at(c, model);
+    if (!m || (!source12 && count)) return MF_EINVAL;
+    uint32_t nt = 0;
+    int rc = mf_get_surfel_count(c, model, &nt);
+    if (rc != MF_OK) return rc;
+    std::vector<float> rec((size_t)std::max<uint32_t>(nt, 1) * 12);
+    rc = mf_download_map(c, model, rec.data(), nt, &nt);
+    if (rc != MF_OK) return rc;
+    const uint64_t cap = (uint64_t)nt + count;
+    uint64_t ws_bytes = 0;
+    if (mf_cloud_merge_workspace(nt, count, &ws_bytes) != MF_OK) return MF_EINVAL;
+    const uint64_t t_bytes = ((uint64_t)nt * 48 + 255) & ~255ull, s_bytes = ((uint64_t)count * 48 + 255) & ~255ull, o_bytes = (cap * 48 + 255) & ~255ull;
+    char* d = nullptr;
+    if (hipMalloc(&d, t_bytes + s_bytes + o_bytes + ws_bytes + 256) != hipSuccess) { c->err = "mf_model_merge_map: hipMalloc failed"; return MF_ENOMEM; }
+    float* d_t = (float*)d; float* d_s = (float*)(d + t_bytes); float* d_o = (float*)(d + t_bytes + s_bytes);
+    int64_t n_out = 0;
+    uint64_t st[4] = {0, 0, 0, 0};
+    rc = MF_OK;
+    if ((nt && hipMemcpy(d_t, rec.data(), (size_t)nt * 48, hipMemcpyHostToDevice) != hipSuccess) ||
+        (count && hipMemcpy(d_s, source12, (size_t)count * 48, hipMemcpyHostToDevice) != hipSuccess)) {
+        c->err = "mf_model_merge_map: hipMemcpy failed"; rc = MF_EHIP;
+    }
+    if (rc == MF_OK) {
+        rc = mf_cloud_merge_dev(d_t, nt, d_s, count, source_to_model16, radius, min_cos, d_o, (int64_t)cap, &n_out, nullptr, st,
+                                d + t_bytes + s_bytes + o_bytes, ws_bytes, c->stream);
+        if (rc != MF_OK) { const char* why = cloud_last_error(); c->err = why ? why : "mf_cloud_merge_dev failed"; }
+    }
+    if (rc == MF_OK) {
+        rec.resize((size_t)std::max<int64_t>(n_out, 1) * 12);
+        if (n_out && hipMemcpy(rec.data(), d_o, (size_t)n_out * 48, hipMemcpyDeviceToHost) != hipSuccess) { c->err = "mf_model_merge_map: hipMemcpy failed"; rc = MF_EHIP; }
+    }
+    (void)hipFree(d);
+    if (rc != MF_OK) return rc;
+    if (stats4) memcpy(stats4, st, sizeof(st));
+    if (n_out > (int64_t)m->cap) { c->err = "mf_model_merge_map: the merged map does not fit the model's surfel buffer"; return MF_EINVAL; }
+    return mf_model_upload_map(c, model, rec.data(), (uint32_t)n_out);
+}
