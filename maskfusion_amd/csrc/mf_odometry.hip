@@ -363,6 +363,12 @@ __global__ __launch_bounds__(kT) void k_icp_iter(const IcpKArgs a) {
     __shared__ GNState s_st;      // the Gauss-Newton state: loaded (or seeded), updated in place by gn_finish_wg, stored by workgroup 0
 
     const int tid = threadIdx.x;
+    // Every argument the launch reads is requested HERE, as one batch of scalar loads behind one wait.  Left to itself the compiler loads an
+    // argument in the block that first uses it: st_in in front of the state's load, the maps and gridDim behind it, the partials' in front of the
+    // reduce -- five dependent round trips to the argument buffer, each cold, in a launch that the next one waits for ("Round 14").
+    asm volatile("" :: "s"(a.vc), "s"(a.nc), "s"(a.vp), "s"(a.np), "s"(a.W), "s"(a.H), "s"(a.k.fx), "s"(a.k.fy), "s"(a.k.cx), "s"(a.k.cy),
+                 "s"(a.dist2Max), "s"(a.sine2Min), "s"(a.partials_in), "s"(a.nb_in), "s"(a.partials_out), "s"(a.st_in), "s"(a.st_out), "s"(a.log_out),
+                 "s"(a.trace), "s"(a.it), "s"(a.prof_out), "s"(a.pose_in), "s"(a.so3_in), "s"(gridDim.x));
     if (a.pose_in == nullptr) gn_stage(&s_st, a.st_in);
     else if (tid == 0) gn_seed(*a.pose_in, a.so3_in, s_st);
     const bool prof = a.prof_out != nullptr && blockIdx.x == 0 && tid == 0;
