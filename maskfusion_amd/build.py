@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmaskfusion_amd.so")
 SOURCES = ["mf_preproc.hip", "mf_odometry.hip", "mf_model_pyramid.hip", "mf_rgbd.hip", "mf_surfel.hip", "mf_splat.hip", "mf_segment.hip", "mf_labels.hip", "mf_labels_gpu.hip", "mf_render.hip", "mf_eval.hip", "mf_eval_image.hip", "mf_eval_visibility.hip", "mf_mesh.hip", "mf_eval_trimesh.hip", "mf_trimesh_ray.hip", "mf_register.hip", "mf_merge.hip", "mf_session.hip", "mf_context.hip"]
-HEADERS = ["mf_internal.h", "mf_device.h", "mf_labels.h", os.path.join("..", "..", "include", "maskfusion_amd.h"), "mf_rgbd_device.h", "mf_walk.h", "mf_cloud_grid.h", "mf_trimesh.h",
+HEADERS = ["mf_internal.h", "mf_device.h", "mf_labels.h", os.path.join("..", "..", "include", "maskfusion_amd.h"), "mf_rgbd_device.h", "mf_walk.h", "mf_sprite_device.h", "mf_cloud_grid.h", "mf_trimesh.h",
            "mf_bilateral_device.h", "mf_frame_pyramid_device.h", "mf_model_pyramid_device.h", "mf_gn_device.h",
            "mf_frame.inl", "mf_model_api.inl", "mf_params.inl", "mf_ktest.inl", "mf_render.inl", "mf_eval.inl", "mf_session.inl"]   # (the .inl files are parts of mf_context.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

@@ -353,6 +353,12 @@ static PassModel pass_model(mf_ctx* c, ModelState& m, const SurfelScratch& scr, 
     a.host_frame = m.h_frame; a.log_slot = nullptr; a.global_payload = 0;
     return a;
 }
+// The PassFrame of a sprite pass (prediction, GlobalProjection) of a model drawn on its own: of the frame's planes these read the colour image only
+static PassFrame sprite_frame(const mf_ctx* c) { return pass_frame(c, c->cur_rgb, c->cur_depth, nullptr, nullptr, false, c->stream); }
+// The context's scratch of the tiled sprite passes and its tuning (mf_internal.h: TileLists)
+static TileLists tile_lists(const mf_ctx* c) {
+    return TileLists{c->d_tile_count, c->d_tile_entries, c->tile_entries_cap, c->d_splat_rec0, c->d_splat_rec1, c->d_splat_bbox, c->sw.splat_tune};
+}
 // A frame without a mask (mf_process_frame of a single-model context: every byte of c->d_zero_mask is 0) cannot disagree with the background, id 0:
 // with 16-byte taps the resolve pass then leaves the planes depthT / maskT alone and the clean pass reads neither ("maskFreeClean")
 static bool mask_free(const mf_ctx* c, const ModelState& m, const uint8_t* mask, bool tap16) {
@@ -468,23 +474,22 @@ static void enqueue_predict(mf_ctx* c, ModelState& m, const FrameAdvance* advanc
                             const SplatPyramidJob* pyramid = nullptr) {
     PassTimer timer(c, m.id == 0 ? MF_PASS_BG_PREDICT : -1);
     m.pred_gray_valid = photometric_on(c);
+    // what is drawn and where to, once, for whichever form runs: the view and the outputs the object batch builds (mf_internal.h), plus the
+    // fill-in image a model drawn on its own writes
+    const PassFrame f = sprite_frame(c);
+    const PassModel pm = pass_model(c, m, c->scr, 1.0f, c->cfg.depth_cutoff);
+    const SpriteView view = predict_view(f, pm);
+    PredOut out = pred_out(f, pm);
+    out.fillGray = photometric_on(c) ? m.d_fillGray : nullptr; out.fillPassthrough = c->sw.ftf_rgb ? 1 : 0;
     if (c->sw.splat_tiles && !(c->sw.object_scatter_splat && m.id != 0)) {
-        const bool gray = photometric_on(c);
         VisList vl;
         const VisList* vis = ensure_vis(c, m, vl);
-        if (launch_splat_tiled(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, c->cfg.max_depth_processed, m.confThr,
-                               c->cfg.time_delta, c->d_tile_count, c->d_tile_entries, c->tile_entries_cap, c->d_splat_rec0, c->d_splat_rec1,
-                               c->d_splat_bbox, m.d_predV, m.d_predN, m.d_predImage, m.d_predTime, c->cur_rgb,
-                               gray ? m.d_predGray : nullptr, gray ? m.d_fillGray : nullptr, c->stream, advance, c->sw.ftf_rgb ? 1 : 0,
-                               (c->sw.splat_prof_on && m.id == 0) ? c->d_splat_prof : nullptr, c->sw.splat_tune, vis, filter, pyramid) == 0)
-            return;
+        const SplatRiders riders{advance, filter, pyramid, (c->sw.splat_prof_on && m.id == 0) ? c->d_splat_prof : nullptr};
+        if (launch_splat_tiled(view, tile_lists(c), out, riders, vis, c->stream) == 0) return;
     }
     if (filter) launch_bilateral(filter->depth, filter->out, c->W, c->H, c->stream);   // (not reached: a deferred prediction is a tiled one)
-    launch_splat_scatter(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, c->cfg.max_depth_processed, m.confThr,
-                         c->cfg.time_delta, c->scr.keys, c->stream, surfel_blocks(c, m));
-    const bool gray = photometric_on(c) ;
-    launch_splat_resolve(m.surf[m.cur], m.d_pose, c->scr.keys, c->W, c->H, c->K, m.d_predV, m.d_predN, m.d_predImage, m.d_predTime,
-                         m.d_frame, c->cur_rgb, gray ? m.d_predGray : nullptr, gray ? m.d_fillGray : nullptr, c->stream, c->sw.ftf_rgb ? 1 : 0);
+    launch_splat_scatter(view, c->scr.keys, c->stream, surfel_blocks(c, m));
+    launch_splat_resolve(view, c->scr.keys, out, c->stream);
     if (advance) launch_frame_advance(m.d_frame, c->W, c->H, advance->host_mirror, m.d_pose, advance->bg_pose, advance->log_slot, c->stream);
 }
 
@@ -524,7 +529,7 @@ static int make_obj_batch(mf_ctx* c, const std::vector<ModelState*>& ms, const s
         if (!m.scr.keys) { int rc = ensure_obj_scratch(c, m); if (rc != MF_OK) return rc; }   // first batched pass of a model created at spawn time
         h[i] = pass_model(c, m, m.scr, weightMultiplier, c->cfg.depth_cutoff);
         h[i].log_slot = log_slots ? (*log_slots)[i] : nullptr;
-        h[i].global_payload = ((unsigned)orders[i] << 8) | ((unsigned)m.id & 255u);
+        h[i].global_payload = global_payload(orders[i], m.id);
         blocks = std::max(blocks, surfel_blocks(c, m));
         if ((long)*m.h_count >= (long)c->sw.in_place_elements) b.denseSprites = 1;
     }
@@ -685,18 +690,15 @@ static int download_pose_log(mf_ctx* c, ModelState& m, std::vector<int64_t>& ts,
 // through the tile lists (its ~10^5..10^6 sprites cover millions of pixels: one memory-side atomic each in the scatter form);
 // object models (a few thousand sprites) keep the scatter form, which costs them one short launch.  Both write the same keys.
 static void enqueue_global_projection(mf_ctx* c, ModelState& m, int order) {
-    const mf_config& g = c->cfg;
     PassTimer timer(c, m.id == 0 ? MF_PASS_BG_GLOBAL : -1);
+    const SpriteView view = global_view(sprite_frame(c), pass_model(c, m, c->scr, 1.0f, c->cfg.depth_cutoff));
+    const unsigned payload = global_payload(order, m.id);
     if (m.id == 0 && c->sw.splat_tiles && c->sw.global_tiles) {
         VisList vl;
         const VisList* vis = ensure_vis(c, m, vl);
-        if (launch_global_tiled(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, g.depth_cutoff, 12.0f, g.time_delta, order, m.id, c->d_tile_count,
-                                c->d_tile_entries, c->tile_entries_cap, c->d_splat_rec0, c->d_splat_rec1, c->d_splat_bbox, c->scr.keys, c->stream, c->sw.splat_tune,
-                                vis) == 0)
-            return;
+        if (launch_global_tiled(view, tile_lists(c), payload, c->scr.keys, vis, c->stream) == 0) return;
     }
-    launch_global_scatter(m.surf[m.cur], m.d_frame, m.d_pose, c->W, c->H, c->K, g.depth_cutoff, 12.0f, g.time_delta, order, m.id, c->scr.keys,
-                          c->stream, surfel_blocks(c, m));
+    launch_global_scatter(view, payload, c->scr.keys, c->stream, surfel_blocks(c, m));
 }
 
 // spawnObjectModel (Core/MaskFusion.cpp:671-684): pose = I, makeStatic(globalPose); moveNewModelToList

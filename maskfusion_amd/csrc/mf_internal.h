@@ -316,7 +316,7 @@ struct PassModel {
                                                            // sequence number (append_mirror() below); nullptr: none
     float4* predV; float4* predN; uchar4* predImage; uint16_t* predTime; uint8_t* predGray;
     FrameDev* host_frame; float* log_slot;
-    unsigned global_payload;           // GlobalProjection: order << 8 | id
+    unsigned global_payload;           // GlobalProjection: global_payload(position in the model list, id)
 };
 // The surfel passes of ALL object models of a frame, one launch per pass (grid.z = model).  An object model holds a few thousand surfels: each of
 // its ~11 per-frame launches is pure launch latency (~85 us per object and frame in round 2's profile).  The batched kernels are the single-model
@@ -480,18 +480,43 @@ void launch_run_offsets(Surfels s, const FrameDev* frame, int* offs, int* total,
 // generic ordered compaction of [n_dev] records (3 x float4 each, record-major) -> surfels, sets frame->count
 void launch_compact_records(const float4* rec, const uint8_t* flags, int n, Surfels dst, FrameDev* frame,
                             int* block_counts, int* host_count_mirror, hipStream_t s);
-void launch_splat_scatter(Surfels src, const FrameDev* frame, const PoseDev* pose, int W, int H, Intr k,
-                          float maxDepth, float confThreshold, int timeDelta, unsigned long long* keys,
-                          hipStream_t s, int blocks = kSurfelGridBlocks);
-void launch_splat_resolve(Surfels src, const PoseDev* pose, unsigned long long* keys, int W, int H, Intr k,
-                          float4* predV, float4* predN, uchar4* predImage, uint16_t* predTime, FrameDev* frame,
-                          const uint8_t* rgb /*or null*/, uint8_t* predGray /*or null*/, uint8_t* fillGray /*or null*/,
-                          hipStream_t s, int fillPassthrough = 0 /* fill_rgb.frag's `passthrough` (frameToFrameRGB) */);
-// Tiled form of scatter + resolve (mf_splat.hip): bins surfels to 16x16 tiles, z-test in LDS, writes the maps directly.
-// tile_count must be zero on the first call (it is left zero).  Returns -1 if the image has too many tiles for the LDS
-// histograms (use the scatter form then).
+// ---- the sprite passes: the prediction (combinedPredict) and GlobalProjection, each as a scatter form (mf_surfel.hip, mf_segment.hip) and a tiled
+// form (mf_splat.hip); the arithmetic all four share is mf_sprite_device.h ----
+// What a sprite pass draws: a model's live buffer seen through its pose, with the gates of splat.vert / splat_models.vert
+struct SpriteView { Surfels src; FrameDev* frame; const PoseDev* pose; int W, H; Intr k; float maxDepth, confThreshold; int timeDelta; };
+constexpr float kGlobalConfThreshold = 12.0f;   // GlobalProjection::project draws with a fixed confidence threshold (GlobalProjection.cpp:43)
+__host__ __device__ inline SpriteView sprite_view(const PassFrame& f, const PassModel& m, float maxDepth, float confThreshold) {
+    SpriteView v;
+    v.src = m.a; v.frame = m.frame; v.pose = m.pose; v.W = f.W; v.H = f.H; v.k = f.k; v.maxDepth = maxDepth; v.confThreshold = confThreshold;
+    v.timeDelta = f.timeDelta;
+    return v;
+}
+__host__ __device__ inline SpriteView predict_view(const PassFrame& f, const PassModel& m) { return sprite_view(f, m, f.maxDepthProcessed, m.confThreshold); }
+__host__ __device__ inline SpriteView global_view(const PassFrame& f, const PassModel& m) { return sprite_view(f, m, f.globalMaxDepth, kGlobalConfThreshold); }
+// low word of GlobalProjection's keys: LESS on z, then the earlier model of the list (GL draw order); the resolve pass reads the id
+__host__ __device__ inline unsigned global_payload(int order, int id) { return ((unsigned)order << 8) | ((unsigned)id & 255u); }
+// What the prediction writes.  rgb / predGray / fillGray may be null: the intensity images of the NEXT tracking step's photometric term;
+// fillPassthrough: fill_rgb.frag's `passthrough` (frameToFrameRGB, Model.cpp:981) -- the fill-in image is the raw frame everywhere.
+// The builder is the object batch's; a model drawn on its own adds the fill-in image (mf_frame.inl: pred_out_one)
+struct PredOut { float4* predV; float4* predN; uchar4* predImage; uint16_t* predTime; const uint8_t* rgb; uint8_t* predGray; uint8_t* fillGray; int fillPassthrough; };
+__host__ __device__ inline PredOut pred_out(const PassFrame& f, const PassModel& m) {
+    return PredOut{m.predV, m.predN, m.predImage, m.predTime, f.rgb, m.predGray, nullptr, 0};
+}
+void launch_splat_scatter(const SpriteView& v, unsigned long long* keys, hipStream_t s, int blocks = kSurfelGridBlocks);
+void launch_splat_resolve(const SpriteView& v, unsigned long long* keys, const PredOut& out, hipStream_t s);   // leaves the key image empty; counts v.frame->cover
+void launch_global_scatter(const SpriteView& v, unsigned payload, unsigned long long* keys, hipStream_t s, int blocks = kSurfelGridBlocks);   // nothing if the model is not alive
+// Tiled form of scatter + resolve (mf_splat.hip): bins surfels to 16-pixel-wide tiles, z-test in LDS, writes the maps (the prediction) or merges
+// the tile's winners into the key image (GlobalProjection) directly.
 size_t splat_tiles_scratch_ints(int W, int H);
-struct SplatTuning { int sprite_lanes = 4, tile_threads = 512, tile_h = 24; };   // A/B knobs of the tile passes ("spriteLanes", "tileThreads"), owned by the context
+struct SplatTuning { int sprite_lanes = 4, tile_threads = 512, tile_h = 24; };   // A/B knobs of the tile passes ("spriteLanes", "tileThreads", "tileHeight"), owned by the context
+// The context's scratch of the tile passes (mf_frame.inl: tile_lists).  tile_count [tiles] must be zero on the first call (it is left zero);
+// entries [tiles][entries_cap / tiles]; rec0, rec1, bbox (8 B each) [surfels]: the sprite set-up the binning pass keeps for the tile pass
+struct TileLists { int* tile_count; int* entries; int entries_cap; float4* rec0; float4* rec1; void* bbox; SplatTuning tune; };
+// The launch shape of the tile passes for an image: tiles of 16 x tileH pixels, lanes per sprite, threads per tile workgroup.  fits: the LDS
+// histograms of the binning pass hold that many tiles (else the passes take their scatter form)
+struct TileShape { int tilesX, tilesY, tileH, lanes, threads; bool fits; };
+TileShape splat_tile_shape(int W, int H, SplatTuning tune);
+inline bool splat_tiled_applies(int W, int H, SplatTuning tune) { return splat_tile_shape(W, H, tune).fits; }   // the tiled launches would not return -1
 // The end-of-frame bookkeeping (k_frame_advance: pose log entry, fill-in decision for the next tracking step, tick++, host mirror) as
 // the epilogue of the tiled prediction: its last workgroup to finish runs it, one launch less per model and frame.
 struct FrameAdvance { FrameDev* host_mirror; const PoseDev* bg_pose; float* log_slot; };
@@ -499,18 +524,16 @@ struct FrameAdvance { FrameDev* host_mirror; const PoseDev* bg_pose; float* log_
 // k_bin_bilateral) or as a launch of its own between the binning pass and the tile pass.  The two read and write nothing in common.
 struct SplatFilterJob { const float* depth; float* out; int fused; };
 // pyramid (optional, "tilePyramid"): every tile workgroup also writes the three levels of the model-side pyramid of its tile (vm / nm: launch_model_pyramid's
-// planes; the model pose is `pose`), as launch_model_pyramid computes them WITHOUT fill-in -- a frame whose fill-in decision comes out 1 needs that launch
+// planes; the model pose is the view's), as launch_model_pyramid computes them WITHOUT fill-in -- a frame whose fill-in decision comes out 1 needs that launch
 // behind.  frame_depth != nullptr ("fusedTilePyramid"): launch_frame_pyramid(frame_depth, frame_vmap, frame_nmap, W, H, k, frame_cutoff)'s work rides in
 // the same launch, in workgroups of its own behind the tile workgroups.  The tile pass and that pyramid read and write nothing in common.
 struct SplatPyramidJob { float* vm[3]; float* nm[3]; const float* frame_depth; float* frame_vmap[3]; float* frame_nmap[3]; float frame_cutoff; };
-int launch_splat_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth, float confThreshold,
-                       int timeDelta, int* tile_count, int* entries /*[tiles][entries_cap / tiles]*/, int entries_cap,
-                       float4* rec0 /*[src.cap]*/, float4* rec1 /*[src.cap]*/, void* bbox /*[src.cap] x 8 B*/, float4* predV, float4* predN,
-                       uchar4* predImage, uint16_t* predTime, const uint8_t* rgb, uint8_t* predGray, uint8_t* fillGray, hipStream_t s,
-                       const FrameAdvance* advance = nullptr, int fillPassthrough = 0, unsigned long long* prof = nullptr /*[tiles][8] stamps*/,
-                       SplatTuning tune = SplatTuning(), const VisList* vis = nullptr, const SplatFilterJob* filter = nullptr,
-                       const SplatPyramidJob* pyramid = nullptr);
-bool splat_tiled_applies(int W, int H, SplatTuning tune);   // launch_splat_tiled would not return -1 for this image
+// What may ride on the tiled prediction, each optional (nullptr): the end-of-frame bookkeeping, the two jobs above, and "splatProfile"'s
+// [tiles][8] shader-clock stamps
+struct SplatRiders { const FrameAdvance* advance; const SplatFilterJob* filter; const SplatPyramidJob* pyramid; unsigned long long* prof; };
+// vis: nullptr = every surfel; else the runs launch_cull found possibly visible.  Both return -1 (nothing launched) if the image does not fit
+int launch_splat_tiled(const SpriteView& v, const TileLists& lists, const PredOut& out, const SplatRiders& riders, const VisList* vis, hipStream_t s);
+int launch_global_tiled(const SpriteView& v, const TileLists& lists, unsigned payload, unsigned long long* keys, const VisList* vis, hipStream_t s);
 // ---- the surfel passes of ALL object models of a frame, one launch per pass (struct ObjBatch above) ----
 void launch_obj_global_scatter(const ObjBatch& b, int blocks, hipStream_t s);          // GlobalProjection of every object model (mf_segment.hip)
 void launch_obj_fuse_clean(const ObjBatch& b, int blocks, int clean_blocks, hipStream_t s, int compact_blocks = kCompactBlocks);   // predictIndices -> fuse -> predictIndices -> clean
@@ -521,15 +544,9 @@ void launch_fill_int(int* p, int v, int n, hipStream_t s);
 void launch_edge_map(const float* vmap, const float* nmap, float* out, int W, int H, float wD, float wC, hipStream_t s);
 void launch_edge_binary(const float* edge, uint8_t* out, uint8_t* tmp, int W, int H, float threshold, int radius,
                         int iterations, hipStream_t s);
-void launch_global_scatter(Surfels src, const FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth,
-                           float confThreshold, int timeDelta, int order, int id, unsigned long long* keys, hipStream_t s,
-                           int blocks = kSurfelGridBlocks);
 void launch_global_resolve(unsigned long long* keys, uint8_t* ids, int P, hipStream_t s);
 int gn_solve_standalone(const double* sys29, const double* resultRt16, const float* Rprev9, const float* tprev3, double* x_serial, double* x_wave,
                         double* resultRt_out, float* Rcurr9, float* tcurr3, float* stats2, hipStream_t s);
-int launch_global_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth, float confThreshold,
-                        int timeDelta, int order, int id, int* tile_count, int* entries, int entries_cap, float4* rec0, float4* rec1, void* bbox,
-                        unsigned long long* keys, hipStream_t s, SplatTuning tune = SplatTuning(), const VisList* vis = nullptr);
 void launch_spawn_pose(PoseDev* obj, const PoseDev* bg, FrameDev* objFrame, const FrameDev* bgFrame, PoseDev* host_mirror,
                        hipStream_t s);
 void launch_static_pose(PoseDev* obj, const PoseDev* bg, PoseDev* host_mirror, hipStream_t s);

@@ -9,6 +9,7 @@
 #pragma clang fp contract(off)
 #include "mf_device.h"
 #include "mf_walk.h"
+#include "mf_sprite_device.h"
 
 namespace mf {
 
@@ -95,91 +96,28 @@ void launch_edge_binary(const float* edge, uint8_t* out, uint8_t* tmp, int W, in
 }
 
 // ------------------------------------------------------------------------------------------------
-// GlobalProjection: the splat scatter of mf_surfel.hip with (model order, model id) as payload
-// key = z bits << 32 | order << 8 | id  -> LESS on z, earlier model in the list wins ties (GL draw order)
+// GlobalProjection: the sprite scatter (sprite_scatter_body, mf_sprite_device.h) with global_payload(model order, model id) as the key's
+// low word -> LESS on z, earlier model in the list wins ties (GL draw order).  A model dropped by the jump test earlier in this frame
+// (pose->alive == 0) draws nothing.
 // ------------------------------------------------------------------------------------------------
-// kLanes neighbouring lanes share one surfel and split its sprite's pixels between them as a kLX x kLY block (1: the thread-per-surfel form).
-// The object models' launches use 4: a few thousand sprites of 4-10 px a side kept a handful of threads busy for ~36 us each (round 4 trace),
-// the rest of the GPU idle; the keys are the same bits in any split (atomicMin is order independent).
-template <int kLanes>
-__device__ __forceinline__ void global_scatter_body(Surfels src, const FrameDev* __restrict__ frame,
-                                                    const PoseDev* __restrict__ pose, int W, int H, Intr k, float maxDepth,
-                                                    float confThreshold, int timeDelta, unsigned payload,
-                                                    unsigned long long* __restrict__ keys, bool pretest = false) {
-    if (pose->alive == 0) return;  // model dropped by the jump test earlier in this frame
-    const float time = (float)frame->tick;
-    float Ri[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) Ri[q] = pose->Ri[q];
-    const float3 ti = f3(pose->ti[0], pose->ti[1], pose->ti[2]);
-    constexpr int kLX = kLanes >= 2 ? 2 : 1, kLY = kLanes / kLX;
-    const int sub = threadIdx.x % kLanes, sx = sub % kLX, sy = sub / kLX;
-    for_each_surfel_slice<kLanes>(src, frame, nullptr, nullptr, [&](int i, bool live) {
-        if (!live) return;
-        const float4 pc = src.pc[i];
-        if (pc.w < confThreshold) return;
-        const float lastTime = src.ct[i].w;
-        const float3 h = mul33(Ri, f3(pc.x, pc.y, pc.z)) + ti;
-        if (h.z > maxDepth || h.z < 0 || time - lastTime > (float)timeDelta || lastTime > time) return;  // splat_models.vert:57
-        const float u = ((k.fx * h.x) / h.z) + k.cx, v = ((k.fy * h.y) / h.z) + k.cy;
-        if (!(u >= 0.f && u <= (float)W && v >= 0.f && v <= (float)H)) return;
-        const float4 n4 = src.nr[i];
-        const float3 nrm = normalize_gl(mul33(Ri, f3(n4.x, n4.y, n4.z)));
-        const float rad = n4.w;
-        const float3 x1 = normalize_gl(f3(nrm.y - nrm.z, -nrm.x, nrm.x)) * (rad * 1.41421356f);
-        const float3 y1 = cross3(nrm, x1);
-        float xs0 = INFINITY, xs1 = -INFINITY, ys0 = INFINITY, ys1 = -INFINITY;
-        const float3 corners[4] = {h + x1, h + y1, h - y1, h - x1};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float pxq = ((k.fx * corners[q].x) / corners[q].z) + k.cx;
-            const float pyq = ((k.fy * corners[q].y) / corners[q].z) + k.cy;
-            xs0 = fminf(xs0, pxq); xs1 = fmaxf(xs1, pxq);
-            ys0 = fminf(ys0, pyq); ys1 = fmaxf(ys1, pyq);
-        }
-        float size = fmaxf(0.f, fmaxf(fabsf(xs1 - xs0), fabsf(ys1 - ys0)));
-        if (!(size > 0.f)) return;
-        size = fminf(fmaxf(size, 1.0f), 64.0f);   // GL clamps gl_PointSize to the point size range: at least 1 px (see mf_splat.hip)
-        const float half = size * 0.5f;
-        const int px0 = max(0, (int)ceilf(u - half - 0.5f)), px1 = min(W - 1, (int)ceilf(u + half - 0.5f) - 1);
-        const int py0 = max(0, (int)ceilf(v - half - 0.5f)), py1 = min(H - 1, (int)ceilf(v + half - 0.5f) - 1);
-        const float sqrRad = rad * rad;
-        const float pn = dot3(h, nrm);
-        for (int py = py0 + sy; py <= py1; py += kLY)
-            for (int px = px0 + sx; px <= px1; px += kLX) {
-                const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;
-                const float3 l = normalize_gl(f3((fcx - k.cx) / k.fx, (fcy - k.cy) / k.fy, 1.0f));
-                const float3 cp = l * (pn / dot3(l, nrm));
-                const float3 diff = cp - h;
-                if (!(dot3(diff, diff) <= sqrRad)) continue;
-                if (!(cp.z > 0.f)) continue;
-                if (pretest) zmin_key_pretested(&keys[py * W + px], ((unsigned long long)__float_as_uint(cp.z) << 32) | payload);   // (object models)
-                else zmin_key(&keys[py * W + px], ((unsigned long long)__float_as_uint(cp.z) << 32) | payload);
-            }
-    });
-}
-
-__global__ __launch_bounds__(256) void k_global_scatter(Surfels src, const FrameDev* __restrict__ frame,
-                                                        const PoseDev* __restrict__ pose, int W, int H, Intr k, float maxDepth,
-                                                        float confThreshold, int timeDelta, unsigned payload,
-                                                        unsigned long long* __restrict__ keys) {
-    global_scatter_body<1>(src, frame, pose, W, H, k, maxDepth, confThreshold, timeDelta, payload, keys);
+__global__ __launch_bounds__(256) void k_global_scatter(const SpriteView v, unsigned payload, unsigned long long* __restrict__ keys) {
+    if (v.pose->alive == 0) return;
+    sprite_scatter_body<1, false>(v, payload, keys, false);
 }
 // every object model of the list in one launch (grid.z = model; ObjBatch, mf_internal.h): all of them z-test into the one key image
-__global__ __launch_bounds__(256) void k_obj_global_scatter(const ObjBatch b) {
-    const PassModel& m = b.m[blockIdx.z];
-    if (b.denseSprites) global_scatter_body<1>(m.a, m.frame, m.pose, b.W, b.H, b.k, b.globalMaxDepth, 12.0f, b.timeDelta, m.global_payload, b.global_keys, true);
-    else global_scatter_body<4>(m.a, m.frame, m.pose, b.W, b.H, b.k, b.globalMaxDepth, 12.0f, b.timeDelta, m.global_payload, b.global_keys, true);
+// (f by value, in a function of its own: as obj_splat_scatter, mf_surfel.hip)
+__device__ __forceinline__ void obj_global_scatter(const PassFrame f, const PassModel& m, int dense) {
+    if (m.pose->alive == 0) return;
+    if (dense) sprite_scatter_body<1, false>(global_view(f, m), m.global_payload, f.global_keys, true);
+    else sprite_scatter_body<4, false>(global_view(f, m), m.global_payload, f.global_keys, true);
 }
+__global__ __launch_bounds__(256) void k_obj_global_scatter(const ObjBatch b) { obj_global_scatter(b, b.m[blockIdx.z], b.denseSprites); }
 void launch_obj_global_scatter(const ObjBatch& b, int blocks, hipStream_t s) {
     hipLaunchKernelGGL(k_obj_global_scatter, dim3(blocks, 1, b.n), dim3(256), 0, s, b);
 }
 
-void launch_global_scatter(Surfels src, const FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth,
-                           float confThreshold, int timeDelta, int order, int id, unsigned long long* keys, hipStream_t s, int blocks) {
-    const unsigned payload = ((unsigned)order << 8) | ((unsigned)id & 255u);
-    hipLaunchKernelGGL(k_global_scatter, dim3(blocks), dim3(256), 0, s, src, frame, pose, W, H, k, maxDepth, confThreshold, timeDelta,
-                       payload, keys);
+void launch_global_scatter(const SpriteView& v, unsigned payload, unsigned long long* keys, hipStream_t s, int blocks) {
+    hipLaunchKernelGGL(k_global_scatter, dim3(blocks), dim3(256), 0, s, v, payload, keys);
 }
 
 __global__ void k_global_resolve(unsigned long long* __restrict__ keys, uint8_t* __restrict__ ids, int P) {

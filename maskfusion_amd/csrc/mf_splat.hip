@@ -1,7 +1,7 @@
 // mf_splat.hip -- tiled splat prediction (ModelProjection::combinedPredict, Core/Model/ModelProjection.cpp:187-268 +
-// Core/Shaders/splat.vert, combo_splat.frag): the same raster rule and keys as k_splat_scatter / k_splat_resolve in
-// mf_surfel.hip (which stay as the executable specification: tests compare the two bit for bit), organised so that the
-// z-test happens in LDS.
+// Core/Shaders/splat.vert, combo_splat.frag) and tiled GlobalProjection: the sprite set-up, ray and pixel test of
+// mf_sprite_device.h -- the ones k_splat_scatter / k_splat_resolve in mf_surfel.hip and k_global_scatter in mf_segment.hip run
+// (those stay as the executable specification: tests compare the forms bit for bit) --, organised so that the z-test happens in LDS.
 //
 // Why: the scatter form issues one 64-bit global atomicMin per covered pixel (4.3 M per VGA frame at 270 k surfels).
 // Device-scope atomics are performed memory-side (rocprofv3: TCC_HIT ~ 0, every request a miss; a line touched by an
@@ -13,6 +13,7 @@
 
 #include "mf_internal.h"
 #include "mf_device.h"
+#include "mf_sprite_device.h"
 #include "mf_rgbd_device.h"
 #include "mf_bilateral_device.h"
 #include "mf_frame_pyramid_device.h"
@@ -28,46 +29,8 @@ constexpr int kTileHMax = 32;            // the tallest tile: the height is a la
 constexpr int kBinThreads = 1024;
 constexpr int kMaxTiles = 8192;          // bounds the LDS histograms (VGA: 1200 tiles, 1280x960: 4800); larger images use the scatter form
 
-struct SplatSetup { float3 h, nrm; float sqrRad, pn; int px0, px1, py0, py1; };
 struct TileStamps { unsigned long long t[8]; };   // "splatProfile": shader-clock stamps of a tile workgroup's thread 0 (by reference + constant
                                                   // indices: an array handed over as a pointer lives in scratch memory, for every launch)
-
-// splat.vert:40-105 for surfel i; false if it draws nothing.  Verbatim the per-surfel part of k_splat_scatter.
-__device__ __forceinline__ bool splat_setup(const Surfels& src, int i, float time, const float* Ri, float3 ti, int W, int H, Intr k,
-                                            float maxDepth, float confThreshold, int timeDelta, SplatSetup& o) {
-    const float4 pc = src.pc[i];
-    if (pc.w < confThreshold) return false;
-    const float lastTime = src.ct[i].w;
-    const float3 h = mul33(Ri, f3(pc.x, pc.y, pc.z)) + ti;
-    if (h.z > maxDepth || h.z < 0 || time - lastTime > (float)timeDelta || lastTime > time) return false;  // splat.vert:58
-    const float u = ((k.fx * h.x) / h.z) + k.cx, v = ((k.fy * h.y) / h.z) + k.cy;
-    if (!(u >= 0.f && u <= (float)W && v >= 0.f && v <= (float)H)) return false;
-    const float4 n4 = src.nr[i];
-    const float3 nrm = normalize_gl(mul33(Ri, f3(n4.x, n4.y, n4.z)));
-    const float rad = n4.w;
-    const float3 x1 = normalize_gl(f3(nrm.y - nrm.z, -nrm.x, nrm.x)) * (rad * 1.41421356f);
-    const float3 y1 = cross3(nrm, x1);
-    float xs0 = INFINITY, xs1 = -INFINITY, ys0 = INFINITY, ys1 = -INFINITY;
-    const float3 corners[4] = {h + x1, h + y1, h - y1, h - x1};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float pxq = ((k.fx * corners[q].x) / corners[q].z) + k.cx;
-        const float pyq = ((k.fy * corners[q].y) / corners[q].z) + k.cy;
-        xs0 = fminf(xs0, pxq); xs1 = fmaxf(xs1, pxq);
-        ys0 = fminf(ys0, pyq); ys1 = fmaxf(ys1, pyq);
-    }
-    float size = fmaxf(0.f, fmaxf(fabsf(xs1 - xs0), fabsf(ys1 - ys0)));
-    if (!(size > 0.f)) return false;
-    // gl_PointSize is clamped to the implementation's point size range (OpenGL 3.3 core, 3.4 "Points"; NVIDIA: [1, 2047]): a sprite
-    // smaller than a pixel -- a surfel seen from more than ~4x its creation distance -- still covers the pixel its centre falls into
-    size = fminf(fmaxf(size, 1.0f), 64.0f);
-    const float half = size * 0.5f;
-    o.px0 = max(0, (int)ceilf(u - half - 0.5f)); o.px1 = min(W - 1, (int)ceilf(u + half - 0.5f) - 1);
-    o.py0 = max(0, (int)ceilf(v - half - 0.5f)); o.py1 = min(H - 1, (int)ceilf(v + half - 0.5f) - 1);
-    if (o.px0 > o.px1 || o.py0 > o.py1) return false;
-    o.h = h; o.nrm = nrm; o.sqrRad = rad * rad; o.pn = dot3(h, nrm);
-    return true;
-}
 
 // The three knobs of SplatTuning.  Their legal values are the rows of mf_params.inl (mf_set_param refuses everything else); what follows only guards
 // the launches against a SplatTuning filled in by hand: anything else takes the default.
@@ -83,15 +46,26 @@ int splat_tile_threads(int n) { return (n == 256 || n == 320 || n == 384 || n ==
 // tile height ("tileHeight"): that many rows of 16 pixels; the tile's pixels need a thread each
 int splat_tile_height(int h) { return (h == 16 || h == 20 || h == 32) ? h : 24; }
 
+// The launch shape of the tile passes (mf_internal.h)
+TileShape splat_tile_shape(int W, int H, SplatTuning tune) {
+    TileShape t;
+    t.tileH = splat_tile_height(tune.tile_h);
+    t.tilesX = (W + kTile - 1) / kTile; t.tilesY = (H + t.tileH - 1) / t.tileH;
+    t.lanes = splat_sprite_lanes(tune.sprite_lanes);
+    t.threads = std::max(splat_tile_threads(tune.tile_threads), ((kTile * t.tileH + 63) / 64) * 64);   // the tile's pixels need a thread each
+    t.fits = t.tilesX * t.tilesY <= kMaxTiles;
+    return t;
+}
+
+// What the binning pass writes and the tile pass of the same view reads
 struct BinArgs {
-    Surfels src; const FrameDev* frame; const PoseDev* pose; int W, H; Intr k; float maxDepth, confThreshold; int timeDelta;
+    SpriteView v;         // (v.frame->pad[1]: the overflow flag)
     int tilesX, tilesY, tileH;
     int* tile_count;      // [tiles]  zero on entry (each tile workgroup re-zeroes its own counter when it is done)
     int* entries;         // [tiles][tile_cap]
     int tile_cap;
-    FrameDev* frame_rw;   // overflow flag (pad[1])
     float4* rec0; float4* rec1; short4* bbox;   // [surfels] sprite set-up kept for the tile pass: {h, r^2}, {n, h.n}, pixel box
-    const int* vis_list; const int* vis_count;  // nullptr: every surfel; else the runs of src (Surfels::box) k_cull listed -- no other run can draw
+    const int* vis_list; const int* vis_count;  // nullptr: every surfel; else the runs of v.src (Surfels::box) k_cull listed -- no other run can draw
 };
 
 // Binning in one pass: every tile owns a fixed slice of `entries`, so no scan is needed.  A 1024-thread workgroup counts
@@ -105,16 +79,16 @@ __device__ __forceinline__ void splat_bin_body(const BinArgs& a, int* s_mem, con
     const int nt = a.tilesX * a.tilesY;
     int* s_cnt = s_mem;           // [nt] this workgroup's entries per tile, then the start of its reserved range
     int* s_fill = s_mem + nt;     // [nt] slots handed out
-    const int n = a.frame->phys;      // device-resident: the grid is fixed and walks the buffer in chunks of 2048 slots
+    const int n = a.v.frame->phys;      // device-resident: the grid is fixed and walks the buffer in chunks of 2048 slots
     // by runs: the listed ones (k_cull), or every run of the buffer's table; a dense buffer without a table: slot by slot
-    const int table_runs = a.frame->runs;
+    const int table_runs = a.v.frame->runs;
     const bool by_runs = a.vis_list != nullptr || table_runs > 0;
     const int nruns = a.vis_list ? *a.vis_count : table_runs;
-    const float time = (float)a.frame->tick;
+    const float time = (float)a.v.frame->tick;
     float Ri[9];
 #pragma unroll
-    for (int q = 0; q < 9; ++q) Ri[q] = a.pose->Ri[q];
-    const float3 ti = f3(a.pose->ti[0], a.pose->ti[1], a.pose->ti[2]);
+    for (int q = 0; q < 9; ++q) Ri[q] = a.v.pose->Ri[q];
+    const float3 ti = f3(a.v.pose->ti[0], a.v.pose->ti[1], a.v.pose->ti[2]);
   // a round = 2 kThreads surfel slots (2048 in k_splat_bin): consecutive surfels of the buffer, or -- with a visibility list -- the next 2 kThreads / kRun listed runs
   constexpr int kRunsPerRound = 2 * kThreads / kRun;
   const int rounds = by_runs ? (nruns + kRunsPerRound - 1) / kRunsPerRound : (n + 2 * kThreads - 1) / (2 * kThreads);
@@ -131,7 +105,7 @@ __device__ __forceinline__ void splat_bin_body(const BinArgs& a, int* s_mem, con
             i = n;
             if (v < nruns) {
                 const int run = a.vis_list ? a.vis_list[v] : v;
-                const int beg = run_start(a.src.box, run), len = run_len(a.src.box, run);
+                const int beg = run_start(a.v.src.box, run), len = run_len(a.v.src.box, run);
                 if (slot % kRun < len) i = beg + slot % kRun;
             }
         }
@@ -139,7 +113,7 @@ __device__ __forceinline__ void splat_bin_body(const BinArgs& a, int* s_mem, con
         bb[r] = make_short4(1, 0, 1, 0);
         if (i < n) {
             SplatSetup su;
-            if (splat_setup(a.src, i, time, Ri, ti, a.W, a.H, a.k, a.maxDepth, a.confThreshold, a.timeDelta, su)) {
+            if (splat_setup(a.v, i, time, Ri, ti, su)) {
                 bb[r] = make_short4((short)su.px0, (short)su.px1, (short)su.py0, (short)su.py1);
                 // the tile pass meets this surfel ~1.8 times (once per overlapped tile): it reads the set-up instead of
                 // repeating its ~300 instructions (ten IEEE divisions) each time
@@ -165,7 +139,7 @@ __device__ __forceinline__ void splat_bin_body(const BinArgs& a, int* s_mem, con
                 // a full list is not an error and drops nothing: tile_count keeps counting, and a tile whose count exceeds its
                 // slice scans the sprite boxes of the whole map instead of its list (k_splat_tile); pad[1] only records that it happened
                 if (slot < a.tile_cap) a.entries[(size_t)t * a.tile_cap + slot] = idx[r];
-                else a.frame_rw->pad[1] = 1;
+                else a.v.frame->pad[1] = 1;
             }
     }
     __syncthreads();
@@ -201,58 +175,49 @@ __global__ __launch_bounds__(kBinFilterThreads) __attribute__((amdgpu_waves_per_
 }
 
 struct TileArgs {
-    Surfels src; FrameDev* frame; const PoseDev* pose; int W, H; Intr k; float maxDepth, confThreshold; int timeDelta;
-    int tilesX, tilesY, tileH;
-    int* tile_count; const int* entries; int tile_cap;
-    const float4* rec0; const float4* rec1; const short4* bbox;
-    float4* predV; float4* predN; uchar4* predImage; uint16_t* predTime;
-    const uint8_t* rgb; uint8_t* predGray; uint8_t* fillGray;
-    int fillPassthrough;             // fill_rgb.frag's `passthrough` (frameToFrameRGB, Model.cpp:981): the fill-in image is the raw frame everywhere
-    const int* vis_list; const int* vis_count;   // as BinArgs
+    BinArgs b;                       // the binning pass's arguments: the view, the tile shape, the lists and records it wrote
+    PredOut out;
     int advance; FrameAdvance adv;   // advance != 0: the last workgroup also runs the end-of-frame bookkeeping (k_frame_advance)
     unsigned long long* prof;        // optional ("splatProfile"): [tiles][8] shader-clock stamps of thread 0 + the tile's list length
     float* vm[3]; float* nm[3];      // optional ("tilePyramid"; vm[0] == nullptr: off): the model-side pyramid's planes -- every tile workgroup also writes their texels
     int tile_wgs;                    // workgroups of the launch that run the tile pass (the padded tile count); any behind them build the frame pyramid
 };
 
-// The z-test of one 16x16 tile in LDS, shared by the prediction (payload = surfel index) and the global projection (payload =
+// The z-test of one tile in LDS, shared by the prediction (the key's low word = surfel index) and the global projection (= payload:
 // model order / id): rays of the tile's pixels, the tile's sprite list (or, after a list overflow, every sprite box of the map),
 // ds_min_u64 per covered pixel.  On return s_key[pixel of the tile] holds the winning key (all threads have passed a barrier).
-template <bool kIndexPayload, int kSpriteLanes>
-__device__ __forceinline__ void tile_ztest(int tile, int tilesX, int tileH, Intr k, int* tile_count, const int* entries, int tile_cap,
-                                           const FrameDev* frame, const float4* __restrict__ rec0, const float4* __restrict__ rec1,
-                                           const short4* __restrict__ bbox, unsigned payload, unsigned long long* s_key, float4* s_ray,
-                                           int* s_range, bool prof, TileStamps& stamp, const int* __restrict__ vis_list,
-                                           const int* __restrict__ vis_count, const int4* __restrict__ runs) {
-    const int tx0 = (tile % tilesX) * kTile, ty0 = (tile / tilesX) * tileH;
-    if ((int)threadIdx.x < kTile * tileH) {
+template <bool kIndexKey, int kSpriteLanes>
+__device__ __forceinline__ void tile_ztest(const BinArgs& a, int tile, unsigned payload, unsigned long long* s_key, float4* s_ray, int* s_range, bool prof,
+                                           TileStamps& stamp) {
+    const int tx0 = (tile % a.tilesX) * kTile, ty0 = (tile / a.tilesX) * a.tileH;
+    const float4* __restrict__ const rec0 = a.rec0; const float4* __restrict__ const rec1 = a.rec1; const short4* __restrict__ const bbox = a.bbox;   // (read only here)
+    if ((int)threadIdx.x < kTile * a.tileH) {
     s_key[threadIdx.x] = kEmptyKey;
     {   // the viewing ray of every pixel of the tile, once (combo_splat.frag:40-42); the per-surfel loops below re-used to
         // spend two thirds of their instructions recomputing it (two divisions + a normalisation per covered pixel)
-        const float fcx = (float)(tx0 + (threadIdx.x & (kTile - 1))) + 0.5f, fcy = (float)(ty0 + (threadIdx.x >> 4)) + 0.5f;
-        const float3 l = normalize_gl(f3((fcx - k.cx) / k.fx, (fcy - k.cy) / k.fy, 1.0f));
+        const float3 l = sprite_ray(tx0 + (int)(threadIdx.x & (kTile - 1)), ty0 + (int)(threadIdx.x >> 4), a.v.k);
         s_ray[threadIdx.x] = make_float4(l.x, l.y, l.z, 0.f);
     }
     }
     if (threadIdx.x == 0) {
-        s_range[0] = tile_count[tile];
-        tile_count[tile] = 0;   // consumed: the next binning pass starts from zero
+        s_range[0] = a.tile_count[tile];
+        a.tile_count[tile] = 0;   // consumed: the next binning pass starts from zero
     }
     __syncthreads();
     if (prof) { stamp.t[1] = __builtin_amdgcn_s_memtime(); stamp.t[6] = (unsigned long long)s_range[0]; }
-    const bool overflow = s_range[0] > tile_cap;   // more sprites than list slots (the reference has no such limit): scan every box
+    const bool overflow = s_range[0] > a.tile_cap;   // more sprites than list slots (the reference has no such limit): scan every box
     // (after an overflow: every surfel whose sprite box the binning pass wrote -- the runs of the visibility list, every run of the table, or
     // -- a dense buffer without a table -- every slot)
     // (looked at after an overflow only: the common path waits for nothing but its list)
-    const int table_runs = overflow ? frame->runs : 0;
-    const bool by_runs = vis_list != nullptr || table_runs > 0;
-    const int cnt = overflow ? (by_runs ? (vis_list ? *vis_count : table_runs) * kRun : frame->count) : s_range[0];
-    const int* __restrict__ list = entries + (size_t)tile * tile_cap;
+    const int table_runs = overflow ? a.v.frame->runs : 0;
+    const bool by_runs = a.vis_list != nullptr || table_runs > 0;
+    const int cnt = overflow ? (by_runs ? (a.vis_list ? *a.vis_count : table_runs) * kRun : a.v.frame->count) : s_range[0];
+    const int* __restrict__ list = a.entries + (size_t)tile * a.tile_cap;
     auto entry = [&](int e) -> int {
         if (!overflow) return list[e];
         if (!by_runs) return e;
-        const int run = vis_list ? vis_list[e / kRun] : e / kRun;
-        return e % kRun < run_len(runs, run) ? run_start(runs, run) + e % kRun : -1;
+        const int run = a.vis_list ? a.vis_list[e / kRun] : e / kRun;
+        return e % kRun < run_len(a.v.src.box, run) ? run_start(a.v.src.box, run) + e % kRun : -1;
     };
     // kSpriteLanes neighbouring lanes share one sprite and take every kSpriteLanes-th pixel of its clipped box (with one lane per sprite a
     // wavefront runs as long as its largest box).  The lanes read the same list entry / records (one request) and the z-test is order
@@ -283,7 +248,7 @@ __device__ __forceinline__ void tile_ztest(int tile, int tilesX, int tileH, Intr
         if (i1 >= 0) { bb0 = bbox[i1]; r0 = rec0[i1]; r1 = rec1[i1]; } else bb0 = kNoBox;
         i0 = i1; i1 = i2;
         const int x0 = max((int)bb.x, tx0), x1 = min((int)bb.y, tx0 + kTile - 1);
-        const int y0 = max((int)bb.z, ty0), y1 = min((int)bb.w, ty0 + tileH - 1);
+        const int y0 = max((int)bb.z, ty0), y1 = min((int)bb.w, ty0 + a.tileH - 1);
         if (x0 > x1 || y0 > y1) continue;
         SplatSetup su;
         su.h = f3(c0.x, c0.y, c0.z); su.sqrRad = c0.w; su.nrm = f3(c1.x, c1.y, c1.z); su.pn = c1.w;
@@ -297,13 +262,9 @@ __device__ __forceinline__ void tile_ztest(int tile, int tilesX, int tileH, Intr
                 const int lp = row + px;
                 const float4 r4 = nxt;
                 nxt = s_ray[row + min(px + kLX, x1)];
-                const float3 l = f3(r4.x, r4.y, r4.z);
-                const float3 cp = l * (su.pn / dot3(l, su.nrm));
-                const float3 diff = cp - su.h;
-                if (!(dot3(diff, diff) <= su.sqrRad)) continue;
-                if (!(cp.z > 0.f)) continue;
-                const unsigned long long key = ((unsigned long long)__float_as_uint(cp.z) << 32) | (kIndexPayload ? (unsigned)i : payload);
-                atomicMin(&s_key[lp], key);   // (looking at s_key before the atomic -- most sprites lose -- was measured: no gain)
+                float z;
+                if (!sprite_covers(su, f3(r4.x, r4.y, r4.z), z)) continue;
+                atomicMin(&s_key[lp], sprite_key(z, kIndexKey ? (unsigned)i : payload));   // (looking at s_key before the atomic -- most sprites lose -- was measured: no gain)
             }
         }
     }
@@ -346,15 +307,18 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
                                   (int)threadIdx.x & 255, has);
         return;
     }
+    const BinArgs& bin = a.b;
+    const SpriteView& v = bin.v;
+    const PredOut& o = a.out;
     float4* const s_ray = s_pool;
     unsigned long long* const s_key = reinterpret_cast<unsigned long long*>(s_pool + kTile * kTileHMax);
     // XCD k draws the k-th contiguous eighth of the tile list (mf_device.h): a sprite overlaps 1.8 tiles on average, and neighbouring
     // tiles now find its records in the same L2.  The grid is padded to a multiple of 8; a padding workgroup draws nothing but still
     // takes its ticket below.
-    const int tile = xcd_contiguous_tile(blockIdx.x, a.tilesX * a.tilesY);
-    const bool live = tile < a.tilesX * a.tilesY;
-    const int tx0 = (tile % a.tilesX) * kTile, ty0 = (tile / a.tilesX) * a.tileH;
-    const Intr k = a.k;
+    const int tile = xcd_contiguous_tile(blockIdx.x, bin.tilesX * bin.tilesY);
+    const bool live = tile < bin.tilesX * bin.tilesY;
+    const int tx0 = (tile % bin.tilesX) * kTile, ty0 = (tile / bin.tilesX) * bin.tileH;
+    const Intr k = v.k;
     if (threadIdx.x == 0) s_cover = 0;   // (ordered before its use by the barriers inside tile_ztest)
     TileStamps stamp;
     const bool prof = a.prof != nullptr && live && threadIdx.x == 0;
@@ -363,48 +327,47 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         for (int q = 0; q < 8; ++q) stamp.t[q] = 0;
         stamp.t[0] = __builtin_amdgcn_s_memtime();
     }
-    if (live) tile_ztest<true, kSpriteLanes>(tile, a.tilesX, a.tileH, k, a.tile_count, a.entries, a.tile_cap, a.frame, a.rec0, a.rec1, a.bbox, 0u, s_key, s_ray, s_range,
-                                            prof, stamp, a.vis_list, a.vis_count, a.src.box);
+    if (live) tile_ztest<true, kSpriteLanes>(bin, tile, 0u, s_key, s_ray, s_range, prof, stamp);
     const int px = tx0 + (threadIdx.x & (kTile - 1)), py = ty0 + (threadIdx.x >> 4);
     int covered = 0;   // this pixel is one of the 20x down-sampled samples of MaskFusion::requiresFillIn and carries a colour
     const bool pyr = a.vm[0] != nullptr;
     // (gathering the winners' records along the tile's COLUMNS and transposing the outputs through the LDS -- what made the index map's resolve
     // twice as fast -- changes nothing here: 61.3 against 60.0 us for the stage, profiles/r05r_ab.txt; a sprite covers ~4 x 4 pixels, neighbouring
     // pixels share their winner either way)
-    if (live && (int)threadIdx.x < kTile * a.tileH && px < a.W && py < a.H) {   // (threads beyond the tile's 256 pixels only helped with the list)
-      const int p = py * a.W + px;
+    if (live && (int)threadIdx.x < kTile * bin.tileH && px < v.W && py < v.H) {   // (threads beyond the tile's 256 pixels only helped with the list)
+      const int p = py * v.W + px;
       const unsigned long long key = s_key[threadIdx.x];
       float4 v4 = make_float4(0, 0, 0, 0), n4 = v4;
       if (key == kEmptyKey) {
-        a.predV[p] = a.predN[p] = make_float4(0, 0, 0, 0);
-        a.predImage[p] = make_uchar4(0, 0, 0, 0);
-        a.predTime[p] = 0;
-        if (a.predGray) a.predGray[p] = 0;
-        if (a.fillGray && a.rgb) a.fillGray[p] = intensity_of((float)a.rgb[p * 3], (float)a.rgb[p * 3 + 1], (float)a.rgb[p * 3 + 2]);
+        o.predV[p] = o.predN[p] = make_float4(0, 0, 0, 0);
+        o.predImage[p] = make_uchar4(0, 0, 0, 0);
+        o.predTime[p] = 0;
+        if (o.predGray) o.predGray[p] = 0;
+        if (o.fillGray && o.rgb) o.fillGray[p] = intensity_of((float)o.rgb[p * 3], (float)o.rgb[p * 3 + 1], (float)o.rgb[p * 3 + 2]);
       } else {
         const int i = (int)(unsigned)(key & 0xFFFFFFFFull);
         const float z = __uint_as_float((unsigned)(key >> 32));
-        const float4 pc = a.src.pc[i], c4 = a.src.ct[i], s4 = a.src.nr[i];
-        const float3 n = normalize_gl(mul33(a.pose->Ri, f3(s4.x, s4.y, s4.z)));
+        const float4 pc = v.src.pc[i], c4 = v.src.ct[i], s4 = v.src.nr[i];
+        const float3 n = normalize_gl(mul33(v.pose->Ri, f3(s4.x, s4.y, s4.z)));
         const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;
         v4 = make_float4((fcx - k.cx) * z * (1.f / k.fx), (fcy - k.cy) * z * (1.f / k.fy), z, pc.w);  // combo_splat.frag:56
         n4 = make_float4(n.x, n.y, n.z, s4.w);
-        a.predV[p] = v4;
-        a.predN[p] = n4;
+        o.predV[p] = v4;
+        o.predN[p] = n4;
         const int ci = (int)c4.x;
         const uchar4 col = make_uchar4((ci >> 16) & 0xFF, (ci >> 8) & 0xFF, ci & 0xFF, 255);
-        a.predImage[p] = col;
-        a.predTime[p] = (uint16_t)(unsigned)c4.z;
-        if (a.predGray || a.fillGray) {
+        o.predImage[p] = col;
+        o.predTime[p] = (uint16_t)(unsigned)c4.z;
+        if (o.predGray || o.fillGray) {
             const uint8_t gv = intensity_of((float)col.x, (float)col.y, (float)col.z);
-            if (a.predGray) a.predGray[p] = gv;
-            if (a.fillGray) {
-                const bool empty = (col.x == 0 && col.y == 0 && col.z == 0) || a.fillPassthrough != 0;
-                a.fillGray[p] = (empty && a.rgb) ? intensity_of((float)a.rgb[p * 3], (float)a.rgb[p * 3 + 1], (float)a.rgb[p * 3 + 2]) : gv;
+            if (o.predGray) o.predGray[p] = gv;
+            if (o.fillGray) {
+                const bool empty = (col.x == 0 && col.y == 0 && col.z == 0) || o.fillPassthrough != 0;
+                o.fillGray[p] = (empty && o.rgb) ? intensity_of((float)o.rgb[p * 3], (float)o.rgb[p * 3 + 1], (float)o.rgb[p * 3 + 2]) : gv;
             }
         }
         // MaskFusion::requiresFillIn (MaskFusion.cpp:630-648): nearest sample of the 20x down-sampled colour prediction
-        covered = ((px % 20) == 10 && (py % 20) == 10 && px / 20 < a.W / 20 && py / 20 < a.H / 20 && col.x > 0 && col.y > 0 && col.z > 0) ? 1 : 0;
+        covered = ((px % 20) == 10 && (py % 20) == 10 && px / 20 < v.W / 20 && py / 20 < v.H / 20 && col.x > 0 && col.y > 0 && col.z > 0) ? 1 : 0;
       }
       if (pyr) {
         // copyMapsKernel of the texel; its flags are the values' own NaNs (vok = !isnan(v.x), nok = !isnan(n.x)), so six floats carry it.  Level 0
@@ -412,11 +375,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const MapPx m = copy_maps_px(v4, n4);
         float Rm[9];   // the model pose, as model_pyramid_body reads it (scalar loads; read again behind the barrier rather than kept across it)
 #pragma unroll
-        for (int q = 0; q < 9; ++q) Rm[q] = a.pose->R[q];
-        const float3 tm = f3(a.pose->t[0], a.pose->t[1], a.pose->t[2]);
+        for (int q = 0; q < 9; ++q) Rm[q] = v.pose->R[q];
+        const float3 tm = f3(v.pose->t[0], v.pose->t[1], v.pose->t[2]);
         s_ray[threadIdx.x] = make_float4(m.v.x, m.v.y, m.v.z, m.n.x);
         s_key[threadIdx.x] = ((unsigned long long)__float_as_uint(m.n.z) << 32) | (unsigned long long)__float_as_uint(m.n.y);
-        if (px < 4 * (a.W >> 2) && py < 4 * (a.H >> 2)) store_tx(a.vm[0], a.nm[0], a.W * a.H, p, m.v, m.vok, m.n, m.nok, Rm, tm);
+        if (px < 4 * (v.W >> 2) && py < 4 * (v.H >> 2)) store_tx(a.vm[0], a.nm[0], v.W * v.H, p, m.v, m.vok, m.n, m.nok, Rm, tm);
       }
     }
     // One 64-bit atomic per workgroup carries both its coverage count and its "finished" ticket (the count travels IN the atomic, so
@@ -434,14 +397,14 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     __syncthreads();
     if (threadIdx.x == 0) {
         const int wg_cover = s_cover;
-        const unsigned long long old = atomicAdd(&a.frame->done_cover, (1ull << 32) | (unsigned long long)(unsigned)wg_cover);
+        const unsigned long long old = atomicAdd(&v.frame->done_cover, (1ull << 32) | (unsigned long long)(unsigned)wg_cover);
         if ((unsigned)(old >> 32) == (unsigned)a.tile_wgs - 1u) {   // (the tile workgroups' tickets: others may share the launch)
             const int cover = (int)(unsigned)(old & 0xFFFFFFFFull) + wg_cover;
-            FrameDev* f = a.frame;
+            FrameDev* f = v.frame;
             f->done_cover = 0ull;
             if (a.advance) {
-                if (a.adv.log_slot) pose_log_entry(a.pose, a.adv.bg_pose, a.adv.log_slot);
-                const int rw = a.W / 20, rh = a.H / 20;
+                if (a.adv.log_slot) pose_log_entry(v.pose, a.adv.bg_pose, a.adv.log_slot);
+                const int rw = v.W / 20, rh = v.H / 20;
                 f->pad[0] = f->useFillIn;   // decision the tracking step of THIS frame ran with (mf_get_last_fillin)
                 f->useFillIn = ((float)(f->cover + cover) / (float)(rw * rh) < 0.75f) ? 1 : 0;
                 f->cover = 0;
@@ -456,14 +419,14 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     if (pyr) {
         // levels 1 and 2 of the tile: thread t takes level-1 texel b = t % 4 of the tile's level-2 texel t / 4 (4 per row).  Every thread of the
         // workgroup makes the call -- the quad broadcasts need whole wavefronts -- and only those with a texel inside the image read and write
-        const int W1 = a.W >> 1, H1 = a.H >> 1, W2 = a.W >> 2, H2 = a.H >> 2;
+        const int W1 = v.W >> 1, H1 = v.H >> 1, W2 = v.W >> 2, H2 = v.H >> 2;
         const int q = (int)threadIdx.x >> 2, b = (int)threadIdx.x & 3, bx = b & 1, by = b >> 1, lx2 = q & 3, ly2 = q >> 2;
         const int x2 = (tx0 >> 2) + lx2, y2 = (ty0 >> 2) + ly2;
-        const bool inside = live && ly2 < (a.tileH >> 2) && x2 < W2 && y2 < H2;
+        const bool inside = live && ly2 < (bin.tileH >> 2) && x2 < W2 && y2 < H2;
         float Rm[9];
 #pragma unroll
-        for (int q = 0; q < 9; ++q) Rm[q] = a.pose->R[q];
-        const float3 tm = f3(a.pose->t[0], a.pose->t[1], a.pose->t[2]);
+        for (int q = 0; q < 9; ++q) Rm[q] = v.pose->R[q];
+        const float3 tm = f3(v.pose->t[0], v.pose->t[1], v.pose->t[2]);
         MapPx m4[4];
         if (inside) {
 #pragma unroll
@@ -487,125 +450,89 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 // a pixel belongs to exactly one workgroup of this launch, and the other models' launches are ordered on the stream.  Same keys
 // as k_global_scatter (mf_segment.hip), which stays for small (object) models: one global atomic per covered pixel is memory-side
 // work (see the header) and cost ~170 us per frame for a 250 k-surfel background model against ~25 us here.
-struct GlobalTileArgs {
-    const FrameDev* frame; int W, H; Intr k; int tilesX, tilesY, tileH;
-    int* tile_count; const int* entries; int tile_cap;
-    const float4* rec0; const float4* rec1; const short4* bbox;
-    unsigned payload; unsigned long long* keys;
-    const int* vis_list; const int* vis_count; const int4* runs;   // as BinArgs (runs = src.box)
-};
+struct GlobalTileArgs { BinArgs b; unsigned payload; unsigned long long* keys; };
 template <int kSpriteLanes>
 __global__ __launch_bounds__(1024) void k_global_tile(const GlobalTileArgs a) {
     __shared__ unsigned long long s_key[kTile * kTileHMax];
     __shared__ float4 s_ray[kTile * kTileHMax];
     __shared__ int s_range[1];
-    const int tile = xcd_contiguous_tile(blockIdx.x, a.tilesX * a.tilesY);
-    if (tile >= a.tilesX * a.tilesY) return;
+    const BinArgs& bin = a.b;
+    const int tile = xcd_contiguous_tile(blockIdx.x, bin.tilesX * bin.tilesY);
+    if (tile >= bin.tilesX * bin.tilesY) return;
     TileStamps unused;
-    tile_ztest<false, kSpriteLanes>(tile, a.tilesX, a.tileH, a.k, a.tile_count, a.entries, a.tile_cap, a.frame, a.rec0, a.rec1, a.bbox, a.payload, s_key, s_ray, s_range,
-                                    false, unused, a.vis_list, a.vis_count, a.runs);
-    const int px = (tile % a.tilesX) * kTile + (threadIdx.x & (kTile - 1)), py = (tile / a.tilesX) * a.tileH + (threadIdx.x >> 4);
-    if ((int)threadIdx.x >= kTile * a.tileH || px >= a.W || py >= a.H) return;
+    tile_ztest<false, kSpriteLanes>(bin, tile, a.payload, s_key, s_ray, s_range, false, unused);
+    const int px = (tile % bin.tilesX) * kTile + (threadIdx.x & (kTile - 1)), py = (tile / bin.tilesX) * bin.tileH + (threadIdx.x >> 4);
+    if ((int)threadIdx.x >= kTile * bin.tileH || px >= bin.v.W || py >= bin.v.H) return;
     const unsigned long long key = s_key[threadIdx.x];
     if (key == kEmptyKey) return;
-    const int p = py * a.W + px;
+    const int p = py * bin.v.W + px;
     if (key < a.keys[p]) a.keys[p] = key;
-}
-
-int launch_global_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth, float confThreshold,
-                        int timeDelta, int order, int id, int* tile_count, int* entries, int entries_cap, float4* rec0, float4* rec1, void* bbox,
-                        unsigned long long* keys, hipStream_t s, SplatTuning tune, const VisList* vis) {
-    const int tileH = splat_tile_height(tune.tile_h);
-    const int tilesX = (W + kTile - 1) / kTile, tilesY = (H + tileH - 1) / tileH, nt = tilesX * tilesY;
-    if (nt > kMaxTiles) return -1;
-    const int g_sprite_lanes = splat_sprite_lanes(tune.sprite_lanes), g_tile_threads = std::max(splat_tile_threads(tune.tile_threads), ((kTile * tileH + 63) / 64) * 64);
-    BinArgs b;
-    b.src = src; b.frame = frame; b.pose = pose; b.W = W; b.H = H; b.k = k; b.maxDepth = maxDepth; b.confThreshold = confThreshold;
-    b.timeDelta = timeDelta; b.tilesX = tilesX; b.tilesY = tilesY; b.tileH = tileH; b.tile_count = tile_count;
-    b.entries = entries; b.tile_cap = entries_cap / nt; b.frame_rw = frame;
-    b.rec0 = rec0; b.rec1 = rec1; b.bbox = reinterpret_cast<short4*>(bbox);
-    b.vis_list = vis ? vis->list : nullptr; b.vis_count = vis ? vis->count : nullptr;
-    // two 1024-thread workgroups fit on a CU (60 VGPRs): 512 workgroups are ONE round of chunks up to a million surfels (with 256 a
-    // 0.6 M-surfel map was 293 chunks = two rounds, the second one on 37 CUs)
-    const int nblocks = min(512, (src.cap + 2 * kBinThreads - 1) / (2 * kBinThreads));
-    hipLaunchKernelGGL(k_splat_bin, dim3(nblocks), dim3(kBinThreads), (size_t)2 * nt * sizeof(int), s, b);
-    GlobalTileArgs t;
-    t.frame = frame; t.W = W; t.H = H; t.k = k; t.tilesX = tilesX; t.tilesY = tilesY; t.tileH = tileH; t.tile_count = tile_count; t.entries = entries; t.tile_cap = b.tile_cap;
-    t.rec0 = rec0; t.rec1 = rec1; t.bbox = reinterpret_cast<const short4*>(bbox);
-    t.payload = ((unsigned)order << 8) | ((unsigned)id & 255u); t.keys = keys;
-    t.vis_list = b.vis_list; t.vis_count = b.vis_count; t.runs = src.box;
-    switch (g_sprite_lanes) {
-        case 1: hipLaunchKernelGGL(k_global_tile<1>, dim3(xcd_padded_grid(nt)), dim3(g_tile_threads), 0, s, t); break;
-        case 2: hipLaunchKernelGGL(k_global_tile<2>, dim3(xcd_padded_grid(nt)), dim3(g_tile_threads), 0, s, t); break;
-        case 8: hipLaunchKernelGGL(k_global_tile<8>, dim3(xcd_padded_grid(nt)), dim3(g_tile_threads), 0, s, t); break;
-        case 16: hipLaunchKernelGGL(k_global_tile<16>, dim3(xcd_padded_grid(nt)), dim3(g_tile_threads), 0, s, t); break;
-        default: hipLaunchKernelGGL(k_global_tile<4>, dim3(xcd_padded_grid(nt)), dim3(g_tile_threads), 0, s, t); break;
-    }
-    return 0;
-}
-
-bool splat_tiled_applies(int W, int H, SplatTuning tune) {
-    const int tileH = splat_tile_height(tune.tile_h);
-    return ((W + kTile - 1) / kTile) * ((H + tileH - 1) / tileH) <= kMaxTiles;
 }
 
 size_t splat_tiles_scratch_ints(int W, int H) { return (size_t)((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile); }
 
-int launch_splat_tiled(Surfels src, FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth, float confThreshold,
-                       int timeDelta, int* tile_count, int* entries, int entries_cap, float4* rec0, float4* rec1, void* bbox, float4* predV,
-                       float4* predN, uchar4* predImage, uint16_t* predTime, const uint8_t* rgb, uint8_t* predGray, uint8_t* fillGray, hipStream_t s,
-                       const FrameAdvance* advance, int fillPassthrough, unsigned long long* prof, SplatTuning tune, const VisList* vis,
-                       const SplatFilterJob* filter, const SplatPyramidJob* pyramid) {
-    const int tileH = splat_tile_height(tune.tile_h);
-    const int tilesX = (W + kTile - 1) / kTile, tilesY = (H + tileH - 1) / tileH, nt = tilesX * tilesY;
-    if (nt > kMaxTiles) return -1;
-    const int g_sprite_lanes = splat_sprite_lanes(tune.sprite_lanes), g_tile_threads = std::max(splat_tile_threads(tune.tile_threads), ((kTile * tileH + 63) / 64) * 64);
+// What both tiled passes start with: the arguments their two launches share, and the binning pass enqueued -- in a launch of its own, or
+// (filter->fused, the prediction's rider) in the next frame's depth filter's
+static BinArgs launch_bin(const SpriteView& v, const TileLists& l, const TileShape& t, const VisList* vis, const SplatFilterJob* filter, hipStream_t s) {
+    const int nt = t.tilesX * t.tilesY;
     BinArgs b;
-    b.src = src; b.frame = frame; b.pose = pose; b.W = W; b.H = H; b.k = k; b.maxDepth = maxDepth; b.confThreshold = confThreshold;
-    b.timeDelta = timeDelta; b.tilesX = tilesX; b.tilesY = tilesY; b.tileH = tileH; b.tile_count = tile_count;
-    b.entries = entries; b.tile_cap = entries_cap / nt; b.frame_rw = frame;
-    b.rec0 = rec0; b.rec1 = rec1; b.bbox = reinterpret_cast<short4*>(bbox);
+    b.v = v; b.tilesX = t.tilesX; b.tilesY = t.tilesY; b.tileH = t.tileH;
+    b.tile_count = l.tile_count; b.entries = l.entries; b.tile_cap = l.entries_cap / nt;
+    b.rec0 = l.rec0; b.rec1 = l.rec1; b.bbox = reinterpret_cast<short4*>(l.bbox);
     b.vis_list = vis ? vis->list : nullptr; b.vis_count = vis ? vis->count : nullptr;
-    // two 1024-thread workgroups fit on a CU (60 VGPRs): 512 workgroups are ONE round of chunks up to a million surfels (with 256 a
-    // 0.6 M-surfel map was 293 chunks = two rounds, the second one on 37 CUs)
-    const int nblocks = min(512, (src.cap + 2 * kBinThreads - 1) / (2 * kBinThreads));
     if (filter && filter->fused) {
-        const int nbin = xcd_padded_grid(min(4 * 512, (src.cap + 2 * kBinFilterThreads - 1) / (2 * kBinFilterThreads))), nfil = bilateral_grid(W, H);
+        const int nbin = xcd_padded_grid(min(4 * 512, (v.src.cap + 2 * kBinFilterThreads - 1) / (2 * kBinFilterThreads))), nfil = bilateral_grid(v.W, v.H);
         const size_t lds = std::max((size_t)2 * nt * sizeof(int), (size_t)(kBLdsH * kBLdsW) * sizeof(float));
         // (eight 256-thread workgroups per compute unit: 2 048 are resident at once)
-        hipLaunchKernelGGL(k_bin_bilateral, dim3(nbin + nfil), dim3(kBinFilterThreads), lds, s, b, nbin, (nbin + nfil > 2048) ? 1 : 0, filter->depth, filter->out, W, H);
-    } else {
-        hipLaunchKernelGGL(k_splat_bin, dim3(nblocks), dim3(kBinThreads), (size_t)2 * nt * sizeof(int), s, b);
-        if (filter) launch_bilateral(filter->depth, filter->out, W, H, s);
+        hipLaunchKernelGGL(k_bin_bilateral, dim3(nbin + nfil), dim3(kBinFilterThreads), lds, s, b, nbin, (nbin + nfil > 2048) ? 1 : 0, filter->depth, filter->out, v.W, v.H);
+        return b;
     }
+    // two 1024-thread workgroups fit on a CU (60 VGPRs): 512 workgroups are ONE round of chunks up to a million surfels (with 256 a
+    // 0.6 M-surfel map was 293 chunks = two rounds, the second one on 37 CUs)
+    const int nblocks = min(512, (v.src.cap + 2 * kBinThreads - 1) / (2 * kBinThreads));
+    hipLaunchKernelGGL(k_splat_bin, dim3(nblocks), dim3(kBinThreads), (size_t)2 * nt * sizeof(int), s, b);
+    if (filter) launch_bilateral(filter->depth, filter->out, v.W, v.H, s);
+    return b;
+}
+// the instance of a tile kernel K<lanes per sprite> ("spriteLanes": splat_sprite_lanes admits 1, 2, 4, 8, 16)
+#define MF_LAUNCH_SPRITE_LANES(K, lanes, grid, threads, s, ...)                                              \
+    switch (lanes) {                                                                                         \
+        case 1: hipLaunchKernelGGL(K<1>, dim3(grid), dim3(threads), 0, s, __VA_ARGS__); break;               \
+        case 2: hipLaunchKernelGGL(K<2>, dim3(grid), dim3(threads), 0, s, __VA_ARGS__); break;               \
+        case 8: hipLaunchKernelGGL(K<8>, dim3(grid), dim3(threads), 0, s, __VA_ARGS__); break;               \
+        case 16: hipLaunchKernelGGL(K<16>, dim3(grid), dim3(threads), 0, s, __VA_ARGS__); break;             \
+        default: hipLaunchKernelGGL(K<4>, dim3(grid), dim3(threads), 0, s, __VA_ARGS__); break;              \
+    }
+
+int launch_global_tiled(const SpriteView& v, const TileLists& lists, unsigned payload, unsigned long long* keys, const VisList* vis, hipStream_t s) {
+    const TileShape shape = splat_tile_shape(v.W, v.H, lists.tune);
+    if (!shape.fits) return -1;
+    const GlobalTileArgs t{launch_bin(v, lists, shape, vis, nullptr, s), payload, keys};
+    MF_LAUNCH_SPRITE_LANES(k_global_tile, shape.lanes, xcd_padded_grid(shape.tilesX * shape.tilesY), shape.threads, s, t);
+    return 0;
+}
+
+int launch_splat_tiled(const SpriteView& v, const TileLists& lists, const PredOut& out, const SplatRiders& riders, const VisList* vis, hipStream_t s) {
+    const TileShape shape = splat_tile_shape(v.W, v.H, lists.tune);
+    if (!shape.fits) return -1;
     TileArgs t;
-    t.src = src; t.frame = frame; t.pose = pose; t.W = W; t.H = H; t.k = k; t.maxDepth = maxDepth; t.confThreshold = confThreshold;
-    t.timeDelta = timeDelta; t.tilesX = tilesX; t.tilesY = tilesY; t.tileH = tileH; t.tile_count = tile_count;
-    t.entries = entries; t.tile_cap = b.tile_cap; t.rec0 = rec0; t.rec1 = rec1; t.bbox = reinterpret_cast<const short4*>(bbox);
-    t.predV = predV; t.predN = predN; t.predImage = predImage; t.predTime = predTime; t.rgb = rgb; t.predGray = predGray;
-    t.fillGray = fillGray;
-    t.fillPassthrough = fillPassthrough;
-    t.prof = prof;
-    t.vis_list = b.vis_list; t.vis_count = b.vis_count;
-    t.advance = advance ? 1 : 0;
-    t.adv = advance ? *advance : FrameAdvance{nullptr, nullptr, nullptr};
-    t.tile_wgs = xcd_padded_grid(nt);
+    t.b = launch_bin(v, lists, shape, vis, riders.filter, s);
+    t.out = out;
+    t.prof = riders.prof;
+    t.advance = riders.advance ? 1 : 0;
+    t.adv = riders.advance ? *riders.advance : FrameAdvance{nullptr, nullptr, nullptr};
+    t.tile_wgs = xcd_padded_grid(shape.tilesX * shape.tilesY);
+    const SplatPyramidJob* pyramid = riders.pyramid;
     for (int i = 0; i < 3; ++i) { t.vm[i] = pyramid ? pyramid->vm[i] : nullptr; t.nm[i] = pyramid ? pyramid->nm[i] : nullptr; }
     FramePyrArgs fp{};
     int grid = t.tile_wgs;
-    if (pyramid && pyramid->frame_depth) {   // the next frame's pyramid behind the tile workgroups: g_tile_threads / 256 of its tiles per workgroup
-        fp.depth = pyramid->frame_depth; fp.W = W; fp.H = H; fp.k = k; fp.cutoff = pyramid->frame_cutoff;
+    if (pyramid && pyramid->frame_depth) {   // the next frame's pyramid behind the tile workgroups: shape.threads / 256 of its tiles per workgroup
+        fp.depth = pyramid->frame_depth; fp.W = v.W; fp.H = v.H; fp.k = v.k; fp.cutoff = pyramid->frame_cutoff;
         for (int i = 0; i < 3; ++i) { fp.vmap[i] = pyramid->frame_vmap[i]; fp.nmap[i] = pyramid->frame_nmap[i]; }
-        const int nsub = g_tile_threads >> 8, groups = xcd_padded_grid(frame_pyramid_tiles(W, H)) >> 3;
+        const int nsub = shape.threads >> 8, groups = xcd_padded_grid(frame_pyramid_tiles(v.W, v.H)) >> 3;
         grid += ((groups + nsub - 1) / nsub) << 3;
     }
-    switch (g_sprite_lanes) {
-        case 1: hipLaunchKernelGGL(k_splat_tile<1>, dim3(grid), dim3(g_tile_threads), 0, s, t, fp); break;
-        case 2: hipLaunchKernelGGL(k_splat_tile<2>, dim3(grid), dim3(g_tile_threads), 0, s, t, fp); break;
-        case 8: hipLaunchKernelGGL(k_splat_tile<8>, dim3(grid), dim3(g_tile_threads), 0, s, t, fp); break;
-        case 16: hipLaunchKernelGGL(k_splat_tile<16>, dim3(grid), dim3(g_tile_threads), 0, s, t, fp); break;
-        default: hipLaunchKernelGGL(k_splat_tile<4>, dim3(grid), dim3(g_tile_threads), 0, s, t, fp); break;
-    }
+    MF_LAUNCH_SPRITE_LANES(k_splat_tile, shape.lanes, grid, shape.threads, s, t, fp);
     return 0;
 }
 

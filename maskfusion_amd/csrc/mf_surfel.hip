@@ -26,6 +26,7 @@
 #pragma clang fp contract(off)
 #include "mf_device.h"
 #include "mf_walk.h"
+#include "mf_sprite_device.h"
 #include "mf_rgbd_device.h"
 
 namespace mf {
@@ -1446,146 +1447,64 @@ void launch_densify(Surfels src, Surfels dst, FrameDev* frame, int* offs, int* h
 }
 
 // ------------------------------------------------------------------------------------------------
-// splat prediction: scatter (per-surfel sprite loop, ray-disc test, 64-bit atomicMin) + resolve
-// Raster rule: sprite side s centred on (u,v) covers pixel (px,py) iff u - s/2 <= px + 0.5 < u + s/2; LESS on the
-// corrected z; lower index wins ties; sprites wider than 64 px are clamped.
+// splat prediction: scatter (sprite_scatter_body, mf_sprite_device.h: per-surfel sprite loop, ray-disc test, 64-bit atomicMin with the
+// surfel's index as the key's low word -- the lower index wins ties) + resolve
 // ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_splat_scatter(const SpriteView v, unsigned long long* __restrict__ keys) { sprite_scatter_body<1, true>(v, 0u, keys, false); }
 
-// kLanes neighbouring lanes share one surfel and split its sprite's pixels between them as a kLX x kLY block (1: the thread-per-surfel form).
-// The object models' launches use 4: a few thousand sprites of 4-10 px a side kept a handful of threads busy for ~36 us each (round 4 trace),
-// the rest of the GPU idle; the keys are the same bits in any split (atomicMin is order independent).
-template <int kLanes>
-__device__ __forceinline__ void splat_scatter_body(Surfels src, const FrameDev* __restrict__ frame,
-                                                   const PoseDev* __restrict__ pose, int W, int H, Intr k, float maxDepth,
-                                                   float confThreshold, int timeDelta, unsigned long long* __restrict__ keys, bool pretest = false) {
-    const float time = (float)frame->tick;  // combinedPredict(time = tick, maxTime = tick)
-    float Ri[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) Ri[q] = pose->Ri[q];
-    const float3 ti = f3(pose->ti[0], pose->ti[1], pose->ti[2]);
-    constexpr int kLX = kLanes >= 2 ? 2 : 1, kLY = kLanes / kLX;
-    const int sub = threadIdx.x % kLanes, sx = sub % kLX, sy = sub / kLX;
-    for_each_surfel_slice<kLanes>(src, frame, nullptr, nullptr, [&](int i, bool live) {
-        if (!live) return;
-        const float4 pc = src.pc[i];
-        if (pc.w < confThreshold) return;
-        const float lastTime = src.ct[i].w;
-        const float3 h = mul33(Ri, f3(pc.x, pc.y, pc.z)) + ti;
-        if (h.z > maxDepth || h.z < 0 || time - lastTime > (float)timeDelta || lastTime > time) return;  // splat.vert:58
-        const float u = ((k.fx * h.x) / h.z) + k.cx, v = ((k.fy * h.y) / h.z) + k.cy;
-        if (!(u >= 0.f && u <= (float)W && v >= 0.f && v <= (float)H)) return;
-        const float4 n4 = src.nr[i];
-        const float3 nrm = normalize_gl(mul33(Ri, f3(n4.x, n4.y, n4.z)));
-        const float rad = n4.w;
-        const float3 x1 = normalize_gl(f3(nrm.y - nrm.z, -nrm.x, nrm.x)) * (rad * 1.41421356f);
-        const float3 y1 = cross3(nrm, x1);
-        float xs0 = INFINITY, xs1 = -INFINITY, ys0 = INFINITY, ys1 = -INFINITY;
-        const float3 corners[4] = {h + x1, h + y1, h - y1, h - x1};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float pxq = ((k.fx * corners[q].x) / corners[q].z) + k.cx;
-            const float pyq = ((k.fy * corners[q].y) / corners[q].z) + k.cy;
-            xs0 = fminf(xs0, pxq); xs1 = fmaxf(xs1, pxq);
-            ys0 = fminf(ys0, pyq); ys1 = fmaxf(ys1, pyq);
-        }
-        float size = fmaxf(0.f, fmaxf(fabsf(xs1 - xs0), fabsf(ys1 - ys0)));
-        if (!(size > 0.f)) return;
-        size = fminf(fmaxf(size, 1.0f), 64.0f);   // GL clamps gl_PointSize to the point size range: at least 1 px (see mf_splat.hip)
-        const float half = size * 0.5f;
-        const int px0 = max(0, (int)ceilf(u - half - 0.5f)), px1 = min(W - 1, (int)ceilf(u + half - 0.5f) - 1);
-        const int py0 = max(0, (int)ceilf(v - half - 0.5f)), py1 = min(H - 1, (int)ceilf(v + half - 0.5f) - 1);
-        const float sqrRad = rad * rad;
-        const float pn = dot3(h, nrm);
-        for (int py = py0 + sy; py <= py1; py += kLY) {
-            for (int px = px0 + sx; px <= px1; px += kLX) {
-                const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;
-                const float3 l = normalize_gl(f3((fcx - k.cx) / k.fx, (fcy - k.cy) / k.fy, 1.0f));
-                const float3 cp = l * (pn / dot3(l, nrm));
-                const float3 diff = cp - h;
-                if (!(dot3(diff, diff) <= sqrRad)) continue;
-                if (!(cp.z > 0.f)) continue;
-                const unsigned long long key = ((unsigned long long)__float_as_uint(cp.z) << 32) | (unsigned)i;
-                if (pretest) zmin_key_pretested(&keys[py * W + px], key);   // (the object models' launches)
-                else zmin_key(&keys[py * W + px], key);
-            }
-        }
-    });
+void launch_splat_scatter(const SpriteView& v, unsigned long long* keys, hipStream_t s, int blocks) {
+    hipLaunchKernelGGL(k_splat_scatter, dim3(blocks), dim3(256), 0, s, v, keys);
 }
 
-__global__ __launch_bounds__(256) void k_splat_scatter(Surfels src, const FrameDev* __restrict__ frame,
-                                                       const PoseDev* __restrict__ pose, int W, int H, Intr k, float maxDepth,
-                                                       float confThreshold, int timeDelta, unsigned long long* __restrict__ keys) {
-    splat_scatter_body<1>(src, frame, pose, W, H, k, maxDepth, confThreshold, timeDelta, keys);
-}
-
-void launch_splat_scatter(Surfels src, const FrameDev* frame, const PoseDev* pose, int W, int H, Intr k, float maxDepth,
-                          float confThreshold, int timeDelta, unsigned long long* keys, hipStream_t s, int blocks) {
-    hipLaunchKernelGGL(k_splat_scatter, dim3(blocks), dim3(256), 0, s, src, frame, pose, W, H, k, maxDepth, confThreshold,
-                       timeDelta, keys);
-}
-
-__device__ __forceinline__ void splat_resolve_body(Surfels src, const PoseDev* __restrict__ pose,
-                                                   unsigned long long* __restrict__ keys, int W, int H, Intr k,
-                                                   float4* __restrict__ predV, float4* __restrict__ predN,
-                                                   uchar4* __restrict__ predImage, uint16_t* __restrict__ predTime,
-                                                   FrameDev* __restrict__ frame, const uint8_t* __restrict__ rgb,
-                                                   uint8_t* __restrict__ predGray, uint8_t* __restrict__ fillGray, int fillPassthrough) {
+__device__ __forceinline__ void splat_resolve_body(const SpriteView& v, unsigned long long* __restrict__ keys, const PredOut& o) {
     const int px = blockIdx.x * 64 + (threadIdx.x & 63);
     const int py = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (px >= W || py >= H) return;
+    if (px >= v.W || py >= v.H) return;
+    const int W = v.W, H = v.H;
+    const Intr k = v.k;
     const int p = py * W + px;
     const unsigned long long key = keys[p];
     keys[p] = kEmptyKey;
     if (key == kEmptyKey) {
-        predV[p] = predN[p] = make_float4(0, 0, 0, 0);
-        predImage[p] = make_uchar4(0, 0, 0, 0);
-        predTime[p] = 0;
+        o.predV[p] = o.predN[p] = make_float4(0, 0, 0, 0);
+        o.predImage[p] = make_uchar4(0, 0, 0, 0);
+        o.predTime[p] = 0;
         // intensity images for the photometric term of the NEXT tracking step (imageBGRToIntensity of the RGB projection,
         // and of the fill-in image: fill_rgb.frag takes the raw frame where the projection is empty)
-        if (predGray) predGray[p] = 0;
-        if (fillGray && rgb) fillGray[p] = intensity_of((float)rgb[p * 3], (float)rgb[p * 3 + 1], (float)rgb[p * 3 + 2]);
+        if (o.predGray) o.predGray[p] = 0;
+        if (o.fillGray && o.rgb) o.fillGray[p] = intensity_of((float)o.rgb[p * 3], (float)o.rgb[p * 3 + 1], (float)o.rgb[p * 3 + 2]);
         return;
     }
     const int i = (int)(unsigned)(key & 0xFFFFFFFFull);
     const float z = __uint_as_float((unsigned)(key >> 32));
-    const float4 pc = src.pc[i], c4 = src.ct[i], n4 = src.nr[i];
-    const float3 n = normalize_gl(mul33(pose->Ri, f3(n4.x, n4.y, n4.z)));
+    const float4 pc = v.src.pc[i], c4 = v.src.ct[i], n4 = v.src.nr[i];
+    const float3 n = normalize_gl(mul33(v.pose->Ri, f3(n4.x, n4.y, n4.z)));
     const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;
-    predV[p] = make_float4((fcx - k.cx) * z * (1.f / k.fx), (fcy - k.cy) * z * (1.f / k.fy), z, pc.w);  // combo_splat.frag:56
-    predN[p] = make_float4(n.x, n.y, n.z, n4.w);
+    o.predV[p] = make_float4((fcx - k.cx) * z * (1.f / k.fx), (fcy - k.cy) * z * (1.f / k.fy), z, pc.w);  // combo_splat.frag:56
+    o.predN[p] = make_float4(n.x, n.y, n.z, n4.w);
     const int ci = (int)c4.x;
     const uchar4 col = make_uchar4((ci >> 16) & 0xFF, (ci >> 8) & 0xFF, ci & 0xFF, 255);
-    predImage[p] = col;
-    predTime[p] = (uint16_t)(unsigned)c4.z;
-    if (predGray || fillGray) {
+    o.predImage[p] = col;
+    o.predTime[p] = (uint16_t)(unsigned)c4.z;
+    if (o.predGray || o.fillGray) {
         const uint8_t gv = intensity_of((float)col.x, (float)col.y, (float)col.z);
-        if (predGray) predGray[p] = gv;
-        if (fillGray) {
+        if (o.predGray) o.predGray[p] = gv;
+        if (o.fillGray) {
             // fill_rgb.frag:31-34: the raw frame where the projection is empty -- or everywhere with `passthrough` (frameToFrameRGB, Model.cpp:981)
-            const bool empty = (col.x == 0 && col.y == 0 && col.z == 0) || fillPassthrough != 0;
-            fillGray[p] = (empty && rgb) ? intensity_of((float)rgb[p * 3], (float)rgb[p * 3 + 1], (float)rgb[p * 3 + 2]) : gv;
+            const bool empty = (col.x == 0 && col.y == 0 && col.z == 0) || o.fillPassthrough != 0;
+            o.fillGray[p] = (empty && o.rgb) ? intensity_of((float)o.rgb[p * 3], (float)o.rgb[p * 3 + 1], (float)o.rgb[p * 3 + 2]) : gv;
         }
     }
     // MaskFusion::requiresFillIn (MaskFusion.cpp:630-648): nearest sample of the 20x down-sampled colour prediction
     if ((px % 20) == 10 && (py % 20) == 10 && px / 20 < W / 20 && py / 20 < H / 20 && col.x > 0 && col.y > 0 && col.z > 0)
-        atomicAdd(&frame->cover, 1);
+        atomicAdd(&v.frame->cover, 1);
 }
 
-__global__ __launch_bounds__(256) void k_splat_resolve(Surfels src, const PoseDev* __restrict__ pose,
-                                                       unsigned long long* __restrict__ keys, int W, int H, Intr k,
-                                                       float4* __restrict__ predV, float4* __restrict__ predN,
-                                                       uchar4* __restrict__ predImage, uint16_t* __restrict__ predTime,
-                                                       FrameDev* __restrict__ frame, const uint8_t* __restrict__ rgb,
-                                                       uint8_t* __restrict__ predGray, uint8_t* __restrict__ fillGray, int fillPassthrough) {
-    splat_resolve_body(src, pose, keys, W, H, k, predV, predN, predImage, predTime, frame, rgb, predGray, fillGray, fillPassthrough);
-}
+__global__ __launch_bounds__(256) void k_splat_resolve(const SpriteView v, unsigned long long* __restrict__ keys, const PredOut o) { splat_resolve_body(v, keys, o); }
 
-void launch_splat_resolve(Surfels src, const PoseDev* pose, unsigned long long* keys, int W, int H, Intr k, float4* predV,
-                          float4* predN, uchar4* predImage, uint16_t* predTime, FrameDev* frame, const uint8_t* rgb,
-                          uint8_t* predGray, uint8_t* fillGray, hipStream_t s, int fillPassthrough) {
-    dim3 grid((W + 63) / 64, (H + 3) / 4);
-    hipLaunchKernelGGL(k_splat_resolve, grid, dim3(256), 0, s, src, pose, keys, W, H, k, predV, predN, predImage, predTime, frame, rgb,
-                       predGray, fillGray, fillPassthrough);
+void launch_splat_resolve(const SpriteView& v, unsigned long long* keys, const PredOut& out, hipStream_t s) {
+    dim3 grid((v.W + 63) / 64, (v.H + 3) / 4);
+    hipLaunchKernelGGL(k_splat_resolve, grid, dim3(256), 0, s, v, keys, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1698,16 +1617,17 @@ __global__ __launch_bounds__(256) void k_obj_clean_small_flags(const ObjBatch b)
     clean_small_flags_body<kTap16, kGroup, kMaskFree>(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1));
 }
 __global__ __launch_bounds__(256) void k_obj_clean_small_compact(const ObjBatch b) { clean_small_compact_body(obj_clean_args(b, b.m[blockIdx.z], b.cleanSmall ? 0 : 1)); }
-__global__ __launch_bounds__(256) void k_obj_splat_scatter(const ObjBatch b) {
-    const PassModel& m = b.m[blockIdx.z];
+// The prediction of one model of the batch.  (f by value, in functions of their own: a kernel that hands its argument struct to the builders by
+// reference itself addresses everything it reaches through that struct as flat memory -- flat_load / flat_store where these kernels have
+// global_load / global_store)
+__device__ __forceinline__ void obj_splat_scatter(const PassFrame f, const PassModel& m, int dense) {
     // (both forms write the same keys: the z-test is a minimum)
-    if (b.denseSprites) splat_scatter_body<1>(m.a, m.frame, m.pose, b.W, b.H, b.k, b.maxDepthProcessed, m.confThreshold, b.timeDelta, m.scr.keys, true);
-    else splat_scatter_body<4>(m.a, m.frame, m.pose, b.W, b.H, b.k, b.maxDepthProcessed, m.confThreshold, b.timeDelta, m.scr.keys, true);
+    if (dense) sprite_scatter_body<1, true>(predict_view(f, m), 0u, m.scr.keys, true);
+    else sprite_scatter_body<4, true>(predict_view(f, m), 0u, m.scr.keys, true);
 }
-__global__ __launch_bounds__(256) void k_obj_splat_resolve(const ObjBatch b) {
-    const PassModel& m = b.m[blockIdx.z];
-    splat_resolve_body(m.a, m.pose, m.scr.keys, b.W, b.H, b.k, m.predV, m.predN, m.predImage, m.predTime, m.frame, b.rgb, m.predGray, nullptr, 0);
-}
+__device__ __forceinline__ void obj_splat_resolve(const PassFrame f, const PassModel& m) { splat_resolve_body(predict_view(f, m), m.scr.keys, pred_out(f, m)); }
+__global__ __launch_bounds__(256) void k_obj_splat_scatter(const ObjBatch b) { obj_splat_scatter(b, b.m[blockIdx.z], b.denseSprites); }
+__global__ __launch_bounds__(256) void k_obj_splat_resolve(const ObjBatch b) { obj_splat_resolve(b, b.m[blockIdx.z]); }
 __global__ void k_obj_frame_advance(const ObjBatch b) {
     const PassModel& m = b.m[blockIdx.z];
     frame_advance_body(m.frame, b.W, b.H, m.host_frame, m.pose, b.bg_pose, m.log_slot);
