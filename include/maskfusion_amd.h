@@ -987,6 +987,13 @@ int mf_k_rgb_residual(float min_scale, const int16_t* d_dIdx, const int16_t* d_d
                       const float* d_next_depth, const uint8_t* d_last_image, const uint8_t* d_next_image,
                       float max_depth_delta, const float* kt3, const float* krkinv9, int32_t W, int32_t H, void* d_corres,
                       int32_t* count_sigma2, void* stream);
+/* mf_k_rgb_residual (which is this call with a null gate) with an optional gate image, W*H bytes as mf_k_rgb_gate returns
+ * them: given, the border / 4x4 window / gradient tests are read from it, as a frame's iterations do, and min_scale, d_dIdx,
+ * d_dIdy are not consulted.  Synchronous. */
+int mf_k_rgb_residual_gated(float min_scale, const int16_t* d_dIdx, const int16_t* d_dIdy, const float* d_last_depth,
+                            const float* d_next_depth, const uint8_t* d_last_image, const uint8_t* d_next_image,
+                            float max_depth_delta, const float* kt3, const float* krkinv9, int32_t W, int32_t H,
+                            void* d_corres, int32_t* count_sigma2, const uint8_t* d_gate_or_null, void* stream);
 /* rgbStep (Core/Cuda/reduce.cu:529-713) with projectToPointCloud (Core/Cuda/cudafuncs.cu:722-751) evaluated on the
  * fly from d_last_depth; out32 (host, double) = {27 upper-tri products, row6^2, inliers, pad}.  Synchronous. */
 int mf_k_rgb_step(const void* d_corres, float sigma, const float* d_last_depth, float fx, float fy, float cx, float cy,
@@ -1006,6 +1013,23 @@ int mf_k_icp_step(const float* Rcurr9, const float* tcurr3, const float* d_vmap_
                   const float* Rprev_inv9, const float* tprev3, float fx, float fy, float cx, float cy,
                   const float* d_vmap_g_prev, const float* d_nmap_g_prev, float dist_thresh, float angle_thresh,
                   int32_t W, int32_t H, float* d_out32, void* stream);
+/* mf_k_icp_step (form 0: k_icp_iter) through the other kernels that share its per-pixel functions, for the tests of the
+ * correspondence gates: form 1 the batched pixel pass for one model, unfused, without slab culling; form 2 the same with slab
+ * culling against rect4 = {x0, y0, x1, y1}, the level-0 rectangle of the model's normals (required); form 3 the RGB-D iteration
+ * kernel with the geometric term on and a blank photometric level.  The same 32 floats.  Both entries return MF_EINVAL for a
+ * threshold that is negative, NaN or infinite, before anything is allocated or launched.  Synchronous. */
+int mf_k_icp_step_form(int32_t form, const float* Rcurr9, const float* tcurr3, const float* d_vmap_curr,
+                       const float* d_nmap_curr, const float* Rprev_inv9, const float* tprev3, float fx, float fy, float cx,
+                       float cy, const float* d_vmap_g_prev, const float* d_nmap_g_prev, float dist_thresh,
+                       float angle_thresh, int32_t W, int32_t H, float* d_out32, const int32_t* rect4_or_null, void* stream);
+/* The level-0 gate image (1 where the border, 4x4 window and gradient tests of RGBResidual::getProducts pass) from both kernels
+ * that write it: d_gate_single, d_dIdx, d_dIdy from the derivative kernel on d_src; d_gate_pyramid from the one-launch pyramid
+ * on an RGB image whose three channels equal d_src, with d_gray_pyramid, the intensity image that launch derived (the caller
+ * checks that it equals d_src).  min_scale3: the three levels' thresholds (host).  *pyramid_ran = 0, and the two pyramid
+ * outputs untouched, where W or H is no multiple of 4 (sizes the pyramid's tiling does not cover).  W, H >= 4.  Synchronous. */
+int mf_k_rgb_gate(const uint8_t* d_src, int32_t W, int32_t H, const float* min_scale3, uint8_t* d_gate_single,
+                  uint8_t* d_gate_pyramid, int16_t* d_dIdx, int16_t* d_dIdy, uint8_t* d_gray_pyramid, int32_t* pyramid_ran,
+                  void* stream);
 /* The launch form the geometric Gauss-Newton kernel takes for a pyramid level of W x H pixels (host only, no GPU involved):
  * out = {threads per workgroup, pixel slots per thread, workgroups, pixels per workgroup, workgroups that hold at least one
  * pixel}.  Read from the functions the launch itself calls, so that a test can name the form its image sizes select. */

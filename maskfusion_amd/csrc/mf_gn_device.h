@@ -218,7 +218,8 @@ struct IcpCorr { float3 vcurr_g, vcurr_cp, ncurr_g; int j; bool ok; };
 // parity tests check against (its m33_mul / f3_dot / f3_cross: a plain reading of Core/Cuda/reduce.cu:292-415), contraction off.  Two reasons:
 //  * everything that DECIDES something -- the rounded projection (ux, uy), the 0.10 m distance gate, the sin 20 degrees gate, the
 //    NaN tests -- is then bit-identical to the oracle, so the inlier set (not just its size) matches by construction, and the
-//    seven row entries of every inlier do too; only the accumulation of the 28 products differs (fp32 block sums here, double there);
+//    seven row entries of every inlier do too; only the accumulation of the 28 products differs (fp32 block sums here, double there)
+//    -- held on inputs that sit ON each decision, through every kernel that inlines these functions, by tests/test_gpu_gn_gates.py;
 //  * k_icp_iter<512>, k_icp_iter<256>, k_icp_batch_pixels and k_rgbd_iter are separate functions, and left to itself the compiler
 //    contracts a * b + c differently in each.  The 1e-7 relative spread that causes is invisible for a room-sized model, but a freshly
 //    spawned object (2 000 pixels on two box faces: a 6x6 system with condition ~1e5) turns it into millimetres of pose: the batched

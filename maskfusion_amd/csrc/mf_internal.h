@@ -216,6 +216,10 @@ void launch_icp_step_standalone(const float* Rcurr, const float* tcurr, const fl
                                 const float* Rpi, const float* tprev, Intr k, const float* vp, const float* np,
                                 float distThres, float angleThres, int W, int H, float* partials, GNState* st2,
                                 float* out32, hipStream_t s);
+// The same through k_icp_batch_pixels (form 1; form 2: with slab culling against rect4, host {x0, y0, x1, y1}) or k_rgbd_iter (form 3).  dpose: device
+// Rcurr[9] tcurr[3] Rprev_inv[9] tprev[3].  Own scratch, synchronous; 0, -1 (no memory) or -2 (HIP error).
+int icp_step_form_standalone(int form, const float* dpose, const float* vc, const float* nc, Intr k, const float* vp, const float* np, float distThres,
+                             float angleThres, int W, int H, const int* rect4, float* out32, hipStream_t s);
 
 struct RgbCorr { int16_t u0, v0; float diff; };  // DataTerm (types.cuh:75-81) packed to 8 B; u0 < 0: no correspondence
 

@@ -59,10 +59,10 @@ static RgbLevel make_level(const int16_t* dIdx, const int16_t* dIdy, const float
     L.W = W; L.H = H; L.minScale = minScale; L.maxDepthDelta = maxDepthDelta; L.gate = nullptr;
     return L;
 }
-extern "C" int mf_k_rgb_residual(float min_scale, const int16_t* d_dIdx, const int16_t* d_dIdy, const float* d_last_depth,
-                                 const float* d_next_depth, const uint8_t* d_last_image, const uint8_t* d_next_image, float max_depth_delta,
-                                 const float* kt3, const float* krkinv9, int32_t W, int32_t H, void* d_corres, int32_t* count_sigma2,
-                                 void* stream) {
+extern "C" int mf_k_rgb_residual_gated(float min_scale, const int16_t* d_dIdx, const int16_t* d_dIdy, const float* d_last_depth,
+                                       const float* d_next_depth, const uint8_t* d_last_image, const uint8_t* d_next_image, float max_depth_delta,
+                                       const float* kt3, const float* krkinv9, int32_t W, int32_t H, void* d_corres, int32_t* count_sigma2,
+                                       const uint8_t* d_gate_or_null, void* stream) {
     if (!d_dIdx || !d_dIdy || !d_last_depth || !d_next_depth || !d_last_image || !d_next_image || !kt3 || !krkinv9 || !d_corres ||
         !count_sigma2)
         return MF_EINVAL;
@@ -76,13 +76,21 @@ extern "C" int mf_k_rgb_residual(float min_scale, const int16_t* d_dIdx, const i
     hipError_t e = hipMemcpyAsync(d_k, h, 48, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_sums, 0, 8, s);
     if (e == hipSuccess) {
-        launch_rgb_residual_only(make_level(d_dIdx, d_dIdy, d_last_depth, d_next_depth, d_last_image, d_next_image, W, H, min_scale,
-                                            max_depth_delta), d_k, reinterpret_cast<RgbCorr*>(d_corres), d_sums, s);
+        RgbLevel L = make_level(d_dIdx, d_dIdy, d_last_depth, d_next_depth, d_last_image, d_next_image, W, H, min_scale, max_depth_delta);
+        L.gate = d_gate_or_null;   // the branch production takes: the pose-independent tests read from the frame's gate image
+        launch_rgb_residual_only(L, d_k, reinterpret_cast<RgbCorr*>(d_corres), d_sums, s);
         e = hipMemcpyAsync(count_sigma2, d_sums, 8, hipMemcpyDeviceToHost, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(scratch);
     return e == hipSuccess ? MF_OK : MF_EHIP;
+}
+extern "C" int mf_k_rgb_residual(float min_scale, const int16_t* d_dIdx, const int16_t* d_dIdy, const float* d_last_depth,
+                                 const float* d_next_depth, const uint8_t* d_last_image, const uint8_t* d_next_image, float max_depth_delta,
+                                 const float* kt3, const float* krkinv9, int32_t W, int32_t H, void* d_corres, int32_t* count_sigma2,
+                                 void* stream) {
+    return mf_k_rgb_residual_gated(min_scale, d_dIdx, d_dIdy, d_last_depth, d_next_depth, d_last_image, d_next_image, max_depth_delta, kt3, krkinv9,
+                                   W, H, d_corres, count_sigma2, nullptr, stream);
 }
 extern "C" int mf_k_rgb_step(const void* d_corres, float sigma, const float* d_last_depth, float fx, float fy, float cx, float cy,
                              const int16_t* d_dIdx, const int16_t* d_dIdy, float sobel_scale, int32_t W, int32_t H, double* out32,
@@ -243,10 +251,15 @@ extern "C" int mf_k_icp_launch_form(int32_t W, int32_t H, int32_t out[5]) {
     out[0] = f.threads; out[1] = f.slots; out[2] = f.blocks; out[3] = f.chunk; out[4] = f.live;
     return MF_OK;
 }
-extern "C" int mf_k_icp_step(const float* Rcurr9, const float* tcurr3, const float* d_vc, const float* d_nc, const float* Rpi9,
-                             const float* tprev3, float fx, float fy, float cx, float cy, const float* d_vp, const float* d_np,
-                             float dist_thresh, float angle_thresh, int32_t W, int32_t H, float* d_out32, void* stream) {
-    if (!Rcurr9 || !tcurr3 || !d_vc || !d_nc || !Rpi9 || !tprev3 || !d_vp || !d_np || !d_out32 || (W * H) % 4) return MF_EINVAL;
+// a threshold icp_gates can bracket: not negative (its first loop would walk down to 0 and stay there), not NaN, not infinite
+static bool icp_threshold_ok(float t) { return t >= 0.f && t <= 3.4028234664e38f; }
+extern "C" int mf_k_icp_step_form(int32_t form, const float* Rcurr9, const float* tcurr3, const float* d_vc, const float* d_nc, const float* Rpi9,
+                                  const float* tprev3, float fx, float fy, float cx, float cy, const float* d_vp, const float* d_np,
+                                  float dist_thresh, float angle_thresh, int32_t W, int32_t H, float* d_out32, const int32_t* rect4_or_null,
+                                  void* stream) {
+    if (!Rcurr9 || !tcurr3 || !d_vc || !d_nc || !Rpi9 || !tprev3 || !d_vp || !d_np || !d_out32 || W <= 0 || H <= 0 || (W * H) % 4 || form < 0 ||
+        form > 3 || (form == 2 && !rect4_or_null) || !icp_threshold_ok(dist_thresh) || !icp_threshold_ok(angle_thresh))
+        return MF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     float* scratch = nullptr;
     const size_t nb = (size_t)icp_geo_grid_blocks(W, H);
@@ -261,9 +274,55 @@ extern "C" int mf_k_icp_step(const float* Rcurr9, const float* tcurr3, const flo
     memcpy(hp, Rcurr9, 36); memcpy(hp + 9, tcurr3, 12); memcpy(hp + 12, Rpi9, 36); memcpy(hp + 21, tprev3, 12);
     (void)hipMemcpyAsync(dpose, hp, sizeof(hp), hipMemcpyHostToDevice, s);
     (void)hipStreamSynchronize(s);  // hp is a stack buffer
-    launch_icp_step_standalone(dpose, dpose + 9, d_vc, d_nc, dpose + 12, dpose + 21, Intr{fx, fy, cx, cy}, d_vp, d_np, dist_thresh,
-                               angle_thresh, W, H, scratch, st, d_out32, s);
+    int rc = 0;
+    if (form == 0)
+        launch_icp_step_standalone(dpose, dpose + 9, d_vc, d_nc, dpose + 12, dpose + 21, Intr{fx, fy, cx, cy}, d_vp, d_np, dist_thresh,
+                                   angle_thresh, W, H, scratch, st, d_out32, s);
+    else
+        rc = icp_step_form_standalone(form, dpose, d_vc, d_nc, Intr{fx, fy, cx, cy}, d_vp, d_np, dist_thresh, angle_thresh, W, H, rect4_or_null,
+                                      d_out32, s);
     (void)hipStreamSynchronize(s);
     (void)hipFree(scratch);
+    if (rc != 0) return rc == -1 ? MF_ENOMEM : MF_EHIP;
     return launch_rc();
+}
+extern "C" int mf_k_icp_step(const float* Rcurr9, const float* tcurr3, const float* d_vc, const float* d_nc, const float* Rpi9,
+                             const float* tprev3, float fx, float fy, float cx, float cy, const float* d_vp, const float* d_np,
+                             float dist_thresh, float angle_thresh, int32_t W, int32_t H, float* d_out32, void* stream) {
+    return mf_k_icp_step_form(0, Rcurr9, tcurr3, d_vc, d_nc, Rpi9, tprev3, fx, fy, cx, cy, d_vp, d_np, dist_thresh, angle_thresh, W, H, d_out32,
+                              nullptr, stream);
+}
+// The level-0 gate image (the pose-independent tests of RGBResidual::getProducts, once per frame) from both kernels that write it: k_derivative
+// on d_src, and k_rgb_pyramid on an RGB image whose three channels equal d_src -- with the intensity image that kernel derived from it, which
+// the caller compares with d_src.  *pyramid_ran = 0 (and d_gate_pyramid / d_gray_pyramid untouched) at sizes the pyramid's tiling does not cover.
+extern "C" int mf_k_rgb_gate(const uint8_t* d_src, int32_t W, int32_t H, const float* min_scale3, uint8_t* d_gate_single, uint8_t* d_gate_pyramid,
+                             int16_t* d_dIdx, int16_t* d_dIdy, uint8_t* d_gray_pyramid, int32_t* pyramid_ran, void* stream) {
+    if (!d_src || !min_scale3 || !d_gate_single || !d_gate_pyramid || !d_dIdx || !d_dIdy || !d_gray_pyramid || !pyramid_ran || W < 4 || H < 4)
+        return MF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    *pyramid_ran = 0;
+    launch_derivative(d_src, d_dIdx, d_dIdy, W, H, min_scale3[0], d_gate_single, s);
+    if (hipStreamSynchronize(s) != hipSuccess) return MF_EHIP;
+    if ((W & 3) || (H & 3)) return launch_rc();
+    const size_t P = (size_t)W * H, P1 = P / 4, P2 = P / 16, PS = P + P1 + P2;
+    std::vector<uint8_t> h_src(P), h_rgb(3 * P);
+    if (hipMemcpy(h_src.data(), d_src, P, hipMemcpyDeviceToHost) != hipSuccess) return MF_EHIP;
+    for (size_t i = 0; i < P; ++i) h_rgb[3 * i] = h_rgb[3 * i + 1] = h_rgb[3 * i + 2] = h_src[i];
+    char* buf = nullptr;   // int16 dIdx[3 levels], dIdy[3 levels] | gray 1, 2 | gate 1, 2 | rgb
+    if (hipMalloc((void**)&buf, 4 * PS + 2 * (P1 + P2) + 3 * P) != hipSuccess) return MF_ENOMEM;
+    int16_t* dx = reinterpret_cast<int16_t*>(buf);
+    int16_t* dy = dx + PS;
+    uint8_t* bytes = reinterpret_cast<uint8_t*>(buf + 4 * PS);
+    uint8_t* rgb = bytes + 2 * (P1 + P2);
+    uint8_t* const gray[3] = {d_gray_pyramid, bytes, bytes + P1};
+    uint8_t* const gate[3] = {d_gate_pyramid, bytes + P1 + P2, bytes + 2 * P1 + P2};
+    int16_t* const dIdx[3] = {dx, dx + P, dx + P + P1};
+    int16_t* const dIdy[3] = {dy, dy + P, dy + P + P1};
+    hipError_t e = hipMemcpy(rgb, h_rgb.data(), 3 * P, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        *pyramid_ran = launch_rgb_pyramid(rgb, W, H, gray, dIdx, dIdy, gate, min_scale3, true, s) ? 1 : 0;
+        e = hipStreamSynchronize(s);
+    }
+    (void)hipFree(buf);
+    return e == hipSuccess ? launch_rc() : MF_EHIP;
 }

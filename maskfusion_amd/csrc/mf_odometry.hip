@@ -860,6 +860,76 @@ void launch_icp_step_standalone(const float* Rcurr, const float* tcurr, const fl
     hipLaunchKernelGGL(k_icp_reduce_only, dim3(1), dim3(256), 0, s, partials, icp_geo_grid_blocks(W, H), out32);
 }
 
+// The same stand-alone icpStep through the OTHER kernels that inline icp_project / icp_accumulate (tests/test_gpu_gn_gates.py), each launched by the
+// production launch function and reduced by k_icp_reduce_only into the same 32 floats:
+//   form 1  k_icp_batch_pixels for a one-model TrackBatch, unfused, no row_z (every workgroup walks its pixels)
+//   form 2  form 1 with row_z from launch_row_zrange, allow_fill = 0 and the given level-0 rectangle of model normals: the slab culling
+//   form 3  k_rgbd_iter with icpOn = 1 on a blank photometric level (zero images: no photometric correspondence), followed by its k_rgb_step
+// dpose: device Rcurr[9] tcurr[3] Rprev_inv[9] tprev[3].  Allocates and frees its own scratch; synchronous.  Returns 0, -1 (no memory), -2 (HIP error).
+int icp_step_form_standalone(int form, const float* dpose, const float* vc, const float* nc, Intr k, const float* vp, const float* np, float distThres,
+                             float angleThres, int W, int H, const int* rect4, float* out32, hipStream_t s) {
+    const size_t P = (size_t)W * H;
+    const int nb = form == 3 ? icp_grid_blocks(W, H) : icp_batch_blocks(W, H, 1);
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t b_part = up16((size_t)nb * kIcpSlots * sizeof(float)), b_st = up16(2 * sizeof(GNState));
+    const size_t n_rowz = (size_t)H + (H >> 1) + (H >> 2);
+    const size_t b_rest = form == 3 ? b_part + up16((size_t)nb * sizeof(int2)) + up16(P * sizeof(RgbCorr)) + up16(P * sizeof(float))
+                                    : up16(sizeof(TrackModelDev)) + up16(4 * sizeof(int)) + up16(n_rowz * sizeof(float2));
+    char* base = nullptr;
+    if (hipMalloc((void**)&base, b_part + b_st + b_rest) != hipSuccess) return -1;
+    float* partials = reinterpret_cast<float*>(base);
+    GNState* st = reinterpret_cast<GNState*>(base + b_part);
+    char* rest = base + b_part + b_st;
+    hipLaunchKernelGGL(k_state_from_args, dim3(1), dim3(64), 0, s, st, dpose, dpose + 9, dpose + 12, dpose + 21);
+    bool ok = true;
+    if (form == 3) {
+        float* rgb_partials = reinterpret_cast<float*>(rest);
+        int2* cnt = reinterpret_cast<int2*>(rest + b_part);
+        RgbCorr* corres = reinterpret_cast<RgbCorr*>(rest + b_part + up16((size_t)nb * sizeof(int2)));
+        char* zeros = reinterpret_cast<char*>(corres) + up16(P * sizeof(RgbCorr));   // every image of the blank level: P zero floats / shorts / bytes
+        ok = hipMemsetAsync(zeros, 0, P * sizeof(float), s) == hipSuccess;
+        RgbdLaunch r;
+        IcpLaunch& l = r.icp;
+        l.vmap_curr = vc; l.nmap_curr = nc; l.vmap_prev = vp; l.nmap_prev = np; l.W = W; l.H = H; l.k = k;
+        l.distThres = distThres; l.angleThres = angleThres; l.partials_in = nullptr; l.nblocks_in = 0;
+        l.partials_out = partials; l.state_in = st; l.state_out = st + 1; l.log_out = nullptr;
+        RgbLevel& L = r.L;
+        L.dIdx = reinterpret_cast<const int16_t*>(zeros); L.dIdy = L.dIdx;
+        L.lastDepth = reinterpret_cast<const float*>(zeros); L.nextDepth = L.lastDepth;
+        L.lastImage = reinterpret_cast<const uint8_t*>(zeros); L.nextImage = L.lastImage;
+        L.W = W; L.H = H; L.minScale = 0.f; L.maxDepthDelta = 0.07f; L.gate = nullptr;
+        r.corres = corres; r.rgb_partials_in = nullptr; r.rgb_partials_out = rgb_partials; r.cnt_in = nullptr; r.cnt_out = cnt;
+        r.icpWeight = 10.f; r.icpOn = 1; r.rgbOnly = 0; r.sobelScale = 0.125f; r.level = 0; r.prev_level = 0; r.so3_in = nullptr;
+        if (ok) launch_rgbd_iteration(r, s);
+    } else {
+        TrackModelDev* d_md = reinterpret_cast<TrackModelDev*>(rest);
+        int* d_rect = reinterpret_cast<int*>(rest + up16(sizeof(TrackModelDev)));
+        float2* d_rowz = reinterpret_cast<float2*>(rest + up16(sizeof(TrackModelDev)) + up16(4 * sizeof(int)));
+        TrackModelDev md;
+        memset(&md, 0, sizeof(md));
+        md.vm[0] = const_cast<float*>(vp); md.nm[0] = const_cast<float*>(np);
+        md.partials[0] = partials; md.partials[1] = partials; md.st = st; md.allow_fill = 0; md.rect = d_rect;
+        const int full[4] = {0, 0, W - 1, H - 1};
+        ok = hipMemcpyAsync(d_md, &md, sizeof(md), hipMemcpyHostToDevice, s) == hipSuccess &&
+             hipMemcpyAsync(d_rect, rect4 ? rect4 : full, sizeof(full), hipMemcpyHostToDevice, s) == hipSuccess &&
+             hipStreamSynchronize(s) == hipSuccess;   // md and full are stack buffers
+        if (ok && form == 2) {
+            // (only level 0's ranges are read; the coarser levels' rows are computed from planes inside the same map: [2 P / 4, 3 P / 4) and [2 P / 16, 3 P / 16))
+            const float* const vm3[3] = {vc, vc, vc};
+            launch_row_zrange(vm3, W, H, d_rowz, s);
+        }
+        TrackBatch b;
+        memset(&b, 0, sizeof(b));
+        b.m[0] = d_md; b.n = 1;
+        const IcpBatchLevel lv{0, vc, nc, W, H, k, distThres, angleThres, form == 2 ? d_rowz : nullptr};
+        if (ok) launch_icp_batch_pixels(b, 0, lv, false, 0, nullptr, s);
+    }
+    if (ok) hipLaunchKernelGGL(k_icp_reduce_only, dim3(1), dim3(256), 0, s, partials, nb, out32);
+    ok = hipStreamSynchronize(s) == hipSuccess && ok;
+    (void)hipFree(base);
+    return ok && hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 // ------------------------------------------------------------------------------------------------
 // RGB-D Gauss-Newton loop (icpWeight < 100 or rgbOnly): two launches per iteration.
 //   A  k_rgbd_iter : [finish the previous iteration: reduce ICP + RGB partials, combine, solve, pose] ->

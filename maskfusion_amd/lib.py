@@ -110,6 +110,8 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_k_rgb_residual": (C.c_int, [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mf_k_rgb_residual_gated": (C.c_int, [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_k_rgb_step": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                 C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mf_download_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
@@ -239,6 +241,11 @@ SYMBOLS = {
     "mf_k_icp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                 C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
                                 C.c_int32, C.c_void_p, C.c_void_p]),
+    "mf_k_icp_step_form": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                     C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
+                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mf_k_rgb_gate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
     "mf_k_icp_launch_form": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
     "mf_session_save": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]),
     "mf_session_load": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]),

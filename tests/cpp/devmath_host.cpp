@@ -50,6 +50,8 @@ void dm_rodrigues(const double* w, double* R9) {
     mf::rodrigues_d(w[0], w[1], w[2], R);
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R9[r * 3 + c] = R[r][c];
 }
+// the boundary floats of the two ICP gates on the squared quantities, as the launches compute them: out = {dist2Max, sine2Min}
+void dm_icp_gates(float distThres, float angleThres, float* out2) { mf::icp_gates(distThres, angleThres, out2[0], out2[1]); }
 void dm_rodrigues2(const float* R9, double* r3) { mf::rodrigues2_d(R9, r3); }
 void dm_quat_from_rot(const float* R9, float* q4) { mf::quat_from_rot(R9, q4); }
 // copy_unstable.vert's window along one axis as the device walks it: texels u[3], multiplicities m[3]

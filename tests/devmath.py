@@ -17,6 +17,7 @@ OUT = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT, "libdevmath.so")
 SLICES = [("mf_odometry.hip", "ldlt6_solve"), ("mf_odometry.hip", "gn_update_from_x"), ("mf_odometry.hip", "gn_solve_update_serial"),
           ("mf_gn_device.h", "pose_from_state"), ("mf_surfel.hip", "window_slots_literal")]
+HOST_SLICES = [("mf_odometry.hip", "icp_gates")]   # host functions of the product (`static ... name(`), cut the same way
 
 f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
@@ -24,9 +25,10 @@ i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _lib = None
 
 
-def cut_function(text: str, name: str) -> str:
-    """the definition of the __device__ function `name` (signature to matching closing brace), `__device__ __forceinline__` included"""
-    m = re.search(r"^(?:template\s*<[^>]*>\s*\n)?__device__[^\n;{]*\b" + re.escape(name) + r"\s*\(", text, re.M)
+def cut_function(text: str, name: str, qualifier: str = "__device__") -> str:
+    """the definition of the __device__ function `name` (signature to matching closing brace), `__device__ __forceinline__` included
+    (qualifier "static": a host function)"""
+    m = re.search(r"^(?:template\s*<[^>]*>\s*\n)?" + qualifier + r"[^\n;{]*\b" + re.escape(name) + r"\s*\(", text, re.M)
     assert m, name
     i = text.index("{", m.end())
     depth, j = 0, i
@@ -41,6 +43,8 @@ def translation_unit() -> str:
     parts = []
     for fn, name in SLICES:
         parts.append(cut_function(open(os.path.join(CSRC, fn)).read(), name))
+    for fn, name in HOST_SLICES:
+        parts.append(cut_function(open(os.path.join(CSRC, fn)).read(), name, "static"))
     api = open(os.path.join(HERE, "cpp", "devmath_host.cpp")).read()
     assert api.count("\nDEVMATH_SLICES\n") == 1
     return api.replace("\nDEVMATH_SLICES\n", "\n" + "\n\n".join(parts) + "\n")
@@ -76,6 +80,7 @@ def lib():
         L.dm_quat_from_rot.argtypes = [f32p, f32p]
         L.dm_window_slots_literal.argtypes = [C.c_float, C.c_int, i32p, i32p]
         L.dm_gn_solve_update.argtypes = [f64p, f64p, f32p, f32p, f64p, f64p, f32p, f32p, f32p, f32p, f32p]
+        L.dm_icp_gates.argtypes = [C.c_float, C.c_float, f32p]
         L.dm_pose_derive.argtypes = [f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int]
         L.dm_pose_from_state.argtypes = [f32p, f32p, f32p, f32p, f32p, f32p, C.c_float, C.c_int, f32p, f32p, f32p, f32p, i32p]
         _lib = L
